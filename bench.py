@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Msamples/s of the Cornell box, 1920x1080 at 4096 spp (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config headline|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the JSON line (Msamples/s, ms_per_step, the roofline block computed
+from the timed steps' own kernel timers). --full adds what takes runs of its own: the device-to-device copy probe and the
+CPU baseline. --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 One process per GPU. Started as `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment, this
 process starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a fresh CHILD before it imports
@@ -38,6 +42,7 @@ CONFIGS = {
     "c5": dict(scene=0, w=7680, h=4320, spp=4096, name="Cornell box 7680x4320 4096spp (BASELINE config 5)",
                what="Cornell box (reference scene 0)", light="NEE mixture PDF (cosine + light rect)"),
 }
+DUMP_IMAGE_BYTES = 48 << 20  # --dump-outputs stays under 64 MB in all (the headline frame, 31.6 MiB, is written whole)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0  # wave64 VALU instructions per ns, chip-wide: 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles (same guide)
 PIPELINES = {
@@ -55,10 +60,13 @@ def parse_args(argv=None):
                     help="headline: Cornell box 1920x1080 4096 spp (the metric); c2 / c3 / c4 / c5: BASELINE.json configs 2-5")
     ap.add_argument("--spp", type=int, default=None, help="override samples per pixel (a reduced-spp line is not the configuration's metric)")
     ap.add_argument("--rng", type=int, default=0, help="0 Philox4x32-10 (default), 1 the reference's TEA+LCG")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1: nccl (= RCCL over xGMI) or gloo "
                                                     "(rehearsal on one GPU: ranks share device 0, shards are gathered through host memory)")
     ap.add_argument("--check", action="store_true", help="rank 0 re-renders the full frame alone and asserts the gathered image is identical")
+    ap.add_argument("--full", action="store_true", help="also measure what needs runs of its own: the device copy probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's image and sample counts as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args(argv)
 
 
@@ -74,6 +82,8 @@ def spawn_ranks(args):
     env.setdefault("OMP_NUM_THREADS", "8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:  # the ranks run in ROOT: a relative DIR is this process's (the last --dump-outputs given wins)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, cwd=ROOT)
     for line in proc.stdout:  # the JSON line goes to stdout, whatever else the ranks' libraries print there (gloo does) to stderr
         out = sys.stdout if line.startswith('{"metric"') else sys.stderr
@@ -111,6 +121,21 @@ def cpu_baseline(blob, abi, cfg):
         "single_thread_value": round(s1.samples / dt1 / 1e6, 4),
         "segments_per_sample": round(sn.segments / sn.samples, 4),
     }
+
+
+def dump_outputs(out_dir, image, counts):
+    """--dump-outputs: the frame the timed path returned in its last step (float32, height x width x 4) and that step's
+    (samples, segments, shadow rays) summed over ranks (float64). A frame above DUMP_IMAGE_BYTES is cut to a fixed, seeded
+    sample of whole rows; image_rows.npy then holds their indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if image.nbytes > DUMP_IMAGE_BYTES:
+        n = DUMP_IMAGE_BYTES // image[0].nbytes
+        rows = np.sort(np.random.default_rng(SEED).choice(image.shape[0], n, replace=False))
+        np.save(os.path.join(out_dir, "image_rows.npy"), rows.astype(np.float64))
+        image = image[rows]
+    np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(image, dtype=np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts, dtype=np.float64))
 
 
 def pmc_record(config, kernel):
@@ -209,19 +234,27 @@ def main():
 
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     agg = torch.tensor([float(sum(s.segments for s in stats)), float(sum(s.samples for s in stats)),
-                        float(sum(s.shadow_rays for s in stats))], dtype=torch.float64, device=dev)
+                        float(sum(s.shadow_rays for s in stats)),
+                        float(stats[-1].samples), float(stats[-1].segments), float(stats[-1].shadow_rays)], dtype=torch.float64, device=dev)
     if host_gather:
         t, agg = t.cpu(), agg.cpu()
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(agg, op=dist.ReduceOp.SUM)
     dt_max = float(t.item())
-    segments, samples, shadow = (float(x) for x in agg.tolist())
+    segments, samples, shadow, *last_counts = (float(x) for x in agg.tolist())
 
-    if args.check and rank == 0:
+    def full_frame():
+        """rank 0: the frame of the last step, row shards re-interleaved, on the host"""
         full = torch.empty((HEIGHT, WIDTH, 4), dtype=torch.float32)
         for g in range(world):
             full[g::world] = (gathered[g] if use_dist else tile)[: n_rows[g]].cpu()
+        return full
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full_frame().numpy(), last_counts)
+    if args.check and rank == 0:
+        full = full_frame()
         alone = torch.zeros((HEIGHT, WIDTH, 4), dtype=torch.float32, device=dev)
         r.render_device(abi.make_params(WIDTH, HEIGHT, args.spp, DEPTH, seed=SEED, rng_kind=args.rng), alone.data_ptr(), stream)
         torch.cuda.synchronize(dev)
@@ -325,7 +358,7 @@ def main():
                        "pipeline": PIPELINES["k_path" if in_regs else "wavefront"]},
             "roofline": roof,
         }
-        if world == 1:
+        if world == 1 and args.full:
             # what a plain device-to-device copy of 2 GiB reaches on this very GPU, measured after the timed region:
             # the practical ceiling for a read+write stream, to read the fractions of the 8 TB/s spec peak against
             try:
@@ -342,7 +375,7 @@ def main():
             except Exception as ex:  # measurement aid only
                 line["roofline"]["device_copy_GBps"] = None
                 print(f"[bench] device copy probe failed: {ex}", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(blob, abi, cfg)
         print(json.dumps(line), flush=True)
     r.close()

@@ -2,7 +2,7 @@
 # usage (on the GPU box, through gpurun): bash scripts/profile_round2.sh r02 -> gpurun_out/profile_<tag>/
 #   1. rocprofv3 --kernel-trace --stats of the default bench command (kernel_stats.csv + the JSON line of that run)
 #   2. rocprofv3 --pmc passes (one per counter group, never combined with tracing) of k_path on the metric scene
-#   3. a plain bench.py run (with cpu_baseline) and scripts/bench_configs.py
+#   3. a bench.py --full run (with cpu_baseline) and scripts/bench_configs.py
 set -e
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -17,7 +17,7 @@ echo "trace done"
 bash scripts/pmc_kernel.sh ${TAG}_k_path k_path 0 1920 1080 256 50 > $OUT/pmc_k_path.log 2>&1
 cp gpurun_out/pmc_${TAG}_k_path/summary.json $OUT/pmc_k_path.json
 echo "pmc done"
-timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 timeout -k 10 600 python3 scripts/bench_configs.py > $OUT/bench_configs.jsonl 2> $OUT/bench_configs.err
 echo "configs done"

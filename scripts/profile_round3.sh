@@ -4,7 +4,7 @@
 #      line of the SAME run, whose roofline.avg_launch_us must agree with the CSV's AverageNs of that kernel)
 #   2. rocprofv3 --pmc passes (scripts/pmc_all.sh: one pass per counter group, never combined with tracing) of every kernel of one
 #      warm-up-free render of the metric scene (k_path), scene 1 (k_first / k_trace_bvh / k_shade) and scene 3 (k_path, cold)
-#   3. plain bench.py runs (with cpu_baseline) of the headline and of configs c2, c3, c4
+#   3. bench.py --full runs (with cpu_baseline) of the headline and of configs c2, c3, c4
 #   4. kernel-trace statistics of scenes 1, 2, 4 with the per-kernel units beside them (scripts/profile_scene.sh)
 # `quick`: steps 1 (c3 only), 2 (scene 1 only) and the c3 bench line
 set -e
@@ -52,10 +52,10 @@ pmc scene1 1 1920 1080 256 50
 if [ -z "$QUICK" ]; then
   pmc headline 0 1920 1080 256 50
   pmc scene3 3 1920 1080 256 50
-  timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench done"
-  for c in c2 c4; do timeout -k 10 600 python3 bench.py --config $c --steps 4 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; echo "bench $c done"; done
+  timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench done"
+  for c in c2 c4; do timeout -k 10 600 python3 bench.py --full --config $c --steps 4 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; echo "bench $c done"; done
 fi
-timeout -k 10 600 python3 bench.py --config c3 --steps 6 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench c3 done"
+timeout -k 10 600 python3 bench.py --full --config c3 --steps 6 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench c3 done"
 if [ -z "$QUICK" ]; then
   for sc in "s1 1 1920 1080 512 50" "s2 2 1920 1080 256 50" "s4 4 1920 1080 128 50"; do
     set -- $sc

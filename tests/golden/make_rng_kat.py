@@ -30,5 +30,9 @@ for seed in (0x6314759, 0x314759, 1, 0xFFFFFFFF, 0xDEADBEEF):
     kat["xorshift32"][str(seed)] = [lib.ref_xorshift32(C.byref(s)) for _ in range(16)]
     s = C.c_uint32(seed)
     kat["randf"][str(seed)] = [float.hex(lib.ref_randf(C.byref(s))) for _ in range(16)]
+# the sweep of tests/test_oracle_rng.py::test_oracle_rng_against_live_reference_build, recorded so that it runs without the build
+kat["tea64_frame"] = [[px, smp, lib.ref_tea64(px, smp)] for px in range(0, 2073600, 50021) for smp in (0, 1, 4095)]
+s = C.c_uint32(0xC0FFEE)
+kat["randf_c0ffee"] = [float.hex(lib.ref_randf(C.byref(s))) for _ in range(2000)]
 json.dump(kat, open(os.path.join(ROOT, "tests", "golden", "rng_kat.json"), "w"), indent=1)
 print("wrote rng_kat.json")

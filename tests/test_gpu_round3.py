@@ -174,6 +174,19 @@ def test_bench_other_baseline_configs(config, kernel):
     assert d["roofline"]["per_kernel"] and d["config"]["Msegments_per_s"] > 0
 
 
+def test_bench_dump_outputs_are_the_last_steps_frame(gpu, tmp_path):
+    """--dump-outputs DIR: the frame and counts the timed path computed in its last step are the C ABI's render of the same
+    workload; a plain run carries no CPU baseline and no copy probe (those are --full's)."""
+    d = run_bench(["--config", "c2", "--steps", "3", "--warmup", "0", "--spp", "8", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert "cpu_baseline" not in d and "device_copy_GBps" not in d["roofline"]
+    img, counts = np.load(tmp_path / "image.npy"), np.load(tmp_path / "counts.npy")
+    assert img.dtype == np.float32 and counts.dtype == np.float64 and not (tmp_path / "image_rows.npy").exists()
+    gpu.upload_scene(abi.build_scene(0, 800, 800))
+    want, st = gpu.render(abi.make_params(800, 800, 8, 50, seed=0x6314759))
+    assert np.array_equal(img, want) and tuple(counts) == (st.samples, st.segments, st.shadow_rays)
+
+
 def test_faults_inside_the_library_become_error_codes(monkeypatch):
     """The C ABI's exception barrier (include/rtw.h) with the fault where it would really happen: a std::bad_alloc in the
     middle of rtw_upload_scene (host vectors built, device not yet touched) and one inside a group's worker thread. Either

@@ -1,7 +1,7 @@
 """The host's own baseline JPEG decoder (raytracing_weekend_amd/host/JpegDecode.h, SURVEY 8f rank 1 "stb image load") against
 Pillow's decoder (libjpeg-turbo) on files written here: every chroma layout, grey, odd sizes, restart intervals, quality
 levels. Decoders may differ by rounding in the inverse DCT and the colour conversion; chroma upsampling adds a little where
-chroma is subsampled. The reference's own asset is decoded too where the reference tree is present. CPU only."""
+chroma is subsampled. The reference's own asset (assets/earthmap.jpg, stored as tests/golden/earthmap.jpg) is decoded too. CPU only."""
 import ctypes as C
 import io
 import os
@@ -122,16 +122,14 @@ def test_truncated_scan_and_header_bombs_are_refused():
 
 
 def test_reference_asset_decodes_like_pillow():
-    path = "/root/reference/RestOfLife/assets/earthmap.jpg"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "earthmap.jpg")
     data = open(path, "rb").read()
     got = decode(data)
     ref = np.asarray(PIL.open(path).convert("RGB"))
     assert got.shape == ref.shape == (512, 1024, 3)
     d = np.abs(got.astype(int) - ref.astype(int))
     assert d.max() <= 3 and d.mean() < 0.5
-    # and through the scene description: with RTW_ASSET_DIR pointing at the reference's assets, scene 2's image texture is that file
+    # and through the scene description: with RTW_ASSET_DIR pointing at the asset's directory, scene 2's image texture is that file
     os.environ["RTW_ASSET_DIR"] = os.path.dirname(path)
     try:
         parts = abi.parse_scene(abi.build_scene(2, 32, 32))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RTW_ABI_VERSION 2   /* entry points and the structs they take (rtw_params, rtw_stats) */
+#define RTW_ABI_VERSION 3   /* entry points and the structs they take (rtw_params, rtw_stats, rtw_guides) */
 #define RTW_SCENE_VERSION 1 /* layout of the scene blob (rtw_scene_header.version) */
 #define RTW_SCENE_MAGIC 0x57545221u /* "!RTW" */
 /* Summation order of a pixel's samples (part of the arithmetic contract). Three levels, all counted from
@@ -306,6 +306,46 @@ const char* rtw_last_error(rtw_ctx* ctx);
  * alias; alpha is copied. Meant for display-encoded values in [0, 1] (the reference's LDR model sees sqrt(colour));
  * not part of rtw_render: 4096-spp frames need none. iterations in 1..8, sigma > 0. */
 int rtw_denoise(rtw_ctx* ctx, const float* rgba_in, float* rgba_out, int32_t width, int32_t height, int32_t iterations, float sigma);
+
+/* Guide buffers (AOVs) of the first hit, for denoisers and compositing (the guide layers - albedo, normal - that the OptiX
+ * denoiser under the reference's Director::initDenoiser, Director.cpp:887-949, accepts and the reference never fills).
+ * Every pointer is host memory of the shard's rows*width pixels (same rows, same order as rtw_render's output), or NULL
+ * for a buffer the caller does not want. */
+typedef struct rtw_guides {
+    float* albedo;  /* rows*width float4: mean first-hit albedo; alpha = fraction of the samples that hit something      */
+    float* normal;  /* rows*width float4: mean first-hit world-space shading normal (not renormalised); alpha as albedo */
+    float* depth;   /* rows*width float: t * |d| of sample sample_offset's camera ray (distance to the hit), +inf: miss */
+    int32_t* prim;  /* rows*width int32: primitive index hit by sample sample_offset's camera ray, -1: miss            */
+} rtw_guides;
+
+/* First-hit guides of samples [sample_offset, sample_offset+spp) of the rows rtw_render would render with the same params.
+ *   Rays: the same camera rays as rtw_render (raygen: jitter, lens sample, ray time and gather time from the same draws
+ *     of the same generator, row0 / row1 / row_stride / seed / rng_kind honoured), so guide edges line up with the beauty's.
+ *     max_depth, estimator and samples_per_pass are ignored; the ray starts at the reference's 1e-6.
+ *   Normal: the world-space shading normal at the first hit, exactly the vector the closest-hit code hands to the material
+ *     (the one RTW_MAT_NORMAL turns into a colour): rectangles +-axis by their flip flag, spheres (p - c) / r.
+ *   Albedo: lambertian, metal, isotropic: the texture value at the hit (the shading code's texture evaluation, same
+ *     arguments); dielectric: (1,1,1); normal material: its colour n * 0.5 + 0.5 (fma); diffuse light: the emitted value
+ *     under the shading code's front-face rule (dot(n, d) < 0; 0 on the back), clamped to [0,1].
+ *   Means: albedo and normal are summed over the samples in the summation order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS
+ *     (plain ascending order for spp <= 16), then divided by spp. A miss adds 0 (the sky is not a hit).
+ *   Depth and prim come from the first sample (sample_offset) alone; a miss gives depth +inf, prim -1.
+ *   Participating media are transparent to the guides (volume primitives are skipped): a medium's first scatter is random
+ *     and a guide must not be noisy.
+ *   Groups (n_devices > 1): the guides are rendered on device_ids[0]; the bits are those of a single-device context.
+ *   Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for bad params or when all four pointers are NULL.
+ *   stats (may be NULL): samples = segments = rows*width*spp (one camera segment per sample), seconds = device time. */
+int rtw_render_guides(rtw_ctx* ctx, const rtw_params* params, const rtw_guides* out, rtw_stats* stats);
+
+/* rtw_denoise steered by guides (edge-avoiding a-trous with albedo and normal edge-stopping, Dammertz et al. 2010): the
+ * same 25 taps, tap order, border clamp, B3 kernel and colour weight as rtw_denoise, the colour weight then divided by
+ * (1 + |a_p - a_q|^2 / sigma_albedo^2) and by (1 + |n_p - n_q|^2 / sigma_normal^2), squared norms summed as
+ * (x^2 + y^2) + z^2 over the first three channels. The colour sigma halves per pass as in rtw_denoise; the guide sigmas
+ * stay fixed. With constant guides both divisors are exactly 1 and the result is bit-identical to rtw_denoise.
+ * rgba_in, albedo, normal, rgba_out: host, width*height float4 (albedo and normal as rtw_render_guides writes them);
+ * rgba_out may alias none of them; alpha is copied. iterations in 1..8; sigma, sigma_albedo, sigma_normal > 0. */
+int rtw_denoise_guided(rtw_ctx* ctx, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out,
+                       int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal);
 
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.

@@ -14,7 +14,7 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 HOST_LIB = os.path.join(PKG_DIR, "host", "librtw_host.so")
 HIP_LIB = os.environ.get("RTW_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "librtw_hip.so")
 
-RTW_ABI_VERSION = 2
+RTW_ABI_VERSION = 3
 RTW_SCENE_VERSION = 1
 RTW_SCENE_MAGIC = 0x57545221
 RTW_RNG_PHILOX = 0
@@ -95,8 +95,16 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class Guides(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
-               "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise"]
+               "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided"]
+GUIDES = ("albedo", "normal", "depth", "prim")
+# Default edge-stopping sigmas of Renderer.denoise_guided (see there)
+DENOISE_SIGMA_ALBEDO = 0.4
+DENOISE_SIGMA_NORMAL = 0.5
 
 _host = None
 _hip = None
@@ -137,6 +145,11 @@ def load_hip():
         lib.rtw_last_error.argtypes = [C.c_void_p]
         lib.rtw_denoise.restype = C.c_int
         lib.rtw_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]
+        lib.rtw_render_guides.restype = C.c_int
+        lib.rtw_render_guides.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Guides), C.POINTER(Stats)]
+        lib.rtw_denoise_guided.restype = C.c_int
+        lib.rtw_denoise_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_float, C.c_float]
         lib.rtw_debug_intersect.restype = C.c_int
         lib.rtw_debug_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
@@ -262,6 +275,46 @@ class Renderer:
         h, w = src.shape[:2]
         out = np.empty_like(src)
         self._check(self.lib.rtw_denoise(self.ctx, src.ctypes.data, out.ctypes.data, w, h, iterations, sigma), "rtw_denoise")
+        return out
+
+    def render_guides(self, params, which=GUIDES, stats=None):
+        """rtw_render_guides: first-hit guide buffers of the rows `params` renders, as a dict of the requested names:
+        albedo and normal (rows, w, 4) float32 (alpha = fraction of the samples that hit), depth (rows, w) float32,
+        prim (rows, w) int32. `stats`: a Stats to fill, or None."""
+        which = tuple(which)
+        bad = [k for k in which if k not in GUIDES]
+        if bad or not which:
+            raise ValueError(f"render_guides: unknown or no guide names {bad or which}")
+        rows = local_rows(params)
+        shapes = {"albedo": ((rows, params.width, 4), np.float32), "normal": ((rows, params.width, 4), np.float32),
+                  "depth": ((rows, params.width), np.float32), "prim": ((rows, params.width), np.int32)}
+        out = {k: np.empty(*shapes[k]) for k in which}
+        g = Guides(**{k: v.ctypes.data for k, v in out.items()})
+        self._check(self.lib.rtw_render_guides(self.ctx, C.byref(params), C.byref(g), None if stats is None else C.byref(stats)),
+                    "rtw_render_guides")
+        return out
+
+    def denoise_guided(self, img, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=DENOISE_SIGMA_ALBEDO,
+                       sigma_normal=DENOISE_SIGMA_NORMAL):
+        """rtw_denoise_guided on an (h, w, 4) float32 image with (h, w, 3 or 4) albedo and normal guides; returns the
+        filtered image. The colour sigma is rtw_denoise's (display-encoded input in [0, 1]). The default guide sigmas,
+        0.4 for the albedo and 0.5 for the normal, are the best of a sweep (scripts/guide_sweep.py: sigma_albedo
+        0.05 ... 1, sigma_normal 0.1 ... 1) on 8-spp display-encoded renders of scenes 0 and 2 at 256 x 256 against
+        1024-spp references: RMSE 4.5 % (scene 0) and 1.8 % (scene 2) below the colour-only filter's."""
+        src = np.ascontiguousarray(img, dtype=np.float32)
+        h, w = src.shape[:2]
+
+        def guide(g):
+            g = np.asarray(g, dtype=np.float32)
+            if g.shape[:2] != (h, w) or g.ndim != 3 or g.shape[2] not in (3, 4):
+                raise ValueError(f"denoise_guided: guide of shape {g.shape} for a {h}x{w} image")
+            if g.shape[2] == 3:
+                g = np.concatenate([g, np.zeros((h, w, 1), np.float32)], axis=2)
+            return np.ascontiguousarray(g)
+        a, n = guide(albedo), guide(normal)
+        out = np.empty_like(src)
+        self._check(self.lib.rtw_denoise_guided(self.ctx, src.ctypes.data, a.ctypes.data, n.ctypes.data, out.ctypes.data, w, h,
+                                                iterations, sigma, sigma_albedo, sigma_normal), "rtw_denoise_guided")
         return out
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):

@@ -42,6 +42,10 @@
 #include "rtw_bvh.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"
+#include "rtw_guides.h"
+#ifndef RTW_SPLIT_BUILD
+#include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
+#endif
 
 using namespace rtwdev;
 using namespace rtwk;
@@ -1659,6 +1663,110 @@ int impl_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t widt
     return RTW_OK;
 }
 
+// rtw.h rtw_render_guides: one k_guides launch on the context's device (a group's: device_ids[0], with that device's copy of the scene)
+int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = check_render_args(c, P);
+    if (rc) return rc;
+    if (!G || (!G->albedo && !G->normal && !G->depth && !G->prim)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_render_guides: no output buffer");
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    if (stats) memset(stats, 0, sizeof *stats);
+    const size_t rows = shard_rows(P);
+    const size_t npix = rows * (size_t)P->width;
+    if (npix == 0) return RTW_OK;
+    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_render_guides: tile too large");
+    HIP_TRY(c, hipSetDevice(d->device));
+    KArgs a{};
+    a.sc = d->sc;  // the uploaded scene as it is: the reference's ray tmin whatever P->estimator says
+    a.npix = (uint32_t)npix;
+    a.width = (uint32_t)P->width;
+    a.height = (uint32_t)P->height;
+    a.row0 = (uint32_t)P->row0;
+    a.row_stride = P->row_stride > 1 ? (uint32_t)P->row_stride : 1u;
+    a.seed = P->seed;
+    a.sample0 = (uint32_t)P->sample_offset;
+    a.spp = (uint32_t)P->spp;
+    a.stack_stride = kBlock;
+    // one device allocation: albedo, normal (16 B per pixel each), depth, prim (4 B each), whichever were asked for
+    const size_t sz[4] = {G->albedo ? npix * 16 : 0, G->normal ? npix * 16 : 0, G->depth ? npix * 4 : 0, G->prim ? npix * 4 : 0};
+    size_t off[5] = {0};
+    for (int k = 0; k < 4; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
+    char* slab = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto cleanup = [&]() {
+        if (slab) (void)hipFree(slab);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    };
+    hipError_t e = hipMalloc(&slab, off[4]);
+    if (e != hipSuccess) { slab = nullptr; return fail(c, RTW_ERR_OOM, "rtw_render_guides: device allocation failed"); }
+    GuideOut g;
+    g.albedo = sz[0] ? (float4*)(slab + off[0]) : nullptr;
+    g.normal = sz[1] ? (float4*)(slab + off[1]) : nullptr;
+    g.depth = sz[2] ? (float*)(slab + off[2]) : nullptr;
+    g.prim = sz[3] ? (int32_t*)(slab + off[3]) : nullptr;
+    g.rng_kind = P->rng_kind;
+    if (stats) {
+        e = hipEventCreate(&ev[0]);
+        if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+        if (e == hipSuccess) e = hipEventRecord(ev[0], d->stream);
+    }
+    const unsigned grid = (unsigned)std::min<size_t>((npix + kBlock - 1) / kBlock, (size_t)d->n_cu * 8);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_guides, dim3(grid), dim3(kBlock), d->lds_bytes, d->stream, a, g);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && stats) e = hipEventRecord(ev[1], d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    void* dst[4] = {G->albedo, G->normal, G->depth, G->prim};
+    for (int k = 0; k < 4 && e == hipSuccess; k++)
+        if (sz[k]) e = hipMemcpy(dst[k], slab + off[k], sz[k], hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stats) {
+        float ms = 0.f;
+        e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        stats->samples = stats->segments = (uint64_t)npix * (uint64_t)P->spp;
+        stats->seconds = ms * 1e-3;
+    }
+    cleanup();
+    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_render_guides: ") + hipGetErrorString(e));
+    return RTW_OK;
+}
+
+// rtw.h rtw_denoise_guided: rtw_denoise's passes with k_atrous_guided
+int impl_denoise_guided(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, int32_t width, int32_t height,
+                        int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    const float inv_a = 1.0f / (sigma_albedo * sigma_albedo), inv_n = 1.0f / (sigma_normal * sigma_normal);
+    if (!rgba_in || !albedo || !normal || !rgba_out || rgba_out == rgba_in || rgba_out == albedo || rgba_out == normal || width <= 0 ||
+        height <= 0 || iterations < 1 || iterations > 8 || !(sigma > 0.f) || !(sigma_albedo > 0.f) || !(sigma_normal > 0.f) ||
+        !std::isfinite(inv_a) || !std::isfinite(inv_n) || (int64_t)width * height > (1 << 28))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise_guided: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};  // ping, pong, albedo, normal
+    auto cleanup = [&]() { for (float4* p : d) if (p) (void)hipFree(p); };
+    for (int k = 0; k < 4; k++)
+        if (hipMalloc(&d[k], bytes) != hipSuccess) { d[k] = nullptr; cleanup(); return fail(c, RTW_ERR_OOM, "rtw_denoise_guided: device allocation failed"); }
+    hipError_t e = hipMemcpyAsync(d[0], rgba_in, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d[2], albedo, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d[3], normal, bytes, hipMemcpyHostToDevice, c->stream);
+    const int n = width * height;
+    const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)n + kBlock - 1) / kBlock, (int64_t)c->n_cu * 8);
+    int cur = 0;
+    float s_i = sigma;
+    for (int it = 0; it < iterations && e == hipSuccess; it++) {
+        hipLaunchKernelGGL(k_atrous_guided, dim3(grid), dim3(kBlock), 0, c->stream, (const float4*)d[cur], (const float4*)d[2], (const float4*)d[3],
+                           d[cur ^ 1], (int)width, (int)height, 1 << it, 1.0f / (s_i * s_i), inv_a, inv_n);
+        e = hipGetLastError();
+        cur ^= 1;
+        s_i = s_i * 0.5f;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, d[cur], bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    cleanup();
+    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_denoise_guided: ") + hipGetErrorString(e));
+    return RTW_OK;
+}
+
 int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, int n, float* out_t, int32_t* out_prim) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, "no scene");
@@ -1715,6 +1823,13 @@ int rtw_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t width
 }
 int rtw_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, int n, float* out_t, int32_t* out_prim) {
     return guarded(c, [&] { return impl_debug_intersect(c, rays, ray_time, gather_time, n, out_t, out_prim); });
+}
+int rtw_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_render_guides(c, P, out, stats); });
+}
+int rtw_denoise_guided(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, int32_t width, int32_t height,
+                       int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
+    return guarded(c, [&] { return impl_denoise_guided(c, rgba_in, albedo, normal, rgba_out, width, height, iterations, sigma, sigma_albedo, sigma_normal); });
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <fstream>
 #include <iostream>
 
+#include "PfmWriter.h"
 #include "SceneMarshal.h"
 
 namespace {
@@ -65,6 +66,21 @@ void Director::renderFrame() {
     p.estimator = m_estimator;
     int rc = rtw_render(m_ctx, &p, m_hostBuffer.data(), &m_stats);
     if (rc != RTW_OK) die(m_ctx, "rtw_render", rc);
+    const bool guidedDenoise = m_guided && m_denoiseIterations > 0;
+    if (!m_aovPrefix.empty() || guidedDenoise) {
+        // the guide layers the reference's OptiX denoiser could take (Director.cpp:887-949 sets up the beauty layer alone)
+        const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
+        m_albedo.assign(npix * 4, 0.f);
+        m_normal.assign(npix * 4, 0.f);
+        m_depth.assign(npix, 0.f);
+        rtw_params g = p;
+        g.spp = m_guideSpp > 0 ? m_guideSpp : std::min(m_Ns, 16);
+        rtw_guides out{m_albedo.data(), m_normal.data(), m_depth.data(), nullptr};
+        rtw_stats gs{};
+        rc = rtw_render_guides(m_ctx, &g, &out, &gs);
+        if (rc != RTW_OK) die(m_ctx, "rtw_render_guides", rc);
+        if (_verbose) std::cerr << "INFO: guides: " << g.spp << " spp in " << gs.seconds << " s on the GPU" << std::endl;
+    }
     if (m_denoiseIterations > 0) {
         // Director.cpp:986-997: the denoiser pass closes the frame. The reference feeds its LDR model the display-encoded
         // image (raygen.cu:151-155 writes sqrt(colour)); the stand-in filters the same encoding, clamped to [0, 1], and
@@ -75,8 +91,14 @@ void Director::renderFrame() {
             if ((i & 3) != 3) { c = !(c == c) || c < 0.f ? 0.f : (c > 1.f ? 1.f : c); c = std::sqrt(c); }
             enc[i] = c;
         }
-        rc = rtw_denoise(m_ctx, enc.data(), filtered.data(), m_Nx, m_Ny, m_denoiseIterations, m_denoiseSigma);
-        if (rc != RTW_OK) die(m_ctx, "rtw_denoise", rc);
+        if (guidedDenoise) {
+            rc = rtw_denoise_guided(m_ctx, enc.data(), m_albedo.data(), m_normal.data(), filtered.data(), m_Nx, m_Ny, m_denoiseIterations,
+                                    m_denoiseSigma, kDenoiseSigmaAlbedo, kDenoiseSigmaNormal);
+            if (rc != RTW_OK) die(m_ctx, "rtw_denoise_guided", rc);
+        } else {
+            rc = rtw_denoise(m_ctx, enc.data(), filtered.data(), m_Nx, m_Ny, m_denoiseIterations, m_denoiseSigma);
+            if (rc != RTW_OK) die(m_ctx, "rtw_denoise", rc);
+        }
         for (size_t i = 0; i < enc.size(); i++) m_hostBuffer[i] = (i & 3) != 3 ? filtered[i] * filtered[i] : filtered[i];
     }
     if (_verbose) {
@@ -136,18 +158,14 @@ bool Director::writeBinaryPPM(const std::string& path) const {
 }
 
 bool Director::writePFM(const std::string& path) const {
-    std::ofstream f(path, std::ios::binary);
-    if (!f) return false;
-    f << "PF\n" << m_Nx << " " << m_Ny << "\n-1.0\n";  // negative scale = little-endian; PFM rows run bottom-up
-    std::vector<float> row(static_cast<size_t>(m_Nx) * 3);
-    for (int j = 0; j < m_Ny; j++) {
-        for (int i = 0; i < m_Nx; i++) {
-            const float* px = &m_hostBuffer[(static_cast<size_t>(m_Nx) * j + i) * 4];
-            row[3 * i] = px[0]; row[3 * i + 1] = px[1]; row[3 * i + 2] = px[2];
-        }
-        f.write(reinterpret_cast<const char*>(row.data()), static_cast<std::streamsize>(row.size() * sizeof(float)));
-    }
-    return static_cast<bool>(f);
+    return rtwhost::writePfm(path, m_hostBuffer.data(), m_Nx, m_Ny, 4, 3);  // linear radiance, little-endian, rows bottom-up
+}
+
+bool Director::writeGuides(const std::string& prefix) const {
+    if (m_albedo.empty()) return false;
+    return rtwhost::writePfm(prefix + "_albedo.pfm", m_albedo.data(), m_Nx, m_Ny, 4, 3) &&
+           rtwhost::writePfm(prefix + "_normal.pfm", m_normal.data(), m_Nx, m_Ny, 4, 3) &&
+           rtwhost::writePfm(prefix + "_depth.pfm", m_depth.data(), m_Nx, m_Ny, 1, 1);
 }
 
 // PNG without a compression library: zlib stream of stored deflate blocks (the reference vendors stb_image_write.h for

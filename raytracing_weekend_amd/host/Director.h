@@ -12,6 +12,11 @@
 
 class Director {
 public:
+    // edge-stopping sigmas of the guided denoiser (the defaults of raytracing_weekend_amd.abi.Renderer.denoise_guided, where they
+    // are measured)
+    static constexpr float kDenoiseSigmaAlbedo = 0.4f;
+    static constexpr float kDenoiseSigmaNormal = 0.5f;
+
     Director(bool verbose, bool debug) : _verbose(verbose), _debug(debug) {}
 
     void init(unsigned int width, unsigned int height, unsigned int samples);
@@ -38,6 +43,11 @@ public:
     // the reference's renderFrame ends with the OptiX AI denoiser (Director.cpp:986-997); iterations > 0 runs the
     // a-trous stand-in (rtw_denoise) on the frame instead
     void setDenoise(int iterations, float sigma) { m_denoiseIterations = iterations; m_denoiseSigma = sigma; }
+    // guide buffers (rtw_render_guides) of `spp` samples (0: min(Ns, 16)), rendered by renderFrame when an -aov prefix is set or the
+    // denoiser is guided; guided: the denoiser pass is rtw_denoise_guided, steered by the albedo and normal guides
+    void setGuides(const std::string& aovPrefix, int spp, bool guided) { m_aovPrefix = aovPrefix; m_guideSpp = spp; m_guided = guided; }
+    // PREFIX_albedo.pfm, PREFIX_normal.pfm (PF, rgb) and PREFIX_depth.pfm (Pf), rows bottom-up as writePFM
+    bool writeGuides(const std::string& prefix) const;
     const rtw_stats& stats() const { return m_stats; }
     const std::vector<float>& hostBuffer() const { return m_hostBuffer; }  // linear RGBA, row 0 = bottom row
 
@@ -53,6 +63,10 @@ private:
     int m_cameraKind = RTW_CAM_PERSPECTIVE;
     int m_denoiseIterations = 0;
     float m_denoiseSigma = 0.5f;
+    std::string m_aovPrefix;
+    int m_guideSpp = 0;
+    bool m_guided = false;
+    std::vector<float> m_albedo, m_normal, m_depth;  // guide buffers of the last renderFrame (empty when none were rendered)
     rtw_ctx* m_ctx = nullptr;
     rtwhost::ioScene m_scene;
     std::vector<float> m_hostBuffer;

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <new>
 
+#include "PfmWriter.h"
 #include "SceneMarshal.h"
 
 // No exception crosses these entry points (the scene description allocates: std::vector, std::string, texture decode)
@@ -51,6 +52,16 @@ int rtw_host_decode_jpeg(const void* data, size_t size, int* width, int* height,
     if (!rgb || cap < out.size()) return RTW_ERR_OOM;
     memcpy(rgb, out.data(), out.size());
     return RTW_OK;
+    RTW_HOST_GUARD_END
+}
+
+// The Director's PFM writer (PfmWriter.h: the beauty file and the -aov guide files), for the tests: width*height pixels of
+// `stride` floats, rows bottom-up, the first `channels` (1 or 3) written. Returns 0, RTW_ERR_INVALID_ARG, or RTW_ERR_DEVICE
+// when the file cannot be written.
+int rtw_host_write_pfm(const char* path, const float* data, int width, int height, int stride, int channels) {
+    RTW_HOST_GUARD_BEGIN
+    if (!path || !data || width <= 0 || height <= 0 || (channels != 1 && channels != 3) || stride < channels) return RTW_ERR_INVALID_ARG;
+    return rtwhost::writePfm(path, data, width, height, stride, channels) ? RTW_OK : RTW_ERR_DEVICE;
     RTW_HOST_GUARD_END
 }
 }

@@ -62,6 +62,9 @@ int main(int argc, char* argv[]) {
     -est K         reference (default: the reference's estimator, quirks included), corrected, brute
                    (corrected without light sampling) or mixture (the book's 50/50 mixture of light and cosine sampling)
     -cam K         perspective (default), environment or orthographic (the reference's two unused camera kinds, scene/ioCamera.h:118-179)
+    -guided        With -denoise: steer the filter with the albedo and normal guides (rtw_denoise_guided)
+    -aov PREFIX    Also write the guide buffers: PREFIX_albedo.pfm, PREFIX_normal.pfm (PF) and PREFIX_depth.pfm (Pf)
+    -guide_spp N   Samples per pixel of the guide buffers (default: min(Ns, 16))
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -118,6 +121,10 @@ int main(int argc, char* argv[]) {
     director.setRngKind(rng);
     director.setEstimator(estimator);
     if (intOption(cl_input, "-denoise", "denoise passes", x)) director.setDenoise(clampWarn("Denoise passes", x, 0, 8), 0.5f);
+    const std::string& aovPrefix = cl_input.getCmdOption("-aov");
+    int guideSpp = 0;
+    if (intOption(cl_input, "-guide_spp", "guide samples (-guide_spp)", x)) guideSpp = clampWarn("Guide samples (-guide_spp)", x, 1, Ns_MAX);
+    director.setGuides(aovPrefix, guideSpp, cl_input.cmdOptionExists("-guided"));
 
     auto start = std::chrono::system_clock::now();
     director.init(Nx, Ny, Ns);
@@ -142,6 +149,11 @@ int main(int argc, char* argv[]) {
             director.destroy();
             return EXIT_FAILURE;
         }
+    }
+    if (!aovPrefix.empty() && !director.writeGuides(aovPrefix)) {
+        std::cerr << "ERROR: cannot write the guide files " << aovPrefix << "_*.pfm" << std::endl;
+        director.destroy();
+        return EXIT_FAILURE;
     }
     director.destroy();
     return EXIT_SUCCESS;

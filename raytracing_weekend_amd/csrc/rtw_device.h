@@ -585,7 +585,7 @@ RTW_DEV bool prim_test(const rtw_prim& pr, v3 oo, v3 dd, v3 inv, float tmin, flo
     }
 }
 
-// ---- tree walk, shared by traverse<> and the refilling trace kernels (rtw_kernels.h k_trace_bvh, k_path_tree) ----
+// ---- tree walk, shared by traverse<> and the refilling trace kernels (rtw_kernels.h k_trace_bvh) ----
 
 // sp is the byte offset of the top of this thread's stack column (0 = empty). A pop never branches: under the stack
 // lies a row that says "nothing left" (16-bit entries are sign-extended, so 0xffff reads as kBvhDone; references stay

@@ -20,6 +20,9 @@
 //   k_finish (once)               mean radiance -> float4 framebuffer tile
 //   n_devices > 1: one host thread + context per device, interleaved row shards, peer-copy gather, k_interleave
 //
+// render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
+// (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU).
+//
 // No OptiX, no CUDA shims, no Triton, no MFMA (divergent scalar fp32). Results do not depend on
 // scheduling: every path owns a counter-based RNG stream and every (pixel, block) its own sum.
 #include <hip/hip_runtime.h>
@@ -41,6 +44,7 @@
 #include "../../include/rtw.h"
 #include "rtw_bvh.h"
 #include "rtw_device.h"
+#include "rtw_plan.h"
 #include "rtw_kernels.h"
 #include "rtw_guides.h"
 #ifndef RTW_SPLIT_BUILD
@@ -68,8 +72,6 @@ extern template __global__ void k_classify<true>(const KArgs, uint32_t*, uint32_
 extern template __global__ void k_classify<false>(const KArgs, uint32_t*, uint32_t*, uint32_t);
 }  // namespace rtwk
 #endif
-
-constexpr int kBruteMaxPrims = 24;  // at or below: scalar-cache brute lists; above: BVH with the LDS stack
 
 // =============================================================================================
 // host side of the library
@@ -119,7 +121,7 @@ struct rtw_ctx {
     std::vector<rtw_ctx*> kids;
     float4* stage = nullptr;
     size_t stage_pix = 0;
-    size_t pool_cap = ~(size_t)0;  // paths in flight this device has room for (halved when a pool allocation fails: render_single)
+    size_t pool_cap = ~(size_t)0;  // paths in flight this device has room for (halved when a pool allocation fails: render_wavefront)
     struct Worker* worker = nullptr;  // a kid's host thread: created with the group, lives until rtw_destroy
 };
 
@@ -248,139 +250,24 @@ int ensure_pool(rtw_ctx* c, int n_lanes, size_t paths, size_t npix, size_t cnt_w
     return RTW_OK;
 }
 
-// multiply-high constants for exact 32-bit division by an invariant d >= 1 (Granlund & Montgomery 1994)
-void magic_div(uint32_t d, uint32_t& m, uint32_t& s1, uint32_t& s2) {
-    uint32_t l = 0;
-    while (l < 32 && ((uint64_t)1 << l) < d) l++;
-    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
-    s1 = l < 1 ? l : 1;
-    s2 = l > 0 ? l - 1 : 0;
-}
-
-// Tuning knobs, read from the environment once per call site (defaults are what profiles/ was measured with):
-//   RTW_POOL_PATHS  paths in flight over all lanes (default 2^30: sized for 288 GB of HBM - a full-HD frame at 512+ spp takes 178 GB of
-//                   state without listed lights, 238 GB with; an allocation that fails is halved, see render_single. Round 3, BASELINE
-//                   config 3: 2^28 (8 batches of 64 spp) 6.7, 2^29 (4 x 128) 7.0, 2^30 (2 x 256) 7.3 Gsamples/s)
-//   RTW_LANES       stream lanes that overlap consecutive batches (default 2; 1..4)
-//   RTW_GRID_MULT   persistent workgroups per CU (default 8 with one lane, 4 with two)
-//   RTW_TAIL_START  first bounce handled by the fused multi-bounce tail launches (default 6; 20 for tree scenes, 40 for tree scenes with media)
-//   RTW_FUSED=1     every bounce through the fused k_bounce
-//   RTW_SPLIT_MEDIA=0  scenes with media: every bounce through k_bounce (default: split pipeline, volumes tested in the shading kernels)
-//   RTW_BRUTE_MAX   largest primitive count walked with the scalar-cache brute lists (default 24; 0 forces the BVH)
-//   RTW_LDS_KB      dynamic LDS per workgroup for traversal stacks + staged tree nodes (default 16)
-//   RTW_TAIL_GROUP  bounces per launch of the first tail group (default 2; groups grow by half every second launch)
-//   RTW_PAIRED=1    tree scenes, two lanes: batches run in pairs whose trace launches alternate, so that a k_trace_bvh always has the
-//                   other batch's k_shade beside it (measured 12 % slower than the free-running lanes: off; RTW_PAIRED_TRACE_WAVES
-//                   = waves per SIMD of the trace kernel in that mode, default 4)
-//   RTW_FIRST_GROUP_LOG2  k_first: 2^n neighbouring threads start samples of one pixel (default 3; 0 = one sample of 64 pixels per wave)
-//   RTW_STAGGER     how far the second lane starts behind the first, in percent of a batch (its first batch is cut short by that
-//                   much; 0 = no offset). Default: 50 for the candidate-list scenes under RTW_PATH=0, 0 for tree scenes (there the
-//                   extra batch costs more than the offset gains: scenes 1, 2, 4 +1-4 % at 512+ spp, +6-13 % at 128-256 spp)
-//   RTW_PATH        1 (default): scenes walked with the brute lists render through k_path (paths in registers, in-wave
-//                   regeneration); 0: always the wavefront pipeline
-//   RTW_PATH_TREE   1: tree scenes render through k_path_tree (k_path's idea with a per-lane walk state machine and a vote on the
-//                   kind of step; bit-identical, measured 25-45 % slower than the wavefront kernels on scenes 1, 2, 4); 0 (default): wavefront
-//   RTW_PATH_UNIT_BLOCKS 16-sample blocks a lane takes as one unit in the bulk launch (default: 8 = 128 samples when a lane has
-//                        600+ blocks to do, else 4)
-//   RTW_PATH_FINE_BLOCKS blocks at the end of a pass that a second, concurrent launch hands out one by one (default: 8 behind 8-block
-//                        units, 16 behind shorter ones)
-//   RTW_PATH_JOB_BLOCKS  units per pixel in one k_path job (default 2: a job is 64 pixels x 2 units)
-//   RTW_PATH_GRID_MULT   k_path workgroups per CU (default: what the occupancy query admits)
-//   RTW_BLOCKSUM_BYTES   cap of the k_path block-sum buffer (default 16 GiB); larger renders run in passes over the samples
-//   RTW_KERNEL_TIMING    0: no per-launch events even when the caller asks for rtw_stats (kernel_seconds stay 0)
-struct Tuning {
-    size_t pool_paths = (size_t)1 << 30;
-    int lanes = 2;
-    int grid_mult = 0;   // 0 = automatic
-    int tail_start = 0;  // 0 = automatic: 6 for the brute-list scenes, 20 for tree scenes (40 with media)
-    bool fused = false;
-    bool split_media = true;  // RTW_SPLIT_MEDIA=0: scenes with media keep every bounce in k_bounce
-    int brute_max = kBruteMaxPrims;
-    size_t lds_kb = 16;
-    int trace_block = 256;       // threads per workgroup of k_trace_bvh (256, 512, 1024)
-    size_t trace_lds_kb = 16;    // its LDS budget: stacks + tree nodes + leaf records
-    bool trace_auto = true;      // neither RTW_TRACE_BLOCK nor RTW_TRACE_LDS_KB given: the render picks the pair (see render_single)
-    int trace_waves = 5;         // waves per SIMD it is launched for (the kernel is compiled for 6: 78 VGPRs). 5 leaves a SIMD the 96 VGPRs of one
-                                 // wave of the other lane's k_shade; medians of 5 renders, 6 -> 5 -> 4: scene 1 7 242 / 7 285 / 7 072 Msamples/s,
-                                 // scene 2 3 593 / 3 664 / 3 646, scene 4 2 123 / 2 128 / 2 059 (profiles/r03_trace_waves_sweep.txt)
-    int stagger_pct = -1;  // -1 = automatic
-    int tail_group = 2;
-    bool paired = false;         // RTW_PAIRED=1: tree scenes, two lanes: the batches of a pair alternate their trace launches
-    int paired_trace_waves = 4;  // RTW_PAIRED_TRACE_WAVES: waves per SIMD of k_trace_bvh then (room for the other batch's k_shade)
-    int first_group_log2 = 3;    // k_first: up to 2^this neighbouring threads take samples of one pixel (RTW_FIRST_GROUP_LOG2; round 2: 16;
-                                 // round 3, with the wave-coherent walk: 8 (scene 1 medians of 5: 7 085 against 6 948-6 998 Msamples/s; 4: 7 091;
-                                 // 2: 7 066; 1: 7 011; scenes 2 and 4 do not care). Round 2's note on 16:
-                                 // k_first -6 ... -14 %; at 64 the later launches lose more - their finished paths then write
-                                 // 16-byte results npix apart - than k_first gains)
-    int path = 1;
-    int path_tree = 0;
-    int path_job_blocks = 2;
-    int path_unit_blocks = 0;    // 0 = automatic (8 for large renders, else 4)
-    int path_fine_blocks = -1;   // -1 = automatic (8 behind 8-block units, 16 behind shorter ones)
-    int path_grid_mult = 0;
-    size_t blocksum_bytes = (size_t)16 << 30;
-    bool kernel_timing = true;
-    bool verbose = false;  // RTW_VERBOSE=1: table sizes at upload (stderr)
-};
-Tuning read_tuning() {
-    Tuning t;
-    auto geti = [](const char* name, long long& out) {
-        const char* e = getenv(name);
-        if (!e || !*e) return false;
-        out = atoll(e);
-        return true;
-    };
-    long long v;
-    if (geti("RTW_POOL_PATHS", v) && v >= 1024) t.pool_paths = (size_t)v;
-    if (geti("RTW_LANES", v)) t.lanes = (int)std::max<long long>(1, std::min<long long>(4, v));
-    if (geti("RTW_GRID_MULT", v)) t.grid_mult = (int)std::max<long long>(1, v);
-    if (geti("RTW_TAIL_START", v)) t.tail_start = (int)std::max<long long>(1, v);
-    if (geti("RTW_FUSED", v)) t.fused = v == 1;
-    if (geti("RTW_SPLIT_MEDIA", v)) t.split_media = v != 0;
-    if (geti("RTW_BRUTE_MAX", v)) t.brute_max = (int)v;
-    if (geti("RTW_LDS_KB", v)) t.lds_kb = (size_t)std::max<long long>(0, v);
-    if (geti("RTW_TRACE_BLOCK", v) && (v == 256 || v == 512 || v == 1024)) { t.trace_block = (int)v; t.trace_auto = false; }
-    if (geti("RTW_TRACE_LDS_KB", v)) { t.trace_lds_kb = (size_t)std::max<long long>(0, std::min<long long>(150, v)); t.trace_auto = false; }
-    if (geti("RTW_TRACE_WAVES", v)) t.trace_waves = (int)std::max<long long>(1, std::min<long long>(8, v));
-    if (geti("RTW_TAIL_GROUP", v)) t.tail_group = (int)std::max<long long>(1, std::min<long long>(64, v));
-    if (geti("RTW_FIRST_GROUP_LOG2", v)) t.first_group_log2 = (int)std::max<long long>(0, std::min<long long>(8, v));
-    if (geti("RTW_PAIRED", v)) t.paired = v != 0;
-    if (geti("RTW_PAIRED_TRACE_WAVES", v)) t.paired_trace_waves = (int)std::max<long long>(1, std::min<long long>(8, v));
-    if (geti("RTW_STAGGER", v)) t.stagger_pct = (int)std::max<long long>(0, std::min<long long>(99, v));
-    if (geti("RTW_PATH", v)) t.path = (int)std::max<long long>(0, std::min<long long>(2, v));
-    if (geti("RTW_PATH_TREE", v)) t.path_tree = v != 0;
-    if (geti("RTW_PATH_JOB_BLOCKS", v)) t.path_job_blocks = (int)std::max<long long>(1, std::min<long long>(1024, v));
-    if (geti("RTW_PATH_UNIT_BLOCKS", v)) t.path_unit_blocks = (int)std::max<long long>(0, std::min<long long>(4096, v));
-    if (geti("RTW_PATH_FINE_BLOCKS", v)) t.path_fine_blocks = (int)std::max<long long>(-1, std::min<long long>(4096, v));
-    if (geti("RTW_PATH_GRID_MULT", v)) t.path_grid_mult = (int)std::max<long long>(1, std::min<long long>(16, v));
-    if (geti("RTW_BLOCKSUM_BYTES", v) && v >= (1 << 16)) t.blocksum_bytes = (size_t)v;
-    if (geti("RTW_KERNEL_TIMING", v)) t.kernel_timing = v != 0;
-    if (geti("RTW_VERBOSE", v)) t.verbose = v != 0;
-    return t;
-}
-
-// LDS of a tree-walking workgroup of `block` threads: the traversal stacks (16-bit entries unless a reference needs more),
-// then as many leading (breadth-first) tree nodes and, once all nodes are in, leaf records as fit `budget` bytes.
-size_t tree_lds_layout(size_t n_nodes_all, size_t n_leaves_all, int stack_depth, bool wide, size_t block, size_t budget, int32_t& n_nodes, int32_t& n_leaves) {
-    const size_t stack_words = wide ? (size_t)stack_depth * block : ((size_t)stack_depth * block + 1) / 2;
-    const size_t stack_bytes = ((stack_words + 3) & ~size_t(3)) * 4;
-    size_t room = budget > stack_bytes ? budget - stack_bytes : 0;
-    n_nodes = (int32_t)std::min<size_t>(n_nodes_all, room / sizeof(rtwbvh::Q4Node));
-    room -= (size_t)n_nodes * sizeof(rtwbvh::Q4Node);
-    n_leaves = (size_t)n_nodes == n_nodes_all ? (int32_t)std::min<size_t>(n_leaves_all, room / sizeof(rtwbvh::LeafRec)) : 0;
-    return stack_bytes + (size_t)n_nodes * sizeof(rtwbvh::Q4Node) + (size_t)n_leaves * sizeof(rtwbvh::LeafRec);
-}
-
 // k_trace_bvh's instantiation for a workgroup size and a tree (mode: see the kernel)
-typedef void (*TraceBvhKernel)(const KArgs);
+typedef void (*Kernel)(const KArgs);
 int trace_bvh_mode(const DScene& sc) { return sc.stack_wide ? 0 : sc.n_lds_nodes >= sc.n_nodes ? 2 : 1; }
-TraceBvhKernel trace_bvh_kernel(int block, int mode) {
+Kernel trace_bvh_kernel(int block, int mode) {
 #define RTW_TB(B_) (mode == 0 ? k_trace_bvh<B_, 0> : mode == 1 ? k_trace_bvh<B_, 1> : k_trace_bvh<B_, 2>)
     return block == 1024 ? RTW_TB(1024) : block == 512 ? RTW_TB(512) : RTW_TB(256);
 #undef RTW_TB
 }
 
-enum { LK_FIRST = RTW_K_FIRST, LK_SHADE = RTW_K_SHADE, LK_TRACE = RTW_K_TRACE, LK_BOUNCE = RTW_K_BOUNCE, LK_PATH = RTW_K_PATH, LK_PATH_TREE = RTW_K_COUNT };
+// k_path's instantiation: RNG kind x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator); media scenes
+// take the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5)
+Kernel path_kernel(int rng_kind, int feat, int n_vol) {
+#define RTW_PK(R_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1> : feat == 2 ? k_path<R_, 2> : feat == 1 ? k_path<R_, 1> : k_path<R_, 0>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG) : RTW_PK(RTW_RNG_PHILOX);
+#undef RTW_PK
+}
+
+// which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH
 void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock) {
     const bool lcg = rng_kind == RTW_RNG_TEA_LCG;
     // kernels that shade exist in six instantiations: RNG kind x feature level
@@ -396,24 +283,14 @@ void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipSt
         if (lcg) RTW_LAUNCH_SHADING_R(K_, LDS_, RTW_RNG_TEA_LCG); else RTW_LAUNCH_SHADING_R(K_, LDS_, RTW_RNG_PHILOX); \
     } while (0)
     switch (which) {
-    case LK_FIRST: RTW_LAUNCH_SHADING(k_first, lds); break;
-    case LK_SHADE: RTW_LAUNCH_SHADING(k_shade, 0); break;
-    case LK_TRACE:
+    case RTW_K_FIRST: RTW_LAUNCH_SHADING(k_first, lds); break;
+    case RTW_K_SHADE: RTW_LAUNCH_SHADING(k_shade, 0); break;
+    case RTW_K_TRACE:
         if (a.sc.use_bvh) hipLaunchKernelGGL(trace_bvh_kernel(block, trace_bvh_mode(a.sc)), dim3(grid), dim3(block), lds, s, a);
         else if (a.sc.n_generic == 0) hipLaunchKernelGGL((k_trace<true>), dim3(grid), dim3(kBlock), lds, s, a);
         else hipLaunchKernelGGL((k_trace<false>), dim3(grid), dim3(kBlock), lds, s, a);
         break;
-    case LK_PATH:
-        if (feat == 1 && a.sc.n_vol > 0) {  // media scenes: the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5)
-            if (lcg) hipLaunchKernelGGL((k_path<RTW_RNG_TEA_LCG, 1, 1>), dim3(grid), dim3(kBlock), lds, s, a);
-            else hipLaunchKernelGGL((k_path<RTW_RNG_PHILOX, 1, 1>), dim3(grid), dim3(kBlock), lds, s, a);
-        } else {
-            RTW_LAUNCH_SHADING(k_path, lds);
-        }
-        break;
-#ifdef RTW_EXPERIMENTS
-    case LK_PATH_TREE: RTW_LAUNCH_SHADING(k_path_tree, lds); break;
-#endif
+    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, feat, a.sc.n_vol), dim3(grid), dim3(kBlock), lds, s, a); break;
     default: RTW_LAUNCH_SHADING(k_bounce, lds); break;
 #undef RTW_LAUNCH_SHADING
 #undef RTW_LAUNCH_SHADING_R
@@ -905,23 +782,39 @@ size_t shard_rows(const rtw_params* P) {
     return ((size_t)(P->row1 - P->row0) + k - 1) / k;
 }
 
-// One device: the whole render of the shard P describes, result in d_rgba (device memory of c->device).
-int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, rtw_stats* stats) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!s) s = c->stream;
+unsigned pixel_grid(const rtw_ctx* c, size_t npix) { return (unsigned)std::min<size_t>((npix + kBlock - 1) / kBlock, (size_t)c->n_cu * 8); }
 
-    const uint32_t row_stride = P->row_stride > 1 ? (uint32_t)P->row_stride : 1u;
-    const size_t rows = shard_rows(P);
-    const size_t npix = rows * (size_t)P->width;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (npix == 0) return RTW_OK;
-    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "tile too large");
+// kernel arguments that every kernel of a render shares: the scene as uploaded, the shard, the seed, depth and sample count
+KArgs shard_args(const DScene& sc, const rtw_params* P, size_t npix) {
+    KArgs a{};
+    a.sc = sc;
+    a.npix = (uint32_t)npix;
+    a.width = (uint32_t)P->width;
+    a.height = (uint32_t)P->height;
+    a.row0 = (uint32_t)P->row0;
+    a.row_stride = P->row_stride > 1 ? (uint32_t)P->row_stride : 1u;
+    magic_div((uint32_t)P->width, a.divw_m, a.divw_s1, a.divw_s2);
+    magic_div(a.row_stride, a.divs_m, a.divs_s1, a.divs_s2);
+    a.seed = P->seed;
+    a.max_depth = (uint32_t)P->max_depth;
+    a.stack_stride = kBlock;
+    a.spp = (uint32_t)P->spp;
+    return a;
+}
 
-    const Tuning tune = read_tuning();
-    const bool timing = stats != nullptr && tune.kernel_timing;
-    // timing events come from a pool kept in the context: (kernel kind, start, stop) triples of this call
+// One render call's record: timing events from a pool kept in the context (reused across launches and calls), the (kernel kind,
+// start, stop) triples of its timed launches, and the launches rtw_stats.bounce_launches counts
+struct CallLog {
+    rtw_ctx* c;
+    int rng_kind;
+    bool timing;  // per-launch events: the caller asked for rtw_stats and RTW_KERNEL_TIMING is not 0
+    struct Timed { int kind; hipEvent_t a, b; };
+    std::vector<Timed> timed;
     size_t ev_used = 0;
-    auto new_event = [&](hipEvent_t& e) -> hipError_t {
+    hipEvent_t begin = nullptr, end = nullptr;
+    uint64_t launches = 0;
+
+    hipError_t event(hipEvent_t& e) {
         if (ev_used == c->ev_pool.size()) {
             hipEvent_t n = nullptr;
             hipError_t er = hipEventCreate(&n);
@@ -930,502 +823,232 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
         }
         e = c->ev_pool[ev_used++];
         return hipSuccess;
-    };
-    struct Timed { int kind; hipEvent_t a, b; };
-    std::vector<Timed> ev_k;
-    auto timed_launch = [&](hipStream_t ls, int kind, const KArgs& ka, int grid_, size_t lds_, int block_ = kBlock) -> hipError_t {
-        if (!timing) {
-            launch(kind, P->rng_kind, ka, grid_, lds_, ls, block_);
-            return hipSuccess;
-        }
-        Timed t{kind == LK_PATH_TREE ? (int)RTW_K_PATH : kind, nullptr, nullptr};
-        hipError_t er = new_event(t.a);
-        if (er == hipSuccess) er = new_event(t.b);
-        if (er == hipSuccess) er = hipEventRecord(t.a, ls);
+    }
+    // work issued on stream s between open() and close() is timed as one launch of `kind`
+    hipError_t open(Timed& t, int kind, hipStream_t s) {
+        t = Timed{kind, nullptr, nullptr};
+        if (!timing) return hipSuccess;
+        hipError_t er = event(t.a);
+        if (er == hipSuccess) er = event(t.b);
+        if (er == hipSuccess) er = hipEventRecord(t.a, s);
+        return er;
+    }
+    hipError_t close(const Timed& t, hipStream_t s) {
+        if (!timing) return hipSuccess;
+        timed.push_back(t);
+        return hipEventRecord(t.b, s);
+    }
+    hipError_t launch(hipStream_t s, int kind, const KArgs& a, int grid, size_t lds, int block = kBlock) {
+        Timed t;
+        hipError_t er = open(t, kind, s);
         if (er != hipSuccess) return er;
-        launch(kind, P->rng_kind, ka, grid_, lds_, ls, block_);
-        ev_k.push_back(t);
-        return hipEventRecord(t.b, ls);
-    };
-#define HIP_TRY_C(expr) HIP_TRY(c, expr)
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    HIP_TRY_C(new_event(ev_begin));
-    HIP_TRY_C(new_event(ev_end));
-
-    // kernel arguments common to both pipelines
-    KArgs base{};
-    base.sc = c->sc;
-    if (P->estimator != RTW_EST_REFERENCE) {  // the corrected estimators live in the cold-feature instantiations
-        base.sc.estimator = P->estimator; base.sc.has_tex = P->estimator == RTW_EST_MIXTURE ? 2 : 1;
-        base.sc.ray_tmin = 1.0e-3f; base.sc.probe_eps = 1.0e-3f;
+        ::launch(kind, rng_kind, a, grid, lds, s, block);
+        return close(t, s);
     }
-    base.npix = (uint32_t)npix;
-    base.width = (uint32_t)P->width;
-    base.height = (uint32_t)P->height;
-    base.row0 = (uint32_t)P->row0;
-    base.row_stride = row_stride;
-    magic_div((uint32_t)P->width, base.divw_m, base.divw_s1, base.divw_s2);
-    magic_div(row_stride, base.divs_m, base.divs_s1, base.divs_s2);
-    base.seed = P->seed;
-    base.max_depth = (uint32_t)P->max_depth;
-    base.stack_stride = kBlock;
-    base.spp = (uint32_t)P->spp;
-    const size_t lds = c->lds_bytes;
-    const unsigned pix_grid = (unsigned)std::min<size_t>((npix + kBlock - 1) / kBlock, (size_t)c->n_cu * 8);
-    uint64_t launches = 0;
-    const bool path_small = !c->sc.use_bvh && c->sc.n_prims <= kPathMaxPrims && (c->sc.n_walk_words > 0 || c->sc.has_tex);
-#ifdef RTW_EXPERIMENTS
-    const bool path_tree = c->sc.use_bvh && tune.path_tree != 0;
-#else
-    const bool path_tree = false;  // (k_path_tree exists in -DRTW_EXPERIMENTS builds only: RTW_PATH_TREE is ignored here)
-#endif
-    // k_path packs a unit's pixel as x | y << 16: frames wider or taller than 65535 take the wavefront kernels
-    const bool fits16 = P->width <= 65535 && P->height <= 65535;
-    const bool use_path = P->max_depth > 0 && tune.path != 0 && fits16 && (path_small || path_tree);
+};
 
-    if (use_path) {
-        // ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
-        int rc = ensure_pool(c, 0, 0, npix, 0);
-        if (rc) return rc;
-        const size_t n_blocks = ((size_t)P->spp + kSumBlock - 1) / kSumBlock;
-        int wg_per_cu = tune.path_grid_mult;
-        const size_t path_lds = path_tree ? lds : 0;
-        if (wg_per_cu <= 0) {
-            const bool lcg = P->rng_kind == RTW_RNG_TEA_LCG;
-            const int feat = base.sc.has_tex;
-            int nb = 0;
-            hipError_t qe;
-#define RTW_OCC_R(K_, R_) (feat == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_<R_, 2>, kBlock, path_lds)   \
-                           : feat == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_<R_, 1>, kBlock, path_lds) \
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_<R_, 0>, kBlock, path_lds))
-#define RTW_OCC(K_) (lcg ? RTW_OCC_R(K_, RTW_RNG_TEA_LCG) : RTW_OCC_R(K_, RTW_RNG_PHILOX))
-#ifdef RTW_EXPERIMENTS
-            if (path_tree) qe = RTW_OCC(k_path_tree); else
-#endif
-            if (feat == 1 && base.sc.n_vol > 0)
-                qe = lcg ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path<RTW_RNG_TEA_LCG, 1, 1>, kBlock, path_lds)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_path<RTW_RNG_PHILOX, 1, 1>, kBlock, path_lds);
-            else
-                qe = RTW_OCC(k_path);
-#undef RTW_OCC
-#undef RTW_OCC_R
-            wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
-        }
-        const size_t n_groups = (npix + 63) / 64;
-        if (n_groups > c->order_groups) {
-            if (c->d_order) (void)hipFree(c->d_order);
-            c->d_order = nullptr; c->order_groups = 0;
-            HIP_TRY(c, hipMalloc(&c->d_order, 3 * n_groups * sizeof(uint32_t)));
-            c->order_groups = n_groups;
-        }
-        if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));  // low priority: it fills the slots the bulk launch vacates
-        HIP_TRY_C(hipEventRecord(ev_begin, s));
-        HIP_TRY_C(hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
-        HIP_TRY_C(hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
-        {   // job order: longest units first (k_classify)
-            HIP_TRY_C(hipMemsetAsync(c->d_queue, 0, 64, s));
+// ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
+int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
+    const size_t npix = base.npix;
+    int rc = ensure_pool(c, 0, 0, npix, 0);
+    if (rc) return rc;
+    int wg_per_cu = tune.path_grid_mult;
+    if (wg_per_cu <= 0) {
+        int nb = 0;
+        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), kBlock, 0);
+        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+    }
+    const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu);
+    if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
+    if (plan.n_groups > c->order_groups) {
+        if (c->d_order) (void)hipFree(c->d_order);
+        c->d_order = nullptr; c->order_groups = 0;
+        HIP_TRY(c, hipMalloc(&c->d_order, 3 * plan.n_groups * sizeof(uint32_t)));
+        c->order_groups = plan.n_groups;
+    }
+    if (plan.need_slots * npix > c->blocksum_elems) {
+        if (c->blocksum) (void)hipFree(c->blocksum);
+        c->blocksum = nullptr; c->blocksum_elems = 0;
+        HIP_TRY(c, hipMalloc(&c->blocksum, plan.need_slots * npix * sizeof(float4)));
+        c->blocksum_elems = plan.need_slots * npix;
+    }
+    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));  // low priority: it fills the slots the bulk launch vacates
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    {   // job order: longest units first (k_classify)
+        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
+        const dim3 cg((unsigned)std::min<size_t>((plan.n_groups + 3) / 4, (size_t)c->n_cu * 8));
+        if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)plan.n_groups);
+        else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)plan.n_groups);
+    }
+    const unsigned pix_grid = pixel_grid(c, npix);
+    for (const PathPass& ps : plan.passes) {
+        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
+        HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
+        HIP_TRY(c, log.event(ev_a));
+        HIP_TRY(c, log.event(ev_b));
+        HIP_TRY(c, hipEventRecord(ev_a, s));
+        // the two launches of a pass overlap, so they are timed as one: from before the first to after both (on s, which waits
+        // for the second stream's launch below); rocprofv3 lists them as two dispatches whose durations both span the pass
+        CallLog::Timed tp;
+        HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
+        for (int part = 0; part < 2; part++) {
+            const PathLaunch& l = ps.part[part];
+            if (l.count == 0) continue;
             KArgs a = base;
-            const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
-            if (path_small && c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, a, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
-            else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, a, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
-        }
-        // A launch ends when its slowest unit ends, and a unit through a glass sphere runs several milliseconds. So the bulk of
-        // a pass is handed out in units of `unit_blocks` blocks (one lane keeps a pixel for 64 samples: little bookkeeping), and
-        // its last `fine_blocks` blocks in single-block units by a SECOND launch on a second stream: its workgroups move into the
-        // slots the first launch's workgroups vacate as they run dry, so the machine stays full until only 16-sample units are
-        // left (measured on the 1/8 shard of the metric frame: see DESIGN.md section 6).
-        // Unit size: every unit costs a little (queue, camera-ray set-up, a 16-byte store per block either way) and a launch
-        // ends with its longest units, so long renders want long units and short ones short units. Measured on the metric
-        // frame (1 620 blocks per lane): 8-block units 0.556 s, 4-block 0.562 s, 2-block 0.581 s; on its 1/8 shard (202
-        // blocks per lane): 0.0773, 0.0722, 0.0736 s; on the 1/2 shard 8 and 4 are level.
-        const size_t blocks_per_lane = npix * n_blocks / ((size_t)c->n_cu * (size_t)wg_per_cu * kBlock);
-        const size_t U = tune.path_unit_blocks > 0 ? (size_t)tune.path_unit_blocks : (blocks_per_lane >= 600 ? 8 : 4);
-        // the end-game region: the last 8 blocks of a pass behind 8-block units, the last 16 behind 4-block units (a shard-sized
-        // render: the bulk launch drains for a unit's length at its end, and the single-block work beside it must last that long;
-        // 1/8 shard of the metric frame, medians of 12 runs: F = 8 0.0739 s, 16 0.0725, 24 0.0728, 32 0.0727, 48 0.0729; the full
-        // frame does not care: 0.5597 against 0.5593)
-        const size_t F = tune.path_fine_blocks >= 0 ? (size_t)tune.path_fine_blocks : (U >= 8 ? 8 : 16);
-        // Sums in memory (the arithmetic spec's three levels, rtw.h): a bulk launch whose lane units are whole summation units
-        // (U a multiple of 8 blocks) stores ONE float4 per unit and pixel, everything else one per block; k_resolve_blocks adds
-        // them up in the spec's order. A pass covers a multiple of 8 blocks, so no summation unit straddles two passes.
-        const bool unit_sums = !path_tree && (U % kSumUnitBlocks) == 0;
-        auto coarse_of = [&](size_t nb) { return nb > 4 * F ? ((nb - F) / U) * U : (size_t)0; };  // short passes are all fine units
-        auto slots_of = [&](size_t nb) { const size_t nc = coarse_of(nb); return unit_sums ? nc / kSumUnitBlocks + (nb - nc) : nb; };
-        const size_t cap_slots = std::max<size_t>(1, tune.blocksum_bytes / (npix * sizeof(float4)));
-        size_t pass_blocks = n_blocks;
-        if (slots_of(n_blocks) > cap_slots) {
-            pass_blocks = kSumUnitBlocks;
-            while (pass_blocks + kSumUnitBlocks < n_blocks && slots_of(pass_blocks + kSumUnitBlocks) <= cap_slots) pass_blocks += kSumUnitBlocks;
-        }
-        size_t need_slots = 0;
-        for (size_t b0 = 0; b0 < n_blocks; b0 += pass_blocks) need_slots = std::max(need_slots, slots_of(std::min(pass_blocks, n_blocks - b0)));
-        if (need_slots * npix > c->blocksum_elems) {
-            if (c->blocksum) (void)hipFree(c->blocksum);
-            c->blocksum = nullptr; c->blocksum_elems = 0;
-            HIP_TRY(c, hipMalloc(&c->blocksum, need_slots * npix * sizeof(float4)));
-            c->blocksum_elems = need_slots * npix;
-        }
-        for (size_t b0 = 0; b0 < n_blocks; b0 += pass_blocks) {
-            const size_t nb = std::min(pass_blocks, n_blocks - b0);
-            const size_t nb_coarse = coarse_of(nb);
-            const size_t slots_coarse = unit_sums ? nb_coarse / kSumUnitBlocks : nb_coarse;
-            HIP_TRY_C(hipMemsetAsync(c->d_queue, 0, 4, s));
-            HIP_TRY_C(hipMemsetAsync(c->d_queue + 4, 0, 4, s));
-            hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
-            HIP_TRY_C(new_event(ev_a));
-            HIP_TRY_C(new_event(ev_b));
-            HIP_TRY_C(hipEventRecord(ev_a, s));
-            // the two launches of a pass overlap, so they are timed as one: from before the first to after both (on s, which waits
-            // for the second stream's launch below); rocprofv3 lists them as two dispatches whose durations both span the pass
-            Timed tp{(int)RTW_K_PATH, nullptr, nullptr};
-            if (timing) {
-                HIP_TRY_C(new_event(tp.a));
-                HIP_TRY_C(new_event(tp.b));
-                HIP_TRY_C(hipEventRecord(tp.a, s));
+            a.stats = c->d_stats;
+            a.sample0 = (uint32_t)P->sample_offset;
+            a.queue = c->d_queue + (part == 0 ? 0 : 4);
+            a.order = c->d_order;
+            a.order_counts = c->d_queue + 1;
+            a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * npix;
+            a.unit_sums = (part == 0 && plan.unit_sums) ? 1u : 0u;
+            a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
+            a.block0 = (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
+            hipStream_t ls = part == 0 ? s : c->stream2;
+            if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
+            launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls);
+            log.launches++;
+            if (part == 1) {
+                HIP_TRY(c, hipEventRecord(ev_b, ls));
+                HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
             }
-            for (int part = 0; part < 2; part++) {
-                const size_t first = part == 0 ? 0 : nb_coarse, count = part == 0 ? nb_coarse : nb - nb_coarse;
-                if (count == 0) continue;
-                const size_t ub = part == 0 ? U : 1;
-                const size_t n_units = (count + ub - 1) / ub;                     // units per pixel in this launch
-                const size_t jb = std::min<size_t>((size_t)tune.path_job_blocks, n_units);  // units per pixel and job
-                const size_t n_ranges = (n_units + jb - 1) / jb;
-                const size_t n_jobs = n_groups * n_ranges;
-                if (n_jobs > 0xfffffff0ull) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
-                KArgs a = base;
-                a.stats = c->d_stats;
-                a.sample0 = (uint32_t)P->sample_offset;
-                a.queue = c->d_queue + (part == 0 ? 0 : 4);
-                a.order = c->d_order;
-                a.order_counts = c->d_queue + 1;
-                a.blocksum = c->blocksum + (part == 0 ? 0 : slots_coarse) * npix;
-                a.unit_sums = (part == 0 && unit_sums) ? 1u : 0u;
-                a.n_jobs = (uint32_t)n_jobs; a.n_ranges = (uint32_t)n_ranges; a.units_per_job = (uint32_t)jb;
-                a.block0 = (uint32_t)(b0 + first); a.n_blocks_pass = (uint32_t)count; a.unit_blocks = (uint32_t)ub;
-                const int grid = (int)std::min<size_t>((size_t)c->n_cu * (size_t)wg_per_cu, (n_jobs + 3) / 4);
-                hipStream_t ls = part == 0 ? s : c->stream2;
-                if (part == 1) HIP_TRY_C(hipStreamWaitEvent(ls, ev_a, 0));
-                launch(path_tree ? LK_PATH_TREE : LK_PATH, P->rng_kind, a, grid, path_lds, ls);
-                launches++;
-                if (part == 1) {
-                    HIP_TRY_C(hipEventRecord(ev_b, ls));
-                    HIP_TRY_C(hipStreamWaitEvent(s, ev_b, 0));
-                }
-            }
-            if (timing) {
-                HIP_TRY_C(hipEventRecord(tp.b, s));
-                ev_k.push_back(tp);
-            }
-            // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
-            if (unit_sums)
-                hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)slots_coarse,
-                                   (uint32_t)(nb - nb_coarse), (uint32_t)(b0 + nb_coarse));
-            else
-                hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)nb, (uint32_t)b0);
         }
-        hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, (float4*)d_rgba, (uint32_t)npix, (float)P->spp);
-    } else {
-    // ---- wavefront pipeline (tree scenes; RTW_PATH=0)
-    // samples per pass: keep about pool_target paths in flight, split over the lanes
-    const int want_lanes = tune.lanes;
-    size_t S = P->samples_per_pass > 0 ? (size_t)P->samples_per_pass
-                                       : std::max<size_t>(1, std::min(tune.pool_paths, c->pool_cap) / (size_t)want_lanes / npix);
-    S = std::min<size_t>(S, (size_t)P->spp);
-    while (S > 1 && npix * S > 0xfffffff0ull) S--;
-    if (P->samples_per_pass <= 0 && want_lanes > 1 && (size_t)P->spp >= (size_t)want_lanes) {
-        // equal batches, as many as a multiple of the lanes: every lane gets the same number of batches of the same size (a
-        // render of 128 spp whose pool would take it in one batch would leave the second lane idle; 512 spp in batches of 129
-        // would end with a short fourth one). Sizes are kept multiples of 16 where that fits (k_first's sample grouping).
-        size_t nb = ((size_t)P->spp + S - 1) / S;
-        nb = (nb + (size_t)want_lanes - 1) / (size_t)want_lanes * (size_t)want_lanes;
-        size_t s_eq = ((size_t)P->spp + nb - 1) / nb;
-        if (((s_eq + 15) & ~(size_t)15) <= S) s_eq = (s_eq + 15) & ~(size_t)15;
-        S = std::max<size_t>(1, std::min(S, s_eq));
+        HIP_TRY(c, log.close(tp, s));
+        // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
+        if (plan.unit_sums)
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
+                               (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse));
+        else
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0);
     }
-    const size_t paths_max = npix * S;
-    // Persistent compacting grid: G workgroups (8 per CU when a lane has the GPU to itself, 4 when two lanes share it).
-    // Output region b belongs to workgroup b, which is handed every G-th 256-path chunk of its input: at most
-    // ceil(chunks / G) + 1 chunks (the work list of a later launch has up to one partial chunk per region more than
-    // the first), so a region of (ceil(chunks / G) + 2) * 256 slots cannot overflow.
-    const size_t n_batches = ((size_t)P->spp + S - 1) / S;
-    const int n_lanes = (int)std::min<size_t>((size_t)want_lanes, std::max<size_t>(n_batches, 1));
-    const uint32_t grid_mult = tune.grid_mult > 0 ? (uint32_t)tune.grid_mult : (n_lanes > 1 ? 4u : 8u);
-    auto grid_for = [&](size_t paths) {
-        const size_t chunks = (paths + kBlock - 1) / kBlock;
-        return (uint32_t)std::min<size_t>(std::min<size_t>(chunks, (size_t)c->n_cu * grid_mult), (size_t)kMaxRegions);
-    };
-    auto cap_for = [&](size_t paths) {
-        const size_t chunks = (paths + kBlock - 1) / kBlock;
-        const size_t g = grid_for(paths);
-        return ((chunks + g - 1) / g + 2) * (size_t)kBlock;
-    };
-    // RTW_PAIRED: batches run two at a time with their trace launches alternating (see the batch loop)
-#ifdef RTW_EXPERIMENTS
-    const bool paired = tune.paired && n_lanes == 2 && c->sc.use_bvh;
-#else
-    const bool paired = false;  // (measured 12 % slower: -DRTW_EXPERIMENTS builds only)
-#endif
-    // k_trace_bvh: large workgroups share one LDS copy of the tree (nodes, then leaf records) between more waves
-    int trace_block = tune.trace_block;
-    size_t trace_budget = tune.trace_lds_kb * 1024;
-    // LDS the trace launch may plan with per CU: all 160 KB when the knobs say so; 142 KB when the render chooses - the other
-    // lane's kernels (k_shade: 9 KB per workgroup) must find room beside a resident k_trace_bvh, or the two lanes take turns
-    size_t trace_cu_lds = (size_t)160 * 1024;
-    if (c->sc.use_bvh && tune.trace_auto) {
-        // Every node of the tree in the workgroup's LDS image takes the global loads - and the vmcnt waits behind them - out of the
-        // walk loop (k_trace_bvh mode 2), but only pays while the kernel keeps its waves AND leaves the other lane room: a 256-thread
-        // workgroup at 6 per CU has 14 KB for stacks + nodes (scene 1's stacks alone: 21 levels = 10.75 KB), a 512-thread workgroup
-        // shares one image between twice the waves. Measured (round 3, scene 1: 240 nodes = 15.4 KB; k_trace_bvh per 512-spp render):
-        // 256 threads / 16 KB (88 nodes in LDS, the old default) 0.152-0.155 s; 256 / 26 KB (all nodes, 4 waves per SIMD) 0.154;
-        // 512 / 37 KB (all nodes, 3 workgroups = 141 KB per CU) 0.144-0.147; 512 / 40.5 KB (152 KB per CU: no room left for the
-        // other lane's workgroups) 0.155; 512 / 43 KB (three planned, two fit) 0.166; 512 / 44 KB (two planned) 0.143-0.145.
-        // Scene 2: 0.163 -> 0.153. Scene 4 (1 419 nodes = 91 KB) stays at 256 / 16 KB.
-        const size_t cu_lds = (size_t)142 * 1024;
-        const size_t blocks[2] = {256, 512};
-        for (size_t blk : blocks) {
-            int32_t nn = 0, nl = 0;
-            const size_t want = std::max<size_t>(1, (size_t)(4 * tune.trace_waves) / (blk / 64));  // workgroups per CU at the wanted occupancy
-            const size_t fixed = (kMaxRegions + 1 + blk) * 4 + 64;                                // the work list's static LDS
-            // stacks + every node, no leaf records (a partial leaf image makes a wave run both of leaf_test's fetch paths)
-            const size_t need = tree_lds_layout(c->n_tree_nodes, 0, c->stack_depth, c->sc.stack_wide != 0, blk, (size_t)150 * 1024, nn, nl);
-            if ((size_t)nn != c->n_tree_nodes) continue;
-            const size_t fit = cu_lds / (need + fixed);
-            if (fit >= want || (blk == 512 && fit >= 2)) { trace_block = (int)blk; trace_budget = need; trace_cu_lds = cu_lds; break; }
-        }
-    }
-    int32_t trace_nodes = 0, trace_leaves = 0;
-    size_t trace_lds = 0;
-    int trace_grid = 0;
-    if (c->sc.use_bvh) {
-        trace_lds = tree_lds_layout(c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, c->sc.stack_wide != 0, (size_t)trace_block, trace_budget,
-                                    trace_nodes, trace_leaves);
-        const size_t per_wg = trace_lds + (kMaxRegions + 1 + (size_t)trace_block) * 4 + 64;
-        const size_t by_lds = std::max<size_t>(1, trace_cu_lds / per_wg);
-        const size_t by_waves = std::max<size_t>(1, (size_t)(4 * (paired ? tune.paired_trace_waves : tune.trace_waves)) / ((size_t)trace_block / 64));
-        trace_grid = (int)((size_t)c->n_cu * std::min(by_lds, by_waves));
-        if (trace_lds > 48 * 1024) {  // beyond the default dynamic-LDS limit of a launch
+    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
+    return RTW_OK;
+}
+
+// ---- wavefront pipeline (tree scenes; RTW_PATH=0): batches of S samples per pixel alternate between the lanes
+int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
+    const size_t npix = base.npix;
+    const SceneFacts sf{c->sc.use_bvh != 0, c->sc.n_vol, c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, c->sc.stack_wide != 0};
+    WavefrontPlan w;
+    for (;;) {
+        w = plan_wavefront(tune, npix, P->spp, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, sf);
+        if (w.trace_lds > 48 * 1024) {  // beyond the default dynamic-LDS limit of a launch
             DScene ts = c->sc;
-            ts.n_lds_nodes = trace_nodes;
-            const void* f = (const void*)trace_bvh_kernel(trace_block, trace_bvh_mode(ts));
-            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trace_lds));
+            ts.n_lds_nodes = w.trace_nodes;
+            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
+            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
         }
-    }
-    const uint32_t regions_max = grid_for(paths_max);
-    const size_t region_cap_max = cap_for(paths_max);
-    bool split_first = false;
-    // Launch schedule of one batch. Wide bounces: one k_shade + one k_trace per bounce (split pipeline; scenes
-    // whose intersection programs draw random numbers keep trace and shade fused in k_bounce instead).
-    // Thin tail: k_bounce with several bounces in registers, in growing groups.
-    struct Step { int kind, depth, n_iter; };
-    std::vector<Step> sched;
-    {
-        // the fused tail kernel walks the tree one lane per path (lane utilisation 0.2): tree scenes stay in the split
-        // pipeline longer, and longest where media keep many paths alive deep (scene 4, 3.9 segments per sample: 20 -> 40
-        // +5 %; scenes 1 and 2, 2.6 and 3.2: best at 20, -2 % at 30)
-        const int tail_start = tune.tail_start > 0 ? tune.tail_start : (c->sc.use_bvh ? (c->sc.n_vol > 0 ? 40 : 20) : 6);
-        const bool split = !tune.fused && (c->sc.n_vol == 0 || tune.split_media);
-        int d = 0, grp = tune.tail_group, rep = 0;
-        while (d < P->max_depth) {
-            if (d < tail_start) {
-                if (split) {
-                    // k_first has already traced and shaded depth 0
-                    if (d > 0) { sched.push_back({LK_TRACE, d, 1}); sched.push_back({LK_SHADE, d, 1}); }
-                } else {
-                    sched.push_back({LK_BOUNCE, d, 1});
-                }
-                d++;
-            } else {
-                const int n = std::min(grp, P->max_depth - d);
-                if (++rep == 2) { rep = 0; grp += grp / 2; }
-                sched.push_back({LK_BOUNCE, d, n});
-                d += n;
-            }
-        }
-        // a batch must not end with probes still queued: a zero-bounce k_bounce resolves them and retires the zombies
-        if (split && (sched.empty() || sched.back().kind == LK_SHADE)) sched.push_back({LK_BOUNCE, P->max_depth, 0});
-        split_first = split;
-    }
-    const size_t cnt_words = (size_t)regions_max * (sched.size() + 2);
-    int rc = ensure_pool(c, n_lanes, (size_t)regions_max * region_cap_max, npix, cnt_words, c->sc.n_lights > 0);
-    if (rc == RTW_ERR_OOM && P->samples_per_pass <= 0 && S > 1) {
+        const int rc = ensure_pool(c, w.n_lanes, (size_t)w.regions_max * w.region_cap_max, npix, w.cnt_words, c->sc.n_lights > 0);
+        if (rc == RTW_OK) break;
+        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || w.S <= 1) return rc;
         // The pool is sized for an MI355X to itself (2^29 paths: up to 120 GiB). A device with less to give - another process on
         // it, a smaller part - gets half as many paths in flight, and half again, until the allocation fits: smaller batches,
         // the same image (a path's draws and a pixel's summation order do not depend on the batch size).
         free_pool(c);
         (void)hipGetLastError();
-        c->pool_cap = std::max<size_t>((size_t)want_lanes * npix, npix * S * (size_t)want_lanes / 2);
-        return render_single(c, P, d_rgba, s, stats);
+        c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * w.S * (size_t)tune.lanes / 2);
     }
-    if (rc) return rc;
 
-    HIP_TRY_C(hipEventRecord(ev_begin, s));
-    HIP_TRY_C(hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
-    HIP_TRY_C(hipMemsetAsync(c->part, 0, npix * sizeof(float4), s));
-    HIP_TRY_C(hipMemsetAsync(c->upart, 0, npix * sizeof(float4), s));
-    HIP_TRY_C(hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
-
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->part, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->upart, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    const unsigned pix_grid = pixel_grid(c, npix);
+    const size_t lds = c->lds_bytes;
+    // the lanes start once the accumulators are cleared
+    hipEvent_t ev_ready = nullptr;
     if (P->max_depth > 0) {
-        // the lanes start once the accumulators are cleared
-        hipEvent_t ev_ready = nullptr;
-        HIP_TRY_C(new_event(ev_ready));
-        HIP_TRY_C(hipEventRecord(ev_ready, s));
-        size_t bi = 0;
-        // The second lane's first batch is cut short so that the lanes run half a batch apart: one lane's bandwidth-bound
-        // k_shade launches then meet the other's issue-bound k_first / k_trace instead of its own kind (5 runs each on one
-        // box: 9.35-9.58 Gsamples/s with the offset, 8.93-9.59 without).
-        const int stagger_pct = tune.stagger_pct >= 0 ? tune.stagger_pct : (c->sc.use_bvh ? 0 : 50);
-        // One batch in flight on a lane: its arguments and which of the lane's two path buffers is current.
-        struct BatchRun { rtw_ctx::Lane* L; KArgs a; int cur; size_t ci; uint32_t regions; size_t Sb, s0; };
-        auto batch_size = [&](size_t b, size_t s0_) {
-            size_t want = S;
-            if (stagger_pct > 0 && b > 0 && b < (size_t)n_lanes && S > 1)  // lane k starts k/n_lanes of a batch late (at 50 %)
-                want = std::max<size_t>(1, S - S * b * (size_t)stagger_pct * 2 / (100 * (size_t)n_lanes));
-            return std::min(want, (size_t)P->spp - s0_);
-        };
-        // camera rays (+ the primary segment) of a batch on its lane
-        auto begin_batch = [&](size_t b, size_t s0_, size_t Sb_, BatchRun& R) -> hipError_t {
-            R.L = &c->lane[b % (size_t)n_lanes]; R.Sb = Sb_; R.s0 = s0_;
-            rtw_ctx::Lane& L = *R.L;
-            const size_t paths = npix * Sb_;
-            R.regions = grid_for(paths);
-            // this lane's pool is free again once the resolve of its previous batch has run on the main stream
-            hipError_t er = hipStreamWaitEvent(L.st, b < (size_t)n_lanes ? ev_ready : L.ev_free, 0);
-            if (er == hipSuccess) er = hipMemsetAsync(L.cnt, 0, (size_t)R.regions * (sched.size() + 2) * sizeof(uint32_t), L.st);
-            if (er != hipSuccess) return er;
-            KArgs& a = R.a;
-            a = base;
-            a.lbuf = L.lbuf;
-            a.stats = c->d_stats;
-            a.n_regions = R.regions;
-            a.n_paths = (uint32_t)paths;
-            a.sample0 = (uint32_t)(P->sample_offset + (int)s0_);
-            a.region_cap = (uint32_t)cap_for(paths);
-            a.trace_first = split_first ? 1u : 0u;
-            a.first_group_log2 = 0;
-            while (a.first_group_log2 < (uint32_t)tune.first_group_log2 && (Sb_ >> (a.first_group_log2 + 1)) << (a.first_group_log2 + 1) == Sb_) a.first_group_log2++;
-            // k_first fills buffer 0 (and the hit buffer); every compacting launch then flips the buffers
-            R.cur = 0;
-            R.ci = 0;  // index of the region-counter row describing buffer `cur`
-            a.out = L.buf[0];
-            a.hit_out = L.hit[0];
-            a.cnt_out = L.cnt;
-            a.depth = 0; a.n_iter = 1;
-            launches++;
-            return timed_launch(L.st, LK_FIRST, a, (int)R.regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->stack_depth * sizeof(uint32_t) : 0);  // every compacting launch uses exactly this grid: workgroup b owns region b
-        };
-        // step si of the schedule for a batch; a trace launch may wait for an event of the other lane and record one
-        auto run_step = [&](BatchRun& R, size_t si, hipEvent_t wait_for, hipEvent_t record) -> hipError_t {
-            rtw_ctx::Lane& L = *R.L;
-            KArgs& a = R.a;
-            const Step& st = sched[si];
-            const int grid = (int)R.regions;
-            a.in = L.buf[R.cur];
-            a.hit = L.hit[R.cur];
-            a.hit_out = L.hit[R.cur];  // k_trace fills the records of the buffer it reads
-            a.cnt_in = L.cnt + R.ci * R.regions;
+        HIP_TRY(c, log.event(ev_ready));
+        HIP_TRY(c, hipEventRecord(ev_ready, s));
+    }
+    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < (size_t)P->spp; b++) {
+        // batch b on its lane: samples [s0, s0 + Sb) of every pixel
+        const size_t Sb = w.batch_size(b, s0);
+        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
+        const size_t paths = npix * Sb;
+        const uint32_t regions = w.grid_for(paths);
+        // this lane's pool is free again once the resolve of its previous batch has run on the main stream
+        HIP_TRY(c, hipStreamWaitEvent(L.st, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, 0));
+        HIP_TRY(c, hipMemsetAsync(L.cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
+        KArgs a = base;
+        a.lbuf = L.lbuf;
+        a.stats = c->d_stats;
+        a.n_regions = regions;
+        a.n_paths = (uint32_t)paths;
+        a.sample0 = (uint32_t)(P->sample_offset + (int)s0);
+        a.region_cap = (uint32_t)w.cap_for(paths);
+        a.trace_first = w.split_first ? 1u : 0u;
+        a.first_group_log2 = 0;
+        while (a.first_group_log2 < (uint32_t)tune.first_group_log2 && (Sb >> (a.first_group_log2 + 1)) << (a.first_group_log2 + 1) == Sb) a.first_group_log2++;
+        // k_first fills buffer 0 (and the hit buffer); every compacting launch then flips the buffers
+        int cur = 0;
+        size_t ci = 0;  // index of the region-counter row describing buffer `cur`
+        a.out = L.buf[0];
+        a.hit_out = L.hit[0];
+        a.cnt_out = L.cnt;
+        a.depth = 0; a.n_iter = 1;
+        log.launches++;
+        // every compacting launch uses exactly this grid: workgroup b owns region b
+        HIP_TRY(c, log.launch(L.st, RTW_K_FIRST, a, (int)regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->stack_depth * sizeof(uint32_t) : 0));
+        for (const Step& st : w.sched) {
+            a.in = L.buf[cur];
+            a.hit = L.hit[cur];
+            a.hit_out = L.hit[cur];  // k_trace fills the records of the buffer it reads
+            a.cnt_in = L.cnt + ci * regions;
             a.depth = (uint32_t)st.depth;
             a.n_iter = (uint32_t)st.n_iter;
-            hipError_t er = hipSuccess;
-            if (wait_for) er = hipStreamWaitEvent(L.st, wait_for, 0);
-            if (er != hipSuccess) return er;
-            if (st.kind == LK_TRACE) {
+            if (st.kind == RTW_K_TRACE) {
                 if (c->sc.use_bvh) {  // its own workgroup size, LDS image and grid: waves own streams of chunks, not regions
                     KArgs at = a;
-                    at.sc.n_lds_nodes = trace_nodes; at.sc.n_lds_leaves = trace_leaves;
-                    er = timed_launch(L.st, LK_TRACE, at, trace_grid, trace_lds, trace_block);
+                    at.sc.n_lds_nodes = w.trace_nodes; at.sc.n_lds_leaves = w.trace_leaves;
+                    HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, at, w.trace_grid, w.trace_lds, w.trace_block));
                 } else {
-                    er = timed_launch(L.st, LK_TRACE, a, grid, lds);
+                    HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, a, (int)regions, lds));
                 }
             } else {
-                a.out = L.buf[R.cur ^ 1];
-                a.hit_out = L.hit[R.cur ^ 1];
-                a.cnt_out = L.cnt + (R.ci + 1) * R.regions;
-                er = timed_launch(L.st, st.kind, a, grid, st.kind == LK_BOUNCE ? lds : 0);
-                R.cur ^= 1;
-                R.ci++;
+                a.out = L.buf[cur ^ 1];
+                a.hit_out = L.hit[cur ^ 1];
+                a.cnt_out = L.cnt + (ci + 1) * regions;
+                HIP_TRY(c, log.launch(L.st, st.kind, a, (int)regions, st.kind == RTW_K_BOUNCE ? lds : 0));
+                cur ^= 1;
+                ci++;
             }
-            launches++;
-            if (er == hipSuccess && record) er = hipEventRecord(record, L.st);
-            return er;
-        };
-        auto end_batch = [&](BatchRun& R) -> hipError_t {
-            rtw_ctx::Lane& L = *R.L;
-            hipError_t er = hipEventRecord(L.ev_done, L.st);
-            // batches are resolved into the accumulators in order, on the main stream
-            if (er == hipSuccess) er = hipStreamWaitEvent(s, L.ev_done, 0);
-            if (er != hipSuccess) return er;
-            hipLaunchKernelGGL(k_resolve, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, c->accum, c->upart, c->part, (uint32_t)npix, (uint32_t)R.Sb, (uint32_t)R.s0);
-            return hipEventRecord(L.ev_free, s);
-        };
-        for (size_t s0 = 0; s0 < (size_t)P->spp;) {
-            BatchRun A;
-            const size_t SbA = batch_size(bi, s0);
-            HIP_TRY_C(begin_batch(bi, s0, SbA, A));
-            const size_t s1 = s0 + SbA;
-            if (paired && s1 < (size_t)P->spp) {
-                // Two batches in step: the trace launches of the pair never run at the same time - each starts when the
-                // other batch's trace launch of the same depth (or of the depth before) has ended - so an issue-bound
-                // k_trace_bvh always has a bandwidth-bound k_shade of the other batch beside it and not its own kind.
-                BatchRun B;
-                const size_t SbB = batch_size(bi + 1, s1);
-                HIP_TRY_C(begin_batch(bi + 1, s1, SbB, B));
-                hipEvent_t ev_prev = nullptr;
-                for (size_t si = 0; si < sched.size(); si++) {
-                    if (sched[si].kind == LK_TRACE) {
-                        hipEvent_t ea = nullptr, eb = nullptr;
-                        HIP_TRY_C(new_event(ea));
-                        HIP_TRY_C(new_event(eb));
-                        HIP_TRY_C(run_step(A, si, ev_prev, ea));
-                        HIP_TRY_C(run_step(B, si, ea, eb));
-                        ev_prev = eb;
-                    } else {
-                        HIP_TRY_C(run_step(A, si, nullptr, nullptr));
-                        HIP_TRY_C(run_step(B, si, nullptr, nullptr));
-                    }
-                }
-                HIP_TRY_C(end_batch(A));
-                HIP_TRY_C(end_batch(B));
-                s0 = s1 + SbB;
-                bi += 2;
-            } else {
-                for (size_t si = 0; si < sched.size(); si++) HIP_TRY_C(run_step(A, si, nullptr, nullptr));
-                HIP_TRY_C(end_batch(A));
-                s0 = s1;
-                bi++;
-            }
+            log.launches++;
         }
+        // batches are resolved into the accumulators in order, on the main stream
+        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
+        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+        hipLaunchKernelGGL(k_resolve, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, c->accum, c->upart, c->part, (uint32_t)npix, (uint32_t)Sb, (uint32_t)s0);
+        HIP_TRY(c, hipEventRecord(L.ev_free, s));
+        s0 += Sb;
     }
-    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)c->upart, (const float4*)c->part, (float4*)d_rgba, (uint32_t)npix, (float)P->spp);
-    }
-    HIP_TRY_C(hipGetLastError());
-    HIP_TRY_C(hipEventRecord(ev_end, s));
-    HIP_TRY_C(hipEventSynchronize(ev_end));
+    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)c->upart, (const float4*)c->part, out, (uint32_t)npix, (float)P->spp);
+    return RTW_OK;
+}
 
-    unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        unsigned long long rows_[kStatRows * 8];
-        HIP_TRY_C(hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < kStatRows; r++)
-            for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
-    }
+// Diagnostic builds only (scripts/build_variant.sh with -DRTW_PHASE_TIMERS, -DRTW_SUBPHASE_TIMERS or -DRTW_TRACE_COUNT): the kernels'
+// extra counters, printed to stderr once the render has ended. hs: the summed stats rows.
+int print_diagnostics(rtw_ctx* c, bool path, const unsigned long long* hs) {
 #ifdef RTW_PHASE_TIMERS
-    if (use_path) {
+    if (path) {
         unsigned long long ph[8];
-        HIP_TRY_C(hipMemcpy(ph, c->d_stats + kStatRows * 8, sizeof ph, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(ph, c->d_stats + kStatRows * 8, sizeof ph, hipMemcpyDeviceToHost));
         double tot = 0;
         for (int q = 0; q < 6; q++) tot += (double)ph[q];
         const char* nm[6] = {"refill", "regen", "walk_r", "shade_a", "walk_s", "shade_b"};
         fprintf(stderr, "[rtw] k_path wave-cycles by phase:");
         for (int q = 0; q < 6; q++) fprintf(stderr, " %s %.1f%%", nm[q], 100.0 * (double)ph[q] / tot);
         fprintf(stderr, " (total %.3g wave-cycles, %.0f per 64 segments)\n", tot, tot / ((double)hs[0] / 64.0));
-        if (path_tree) fprintf(stderr, "[rtw] k_path_tree wave steps per 64 segments: inner %.1f  leaf %.1f  shade %.2f\n", (double)ph[6] / ((double)hs[0] / 64.0),
-                               (double)(ph[7] % 1000000ull) / ((double)hs[0] / 64.0), (double)(ph[7] / 1000000ull) / ((double)hs[0] / 64.0));
     }
 #endif
 #ifdef RTW_SUBPHASE_TIMERS
-    if (use_path) {
+    if (path) {
         static std::vector<unsigned long long> tab((size_t)kSubWaves * kSubRows);
-        HIP_TRY_C(hipMemcpyFromSymbol(tab.data(), HIP_SYMBOL(g_sub_cyc), tab.size() * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemcpyFromSymbol(tab.data(), HIP_SYMBOL(g_sub_cyc), tab.size() * sizeof(unsigned long long)));
         double sum[kSubRows] = {0};
         for (size_t w = 0; w < (size_t)kSubWaves; w++) for (int q = 0; q < 14; q++) sum[q] += (double)tab[w * kSubRows + q];
         double tot = 0;
@@ -1435,13 +1058,13 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
         for (int q = 0; q < 9; q++) fprintf(stderr, " %s %.1f%%", nm[q], 100.0 * sum[q] / tot);
         fprintf(stderr, " (total %.3g)\n", tot);
         std::fill(tab.begin(), tab.end(), 0ull);
-        HIP_TRY_C(hipMemcpyToSymbol(HIP_SYMBOL(g_sub_cyc), tab.data(), tab.size() * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_sub_cyc), tab.data(), tab.size() * sizeof(unsigned long long)));
     }
 #endif
 #ifdef RTW_TRACE_COUNT
     {
         unsigned long long w[7];
-        HIP_TRY_C(hipMemcpy(w, c->d_stats + kStatRows * 8, sizeof w, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(w, c->d_stats + kStatRows * 8, sizeof w, hipMemcpyDeviceToHost));
         const double rays = (double)w[6];
         fprintf(stderr, "[rtw] k_trace_bvh: rays %.4g; per ray: node visits %.2f, primitive tests %.2f; wave steps per 64 rays: inner %.2f (lanes busy %.2f), leaf %.2f (lanes busy %.2f), outer %.2f\n",
                 rays, (double)hs[6] / rays, (double)hs[7] / rays, (double)w[0] * 64.0 / rays, (double)hs[6] / ((double)w[0] * 64.0), (double)w[1] * 64.0 / rays,
@@ -1452,25 +1075,66 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
                 (double)w[3] / (double)w[0], (double)w[4] / (double)w[1]);
     }
 #endif
+    (void)c; (void)path; (void)hs;
+    return RTW_OK;
+}
+
+// One device: the whole render of the shard P describes, result in d_rgba (device memory of c->device).
+int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, rtw_stats* stats) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!s) s = c->stream;
+    const size_t npix = shard_rows(P) * (size_t)P->width;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (npix == 0) return RTW_OK;
+    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "tile too large");
+
+    const Tuning tune = read_tuning();
+    CallLog log{c, P->rng_kind, stats != nullptr && tune.kernel_timing};
+    HIP_TRY(c, log.event(log.begin));
+    HIP_TRY(c, log.event(log.end));
+    KArgs base = shard_args(c->sc, P, npix);
+    if (P->estimator != RTW_EST_REFERENCE) {  // the corrected estimators live in the cold-feature instantiations
+        base.sc.estimator = P->estimator; base.sc.has_tex = P->estimator == RTW_EST_MIXTURE ? 2 : 1;
+        base.sc.ray_tmin = 1.0e-3f; base.sc.probe_eps = 1.0e-3f;
+    }
+    // k_path: scenes walked with the brute lists; it packs a unit's pixel as x | y << 16, so frames wider or taller than 65535
+    // take the wavefront kernels
+    const bool path_small = !c->sc.use_bvh && c->sc.n_prims <= kPathMaxPrims && (c->sc.n_walk_words > 0 || c->sc.has_tex);
+    const bool fits16 = P->width <= 65535 && P->height <= 65535;
+    const bool use_path = P->max_depth > 0 && tune.path != 0 && fits16 && path_small;
+    int rc = use_path ? render_path(c, P, tune, base, (float4*)d_rgba, s, log) : render_wavefront(c, P, tune, base, (float4*)d_rgba, s, log);
+    if (rc) return rc;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(log.end, s));
+    HIP_TRY(c, hipEventSynchronize(log.end));
+
+    unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    {
+        unsigned long long rows_[kStatRows * 8];
+        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < kStatRows; r++)
+            for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
+    }
+    rc = print_diagnostics(c, use_path, hs);
+    if (rc) return rc;
     if (stats) {
         float ms = 0.f;
-        HIP_TRY_C(hipEventElapsedTime(&ms, ev_begin, ev_end));
+        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
         stats->seconds = (double)ms * 1e-3;
         stats->bounce_seconds = stats->seconds;  // the lanes overlap: the loop time is the elapsed time of the call
-        for (const Timed& t : ev_k) {
+        for (const CallLog::Timed& t : log.timed) {
             float m = 0.f;
-            HIP_TRY_C(hipEventElapsedTime(&m, t.a, t.b));
+            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
             stats->kernel_seconds[t.kind] += (double)m * 1e-3;
             stats->kernel_launches[t.kind]++;
         }
         for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];
-        stats->bounce_launches = launches;
+        stats->bounce_launches = log.launches;
         stats->samples = (uint64_t)npix * (uint64_t)P->spp;
         stats->segments = hs[0];
         stats->shadow_rays = hs[1];
         stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
     }
-#undef HIP_TRY_C
     return RTW_OK;
 }
 
@@ -1633,25 +1297,27 @@ int impl_render(rtw_ctx* c, const rtw_params* P, float* rgba_out, rtw_stats* sta
     return RTW_OK;
 }
 
-int impl_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t width, int32_t height, int32_t iterations, float sigma) {
-    if (!c) return RTW_ERR_INVALID_ARG;
-    if (!rgba_in || !rgba_out || rgba_in == rgba_out || width <= 0 || height <= 0 || iterations < 1 || iterations > 8 || !(sigma > 0.f) ||
-        (int64_t)width * height > (1 << 28))
-        return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise: bad argument");
+// rtw_denoise and rtw_denoise_guided on the context's device: the colour image (and the guides) in, `iterations` a-trous passes
+// that ping-pong between two buffers, the result out. pass(grid, in, out, albedo, normal, step, inv_sigma2) issues one pass.
+template <class Pass>
+int denoise_passes(rtw_ctx* c, const char* what, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, int32_t width,
+                   int32_t height, int32_t iterations, float sigma, Pass&& pass) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    float4* d[2] = {nullptr, nullptr};
+    const float* src[4] = {rgba_in, nullptr, albedo, normal};
+    const int n_buf = albedo ? 4 : 2;
+    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};  // ping, pong, albedo, normal
     auto cleanup = [&]() { for (float4* p : d) if (p) (void)hipFree(p); };
-    for (int k = 0; k < 2; k++)
-        if (hipMalloc(&d[k], bytes) != hipSuccess) { cleanup(); return fail(c, RTW_ERR_OOM, "rtw_denoise: device allocation failed"); }
-    hipError_t e = hipMemcpyAsync(d[0], rgba_in, bytes, hipMemcpyHostToDevice, c->stream);
-    const int n = width * height;
-    const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)n + kBlock - 1) / kBlock, (int64_t)c->n_cu * 8);
+    for (int k = 0; k < n_buf; k++)
+        if (hipMalloc(&d[k], bytes) != hipSuccess) { d[k] = nullptr; cleanup(); return fail(c, RTW_ERR_OOM, std::string(what) + ": device allocation failed"); }
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < n_buf && e == hipSuccess; k++)
+        if (src[k]) e = hipMemcpyAsync(d[k], src[k], bytes, hipMemcpyHostToDevice, c->stream);
+    const unsigned grid = pixel_grid(c, (size_t)width * height);
     int cur = 0;
     float s_i = sigma;
     for (int it = 0; it < iterations && e == hipSuccess; it++) {
-        hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(kBlock), 0, c->stream, (const float4*)d[cur], d[cur ^ 1], (int)width, (int)height, 1 << it,
-                           1.0f / (s_i * s_i));
+        pass(grid, (const float4*)d[cur], d[cur ^ 1], (const float4*)d[2], (const float4*)d[3], 1 << it, 1.0f / (s_i * s_i));
         e = hipGetLastError();
         cur ^= 1;
         s_i = s_i * 0.5f;
@@ -1659,8 +1325,19 @@ int impl_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t widt
     if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, d[cur], bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     cleanup();
-    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_denoise: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     return RTW_OK;
+}
+
+int impl_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t width, int32_t height, int32_t iterations, float sigma) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (!rgba_in || !rgba_out || rgba_in == rgba_out || width <= 0 || height <= 0 || iterations < 1 || iterations > 8 || !(sigma > 0.f) ||
+        (int64_t)width * height > (1 << 28))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise: bad argument");
+    return denoise_passes(c, "rtw_denoise", rgba_in, nullptr, nullptr, rgba_out, width, height, iterations, sigma,
+                          [&](unsigned grid, const float4* in, float4* out, const float4*, const float4*, int step, float inv_s2) {
+                              hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(kBlock), 0, c->stream, in, out, (int)width, (int)height, step, inv_s2);
+                          });
 }
 
 // rtw.h rtw_render_guides: one k_guides launch on the context's device (a group's: device_ids[0], with that device's copy of the scene)
@@ -1676,17 +1353,8 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
     if (npix == 0) return RTW_OK;
     if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_render_guides: tile too large");
     HIP_TRY(c, hipSetDevice(d->device));
-    KArgs a{};
-    a.sc = d->sc;  // the uploaded scene as it is: the reference's ray tmin whatever P->estimator says
-    a.npix = (uint32_t)npix;
-    a.width = (uint32_t)P->width;
-    a.height = (uint32_t)P->height;
-    a.row0 = (uint32_t)P->row0;
-    a.row_stride = P->row_stride > 1 ? (uint32_t)P->row_stride : 1u;
-    a.seed = P->seed;
+    KArgs a = shard_args(d->sc, P, npix);  // the uploaded scene as it is: the reference's ray tmin whatever P->estimator says
     a.sample0 = (uint32_t)P->sample_offset;
-    a.spp = (uint32_t)P->spp;
-    a.stack_stride = kBlock;
     // one device allocation: albedo, normal (16 B per pixel each), depth, prim (4 B each), whichever were asked for
     const size_t sz[4] = {G->albedo ? npix * 16 : 0, G->normal ? npix * 16 : 0, G->depth ? npix * 4 : 0, G->prim ? npix * 4 : 0};
     size_t off[5] = {0};
@@ -1710,9 +1378,8 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
         if (e == hipSuccess) e = hipEventCreate(&ev[1]);
         if (e == hipSuccess) e = hipEventRecord(ev[0], d->stream);
     }
-    const unsigned grid = (unsigned)std::min<size_t>((npix + kBlock - 1) / kBlock, (size_t)d->n_cu * 8);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_guides, dim3(grid), dim3(kBlock), d->lds_bytes, d->stream, a, g);
+        hipLaunchKernelGGL(k_guides, dim3(pixel_grid(d, npix)), dim3(kBlock), d->lds_bytes, d->stream, a, g);
         e = hipGetLastError();
     }
     if (e == hipSuccess && stats) e = hipEventRecord(ev[1], d->stream);
@@ -1740,31 +1407,11 @@ int impl_denoise_guided(rtw_ctx* c, const float* rgba_in, const float* albedo, c
         height <= 0 || iterations < 1 || iterations > 8 || !(sigma > 0.f) || !(sigma_albedo > 0.f) || !(sigma_normal > 0.f) ||
         !std::isfinite(inv_a) || !std::isfinite(inv_n) || (int64_t)width * height > (1 << 28))
         return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise_guided: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};  // ping, pong, albedo, normal
-    auto cleanup = [&]() { for (float4* p : d) if (p) (void)hipFree(p); };
-    for (int k = 0; k < 4; k++)
-        if (hipMalloc(&d[k], bytes) != hipSuccess) { d[k] = nullptr; cleanup(); return fail(c, RTW_ERR_OOM, "rtw_denoise_guided: device allocation failed"); }
-    hipError_t e = hipMemcpyAsync(d[0], rgba_in, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d[2], albedo, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d[3], normal, bytes, hipMemcpyHostToDevice, c->stream);
-    const int n = width * height;
-    const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)n + kBlock - 1) / kBlock, (int64_t)c->n_cu * 8);
-    int cur = 0;
-    float s_i = sigma;
-    for (int it = 0; it < iterations && e == hipSuccess; it++) {
-        hipLaunchKernelGGL(k_atrous_guided, dim3(grid), dim3(kBlock), 0, c->stream, (const float4*)d[cur], (const float4*)d[2], (const float4*)d[3],
-                           d[cur ^ 1], (int)width, (int)height, 1 << it, 1.0f / (s_i * s_i), inv_a, inv_n);
-        e = hipGetLastError();
-        cur ^= 1;
-        s_i = s_i * 0.5f;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, d[cur], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
-    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_denoise_guided: ") + hipGetErrorString(e));
-    return RTW_OK;
+    return denoise_passes(c, "rtw_denoise_guided", rgba_in, albedo, normal, rgba_out, width, height, iterations, sigma,
+                          [&](unsigned grid, const float4* in, float4* out, const float4* alb, const float4* nrm, int step, float inv_s2) {
+                              hipLaunchKernelGGL(k_atrous_guided, dim3(grid), dim3(kBlock), 0, c->stream, in, alb, nrm, out, (int)width, (int)height, step,
+                                                 inv_s2, inv_a, inv_n);
+                          });
 }
 
 int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, int n, float* out_t, int32_t* out_prim) {

@@ -1,6 +1,6 @@
 // rtw_inst_path.hip - the instantiations of k_path (and k_classify), compiled as a translation unit of their own so that
 // __graft_entry__.build() can compile the library's kernels in parallel (-DRTW_SPLIT_BUILD: rtw_hip.hip then only declares
-// them). A single-file build of rtw_hip.hip (scripts/build_variant.sh, the experiments build) instantiates them itself.
+// them). A single-file build of rtw_hip.hip (scripts/build_variant.sh) instantiates them itself.
 #include <hip/hip_runtime.h>
 
 #define RTW_TEMPLATES_ONLY

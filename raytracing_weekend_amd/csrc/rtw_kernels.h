@@ -2,7 +2,6 @@
 //
 //   k_path       small scenes: whole paths in registers, lanes own (pixel, sample block) units and regenerate; LDS candidate
 //                lists and hit records; only 16-byte unit sums reach HBM
-//   k_path_tree  the same for tree scenes, lanes vote on the kind of step (slower than the wavefront kernels: -DRTW_EXPERIMENTS builds only)
 //   k_first      generate primary rays (raygen.cu:123-147, camera.cu:11-19), trace and shade the primary segment
 //   k_shade      closest-hit / miss programs for one bounce of every live path: (media: the volume pass), material
 //                scatter, texture, light sampling (the shadow ray is QUEUED in the path state, not traced), Russian
@@ -27,6 +26,7 @@
 // shadow probe still queued: it survives one more trace pass, collects the contribution and retires.
 #pragma once
 #include "rtw_device.h"
+#include "rtw_plan.h"
 
 namespace rtwk {
 using namespace rtwdev;
@@ -65,14 +65,6 @@ RTW_DEV void rtw_sub_stamp(int id) {
 #define RTW_MARK2(name) asm volatile("; MARK " name)
 #define RTW_SUB(id)
 #endif
-constexpr int kBlock = 256;                       // 4 wave64 per workgroup
-#ifndef RTW_MAX_REGIONS
-#define RTW_MAX_REGIONS 1024
-#endif
-// 1 024 regions = 4 compacting workgroups per CU (what two lanes use; a single lane used to take 8). Round 3 halved the table: it is
-// static LDS of every wavefront kernel (4 KB instead of 8), and LDS is what decides whether the other lane's workgroups find room
-// on a CU beside a resident k_trace_bvh (scene 4 +5 %, scene 1 +2 %).
-constexpr uint32_t kMaxRegions = RTW_MAX_REGIONS;            // region counters scanned in LDS by every workgroup (>= the compacting grid)
 constexpr uint32_t kZombie = 0x80000000u;
 constexpr uint32_t kNeePrev = 0x40000000u;       // gk bit 30 (corrected estimator): a light sample was taken at the previous vertex
 
@@ -1109,24 +1101,11 @@ __global__ void __launch_bounds__(BLOCK, RTW_TRACE_BVH_WAVES) k_trace_bvh(const 
 #ifndef RTW_SHADE_COLD_WAVES
 #define RTW_SHADE_COLD_WAVES 5
 #endif
-// RTW_SHADE_SORT=1 (experiment, off): deal a chunk's paths to the threads by hit material. Measured: k_shade 4-7 % SLOWER on
-// scenes 1, 2, 4 with one lane or two. Round 3 repeated it with the material class carried in the hit record (no lookup at all) and
-// the next chunk's hit records fetched a chunk ahead: still 4 % slower on scene 1, 1-2 % on scenes 2 and 4 (bit-exact). The kernel
-// waits on its path loads (61 % of its wave-cycles, rocprofv3 round 3) and issues VALU for 22 % of them: the serialised material
-// branches hide behind the loads, and the sort's two barriers and permuted loads do not.
-#if !defined(RTW_SHADE_SORT) || !defined(RTW_EXPERIMENTS)
-#undef RTW_SHADE_SORT
-#define RTW_SHADE_SORT 0
-#endif
 template <int KIND, int TEX>
 __global__ void __launch_bounds__(kBlock, TEX ? RTW_SHADE_COLD_WAVES : RTW_SHADE_WAVES) k_shade(const KArgs A) {
     RTW_WORKLIST_SHARED
     RTW_CURSOR_SHARED
     RTW_NOISE_SHARED
-#if RTW_SHADE_SORT
-    __shared__ uint32_t s_sort_cnt[8 * (kBlock / 64)];
-    __shared__ uint16_t s_sort_perm[kBlock];
-#endif
     const uint32_t tid = threadIdx.x;
     cursor_init(s_cursor);
     const uint32_t* noise_lds = stage_noise<(TEX != 0)>(A.sc, s_noise);
@@ -1141,45 +1120,11 @@ __global__ void __launch_bounds__(kBlock, TEX ? RTW_SHADE_COLD_WAVES : RTW_SHADE
         Path p;
         p.gk = 0; p.ltmax = -1.f;
         uint2 h = make_uint2(0u, 0u);
-#if RTW_SHADE_SORT
-        // The chunk's paths are dealt to the threads by the material they hit (a counting sort over 8 keys through LDS:
-        // hit record -> material type -> rank by ballot, two barriers), so that a wave shades one or two kinds of vertex
-        // instead of all of them one after the other: unsorted, k_shade ran at a lane utilisation of 0.29 on scene 1.
-        // Which thread shades which path cannot show in the image (a path's draws are its own).
-        {
-            const size_t base_slot = (size_t)region * A.region_cap + chunk * kBlock;
-            uint32_t key = 7u;  // threads beyond the chunk's paths go last
-            if (valid) {
-                const uint2 h0 = A.hit[base_slot + tid];
-                const int prim0 = (int)(h0.y & 0x3fffffffu) - 1;
-                key = prim0 < 0 ? 6u : min((uint32_t)*as_const(&A.sc.hitrec[prim0].mat_type), 5u);
-            }
-            uint32_t rank = 0u, mine = 0u;
-            for (uint32_t k = 0; k < 8u; k++) {
-                const unsigned long long m = __ballot(key == k);
-                if ((tid & 63u) == 0u) s_sort_cnt[k * (kBlock / 64) + (tid >> 6)] = (uint32_t)__popcll(m);
-                if (key == k) { rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); mine = k * (kBlock / 64) + (tid >> 6); }
-            }
-            __syncthreads();
-            uint32_t before = 0u;
-            for (uint32_t j = 0; j < mine; j++) before += s_sort_cnt[j];  // key-major, wave-minor: <= 31 broadcast reads
-            s_sort_perm[before + rank] = (uint16_t)tid;
-            __syncthreads();
-            if (valid) {
-                const size_t slot = base_slot + s_sort_perm[tid];
-                load_shade_part(A.in, slot, p, A.sc.n_lights > 0);
-                h = A.hit[slot];
-            }
-            // (no barrier is needed before the next chunk's sort: its counts are written while at most s_sort_perm is still being
-            // read, and its first barrier stands before s_sort_perm is written again)
-        }
-#else
         if (valid) {
             const size_t slot = (size_t)region * A.region_cap + chunk * kBlock + tid;
             load_shade_part(A.in, slot, p, A.sc.n_lights > 0);
             h = A.hit[slot];
         }
-#endif
         vc += gridDim.x;
         if (vc < wl.total_chunks) worklist_lookup(wl, A.n_regions, vc, region, chunk, n_valid);
         if (valid) {
@@ -1383,9 +1328,6 @@ __global__ void __launch_bounds__(kBlock) k_classify(const KArgs A, uint32_t* __
 // reaches HBM. The image does not depend on which lane ran which unit: a block's sum is a function of (pixel, block) alone,
 // and the per-pixel sums are taken block by block in order (k_resolve_blocks) - the summation order of the arithmetic spec.
 // The host runs a pass as two overlapping launches (rtw_hip.hip): the bulk in 4-block units, the last blocks one by one.
-constexpr uint32_t kSumBlock = RTW_SUM_BLOCK;
-constexpr uint32_t kSumUnitBlocks = RTW_SUM_UNIT_BLOCKS;
-constexpr int kPathMaxPrims = 64;  // k_path walks the brute lists only: scenes of at most this many primitives
 // RTW_MARK: a phase fence (see RTW_MARK2 above); the diagnostic build -DRTW_PHASE_TIMERS (never shipped) also accumulates
 // s_memtime deltas per phase and wave there (printed by the host)
 #if defined(RTW_PHASE_TIMERS)
@@ -1609,272 +1551,6 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
         if (n_shadow) atomicAdd(&row[1], (unsigned long long)n_shadow);
     }
 }
-
-#ifdef RTW_EXPERIMENTS  // measured slower than the default paths: built by scripts/build_variant.sh only, never by build()
-// ------------------------------------------------------------------ k_path_tree
-// Tree scenes, same idea as k_path (paths in registers, lanes own units of one pixel x one sample block and regenerate,
-// only the unit sums reach HBM), but a ray's walk through the BVH takes a different number of steps in every lane, so a
-// lane is a small state machine and the wave executes ONE kind of step at a time, chosen by vote:
-//   inner step   lanes standing at an inner node test its two children (bvh_inner_step, LDS stack column per lane)
-//   leaf step    lanes standing at a leaf test one of its primitives
-//   shade step   lanes whose radiance ray has come back run the closest-hit / miss program, roulette, and - when the
-//                sample ends - add it to the unit and start the next camera path; it is the expensive step, so it waits
-//                until RTW_TREE_SHADE_AT lanes want it (or nobody can do anything else)
-// A path alternates: [shadow probe of the previous vertex, if a light sample is pending] -> radiance ray -> shade.
-// The probe's contribution c = f * Le * w * T is held in registers and added to L when the probe comes back free: the
-// same floating-point order as the wavefront kernels (and the oracle). Media are tested in the shade step, where the
-// generator is, exactly as k_shade does.
-#ifndef RTW_TREE_SHADE_AT
-#define RTW_TREE_SHADE_AT 40
-#endif
-#ifndef RTW_TREE_WAVES
-#define RTW_TREE_WAVES RTW_MIN_WAVES
-#endif
-template <int KIND, int TEX>
-__global__ void __launch_bounds__(kBlock, RTW_TREE_WAVES) k_path_tree(const KArgs A) {
-    extern __shared__ uint32_t s_stack[];
-    RTW_NOISE_SHARED
-    const uint32_t tid = threadIdx.x;
-    const uint32_t* noise_lds = stage_noise<(TEX != 0)>(A.sc, s_noise);
-    const TravMem tm = trav_mem(A.sc, s_stack, kBlock, tid);
-    const uint32_t lane = tid & 63u;
-    const uint32_t root = A.sc.n_tree > 0 ? 0u : kBvhDone;
-    // wave-uniform: the job stream
-    uint32_t u_next = 0, u_end = 0, job_g = 0, job_b = 0;
-    bool exhausted = false;
-    // per lane: the unit
-    bool need = true;
-    uint32_t pxy = 0, blk = 0, blk_end = 0, s_cur = 0;
-    v3 usum = V(0.f, 0.f, 0.f);
-    // per lane: the path
-    enum { PH_SHADE = 0, PH_PROBE = 1, PH_RAY = 2 };  // what the lane waits for: the shade step, or its walk (probe / radiance ray)
-    uint32_t phase = PH_SHADE;
-    bool alive = false;      // false in PH_SHADE: the sample is over (or none was started): finish it and regenerate
-    bool fresh = true;       // no sample to finish (a new unit)
-    uint32_t depth = 0, rng_a = 0, rng_b = 0, gk = 0, nee_prev = 0;
-    float ray_time = 0.f;
-    v3 o = V(0.f, 0.f, 0.f), d = o, T = o, L = o;
-    v3 ldir = o, c = o;      // pending light sample: probe direction, contribution
-    float ltmax = -1.f;
-    // per lane: the walk
-    uint32_t cur = kBvhDone, pend = 0;
-    int sp = 0, best_prim = -1;
-    float best_t = 0.f, tmin = 0.f, wtime = 0.f;
-    v3 wd = o, inv = o;
-    uint32_t n_seg = 0, n_shadow = 0;
-#ifdef RTW_PHASE_TIMERS
-    unsigned long long ph_cyc[6] = {0, 0, 0, 0, 0, 0}, ph_t0 = __builtin_amdgcn_s_memtime();
-    int ph_cur = 0;
-    unsigned long long st_cnt[3] = {0, 0, 0};
-#endif
-    for (;;) {
-        RTW_MARK("refill");
-        // ---- units
-        unsigned long long need_mask = __ballot(need);
-        while (need_mask != 0ull && !exhausted) {
-            if (u_next >= u_end) {
-                uint32_t q = 0;
-                if (lane == 0) q = atomicAdd(A.queue, 1u);
-                q = __builtin_amdgcn_readfirstlane(q);
-                if (q >= A.n_jobs) { exhausted = true; break; }
-                const uint32_t gi = q / A.n_ranges;
-                job_g = order_lookup(A, gi);
-                job_b = (q - gi * A.n_ranges) * A.units_per_job;
-                u_next = 0; u_end = 64u * A.units_per_job;
-                continue;
-            }
-            const uint32_t avail = u_end - u_next;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
-            if (need && rank < avail) {
-                const uint32_t u = u_next + rank;
-                const uint32_t b = (job_b + (u >> 6)) * A.unit_blocks;
-                const uint32_t p_local = job_g * 64u + (u & 63u);
-                if (p_local < A.npix && b < A.n_blocks_pass) {
-                    need = false;
-                    blk = b;
-                    blk_end = min(b + A.unit_blocks, A.n_blocks_pass);
-                    const uint32_t yl = fastdiv(p_local, A.divw_m, A.divw_s1, A.divw_s2);
-                    pxy = (p_local - yl * A.width) | ((A.row0 + yl * A.row_stride) << 16);
-                    s_cur = (A.block0 + b) * kSumBlock;
-                    usum = V(0.f, 0.f, 0.f);
-                    phase = PH_SHADE; alive = false; fresh = true;
-                }
-            }
-            u_next += min((uint32_t)__popcll(need_mask), avail);
-            need_mask = __ballot(need);
-        }
-        const unsigned long long busy_mask = __ballot(!need);
-        if (busy_mask == 0ull) break;
-        const bool busy = !need;
-        // ---- vote
-        const bool want_shade = busy && phase == PH_SHADE;
-        const uint32_t n_busy = (uint32_t)__popcll(busy_mask);
-        const uint32_t n_shade = (uint32_t)__popcll(__ballot(want_shade));
-        if (n_shade >= (uint32_t)RTW_TREE_SHADE_AT || n_shade == n_busy) {
-            // ---- shade step
-            RTW_MARK("shade_a");
-#ifdef RTW_PHASE_TIMERS
-            st_cnt[0]++;
-#endif
-            if (want_shade) {
-                const uint32_t px = pxy & 0xffffu, py = pxy >> 16;
-                const uint32_t pixel = A.width * py + px;
-                Rng<KIND> g;
-                if (alive) {
-                    if (KIND == RTW_RNG_TEA_LCG) g.init(A.seed, 0, 0, rng_a, rng_b);
-                    else g.init(A.seed, pixel, A.sample0 + s_cur, rng_a, A.sample0 + s_cur);
-                    const float gt = gather_time_of(A, gk);
-                    int prim = best_prim;
-                    float th = best_t;
-                    if (TEX && A.sc.n_vol > 0) {  // media: tested here, before this segment's closest-hit draws (see k_shade)
-                        float tv = 1.e27f;
-                        int pv = -1;
-                        if (volume_pass<Rng<KIND>, false>(A.sc, o, d, A.sc.ray_tmin, ray_time, gt, g, tv, pv) && !(prim >= 0 && th < tv)) { th = tv; prim = pv; }
-                    }
-                    v3 so, sd, att, radiance;
-                    Nee nee;
-                    const int ev = shade_a<KIND, TEX>(A.sc, g, o, d, gt, th, prim, so, sd, att, radiance, nee, noise_lds, nee_prev);
-                    n_seg++;
-                    ltmax = -1.0f;
-                    if (nee.has) {
-                        n_shadow++;
-                        bool fogged = false;
-                        if (TEX && A.sc.n_vol > 0) {  // the probe's volume share (any hit), right after the light-sample draws
-                            float tv = nee.tmax;
-                            int pv = -1;
-                            fogged = volume_pass<Rng<KIND>, true>(A.sc, so, nee.dir, nee.tmin, 0.0f, gt, g, tv, pv);
-                        }
-                        if (!fogged) { ldir = nee.dir; ltmax = nee.tmax; c = vmul(nee.rad, T); }
-                    }
-                    alive = shade_b<KIND>(depth, A.max_depth, g, ev, so, sd, att, radiance, o, d, T, L, TEX == 2 && A.sc.estimator == RTW_EST_MIXTURE);
-                    if (ev == EV_HIT) o = so;  // a pending probe starts at the hit point even when the path stops here
-                    depth++;
-                    rng_a = g.a; rng_b = g.b;
-                    if (alive) {
-                        ray_time = (KIND == RTW_RNG_TEA_LCG || A.sc.has_motion) ? g.ray_time(depth) : 0.0f;
-                        rng_b = g.b;
-                    }
-                    fresh = false;
-                    if (ltmax >= 0.0f) phase = PH_PROBE;        // (a dead path with a probe pending comes back here once it is traced)
-                    else if (alive) phase = PH_RAY;
-                }
-                if (phase == PH_SHADE) {
-                    // the sample is over (or the unit is new): removeNaNs (raygen.cu:17-24), the unit's running sum, the next camera path
-                    if (!fresh) {
-                        usum = vadd(usum, V((L.x == L.x) ? L.x : 0.f, (L.y == L.y) ? L.y : 0.f, (L.z == L.z) ? L.z : 0.f));
-                        s_cur++;
-                        if ((s_cur % kSumBlock) == 0u || s_cur >= A.spp) {
-                            const uint32_t yl_ = A.row_stride > 1 ? fastdiv(py - A.row0, A.divs_m, A.divs_s1, A.divs_s2) : py - A.row0;
-                            A.blocksum[(size_t)blk * A.npix + (yl_ * A.width + px)] = make_float4(usum.x, usum.y, usum.z, 0.f);
-                            usum = V(0.f, 0.f, 0.f);
-                            blk++;
-                            need = blk >= blk_end || s_cur >= A.spp;
-                        }
-                    }
-                    if (!need) {
-                        Path p;
-                        raygen<KIND>(A, px, py, A.sample0 + s_cur, 0u, p, g);
-                        o = p.o; d = p.d; T = p.T; L = p.L; rng_a = p.a; rng_b = p.b; ray_time = p.ray_time; gk = p.gk;
-                        depth = 0; nee_prev = 0; alive = true; fresh = false; ltmax = -1.0f;
-                        phase = PH_RAY;
-                    }
-                }
-                // start the walk the lane now waits for
-                if (!need) {
-                    if (phase == PH_PROBE) { wd = ldir; tmin = A.sc.probe_eps; best_t = ltmax; wtime = 0.0f; }
-                    else { wd = d; tmin = A.sc.ray_tmin; best_t = 1.e27f; wtime = ray_time; }
-                    inv = recip3(wd);
-                    best_prim = -1; sp = 0; cur = root;
-                }
-            }
-            continue;
-        }
-        // ---- walk step: inner nodes while the lanes standing at one are not outnumbered, then the primitives of the leaves
-        // put aside (a lane that comes to a leaf walks on with the next node of its stack: see k_trace_bvh)
-        RTW_MARK("walk_r");
-        const bool walking = busy && phase != PH_SHADE;
-        const uint32_t n_walk = n_busy - n_shade;
-#define RTW_SET_ASIDE if (walking && pend == 0u && ((cur & 3u) - 1u) < 2u) { pend = cur; cur = bvh_pop(tm, sp); }
-        RTW_SET_ASIDE
-        bool at_inner = walking && (cur & 3u) == 0u;
-        for (;;) {
-            const uint32_t n_in = (uint32_t)__popcll(__ballot(at_inner));
-            if (n_in == 0u || n_in * (uint32_t)RTW_LEAF_BIAS < (n_walk - n_in) * (uint32_t)RTW_LEAF_BIAS_DEN) break;
-            if (at_inner) {
-                if (tm.wide) {
-                    cur = bvh_inner_step(A.sc, tm, o, inv, tmin, best_t, cur, sp);
-                    RTW_SET_ASIDE
-                } else {
-                    bvh_step16<false>(A.sc, tm, o, inv, tmin, best_t, cur, pend, sp);
-                }
-                at_inner = (cur & 3u) == 0u;
-            }
-#ifdef RTW_PHASE_TIMERS
-            st_cnt[1]++;
-#endif
-        }
-#ifdef RTW_PHASE_TIMERS
-        st_cnt[2]++;
-#endif
-        RTW_MARK("walk_s");
-        if (walking && pend != 0u) {
-            uint32_t lslot = pend >> 2;
-            const uint32_t cnt = pend & 3u;
-            pend = 0u;
-            bool stop = false;
-#pragma unroll
-            for (uint32_t k = 0; k < (uint32_t)RTW_LEAF_MAX; k++) {
-                if (k < cnt && !stop) {
-                    int pi;
-                    float t;
-                    if (leaf_test(A.sc, tm, lslot, o, wd, inv, tmin, wtime, gather_time_of(A, gk), t, pi, lslot)) {
-                        // same acceptance rule as traverse<>: closest, ties to the lowest primitive index; any hit ends a probe
-                        if (t < best_t || (phase == PH_RAY && t == best_t && best_prim >= 0 && pi < best_prim)) {
-                            best_t = t; best_prim = pi;
-                            stop = phase == PH_PROBE;
-                        }
-                    }
-                }
-            }
-            if (stop) cur = kBvhDone;
-            RTW_SET_ASIDE
-        }
-#undef RTW_SET_ASIDE
-        RTW_MARK("shade_b");
-        if (walking && cur == kBvhDone && pend == 0u) {
-            if (phase == PH_PROBE) {
-                // traceOcclusion (closehit.cu:16-42) is back: a free path to the light adds the held contribution
-                if (best_prim < 0) L = vadd(L, c);
-                ltmax = -1.0f;
-                if (alive) {
-                    phase = PH_RAY;
-                    wd = d; tmin = A.sc.ray_tmin; best_t = 1.e27f; wtime = ray_time;
-                    inv = recip3(wd);
-                    best_prim = -1; sp = 0; cur = root;
-                } else {
-                    phase = PH_SHADE;  // the path ended at that vertex: finish the sample
-                }
-            } else {
-                phase = PH_SHADE;      // best_t / best_prim hold the closest hit
-            }
-        }
-    }
-#ifdef RTW_PHASE_TIMERS
-    RTW_MARK("refill");
-    if (lane == 0) { for (int q = 0; q < 6; q++) atomicAdd(&A.stats[kStatRows * 8 + q], ph_cyc[q]); atomicAdd(&A.stats[kStatRows * 8 + 6], st_cnt[1]); atomicAdd(&A.stats[kStatRows * 8 + 7], st_cnt[0] * 1000000ull + st_cnt[2]); }
-#endif
-    for (int off = 32; off > 0; off >>= 1) {
-        n_seg += __shfl_down(n_seg, off);
-        n_shadow += __shfl_down(n_shadow, off);
-    }
-    if (lane == 0) {
-        unsigned long long* row = stat_row(A);
-        if (n_seg) { atomicAdd(&row[0], (unsigned long long)n_seg); atomicAdd(&row[2 + RTW_K_PATH], (unsigned long long)n_seg); }
-        if (n_shadow) atomicAdd(&row[1], (unsigned long long)n_shadow);
-    }
-}
-
-#endif  // RTW_EXPERIMENTS
 
 #ifndef RTW_TEMPLATES_ONLY  // (the translation units that only instantiate the shading kernels leave the plain kernels to rtw_hip.hip)
 // per-pixel sums of one k_path pass in the arithmetic spec's order (rtw.h: samples in order inside blocks, block sums in order

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: scripts/ab_variants.sh <variant> [<variant> ...] -- "<bench_scene args>" ["<bench_scene args>" ...]
 # bench_scene.py once per (variant library, scene); a variant is a name under csrc/variants (librtw_<name>.so), "tree" for
-# the in-tree library, and may carry environment settings in front: "RTW_PATH_TREE=1 base". One compact line per run; the
+# the in-tree library, and may carry environment settings in front: "RTW_LANES=1 base". One compact line per run; the
 # CRC of the image shows at once when a variant changes a bit.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R

@@ -211,7 +211,7 @@ def test_image_does_not_depend_on_the_launch_schedule(gpu, monkeypatch):
             {"RTW_POOL_PATHS": "30000", "RTW_STAGGER": "0"}, {"RTW_POOL_PATHS": "30000", "RTW_STAGGER": "30"},
             {"RTW_FIRST_GROUP_LOG2": "0"}, {"RTW_FIRST_GROUP_LOG2": "6", "RTW_POOL_PATHS": "200000"},
             {"RTW_TRACE_BLOCK": "512", "RTW_TRACE_LDS_KB": "40"}, {"RTW_TRACE_WAVES": "3", "RTW_TRACE_LDS_KB": "5"}]
-    # (k_path_tree and the paired schedule left the product library in round 3: tests/test_gpu_round3.py keeps one variant test)
+    # (the tree variant of k_path and the paired batch schedule were measured slower and removed: DESIGN.md 4.2)
     knobs = [{}, {"RTW_BRUTE_MAX": "0", "RTW_PATH_JOB_BLOCKS": "1", "RTW_PATH_GRID_MULT": "1"},
              {"RTW_PATH_JOB_BLOCKS": "7", "RTW_BLOCKSUM_BYTES": "65536"}, {"RTW_PATH_GRID_MULT": "2", "RTW_KERNEL_TIMING": "0"},
              {"RTW_PATH_FINE_BLOCKS": "1", "RTW_PATH_UNIT_BLOCKS": "3"}, {"RTW_PATH_FINE_BLOCKS": "0", "RTW_PATH_UNIT_BLOCKS": "4"},

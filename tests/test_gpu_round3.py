@@ -242,32 +242,6 @@ def test_group_render_creates_no_threads_per_call(gpu):
         grp.close()
 
 
-def test_experimental_kernels_stay_bit_exact(tmp_path):
-    """k_path_tree and the paired batch schedule are no longer in the product library; a -DRTW_EXPERIMENTS
-    build keeps them alive. One variant test: built here with hipcc (about a minute), each knob must reproduce the product
-    library's image and counts on a tree scene."""
-    lib = str(tmp_path / "librtw_experiments.so")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this box")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    subprocess.run([hipcc] + ge.HIP_FLAGS + ["-DRTW_EXPERIMENTS", "-o", lib, os.path.join(ge.CSRC, "rtw_hip.hip")], check=True, timeout=900)
-    script = ("import sys, json, zlib; sys.path.insert(0, %r); from raytracing_weekend_amd import abi; r = abi.Renderer(0); "
-              "r.upload_scene(abi.build_scene(1, 160, 120)); img, st = r.render(abi.make_params(160, 120, 24, 20)); "
-              "print(json.dumps([zlib.crc32(img.tobytes()), st.segments, st.shadow_rays]))" % ROOT)
-
-    def run(env_extra):
-        env = dict(os.environ, **env_extra)
-        out = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-        return json.loads(out.stdout.strip().splitlines()[-1])
-    want = run({})
-    assert run({"RTW_HIP_LIB": lib}) == want
-    assert run({"RTW_HIP_LIB": lib, "RTW_PATH_TREE": "1"}) == want
-    assert run({"RTW_HIP_LIB": lib, "RTW_PAIRED": "1", "RTW_POOL_PATHS": "200000"}) == want
-
-
 def test_pool_that_does_not_fit_is_halved_not_refused(monkeypatch):
     """The wavefront pipeline keeps up to 2^29 paths in flight (120 GiB of state on an MI355X it has to itself). When the
     allocation fails - here: a pool of 2^33 paths asked for through the knob, 2 TB - the render halves the pool until it fits

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RTW_ABI_VERSION 3   /* entry points and the structs they take (rtw_params, rtw_stats, rtw_guides) */
+#define RTW_ABI_VERSION 4   /* entry points and the structs they take (rtw_params, rtw_stats, rtw_guides, rtw_adaptive) */
 #define RTW_SCENE_VERSION 1 /* layout of the scene blob (rtw_scene_header.version) */
 #define RTW_SCENE_MAGIC 0x57545221u /* "!RTW" */
 /* Summation order of a pixel's samples (part of the arithmetic contract). Three levels, all counted from
@@ -346,6 +346,43 @@ int rtw_render_guides(rtw_ctx* ctx, const rtw_params* params, const rtw_guides* 
  * rgba_out may alias none of them; alpha is copied. iterations in 1..8; sigma, sigma_albedo, sigma_normal > 0. */
 int rtw_denoise_guided(rtw_ctx* ctx, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out,
                        int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal);
+
+/* Adaptive sampling: every pixel renders until its noise estimate falls below a target, or up to a sample cap.
+ *   Cap and layout: params->spp is the cap, a multiple of RTW_SUM_BLOCK. Every other field of rtw_params means what it means
+ *     for rtw_render (rows, row_stride, seed, rng_kind, sample_offset, estimator, samples_per_pass); the outputs use rtw_render's
+ *     row layout. rgba_out is required (rows*width float4); spp_out (rows*width int32) and error_out (rows*width float) may be NULL.
+ *   Checkpoints: a fixed sequence that depends on (min_spp, step_spp, params->spp) alone: n_0 = min_spp,
+ *     n_{k+1} = min(cap, n_k + step), step = step_spp or, when step_spp is 0, n_k / 2 rounded up to a multiple of RTW_SUM_BLOCK
+ *     (64 to 4096: 64 96 144 224 336 512 768 1152 1728 2592 3888 4096). It never depends on the device, tuning knobs or timing.
+ *   Samples per pixel: pixel p renders samples [sample_offset, sample_offset + n_p), n_p a checkpoint; a pixel that stopped never
+ *     resumes. Its colour is, bit for bit, rtw_render's colour of that pixel with spp = n_p.
+ *   Error estimate: batch means over the pixel's RTW_SUM_BLOCK-sample block sums S_b (the bits both pipelines form):
+ *     y_b = ((0.2126f*S.x + 0.7152f*S.y) + 0.0722f*S.z) * 0.0625f in fp32, no contraction; M1 = sum y_b and M2 = sum y_b*y_b in
+ *     fp64, in block order; with B = n / RTW_SUM_BLOCK: m = M1 / B, v = max(0, (M2 - M1*m) / (B - 1)), se = sqrt(v / B),
+ *     err = se / (2 sqrt(max(m, 1e-3))) in fp64, rounded to fp32. err is the standard error of the display value sqrt(Y), so a
+ *     threshold reads as a fraction of full display scale. A NaN err compares false: that pixel goes on.
+ *   Stop rule: at checkpoint n_k an active pixel stops if n_k is the cap; otherwise if its own err < threshold and, with dilate = 1,
+ *     every still-active pixel of its 3x3 neighbourhood (in the output's own rows, clamped at the edges) has err < threshold too.
+ *     A pixel that stopped earlier never blocks a neighbour.
+ *   Shards: with dilate = 0 every row of a shard (row0 / row1 / row_stride) equals the same row of the full-frame adaptive render;
+ *     with dilate = 1 that holds for whole frames only (the neighbourhood is the shard's own rows).
+ *   error_out: the pixel's err at its last checkpoint.
+ *   Groups (n_devices > 1): the render runs on device_ids[0], as rtw_render_guides does.
+ *   stats (may be NULL): samples = sum of n_p; segments, shadow_rays, kernel_seconds and kernel_launches summed over the passes
+ *     (the list kernels count under their base kinds); seconds = device time from the call's first event to its last;
+ *     algorithmic_bytes = 128*segments + 32*samples.
+ *   Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for bad params, a cap or min_spp that is not a multiple of
+ *     RTW_SUM_BLOCK, min_spp < 2*RTW_SUM_BLOCK or above the cap, step_spp < 0 or not a multiple of RTW_SUM_BLOCK, a negative or
+ *     NaN threshold, dilate not 0 or 1. The context stays usable after an error. */
+typedef struct rtw_adaptive {
+    int32_t min_spp;   /* samples every pixel gets; a multiple of RTW_SUM_BLOCK, >= 2 * RTW_SUM_BLOCK, <= params->spp      */
+    int32_t step_spp;  /* 0: each pass adds half of what the pixel has (rounded up to RTW_SUM_BLOCK); else a fixed multiple */
+    float threshold;   /* a pixel stops once its error estimate is below this (strict <); 0: no pixel stops early; +inf ok   */
+    int32_t dilate;    /* 0: each pixel decides alone; 1: a pixel also continues while an active 3x3 neighbour is above it  */
+} rtw_adaptive;     /* 16 B */
+
+int rtw_render_adaptive(rtw_ctx* ctx, const rtw_params* params, const rtw_adaptive* ad, float* rgba_out, int32_t* spp_out,
+                        float* error_out, rtw_stats* stats);
 
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.

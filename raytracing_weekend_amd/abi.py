@@ -14,7 +14,7 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 HOST_LIB = os.path.join(PKG_DIR, "host", "librtw_host.so")
 HIP_LIB = os.environ.get("RTW_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "librtw_hip.so")
 
-RTW_ABI_VERSION = 3
+RTW_ABI_VERSION = 4
 RTW_SCENE_VERSION = 1
 RTW_SCENE_MAGIC = 0x57545221
 RTW_RNG_PHILOX = 0
@@ -99,8 +99,14 @@ class Guides(C.Structure):
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p)]
 
 
+class Adaptive(C.Structure):
+    """rtw_adaptive (include/rtw.h): the schedule and stop rule of rtw_render_adaptive."""
+    _fields_ = [("min_spp", C.c_int32), ("step_spp", C.c_int32), ("threshold", C.c_float), ("dilate", C.c_int32)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
-               "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided"]
+               "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
+               "rtw_render_adaptive"]
 GUIDES = ("albedo", "normal", "depth", "prim")
 # Default edge-stopping sigmas of Renderer.denoise_guided (see there)
 DENOISE_SIGMA_ALBEDO = 0.4
@@ -145,6 +151,9 @@ def load_hip():
         lib.rtw_last_error.argtypes = [C.c_void_p]
         lib.rtw_denoise.restype = C.c_int
         lib.rtw_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]
+        lib.rtw_render_adaptive.restype = C.c_int
+        lib.rtw_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
         lib.rtw_render_guides.restype = C.c_int
         lib.rtw_render_guides.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Guides), C.POINTER(Stats)]
         lib.rtw_denoise_guided.restype = C.c_int
@@ -316,6 +325,20 @@ class Renderer:
         self._check(self.lib.rtw_denoise_guided(self.ctx, src.ctypes.data, a.ctypes.data, n.ctypes.data, out.ctypes.data, w, h,
                                                 iterations, sigma, sigma_albedo, sigma_normal), "rtw_denoise_guided")
         return out
+
+    def render_adaptive(self, params, threshold, min_spp=64, step_spp=0, dilate=1):
+        """rtw_render_adaptive: params.spp is the cap. Returns (img, spp, err, stats): the (rows, w, 4) float32 image, the
+        (rows, w) int32 sample count of every pixel, the (rows, w) float32 error estimate at its last checkpoint and the Stats.
+        Pixel p of img is, bit for bit, pixel p of render(params with spp = spp[p])."""
+        rows = local_rows(params)
+        img = np.empty((rows, params.width, 4), dtype=np.float32)
+        spp = np.empty((rows, params.width), dtype=np.int32)
+        err = np.empty((rows, params.width), dtype=np.float32)
+        ad = Adaptive(min_spp, step_spp, threshold, dilate)
+        st = Stats()
+        self._check(self.lib.rtw_render_adaptive(self.ctx, C.byref(params), C.byref(ad), img.ctypes.data, spp.ctypes.data,
+                                                 err.ctypes.data, C.byref(st)), "rtw_render_adaptive")
+        return img, spp, err, st
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

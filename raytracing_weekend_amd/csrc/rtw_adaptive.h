@@ -1,0 +1,178 @@
+// rtw_adaptive.h — the per-pixel kernels of rtw_render_adaptive (include/rtw.h): running sums and error moments of the listed
+// pixels, the stop rule and the compaction of the next active list, the final image. The passes themselves are k_path / k_first
+// with LIST = 1 (rtw_kernels.h). Included by rtw_hip.hip.
+//
+// Per shard pixel p the state is: accum (sum of finished summation units), upart (running sum of the current unit's finished
+// blocks), part (running sum of the current block: wavefront pipeline only), mom = (M1, M2) in fp64, n (0 while active, else the
+// sample count the pixel stopped at) and err. A list of active pixels is list[0] = n, list[1 + i] = the pixel of position i (the
+// layout k_path / k_first read with LIST = 1), in ascending pixel order. Checkpoints fall on block boundaries but not on unit boundaries, so a pass leaves the
+// unit open (upart) and only k_adapt_finish closes it - the order in which k_resolve_blocks / k_resolve + k_finish close it.
+#pragma once
+
+namespace rtwk {
+
+// the batch-means statistic of one block sum: luminance of the block's mean (rtw.h, in this order, no contraction)
+RTW_DEV float adapt_y(const float4 S) { return ((0.2126f * S.x + 0.7152f * S.y) + 0.0722f * S.z) * 0.0625f; }
+RTW_DEV void adapt_moments(double2& m, const float4 S) {
+    const double y = (double)adapt_y(S);
+    m.x = m.x + y;
+    m.y = m.y + y * y;
+}
+// standard error of sqrt(Y) from the moments of B blocks (rtw.h); NaN stays NaN (and so never compares below a threshold)
+RTW_DEV float adapt_err(const double2 m, const uint32_t B) {
+    const double b = (double)B;
+    const double mean = m.x / b;
+    double v = (m.y - m.x * mean) / (b - 1.0);
+    v = v < 0.0 ? 0.0 : v;
+    const double se = __builtin_sqrt(v / b);
+    const double mm = mean < 1e-3 ? 1e-3 : mean;
+    return (float)(se / (2.0 * __builtin_sqrt(mm)));
+}
+
+// the start of an adaptive render: every pixel active (identity list), sums and moments zero
+__global__ void __launch_bounds__(kBlock) k_adapt_init(uint32_t* __restrict__ list, float4* __restrict__ accum, float4* __restrict__ upart,
+                                                       float4* __restrict__ part, double2* __restrict__ mom, uint32_t* __restrict__ n,
+                                                       float* __restrict__ err, uint32_t npix) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        list[1u + i] = i;
+        if (i == 0u) list[0] = npix;
+        accum[i] = z; upart[i] = z; part[i] = z;
+        mom[i] = make_double2(0.0, 0.0);
+        n[i] = 0u;
+        err[i] = 0.f;
+    }
+}
+
+// the list counterpart of k_resolve_blocks: n_blocks block sums [block][list position] of one k_path list pass, whose first block
+// is block first_block of the render (counted from sample_offset). The unit is carried across passes in upart, not flushed.
+__global__ void __launch_bounds__(kBlock) k_adapt_resolve_blocks(const float4* __restrict__ slots, const uint32_t* __restrict__ list, uint32_t n_list,
+                                                                 uint32_t n_blocks, uint32_t first_block, float4* __restrict__ accum,
+                                                                 float4* __restrict__ upart, double2* __restrict__ mom) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += gridDim.x * blockDim.x) {
+        const uint32_t p = list[1u + i];
+        float4 a = accum[p], u = upart[p];
+        double2 m = mom[p];
+        for (uint32_t b = 0; b < n_blocks; b++) {
+            const float4 S = slots[(size_t)b * n_list + i];
+            adapt_moments(m, S);
+            u.x += S.x; u.y += S.y; u.z += S.z;
+            if (((first_block + b + 1u) % kSumUnitBlocks) == 0u) {
+                a.x += u.x; a.y += u.y; a.z += u.z;
+                u = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        accum[p] = a; upart[p] = u; mom[p] = m;
+    }
+}
+
+// the list counterpart of k_resolve: nslots sample slots of one wavefront batch (radiance of path slot * npix + p), whose first
+// sample is sample first_sample of the render. A block is closed (moments, unit sum) as soon as its last sample is in.
+__global__ void __launch_bounds__(kBlock) k_adapt_resolve_samples(const float4* __restrict__ lbuf, const uint32_t* __restrict__ list, uint32_t n_list,
+                                                                  uint32_t npix, uint32_t nslots, uint32_t first_sample, float4* __restrict__ accum,
+                                                                  float4* __restrict__ upart, float4* __restrict__ part, double2* __restrict__ mom) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += gridDim.x * blockDim.x) {
+        const uint32_t p = list[1u + i];
+        float4 a = accum[p], u = upart[p], b = part[p];
+        double2 m = mom[p];
+        for (uint32_t s = 0; s < nslots; s++) {
+            const float4 l = lbuf[(size_t)s * npix + p];
+            b.x += l.x; b.y += l.y; b.z += l.z;
+            const uint32_t done = first_sample + s + 1u;
+            if ((done % kSumBlock) == 0u) {
+                adapt_moments(m, b);
+                u.x += b.x; u.y += b.y; u.z += b.z;
+                b = make_float4(0.f, 0.f, 0.f, 0.f);
+                if ((done % (kSumBlock * kSumUnitBlocks)) == 0u) {
+                    a.x += u.x; a.y += u.y; a.z += u.z;
+                    u = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+        }
+        accum[p] = a; upart[p] = u; part[p] = b;
+        mom[p] = m;
+    }
+}
+
+// Checkpoint n_k = 16 B: err of every active pixel (n == 0) and the stop rule (rtw.h), dilation against the current active set
+// (a neighbour's err is recomputed from its moments: no pass over the frame has to finish first). One wave per 64 consecutive
+// pixels; masks[w] = the ballot of the pixels of wave w that stay active. n is only read here (k_adapt_compact writes it).
+__global__ void __launch_bounds__(kBlock) k_adapt_decide(const double2* __restrict__ mom, const uint32_t* __restrict__ n, float* __restrict__ err,
+                                                         unsigned long long* __restrict__ masks, uint32_t width, uint32_t rows, uint32_t B,
+                                                         uint32_t at_cap, float threshold, uint32_t dilate) {
+    const uint32_t npix = width * rows, n_waves = (npix + 63u) / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t w = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); w < n_waves; w += gridDim.x * (kBlock / 64u)) {
+        const uint32_t p = w * 64u + lane;
+        bool keep = false;
+        if (p < npix && n[p] == 0u) {
+            const float e = adapt_err(mom[p], B);
+            err[p] = e;
+            bool stop = at_cap != 0u || e < threshold;
+            if (stop && at_cap == 0u && dilate != 0u) {
+                const int y = (int)(p / width), x = (int)(p - (uint32_t)y * width);
+                for (int dy = -1; dy <= 1; dy++) {
+                    const int yy = min(max(y + dy, 0), (int)rows - 1);
+                    for (int dx = -1; dx <= 1; dx++) {
+                        const int xx = min(max(x + dx, 0), (int)width - 1);
+                        const uint32_t q = (uint32_t)yy * width + (uint32_t)xx;
+                        if (q != p && n[q] == 0u && !(adapt_err(mom[q], B) < threshold)) stop = false;
+                    }
+                }
+            }
+            keep = !stop;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0u) masks[w] = mask;
+    }
+}
+
+// exclusive prefix of the masks' population counts (one workgroup of 1024 threads, each a contiguous run of waves); *count = total
+// (the next list's length word)
+__global__ void __launch_bounds__(1024) k_adapt_scan(const unsigned long long* __restrict__ masks, uint32_t* __restrict__ offsets, uint32_t n_waves,
+                                                     uint32_t* __restrict__ count) {
+    __shared__ uint32_t s_sum[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (n_waves + 1023u) / 1024u, w0 = min(tid * per, n_waves), w1 = min(w0 + per, n_waves);
+    uint32_t sum = 0;
+    for (uint32_t w = w0; w < w1; w++) sum += (uint32_t)__popcll(masks[w]);
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024u; off <<= 1) {  // inclusive Hillis-Steele scan
+        const uint32_t v = tid >= off ? s_sum[tid - off] : 0u;
+        __syncthreads();
+        s_sum[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[tid] - sum;
+    for (uint32_t w = w0; w < w1; w++) {
+        offsets[w] = run;
+        run += (uint32_t)__popcll(masks[w]);
+    }
+    if (tid == 1023u) *count = s_sum[1023];
+}
+
+// the next active list, in ascending pixel order; a pixel that stops records its sample count n_k
+__global__ void __launch_bounds__(kBlock) k_adapt_compact(const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ offsets,
+                                                          uint32_t* __restrict__ n, uint32_t* __restrict__ list_next, uint32_t npix, uint32_t n_k) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
+        const uint32_t w = p >> 6, lane = p & 63u;
+        const unsigned long long mask = masks[w];
+        if ((mask >> lane) & 1ull) list_next[1u + offsets[w] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = p;
+        else if (n[p] == 0u) n[p] = n_k;
+    }
+}
+
+// mean radiance: the open unit joins the total (as k_resolve_blocks / k_finish close the last unit), then the division by (float)n_p
+__global__ void __launch_bounds__(kBlock) k_adapt_finish(const float4* __restrict__ accum, const float4* __restrict__ upart, const uint32_t* __restrict__ n,
+                                                         float4* __restrict__ out, uint32_t npix) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        float4 a = accum[i];
+        const float4 u = upart[i];
+        a.x += u.x; a.y += u.y; a.z += u.z;
+        const float spp = (float)n[i];
+        out[i] = make_float4(a.x / spp, a.y / spp, a.z / spp, 1.0f);
+    }
+}
+
+}  // namespace rtwk

@@ -47,6 +47,7 @@
 #include "rtw_plan.h"
 #include "rtw_kernels.h"
 #include "rtw_guides.h"
+#include "rtw_adaptive.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
 #endif
@@ -70,6 +71,15 @@ RTW_EXT(k_bounce)
 #undef RTW_EXT
 extern template __global__ void k_classify<true>(const KArgs, uint32_t*, uint32_t*, uint32_t);
 extern template __global__ void k_classify<false>(const KArgs, uint32_t*, uint32_t*, uint32_t);
+// the list instantiations of rtw_render_adaptive (rtw_inst_list.hip)
+#define RTW_EXT_LIST(R_) \
+    extern template __global__ void k_path<R_, 0, 0, 1>(const KArgs); extern template __global__ void k_path<R_, 1, 0, 1>(const KArgs); \
+    extern template __global__ void k_path<R_, 2, 0, 1>(const KArgs); extern template __global__ void k_path<R_, 1, 1, 1>(const KArgs); \
+    extern template __global__ void k_first<R_, 0, 1>(const KArgs); extern template __global__ void k_first<R_, 1, 1>(const KArgs); \
+    extern template __global__ void k_first<R_, 2, 1>(const KArgs);
+RTW_EXT_LIST(RTW_RNG_PHILOX)
+RTW_EXT_LIST(RTW_RNG_TEA_LCG)
+#undef RTW_EXT_LIST
 }  // namespace rtwk
 #endif
 
@@ -123,6 +133,10 @@ struct rtw_ctx {
     size_t stage_pix = 0;
     size_t pool_cap = ~(size_t)0;  // paths in flight this device has room for (halved when a pool allocation fails: render_wavefront)
     struct Worker* worker = nullptr;  // a kid's host thread: created with the group, lives until rtw_destroy
+    // rtw_render_adaptive's per-pixel state (rtw_adaptive.h), one allocation made on first use: accum, upart, part, moments, n, err,
+    // two active lists (a length word, then the pixels) and the compaction's masks and offsets (one per 64 pixels)
+    void* adapt = nullptr;
+    size_t adapt_pix = 0;
 };
 
 // One persistent host thread per kid context of a group (n_devices > 1). The caller's thread hands it one shard per render
@@ -260,18 +274,30 @@ Kernel trace_bvh_kernel(int block, int mode) {
 }
 
 // k_path's instantiation: RNG kind x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator); media scenes
-// take the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5)
-Kernel path_kernel(int rng_kind, int feat, int n_vol) {
-#define RTW_PK(R_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1> : feat == 2 ? k_path<R_, 2> : feat == 1 ? k_path<R_, 1> : k_path<R_, 0>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG) : RTW_PK(RTW_RNG_PHILOX);
+// take the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5). list: the LIST = 1 twin (rtw_render_adaptive)
+Kernel path_kernel(int rng_kind, int feat, int n_vol, bool list = false) {
+#define RTW_PK(R_, L_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1, L_> : feat == 2 ? k_path<R_, 2, 0, L_> : feat == 1 ? k_path<R_, 1, 0, L_> : k_path<R_, 0, 0, L_>)
+    if (list) return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 1) : RTW_PK(RTW_RNG_PHILOX, 1);
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 0) : RTW_PK(RTW_RNG_PHILOX, 0);
 #undef RTW_PK
 }
+// k_first's list twin (rtw_render_adaptive's wavefront passes)
+Kernel first_list_kernel(int rng_kind, int feat) {
+#define RTW_FK(R_) (feat == 2 ? k_first<R_, 2, 1> : feat == 1 ? k_first<R_, 1, 1> : k_first<R_, 0, 1>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_FK(RTW_RNG_TEA_LCG) : RTW_FK(RTW_RNG_PHILOX);
+#undef RTW_FK
+}
 
-// which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH
-void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock) {
+// which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH. list: k_first / k_path over a.list (LIST = 1)
+void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock, bool list = false) {
     const bool lcg = rng_kind == RTW_RNG_TEA_LCG;
     // kernels that shade exist in six instantiations: RNG kind x feature level
     const int feat = a.sc.has_tex;  // 0 hot, 1 cold features, 2 cold features + the mixture estimator (rtw_kernels.h shade_a)
+    if (list) {
+        if (which == RTW_K_FIRST) hipLaunchKernelGGL(first_list_kernel(rng_kind, feat), dim3(grid), dim3(kBlock), lds, s, a);
+        else hipLaunchKernelGGL(path_kernel(rng_kind, feat, a.sc.n_vol, true), dim3(grid), dim3(kBlock), lds, s, a);
+        return;
+    }
 #define RTW_LAUNCH_SHADING_R(K_, LDS_, R_)                                                                        \
     do {                                                                                                          \
         if (feat == 2) hipLaunchKernelGGL((K_<R_, 2>), dim3(grid), dim3(kBlock), LDS_, s, a);                     \
@@ -417,6 +443,7 @@ int impl_destroy(rtw_ctx* c) {
     if (c->part) (void)hipFree(c->part);
     if (c->upart) (void)hipFree(c->upart);
     if (c->blocksum) (void)hipFree(c->blocksum);
+    if (c->adapt) (void)hipFree(c->adapt);
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_order) (void)hipFree(c->d_order);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -838,11 +865,11 @@ struct CallLog {
         timed.push_back(t);
         return hipEventRecord(t.b, s);
     }
-    hipError_t launch(hipStream_t s, int kind, const KArgs& a, int grid, size_t lds, int block = kBlock) {
+    hipError_t launch(hipStream_t s, int kind, const KArgs& a, int grid, size_t lds, int block = kBlock, bool list = false) {
         Timed t;
         hipError_t er = open(t, kind, s);
         if (er != hipSuccess) return er;
-        ::launch(kind, rng_kind, a, grid, lds, s, block);
+        ::launch(kind, rng_kind, a, grid, lds, s, block, list);
         return close(t, s);
     }
 };
@@ -928,6 +955,60 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     return RTW_OK;
 }
 
+// One batch of the wavefront pipeline on lane L, once `ready` has happened: k_first starts `paths` camera paths (Sb samples of each
+// pixel; list: of each listed pixel), then the plan's schedule. a: the batch's arguments (the render's, with sample0 of the batch)
+int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a, rtw_ctx::Lane& L, size_t paths, size_t Sb, hipEvent_t ready,
+                CallLog& log, bool list) {
+    const size_t lds = c->lds_bytes;
+    const uint32_t regions = w.grid_for(paths);
+    HIP_TRY(c, hipStreamWaitEvent(L.st, ready, 0));
+    HIP_TRY(c, hipMemsetAsync(L.cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
+    a.lbuf = L.lbuf;
+    a.stats = c->d_stats;
+    a.n_regions = regions;
+    a.n_paths = (uint32_t)paths;
+    a.region_cap = (uint32_t)w.cap_for(paths);
+    a.trace_first = w.split_first ? 1u : 0u;
+    a.first_group_log2 = 0;
+    while (a.first_group_log2 < (uint32_t)tune.first_group_log2 && (Sb >> (a.first_group_log2 + 1)) << (a.first_group_log2 + 1) == Sb) a.first_group_log2++;
+    // k_first fills buffer 0 (and the hit buffer); every compacting launch then flips the buffers
+    int cur = 0;
+    size_t ci = 0;  // index of the region-counter row describing buffer `cur`
+    a.out = L.buf[0];
+    a.hit_out = L.hit[0];
+    a.cnt_out = L.cnt;
+    a.depth = 0; a.n_iter = 1;
+    log.launches++;
+    // every compacting launch uses exactly this grid: workgroup b owns region b
+    HIP_TRY(c, log.launch(L.st, RTW_K_FIRST, a, (int)regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->stack_depth * sizeof(uint32_t) : 0, kBlock, list));
+    for (const Step& st : w.sched) {
+        a.in = L.buf[cur];
+        a.hit = L.hit[cur];
+        a.hit_out = L.hit[cur];  // k_trace fills the records of the buffer it reads
+        a.cnt_in = L.cnt + ci * regions;
+        a.depth = (uint32_t)st.depth;
+        a.n_iter = (uint32_t)st.n_iter;
+        if (st.kind == RTW_K_TRACE) {
+            if (c->sc.use_bvh) {  // its own workgroup size, LDS image and grid: waves own streams of chunks, not regions
+                KArgs at = a;
+                at.sc.n_lds_nodes = w.trace_nodes; at.sc.n_lds_leaves = w.trace_leaves;
+                HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, at, w.trace_grid, w.trace_lds, w.trace_block));
+            } else {
+                HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, a, (int)regions, lds));
+            }
+        } else {
+            a.out = L.buf[cur ^ 1];
+            a.hit_out = L.hit[cur ^ 1];
+            a.cnt_out = L.cnt + (ci + 1) * regions;
+            HIP_TRY(c, log.launch(L.st, st.kind, a, (int)regions, st.kind == RTW_K_BOUNCE ? lds : 0));
+            cur ^= 1;
+            ci++;
+        }
+        log.launches++;
+    }
+    return RTW_OK;
+}
+
 // ---- wavefront pipeline (tree scenes; RTW_PATH=0): batches of S samples per pixel alternate between the lanes
 int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
     const size_t npix = base.npix;
@@ -958,7 +1039,6 @@ int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const 
     HIP_TRY(c, hipMemsetAsync(c->upart, 0, npix * sizeof(float4), s));
     HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
     const unsigned pix_grid = pixel_grid(c, npix);
-    const size_t lds = c->lds_bytes;
     // the lanes start once the accumulators are cleared
     hipEvent_t ev_ready = nullptr;
     if (P->max_depth > 0) {
@@ -969,56 +1049,11 @@ int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const 
         // batch b on its lane: samples [s0, s0 + Sb) of every pixel
         const size_t Sb = w.batch_size(b, s0);
         rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
-        const size_t paths = npix * Sb;
-        const uint32_t regions = w.grid_for(paths);
         // this lane's pool is free again once the resolve of its previous batch has run on the main stream
-        HIP_TRY(c, hipStreamWaitEvent(L.st, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, 0));
-        HIP_TRY(c, hipMemsetAsync(L.cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
         KArgs a = base;
-        a.lbuf = L.lbuf;
-        a.stats = c->d_stats;
-        a.n_regions = regions;
-        a.n_paths = (uint32_t)paths;
         a.sample0 = (uint32_t)(P->sample_offset + (int)s0);
-        a.region_cap = (uint32_t)w.cap_for(paths);
-        a.trace_first = w.split_first ? 1u : 0u;
-        a.first_group_log2 = 0;
-        while (a.first_group_log2 < (uint32_t)tune.first_group_log2 && (Sb >> (a.first_group_log2 + 1)) << (a.first_group_log2 + 1) == Sb) a.first_group_log2++;
-        // k_first fills buffer 0 (and the hit buffer); every compacting launch then flips the buffers
-        int cur = 0;
-        size_t ci = 0;  // index of the region-counter row describing buffer `cur`
-        a.out = L.buf[0];
-        a.hit_out = L.hit[0];
-        a.cnt_out = L.cnt;
-        a.depth = 0; a.n_iter = 1;
-        log.launches++;
-        // every compacting launch uses exactly this grid: workgroup b owns region b
-        HIP_TRY(c, log.launch(L.st, RTW_K_FIRST, a, (int)regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->stack_depth * sizeof(uint32_t) : 0));
-        for (const Step& st : w.sched) {
-            a.in = L.buf[cur];
-            a.hit = L.hit[cur];
-            a.hit_out = L.hit[cur];  // k_trace fills the records of the buffer it reads
-            a.cnt_in = L.cnt + ci * regions;
-            a.depth = (uint32_t)st.depth;
-            a.n_iter = (uint32_t)st.n_iter;
-            if (st.kind == RTW_K_TRACE) {
-                if (c->sc.use_bvh) {  // its own workgroup size, LDS image and grid: waves own streams of chunks, not regions
-                    KArgs at = a;
-                    at.sc.n_lds_nodes = w.trace_nodes; at.sc.n_lds_leaves = w.trace_leaves;
-                    HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, at, w.trace_grid, w.trace_lds, w.trace_block));
-                } else {
-                    HIP_TRY(c, log.launch(L.st, RTW_K_TRACE, a, (int)regions, lds));
-                }
-            } else {
-                a.out = L.buf[cur ^ 1];
-                a.hit_out = L.hit[cur ^ 1];
-                a.cnt_out = L.cnt + (ci + 1) * regions;
-                HIP_TRY(c, log.launch(L.st, st.kind, a, (int)regions, st.kind == RTW_K_BOUNCE ? lds : 0));
-                cur ^= 1;
-                ci++;
-            }
-            log.launches++;
-        }
+        const int rc = issue_batch(c, w, tune, a, L, npix * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, false);
+        if (rc) return rc;
         // batches are resolved into the accumulators in order, on the main stream
         HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
         HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
@@ -1079,6 +1114,23 @@ int print_diagnostics(rtw_ctx* c, bool path, const unsigned long long* hs) {
     return RTW_OK;
 }
 
+// the kernel arguments of a render: shard_args, and the corrected estimators' settings
+KArgs render_args(const rtw_ctx* c, const rtw_params* P, size_t npix) {
+    KArgs base = shard_args(c->sc, P, npix);
+    if (P->estimator != RTW_EST_REFERENCE) {  // the corrected estimators live in the cold-feature instantiations
+        base.sc.estimator = P->estimator; base.sc.has_tex = P->estimator == RTW_EST_MIXTURE ? 2 : 1;
+        base.sc.ray_tmin = 1.0e-3f; base.sc.probe_eps = 1.0e-3f;
+    }
+    return base;
+}
+// k_path: scenes walked with the brute lists; it packs a unit's pixel as x | y << 16, so frames wider or taller than 65535
+// take the wavefront kernels
+bool path_pipeline(const rtw_ctx* c, const rtw_params* P, const Tuning& tune) {
+    const bool path_small = !c->sc.use_bvh && c->sc.n_prims <= kPathMaxPrims && (c->sc.n_walk_words > 0 || c->sc.has_tex);
+    const bool fits16 = P->width <= 65535 && P->height <= 65535;
+    return P->max_depth > 0 && tune.path != 0 && fits16 && path_small;
+}
+
 // One device: the whole render of the shard P describes, result in d_rgba (device memory of c->device).
 int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, rtw_stats* stats) {
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1092,16 +1144,8 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
     CallLog log{c, P->rng_kind, stats != nullptr && tune.kernel_timing};
     HIP_TRY(c, log.event(log.begin));
     HIP_TRY(c, log.event(log.end));
-    KArgs base = shard_args(c->sc, P, npix);
-    if (P->estimator != RTW_EST_REFERENCE) {  // the corrected estimators live in the cold-feature instantiations
-        base.sc.estimator = P->estimator; base.sc.has_tex = P->estimator == RTW_EST_MIXTURE ? 2 : 1;
-        base.sc.ray_tmin = 1.0e-3f; base.sc.probe_eps = 1.0e-3f;
-    }
-    // k_path: scenes walked with the brute lists; it packs a unit's pixel as x | y << 16, so frames wider or taller than 65535
-    // take the wavefront kernels
-    const bool path_small = !c->sc.use_bvh && c->sc.n_prims <= kPathMaxPrims && (c->sc.n_walk_words > 0 || c->sc.has_tex);
-    const bool fits16 = P->width <= 65535 && P->height <= 65535;
-    const bool use_path = P->max_depth > 0 && tune.path != 0 && fits16 && path_small;
+    const KArgs base = render_args(c, P, npix);
+    const bool use_path = path_pipeline(c, P, tune);
     int rc = use_path ? render_path(c, P, tune, base, (float4*)d_rgba, s, log) : render_wavefront(c, P, tune, base, (float4*)d_rgba, s, log);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
@@ -1297,6 +1341,261 @@ int impl_render(rtw_ctx* c, const rtw_params* P, float* rgba_out, rtw_stats* sta
     return RTW_OK;
 }
 
+// ---- rtw_render_adaptive (rtw.h): passes from checkpoint to checkpoint over the list of active pixels (rtw_adaptive.h)
+struct AdaptState {
+    float4 *accum, *upart, *part;
+    double2* mom;
+    uint32_t *n, *list[2], *offsets;
+    float* err;
+    unsigned long long* masks;
+};
+
+int ensure_adapt(rtw_ctx* c, size_t npix, AdaptState& st) {
+    const size_t nw = (npix + 63) / 64;
+    const size_t sz[10] = {npix * 16, npix * 16, npix * 16, npix * 16, npix * 4, npix * 4 + 4, npix * 4 + 4, npix * 4, nw * 8, nw * 4};
+    size_t off[11] = {0};
+    for (int k = 0; k < 10; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
+    if (npix > c->adapt_pix) {
+        if (c->adapt) (void)hipFree(c->adapt);
+        c->adapt = nullptr; c->adapt_pix = 0;
+        HIP_TRY(c, hipMalloc(&c->adapt, off[10]));
+        c->adapt_pix = npix;
+    }
+    char* b = (char*)c->adapt;  // (the layout for npix fits in an allocation made for more pixels)
+    st.accum = (float4*)(b + off[0]); st.upart = (float4*)(b + off[1]); st.part = (float4*)(b + off[2]); st.mom = (double2*)(b + off[3]);
+    st.n = (uint32_t*)(b + off[4]); st.list[0] = (uint32_t*)(b + off[5]); st.list[1] = (uint32_t*)(b + off[6]); st.err = (float*)(b + off[7]);
+    st.masks = (unsigned long long*)(b + off[8]); st.offsets = (uint32_t*)(b + off[9]);
+    return RTW_OK;
+}
+
+// k_path over the n_list pixels of `list` (length word, then the pixels: rtw_adaptive.h): blocks [n_from / 16, n_to / 16) of each, resolved into the state
+int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptState& st, const uint32_t* list,
+                       size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
+    // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
+    Tuning t = tune;
+    if (t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
+    int wg_per_cu = t.path_grid_mult;
+    if (wg_per_cu <= 0) {
+        int nb = 0;
+        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol, true), kBlock, 0);
+        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+    }
+    const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
+    if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
+    if (plan.need_slots * n_list > c->blocksum_elems) {
+        if (c->blocksum) (void)hipFree(c->blocksum);
+        c->blocksum = nullptr; c->blocksum_elems = 0;
+        HIP_TRY(c, hipMalloc(&c->blocksum, plan.need_slots * n_list * sizeof(float4)));
+        c->blocksum_elems = plan.need_slots * n_list;
+    }
+    if (!c->d_queue) HIP_TRY(c, hipMalloc(&c->d_queue, 64));
+    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
+    const uint32_t blk0 = (uint32_t)n_from / kSumBlock;
+    for (const PathPass& ps : plan.passes) {
+        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
+        HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+        HIP_TRY(c, log.event(ev_a));
+        HIP_TRY(c, log.event(ev_b));
+        HIP_TRY(c, hipEventRecord(ev_a, s));
+        CallLog::Timed tp;
+        HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
+        for (int part = 0; part < 2; part++) {  // as in render_path: the bulk launch and the end-game launch beside it
+            const PathLaunch& l = ps.part[part];
+            if (l.count == 0) continue;
+            KArgs a = base;
+            a.stats = c->d_stats;
+            a.sample0 = (uint32_t)P->sample_offset;
+            a.spp = (uint32_t)n_to;
+            a.queue = c->d_queue + (part == 0 ? 0 : 4);
+            a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * n_list;
+            a.unit_sums = 0u;
+            a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
+            a.block0 = blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
+            a.order = list;
+            hipStream_t ls = part == 0 ? s : c->stream2;
+            if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
+            launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls, kBlock, true);
+            log.launches++;
+            if (part == 1) {
+                HIP_TRY(c, hipEventRecord(ev_b, ls));
+                HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
+            }
+        }
+        HIP_TRY(c, log.close(tp, s));
+        hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(c, n_list)), dim3(kBlock), 0, s, (const float4*)c->blocksum, list, (uint32_t)n_list,
+                           (uint32_t)ps.nb, blk0 + (uint32_t)ps.b0, st.accum, st.upart, st.mom);
+    }
+    return RTW_OK;
+}
+
+// the wavefront pipeline over the n_list pixels of `list`: samples [n_from, n_to) of each. Path ids keep the shard's stride
+// (slot * npix + pixel), so a batch's radiance buffer needs Sb * npix slots: a list batch takes at most the samples per pixel that a
+// full-frame batch would (the pool's share per lane over npix), and the lane's buffers are sized for that many slots.
+int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptState& st, const uint32_t* list,
+                            size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
+    const size_t npix = base.npix;
+    const size_t step = (size_t)(n_to - n_from);
+    const SceneFacts sf{c->sc.use_bvh != 0, c->sc.n_vol, c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, c->sc.stack_wide != 0};
+    WavefrontPlan w;
+    for (;;) {
+        size_t S = P->samples_per_pass > 0 ? (size_t)P->samples_per_pass : std::max<size_t>(1, std::min(tune.pool_paths, c->pool_cap) / (size_t)tune.lanes / npix);
+        S = std::min(S, step);
+        while (S > 1 && npix * S > 0xfffffff0ull) S--;
+        w = plan_wavefront(tune, n_list, (int)step, (int)S, P->max_depth, c->pool_cap, c->n_cu, sf);
+        if (w.trace_lds > 48 * 1024) {
+            DScene ts = c->sc;
+            ts.n_lds_nodes = w.trace_nodes;
+            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
+            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
+        }
+        const size_t paths = std::max((size_t)w.regions_max * w.region_cap_max, w.S * npix);
+        const int rc = ensure_pool(c, w.n_lanes, paths, npix, w.cnt_words, c->sc.n_lights > 0);
+        if (rc == RTW_OK) break;
+        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || S <= 1) return rc;
+        free_pool(c);  // as in render_wavefront: half as many paths in flight, the same image
+        (void)hipGetLastError();
+        c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * S * (size_t)tune.lanes / 2);
+    }
+    hipEvent_t ev_ready = nullptr;
+    HIP_TRY(c, log.event(ev_ready));
+    HIP_TRY(c, hipEventRecord(ev_ready, s));  // after the previous checkpoint's decision (the list) on s
+    const unsigned grid = pixel_grid(c, n_list);
+    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < step; b++) {
+        const size_t Sb = w.batch_size(b, s0);
+        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
+        KArgs a = base;
+        a.sample0 = (uint32_t)(P->sample_offset + n_from + (int)s0);
+        a.order = list;
+        const int rc = issue_batch(c, w, tune, a, L, n_list * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
+        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+        hipLaunchKernelGGL(k_adapt_resolve_samples, dim3(grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, list, (uint32_t)n_list, (uint32_t)npix,
+                           (uint32_t)Sb, (uint32_t)(n_from + (int)s0), st.accum, st.upart, st.part, st.mom);
+        HIP_TRY(c, hipEventRecord(L.ev_free, s));
+        s0 += Sb;
+    }
+    return RTW_OK;
+}
+
+// one device (a group's first): the checkpoints, a pass and a decision per checkpoint, the final image
+int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* AD, const std::vector<int>& cps, float* rgba_out, int32_t* spp_out,
+                           float* error_out, rtw_stats* stats) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t rows = shard_rows(P), npix = rows * (size_t)P->width;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (npix == 0) return RTW_OK;
+    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "tile too large");
+    const Tuning tune = read_tuning();
+    CallLog log{c, P->rng_kind, stats != nullptr && tune.kernel_timing};
+    HIP_TRY(c, log.event(log.begin));
+    HIP_TRY(c, log.event(log.end));
+    const KArgs base = render_args(c, P, npix);
+    const bool use_path = path_pipeline(c, P, tune);
+    AdaptState st{};
+    int rc = ensure_adapt(c, npix, st);
+    if (rc) return rc;
+    if (!c->d_stats) HIP_TRY(c, hipMalloc(&c->d_stats, (kStatRows + 1) * 8 * sizeof(unsigned long long)));
+    if (npix > c->out_pix) {
+        if (c->d_out) (void)hipFree(c->d_out);
+        c->d_out = nullptr; c->out_pix = 0;
+        HIP_TRY(c, hipMalloc(&c->d_out, npix * sizeof(float4)));
+        c->out_pix = npix;
+    }
+    const unsigned pix_grid = pixel_grid(c, npix);
+    const uint32_t n_waves = (uint32_t)((npix + 63) / 64);
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_adapt_init, dim3(pix_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.part, st.mom, st.n, st.err, (uint32_t)npix);
+    size_t n_active = npix;
+    uint64_t samples = 0;
+    int cur = 0, n_prev = 0;
+    struct PassRec { int n_from, n_to; size_t active; hipEvent_t a, b; };
+    std::vector<PassRec> passes;  // RTW_VERBOSE=1: the pass table, printed to stderr at the end
+    for (size_t k = 0; k < cps.size() && n_active > 0; k++) {
+        const int n_k = cps[k];
+        if (tune.verbose) {
+            passes.push_back(PassRec{n_prev, n_k, n_active, nullptr, nullptr});
+            HIP_TRY(c, log.event(passes.back().a));
+            HIP_TRY(c, log.event(passes.back().b));
+            HIP_TRY(c, hipEventRecord(passes.back().a, s));
+        }
+        rc = use_path ? adaptive_path_pass(c, P, tune, base, st, st.list[cur], n_active, n_prev, n_k, s, log)
+                      : adaptive_wavefront_pass(c, P, tune, base, st, st.list[cur], n_active, n_prev, n_k, s, log);
+        if (rc) return rc;
+        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
+        hipLaunchKernelGGL(k_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)c->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
+                           (const uint32_t*)st.n, st.err, st.masks, (uint32_t)P->width, (uint32_t)rows, (uint32_t)n_k / kSumBlock,
+                           k + 1 == cps.size() ? 1u : 0u, AD->threshold, (uint32_t)AD->dilate);
+        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
+        hipLaunchKernelGGL(k_adapt_compact, dim3(pix_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
+                           st.list[cur ^ 1], (uint32_t)npix, (uint32_t)n_k);
+        HIP_TRY(c, hipGetLastError());
+        if (tune.verbose) HIP_TRY(c, hipEventRecord(passes.back().b, s));
+        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
+        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        n_active = cnt;
+        cur ^= 1;
+        n_prev = n_k;
+    }
+    hipLaunchKernelGGL(k_adapt_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                       c->d_out, (uint32_t)npix);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(log.end, s));
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, npix * sizeof(float4), hipMemcpyDeviceToHost, s));
+    if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out, st.n, npix * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out, st.err, npix * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (size_t k = 0; k < passes.size(); k++) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, passes[k].a, passes[k].b));
+        const double smp = (double)passes[k].active * (double)(passes[k].n_to - passes[k].n_from);
+        fprintf(stderr, "[rtw] adaptive pass %zu: spp %d -> %d, active %zu, samples %.0f, seconds %.6f, Msamples/s %.1f\n", k, passes[k].n_from,
+                passes[k].n_to, passes[k].active, smp, ms * 1e-3, smp / std::max(ms * 1e-3, 1e-12) / 1e6);
+    }
+    if (stats) {
+        unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long rows_[kStatRows * 8];
+        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < kStatRows; r++)
+            for (int q = 0; q < 8; q++) hs[q] += rows_[r * 8 + q];
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
+        stats->seconds = (double)ms * 1e-3;
+        stats->bounce_seconds = stats->seconds;
+        for (const CallLog::Timed& t : log.timed) {
+            float m = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
+            stats->kernel_seconds[t.kind] += (double)m * 1e-3;
+            stats->kernel_launches[t.kind]++;
+        }
+        for (int q = 0; q < RTW_K_COUNT; q++) stats->kernel_segments[q] = hs[2 + q];
+        stats->bounce_launches = log.launches;
+        stats->samples = samples;
+        stats->segments = hs[0];
+        stats->shadow_rays = hs[1];
+        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    }
+    return RTW_OK;
+}
+
+int impl_render_adaptive(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* AD, float* rgba_out, int32_t* spp_out, float* error_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = check_render_args(c, P);
+    if (rc) return rc;
+    if (!AD || !rgba_out) return fail(c, RTW_ERR_INVALID_ARG, "rtw_render_adaptive: null settings or output");
+    std::vector<int> cps;
+    if (const char* why = adaptive_checkpoints(AD->min_spp, AD->step_spp, P->spp, AD->threshold, AD->dilate, cps))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string("rtw_render_adaptive: ") + why);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];  // a group renders on device_ids[0]
+    rc = render_adaptive_single(d, P, AD, cps, rgba_out, spp_out, error_out, stats);
+    if (rc && d != c) return fail(c, rc, d->err);
+    return rc;
+}
+
 // rtw_denoise and rtw_denoise_guided on the context's device: the colour image (and the guides) in, `iterations` a-trous passes
 // that ping-pong between two buffers, the result out. pass(grid, in, out, albedo, normal, step, inv_sigma2) issues one pass.
 template <class Pass>
@@ -1473,6 +1772,9 @@ int rtw_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, co
 }
 int rtw_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* out, rtw_stats* stats) {
     return guarded(c, [&] { return impl_render_guides(c, P, out, stats); });
+}
+int rtw_render_adaptive(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* ad, float* rgba_out, int32_t* spp_out, float* error_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_render_adaptive(c, P, ad, rgba_out, spp_out, error_out, stats); });
 }
 int rtw_denoise_guided(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, int32_t width, int32_t height,
                        int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {

@@ -95,6 +95,8 @@ struct KArgs {
                                 // stored per summation unit, slot [block / 8][pixel]; 0: one per block, slot [block][pixel]
     const uint32_t* order;      // job order of the 64-pixel groups: three lists, longest units first (k_classify)
     const uint32_t* order_counts;  // lengths of the lists of classes 2, 1, 0
+    // (the k_path / k_first instantiations with LIST = 1, rtw_render_adaptive's passes, read `order` as the list of active pixels:
+    // order[0] = its length n, order[1 + i] = the shard-local pixel of list position i; every other field keeps its meaning)
 };
 
 struct Path {
@@ -117,9 +119,10 @@ struct PathConsts {
     float lnrm[3], larea, lemi[3], pad2;
     // what the end of a sample block needs (k_path: a branch that one or two lanes of a wave take in two iterations out of three):
     // read from here, these launch constants do not sit in SGPRs - which the loop has none to spare of - between those visits
-    uint32_t npix, width, row0, row_stride, divs_m, divs_s1, divs_s2, spp, bs_lo, bs_hi, unit_shift, pad3;
+    uint32_t npix, width, row0, row_stride, divs_m, divs_s1, divs_s2, spp, bs_lo, bs_hi, unit_shift, list_lo;
     // what handing out units needs (the refill at the top of the loop: every few iterations of a wave)
-    uint32_t n_jobs, n_ranges, units_per_job, unit_blocks, n_blocks_pass, block0, divw_m, divw_s1, divw_s2, q_lo, q_hi, pad4;
+    uint32_t n_jobs, n_ranges, units_per_job, unit_blocks, n_blocks_pass, block0, divw_m, divw_s1, divw_s2, q_lo, q_hi, list_hi;
+    // (list_lo, list_hi: k_path with LIST = 1: the list's pixels, A.order + 1; else 0)
 };
 
 // probes = the scene lists lights: only then can a vertex queue a shadow probe (shade_a), so plane p2 - the probe's
@@ -767,7 +770,9 @@ RTW_DEV void raygen(const KArgs& A, const uint32_t x, const uint32_t y, const ui
 #ifndef RTW_FIRST_COLD_WAVES
 #define RTW_FIRST_COLD_WAVES RTW_MIN_WAVES
 #endif
-template <int KIND, int TEX>
+// LIST = 1 (rtw_render_adaptive's list passes): threads map to (slot, list position) and the pixel comes from the list (A.order); path ids stay
+// slot * npix + shard-local pixel, so the later kernels and the radiance buffer's layout do not change
+template <int KIND, int TEX, int LIST = 0>
 __global__ void __launch_bounds__(kBlock, TEX ? RTW_FIRST_COLD_WAVES : RTW_FIRST_WAVES) k_first(const KArgs A) {
     extern __shared__ uint32_t s_stack[];
     RTW_CURSOR_SHARED
@@ -780,6 +785,7 @@ __global__ void __launch_bounds__(kBlock, TEX ? RTW_FIRST_COLD_WAVES : RTW_FIRST
     // candidate lists. What this kernel does not take of a CU's LDS, the other lane's k_trace_bvh can.)
     uint32_t n_seg = 0, n_shadow = 0;
     const uint32_t total_chunks = (A.n_paths + kBlock - 1) / kBlock;
+    const uint32_t nq = LIST ? A.order[0] : A.npix;  // pixels a slot covers
     for (uint32_t vc = blockIdx.x; vc < total_chunks; vc += gridDim.x) {
         // Which camera path a thread starts. Path ids are sample-major (id = sample slot * npix + pixel: what k_resolve
         // reads), but neighbouring THREADS take 2^first_group_log2 samples of one pixel before the next pixel: a wave's
@@ -788,8 +794,9 @@ __global__ void __launch_bounds__(kBlock, TEX ? RTW_FIRST_COLD_WAVES : RTW_FIRST
         // by (pixel, sample).
         const uint32_t t_lin = vc * kBlock + tid;
         const uint32_t s_lo = t_lin & ((1u << A.first_group_log2) - 1u), q = t_lin >> A.first_group_log2;
-        const uint32_t s_hi = q / A.npix;
-        const uint32_t pl = q - s_hi * A.npix;
+        const uint32_t s_hi = q / nq;
+        uint32_t pl = q - s_hi * nq;
+        if (LIST) pl = t_lin < A.n_paths ? A.order[1u + pl] : 0u;
         const uint32_t slot = (s_hi << A.first_group_log2) | s_lo;
         const uint32_t path_id = slot * A.npix + pl;
         bool keep = false;
@@ -1351,7 +1358,11 @@ RTW_DEV constexpr int rtw_phase_id(const char* n) { return n[0] == 'r' && n[2] =
 // MEDIA5: the cold instantiation once more, allocated for 5 waves per SIMD: scenes with media wait on the volume records' loads and
 // gain from the occupancy (BASELINE config 4: +4.5 %), the other users of the cold features (other cameras, corrected
 // estimators, thin lenses) are VALU-bound like the hot instantiation and lose up to 27 % to the spills
-template <int KIND, int TEX, int MEDIA5 = 0>
+// LIST = 1 (rtw_render_adaptive's list passes, instantiated in rtw_inst_list.hip): the refill maps p_local, a position in the list
+// (A.order, see KArgs), to the listed shard-local pixel, jobs are taken in plain position order (no k_classify), and block b of list
+// position i goes to slot [b][i] (stride n_list). The host runs these passes with block sums (unit_sums = 0), so the LDS unit sums
+// are free and s_usum[0] holds each lane's list position. Everything after the refill is the same code.
+template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0>
 __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVES) : RTW_PATH_WAVES) k_path(const KArgs A) {
     RTW_NOISE_SHARED
     __shared__ u32x4 s_hitrec[kPathMaxPrims * 6];
@@ -1378,13 +1389,13 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
             for (int q = 0; q < 3; q++) { s_pc.lnrm[q] = A.sc.lights[0].normal[q]; s_pc.lemi[q] = A.sc.lights[0].emission[q]; }
             s_pc.larea = A.sc.lights[0].area;
         }
-        s_pc.npix = A.npix; s_pc.width = A.width; s_pc.row0 = A.row0; s_pc.row_stride = A.row_stride;
+        s_pc.npix = LIST ? A.order[0] : A.npix; s_pc.width = A.width; s_pc.row0 = A.row0; s_pc.row_stride = A.row_stride;
         s_pc.divs_m = A.divs_m; s_pc.divs_s1 = A.divs_s1; s_pc.divs_s2 = A.divs_s2; s_pc.spp = A.spp;
         s_pc.bs_lo = (uint32_t)(uint64_t)A.blocksum; s_pc.bs_hi = (uint32_t)((uint64_t)A.blocksum >> 32);
-        s_pc.unit_shift = A.unit_sums ? 3u : 0u; s_pc.pad3 = 0u;
+        s_pc.unit_shift = (A.unit_sums && !LIST) ? 3u : 0u; s_pc.list_lo = LIST ? (uint32_t)(uint64_t)(A.order + 1) : 0u;
         s_pc.n_jobs = A.n_jobs; s_pc.n_ranges = A.n_ranges; s_pc.units_per_job = A.units_per_job; s_pc.unit_blocks = A.unit_blocks;
         s_pc.n_blocks_pass = A.n_blocks_pass; s_pc.block0 = A.block0; s_pc.divw_m = A.divw_m; s_pc.divw_s1 = A.divw_s1; s_pc.divw_s2 = A.divw_s2;
-        s_pc.q_lo = (uint32_t)(uint64_t)A.queue; s_pc.q_hi = (uint32_t)((uint64_t)A.queue >> 32); s_pc.pad4 = 0u;
+        s_pc.q_lo = (uint32_t)(uint64_t)A.queue; s_pc.q_hi = (uint32_t)((uint64_t)A.queue >> 32); s_pc.list_hi = LIST ? (uint32_t)((uint64_t)(A.order + 1) >> 32) : 0u;
     }
     // the LDS camera serves the perspective camera without a lens (the reference's only camera); other kinds read the arguments
     // (the host sends other camera kinds and thin lenses through the cold instantiation, which reads the arguments)
@@ -1424,7 +1435,7 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                 if (q >= (uint32_t)__builtin_amdgcn_readfirstlane((int)kc->n_jobs)) { exhausted = true; break; }
                 const uint32_t n_ranges = (uint32_t)__builtin_amdgcn_readfirstlane((int)kc->n_ranges), upj = (uint32_t)__builtin_amdgcn_readfirstlane((int)kc->units_per_job);
                 const uint32_t gi = q / n_ranges;
-                job_g = order_lookup(A, gi);
+                job_g = LIST ? gi : order_lookup(A, gi);
                 job_b = (q - gi * n_ranges) * upj;
                 u_next = 0; u_end = 64u * upj;
                 continue;
@@ -1440,8 +1451,13 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                     need = false;
                     blk = b;
                     blk_end = min(b + ub, nbp);
-                    const uint32_t yl = fastdiv(p_local, kc->divw_m, kc->divw_s1, kc->divw_s2);
-                    pxy = (p_local - yl * kc->width) | ((kc->row0 + yl * kc->row_stride) << 16);
+                    uint32_t pix = p_local;
+                    if (LIST) {
+                        pix = ((const uint32_t*)(((uint64_t)kc->list_hi << 32) | kc->list_lo))[p_local];
+                        s_usum[0][tid] = __uint_as_float(p_local);
+                    }
+                    const uint32_t yl = fastdiv(pix, kc->divw_m, kc->divw_s1, kc->divw_s2);
+                    pxy = (pix - yl * kc->width) | ((kc->row0 + yl * kc->row_stride) << 16);
                     s_cur = (kc->block0 + b) * kSumBlock;
                     usum = V(0.f, 0.f, 0.f);
                     alive = false;
@@ -1517,7 +1533,7 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                     const PathConsts* kc = &s_pc;  // (launch constants from the LDS page: see PathConsts)
                     const uint32_t c_row0 = kc->row0, c_stride = kc->row_stride, c_width = kc->width, c_npix = kc->npix;
                     const uint32_t yl_ = c_stride > 1 ? fastdiv(py - c_row0, kc->divs_m, kc->divs_s1, kc->divs_s2) : py - c_row0;
-                    const uint32_t pix = yl_ * c_width + px;
+                    const uint32_t pix = LIST ? __float_as_uint(s_usum[0][tid]) : yl_ * c_width + px;
                     const uint32_t b_done = blk;
                     blk++;
                     need = blk >= blk_end || s_cur >= A.spp;

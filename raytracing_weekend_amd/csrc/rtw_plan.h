@@ -362,4 +362,25 @@ inline WavefrontPlan plan_wavefront(const Tuning& tune, size_t npix, int spp, in
     return w;
 }
 
+
+// ---- adaptive sampling (rtw.h rtw_render_adaptive): the checkpoints n_0 = min_spp, n_{k+1} = min(cap, n_k + step), step = step_spp
+// or, when step_spp is 0, n_k / 2 rounded up to a multiple of kSumBlock. A function of the three numbers alone. Returns nullptr and
+// fills `out` when the settings are valid, else what is wrong with them.
+inline const char* adaptive_checkpoints(int min_spp, int step_spp, int cap, float threshold, int dilate, std::vector<int>& out) {
+    out.clear();
+    if (cap <= 0 || cap % (int)kSumBlock != 0) return "the cap (params->spp) must be a positive multiple of RTW_SUM_BLOCK";
+    if (min_spp < 2 * (int)kSumBlock || min_spp % (int)kSumBlock != 0) return "min_spp must be a multiple of RTW_SUM_BLOCK, at least 2 * RTW_SUM_BLOCK";
+    if (min_spp > cap) return "min_spp above the cap";
+    if (step_spp < 0 || step_spp % (int)kSumBlock != 0) return "step_spp must be 0 or a positive multiple of RTW_SUM_BLOCK";
+    if (!(threshold >= 0.0f)) return "threshold must be >= 0 (NaN is not)";
+    if (dilate != 0 && dilate != 1) return "dilate must be 0 or 1";
+    for (long long n = min_spp;;) {
+        out.push_back((int)n);
+        if (n >= cap) break;
+        const long long half = (n / 2 + kSumBlock - 1) / kSumBlock * kSumBlock;
+        n = std::min<long long>(cap, n + (step_spp > 0 ? step_spp : half));
+    }
+    return nullptr;
+}
+
 }  // namespace rtwk

@@ -12,6 +12,7 @@
 #include <fstream>
 #include <iostream>
 
+#include "../csrc/rtw_plan.h"  // adaptive_checkpoints (host-only planning, no HIP)
 #include "PfmWriter.h"
 #include "SceneMarshal.h"
 
@@ -64,8 +65,30 @@ void Director::renderFrame() {
     p.row1 = m_Ny;
     p.rng_kind = m_rngKind;
     p.estimator = m_estimator;
-    int rc = rtw_render(m_ctx, &p, m_hostBuffer.data(), &m_stats);
-    if (rc != RTW_OK) die(m_ctx, "rtw_render", rc);
+    int rc = RTW_OK;
+    if (m_adaptive) {
+        const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
+        std::vector<int32_t> spp(npix);
+        m_errMap.assign(npix, 0.f);
+        const rtw_adaptive ad{m_adMinSpp, m_adStepSpp, m_adThreshold, 1};
+        rc = rtw_render_adaptive(m_ctx, &p, &ad, m_hostBuffer.data(), spp.data(), m_errMap.data(), &m_stats);
+        if (rc != RTW_OK) die(m_ctx, "rtw_render_adaptive", rc);
+        m_sppMap.assign(spp.begin(), spp.end());
+        if (_verbose) {
+            int lo = m_Ns, hi = 0;
+            for (int32_t n : spp) { lo = std::min(lo, n); hi = std::max(hi, n); }
+            std::vector<int> cps;  // the library's own schedule: one pass per checkpoint up to the largest count
+            (void)rtwk::adaptive_checkpoints(m_adMinSpp, m_adStepSpp, m_Ns, m_adThreshold, 1, cps);
+            const long passes = std::count_if(cps.begin(), cps.end(), [&](int n) { return n <= hi; });
+            const double uniform = static_cast<double>(npix) * m_Ns;
+            std::cerr << "INFO: adaptive: " << passes << " passes, spp mean " << static_cast<double>(m_stats.samples) / npix << " min " << lo
+                      << " max " << hi << ", " << uniform - static_cast<double>(m_stats.samples) << " samples saved against uniform "
+                      << m_Ns << " spp (" << 100.0 * (1.0 - static_cast<double>(m_stats.samples) / uniform) << " %)" << std::endl;
+        }
+    } else {
+        rc = rtw_render(m_ctx, &p, m_hostBuffer.data(), &m_stats);
+        if (rc != RTW_OK) die(m_ctx, "rtw_render", rc);
+    }
     const bool guidedDenoise = m_guided && m_denoiseIterations > 0;
     if (!m_aovPrefix.empty() || guidedDenoise) {
         // the guide layers the reference's OptiX denoiser could take (Director.cpp:887-949 sets up the beauty layer alone)
@@ -163,6 +186,9 @@ bool Director::writePFM(const std::string& path) const {
 
 bool Director::writeGuides(const std::string& prefix) const {
     if (m_albedo.empty()) return false;
+    if (m_adaptive && (!rtwhost::writePfm(prefix + "_spp.pfm", m_sppMap.data(), m_Nx, m_Ny, 1, 1) ||
+                       !rtwhost::writePfm(prefix + "_error.pfm", m_errMap.data(), m_Nx, m_Ny, 1, 1)))
+        return false;
     return rtwhost::writePfm(prefix + "_albedo.pfm", m_albedo.data(), m_Nx, m_Ny, 4, 3) &&
            rtwhost::writePfm(prefix + "_normal.pfm", m_normal.data(), m_Nx, m_Ny, 4, 3) &&
            rtwhost::writePfm(prefix + "_depth.pfm", m_depth.data(), m_Nx, m_Ny, 1, 1);

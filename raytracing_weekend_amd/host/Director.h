@@ -46,7 +46,11 @@ public:
     // guide buffers (rtw_render_guides) of `spp` samples (0: min(Ns, 16)), rendered by renderFrame when an -aov prefix is set or the
     // denoiser is guided; guided: the denoiser pass is rtw_denoise_guided, steered by the albedo and normal guides
     void setGuides(const std::string& aovPrefix, int spp, bool guided) { m_aovPrefix = aovPrefix; m_guideSpp = spp; m_guided = guided; }
-    // PREFIX_albedo.pfm, PREFIX_normal.pfm (PF, rgb) and PREFIX_depth.pfm (Pf), rows bottom-up as writePFM
+    // adaptive sampling (rtw_render_adaptive): renderFrame renders until every pixel's error estimate is below `threshold` or it has
+    // the -ns cap; minSpp samples first, then checkpoints `stepSpp` apart (0: half of what a pixel has); dilate 1
+    void setAdaptive(float threshold, int minSpp, int stepSpp) { m_adaptive = true; m_adThreshold = threshold; m_adMinSpp = minSpp; m_adStepSpp = stepSpp; }
+    // PREFIX_albedo.pfm, PREFIX_normal.pfm (PF, rgb) and PREFIX_depth.pfm (Pf), rows bottom-up as writePFM; after an adaptive
+    // frame also PREFIX_spp.pfm and PREFIX_error.pfm (Pf: each pixel's sample count and error estimate)
     bool writeGuides(const std::string& prefix) const;
     const rtw_stats& stats() const { return m_stats; }
     const std::vector<float>& hostBuffer() const { return m_hostBuffer; }  // linear RGBA, row 0 = bottom row
@@ -67,6 +71,10 @@ private:
     int m_guideSpp = 0;
     bool m_guided = false;
     std::vector<float> m_albedo, m_normal, m_depth;  // guide buffers of the last renderFrame (empty when none were rendered)
+    bool m_adaptive = false;
+    float m_adThreshold = 0.f;
+    int m_adMinSpp = 64, m_adStepSpp = 0;
+    std::vector<float> m_sppMap, m_errMap;  // the last adaptive frame's sample counts and error estimates
     rtw_ctx* m_ctx = nullptr;
     rtwhost::ioScene m_scene;
     std::vector<float> m_hostBuffer;

@@ -65,6 +65,10 @@ int main(int argc, char* argv[]) {
     -guided        With -denoise: steer the filter with the albedo and normal guides (rtw_denoise_guided)
     -aov PREFIX    Also write the guide buffers: PREFIX_albedo.pfm, PREFIX_normal.pfm (PF) and PREFIX_depth.pfm (Pf)
     -guide_spp N   Samples per pixel of the guide buffers (default: min(Ns, 16))
+    -adaptive T    Adaptive sampling: a pixel stops once its error estimate (standard error of the display value) is below T;
+                   -ns becomes the cap (a multiple of 16). With -aov also PREFIX_spp.pfm and PREFIX_error.pfm (Pf)
+    -min_spp N     With -adaptive: samples every pixel gets first (default 64; a multiple of 16, at least 32)
+    -step N        With -adaptive: samples added per checkpoint (default: half of what a pixel has, rounded up to 16)
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -125,6 +129,19 @@ int main(int argc, char* argv[]) {
     int guideSpp = 0;
     if (intOption(cl_input, "-guide_spp", "guide samples (-guide_spp)", x)) guideSpp = clampWarn("Guide samples (-guide_spp)", x, 1, Ns_MAX);
     director.setGuides(aovPrefix, guideSpp, cl_input.cmdOptionExists("-guided"));
+    if (cl_input.cmdOptionExists("-adaptive")) {
+        const std::string& t = cl_input.getCmdOption("-adaptive");
+        char* end = nullptr;
+        const float thr = std::strtof(t.c_str(), &end);
+        if (t.empty() || *end != '\0') {
+            std::cerr << "ERROR: -adaptive needs a threshold (a number >= 0)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        int minSpp = 64, step = 0;
+        if (intOption(cl_input, "-min_spp", "adaptive minimum samples (-min_spp)", x)) minSpp = x;
+        if (intOption(cl_input, "-step", "adaptive step (-step)", x)) step = x;
+        director.setAdaptive(thr, minSpp, step);
+    }
 
     auto start = std::chrono::system_clock::now();
     director.init(Nx, Ny, Ns);

@@ -391,6 +391,14 @@ int rtw_render_adaptive(rtw_ctx* ctx, const rtw_params* params, const rtw_adapti
 int rtw_debug_intersect(rtw_ctx* ctx, const float* rays, const float* ray_time, const float* gather_time,
                         int n, float* out_t, int32_t* out_prim);
 
+/* Test hook: the proof that the short reciprocal / root forms of csrc/rtw_math.h equal the compiler's correctly rounded forms
+ * on this device. Runs all 2^32 bit patterns x through both. op: 0 = 1.0f / x, 1 = sqrtf(x), 2 = 1.0f / sqrtf(x) as the renderer
+ * takes them; for the record, whatever the header's switches say: 3 / 4 = 1.0f / x with one / two refinement steps, 5 / 6 = sqrtf(x)
+ * without / with the coupled step.
+ * out[0] = patterns inside the form's range window whose results differ (NaN equals NaN), out[1] = patterns inside the window,
+ * out[2] = the lowest differing pattern, or 2^64 - 1 when there is none. Needs no scene. */
+int rtw_debug_math(rtw_ctx* ctx, int op, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

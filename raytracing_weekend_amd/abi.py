@@ -106,7 +106,8 @@ class Adaptive(C.Structure):
 
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
-               "rtw_render_adaptive"]
+               "rtw_render_adaptive", "rtw_debug_math"]
+MATH_OPS = {"rcp": 0, "sqrt": 1, "rcp_sqrt": 2, "rcp_one_step": 3, "rcp_two_steps": 4, "sqrt_residual_only": 5, "sqrt_coupled": 6}  # rtw_debug_math's op
 GUIDES = ("albedo", "normal", "depth", "prim")
 # Default edge-stopping sigmas of Renderer.denoise_guided (see there)
 DENOISE_SIGMA_ALBEDO = 0.4
@@ -161,6 +162,8 @@ def load_hip():
                                            C.c_float, C.c_float, C.c_float]
         lib.rtw_debug_intersect.restype = C.c_int
         lib.rtw_debug_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.rtw_debug_math.restype = C.c_int
+        lib.rtw_debug_math.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -352,6 +355,13 @@ class Renderer:
                                                  None if gt is None else gt.ctypes.data,
                                                  n, t.ctypes.data, prim.ctypes.data), "rtw_debug_intersect")
         return t, prim
+
+    def debug_math(self, op):
+        """All 2^32 bit patterns through a short form of csrc/rtw_math.h and the compiler's form (include/rtw.h rtw_debug_math):
+        (differing patterns, patterns inside the range window, lowest differing pattern or None)."""
+        out = (C.c_uint64 * 3)()
+        self._check(self.lib.rtw_debug_math(self.ctx, MATH_OPS[op], out), "rtw_debug_math")
+        return int(out[0]), int(out[1]), (None if out[2] == 2 ** 64 - 1 else int(out[2]))
 
     def close(self):
         if self.ctx:

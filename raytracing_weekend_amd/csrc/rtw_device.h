@@ -2,7 +2,8 @@
 //
 // Arithmetic contract (DESIGN.md "arithmetic spec"): fp32, compiled -ffp-contract=off, fused
 // multiply-add only where __builtin_fmaf is written, IEEE-correct division and sqrt (hipcc default
-// -fhip-fp32-correctly-rounded-divide-sqrt), own polynomial sincos / log. The same operations in
+// -fhip-fp32-correctly-rounded-divide-sqrt; reciprocals and roots of one float through rtw_math.h's
+// shorter sequences, which give the same bits for every input), own polynomial sincos / log. The same operations in
 // the same order are stated independently in oracle/rtw_oracle.c, which is what the parity tests
 // check this file against.
 //
@@ -14,6 +15,17 @@
 #include "../../include/rtw.h"
 
 #define RTW_DEV __device__ __forceinline__
+
+#define RTW_MATH_FN RTW_DEV
+#include "rtw_math.h"
+
+// One switch per translation unit. 1: reciprocals and roots of one float take the short forms of rtw_math.h (same bits, proved over
+// every input: tests/test_gpu_math_forms.py). 0 (-DRTW_SHORT_FORMS=0, e.g. through __graft_entry__'s RTW_BUILD_FLAGS_<UNIT>): the
+// compiler's correctly rounded forms, for A/B runs. On everywhere: k_path, bound by instruction issue, gains 8 %; the wavefront
+// kernels' units measured not slower and lose no wave.
+#ifndef RTW_SHORT_FORMS
+#define RTW_SHORT_FORMS 1
+#endif
 
 namespace rtwdev {
 
@@ -31,8 +43,23 @@ RTW_DEV float dot3(v3 a, v3 b) { return fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x)
 RTW_DEV v3 cross3(v3 a, v3 b) {
     return V(fma_(a.y, b.z, -(a.z * b.y)), fma_(a.z, b.x, -(a.x * b.z)), fma_(a.x, b.y, -(a.y * b.x)));
 }
-RTW_DEV v3 normalize3(v3 a) { float inv = 1.0f / __builtin_sqrtf(dot3(a, a)); return vscale(a, inv); }
-RTW_DEV float length3(v3 a) { return __builtin_sqrtf(dot3(a, a)); }
+// rtw_math.h's primitives on the hardware: v_rcp_f32, v_rsq_f32, v_fma_f32, and "no active lane of the wave fails"
+struct MathHw {
+    static RTW_DEV float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+    static RTW_DEV float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+    static RTW_DEV float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+    static RTW_DEV bool all(bool ok) { return __builtin_amdgcn_ballot_w64(!ok) == 0ull; }
+};
+// 1.0f / x, sqrtf(x), and sqrtf(x) for an x that the code around the call keeps inside rtw_math.h's window (no range test)
+RTW_DEV float rcp_(float x) { return RTW_SHORT_FORMS ? rtwmath::rcp<MathHw>(x) : 1.0f / x; }
+RTW_DEV float sqrt_(float x) { return RTW_SHORT_FORMS ? rtwmath::sqrt<MathHw>(x) : __builtin_sqrtf(x); }
+RTW_DEV float sqrt_inside_(float x) { return RTW_SHORT_FORMS ? rtwmath::sqrt_inside<MathHw>(x) : __builtin_sqrtf(x); }
+RTW_DEV v3 normalize3(v3 a) {
+    const float s = dot3(a, a);
+    const float inv = RTW_SHORT_FORMS ? rtwmath::rcp_sqrt<MathHw>(s) : 1.0f / __builtin_sqrtf(s);
+    return vscale(a, inv);
+}
+RTW_DEV float length3(v3 a) { return sqrt_(dot3(a, a)); }
 RTW_DEV v3 ld3(const float* p) { return V(p[0], p[1], p[2]); }
 
 RTW_DEV v3 xf_point(const float* m, v3 p) {
@@ -480,7 +507,7 @@ RTW_DEV bool sphere_roots(v3 o, v3 d, v3 c, float r, float tmin, float tmax, flo
     float cc = fma_(-r, r, dot3(oc, oc));
     float disc = fma_(b, b, -(a * cc));
     if (disc < 0.0f) return false;
-    float sq = __builtin_sqrtf(disc);
+    float sq = sqrt_(disc);
     float t = (-b - sq) / a;
     if (t < tmax && t > tmin) { t_out = t; return true; }
     t = (-b + sq) / a;
@@ -746,7 +773,10 @@ RTW_DEV void bvh_step16(const DScene& sc, const TravMem& tm, const v3 o, const v
 }
 
 RTW_DEV bool uses_inv(int type) { return type >= RTW_PRIM_RECT_X && type <= RTW_PRIM_VOLUME_BOX; }
-RTW_DEV v3 recip3(v3 d) { return V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z); }
+RTW_DEV v3 recip3(v3 d) {
+    if (RTW_SHORT_FORMS) { rtwmath::rcp3<MathHw>(d.x, d.y, d.z); return d; }
+    return V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+}
 // The walks that test surfaces only hand this to prim_test (volume kinds, which draw, never reach a tree)
 struct NoDraw {
     RTW_DEV float randf1() { return 0.0f; }

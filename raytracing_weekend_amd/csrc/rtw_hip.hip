@@ -1745,6 +1745,28 @@ int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, c
     return RTW_OK;
 }
 
+int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    unsigned long long* d = nullptr;
+    const unsigned long long init[3] = {0ull, 0ull, ~0ull};
+    unsigned long long got[3];
+    HIP_TRY(c, hipMalloc(&d, sizeof init));
+    hipError_t e = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        // 2^16 blocks of 256 threads: 256 patterns per thread
+        hipLaunchKernelGGL(k_debug_math, dim3(65536), dim3(kBlock), 0, c->stream, op, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(got, d, sizeof got, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_debug_math: ") + hipGetErrorString(e));
+    for (int i = 0; i < 3; i++) out[i] = got[i];
+    return RTW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1770,6 +1792,7 @@ int rtw_denoise(rtw_ctx* c, const float* rgba_in, float* rgba_out, int32_t width
 int rtw_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, int n, float* out_t, int32_t* out_prim) {
     return guarded(c, [&] { return impl_debug_intersect(c, rays, ray_time, gather_time, n, out_t, out_prim); });
 }
+int rtw_debug_math(rtw_ctx* c, int op, uint64_t* out) { return guarded(c, [&] { return impl_debug_math(c, op, out); }); }
 int rtw_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* out, rtw_stats* stats) {
     return guarded(c, [&] { return impl_render_guides(c, P, out, stats); });
 }

@@ -339,10 +339,10 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         }
         float sn, cs;
         sincos2pi(r1, sn, cs);
-        float sq = __builtin_sqrtf(r2);
+        float sq = sqrt_(r2);
         float lx = est ? cs * sq : (cs * 2.0f) * sq;  // corrected: cosine-weighted, without the stray 2 (Q1)
         float ly = est ? sn * sq : (sn * 2.0f) * sq;
-        float lz = __builtin_sqrtf(1.0f - r2);
+        float lz = sqrt_inside_(1.0f - r2);  // r2 is a multiple of 2^-24 in [0, 1): 1 - r2 is exact and in [2^-24, 1]
         float pdf = lz * RTW_1_PI_F;
         v3 sdir = V(fma_(lz, w.x, fma_(ly, v.x, lx * u.x)),
                     fma_(lz, w.y, fma_(ly, v.y, lx * u.y)),
@@ -383,7 +383,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         if (dot3(dir, hn) < 0.0f) { ln = hn; eta_i = 1.0f; eta_t = mparam; }
         else { ln = vneg(hn); eta_i = mparam; eta_t = 1.0f; }
         float cos_i = __builtin_fminf(dot3(vneg(unit), ln), 1.0f);
-        float sin_i = __builtin_sqrtf(fma_(-cos_i, cos_i, 1.0f));
+        float sin_i = sqrt_(fma_(-cos_i, cos_i, 1.0f));
         float ratio = eta_i / eta_t;
         v3 sdir;
         if (ratio * sin_i > 1.0f) {
@@ -399,7 +399,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
                 sdir = reflect3(unit, ln);
             } else {
                 float sin_t = __builtin_fminf(ratio * sin_i, 1.0f);
-                float cos_t = __builtin_sqrtf(fma_(-sin_t, sin_t, 1.0f));
+                float cos_t = sqrt_(fma_(-sin_t, sin_t, 1.0f));
                 v3 a = vscale(vfma(ln, cos_i, unit), ratio);
                 sdir = vfma(ln, -cos_t, a);
             }
@@ -443,7 +443,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         v3 ldir = vsub(rp, so);
         const float ldist = length3(ldir);
         if (ldist > 1.0e-6f && hr.bsdf_eval == 0) {
-            ldir = vscale(ldir, 1.0f / ldist);
+            ldir = vscale(ldir, rcp_(ldist));
             const float costa = dot3(vneg(ldir), ld3(lt.normal));
             const float ndl = dot3(ldir, hn);
             const v3 f = vscale(att, RTW_1_PI_F);
@@ -475,7 +475,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
             const v3 rp = vfma(ld3(lt.vec_v), rb, vfma(ld3(lt.vec_u), ra, ld3(lt.position)));
             const v3 ldir = vsub(rp, so);
             const float ldist = length3(ldir);
-            if (ldist > 1.0e-6f) sd = vscale(ldir, 1.0f / ldist);
+            if (ldist > 1.0e-6f) sd = vscale(ldir, rcp_(ldist));
         }
         const float ndl = dot3(sd, hn);
         const float pb = __builtin_fmaxf(0.0f, ndl) * RTW_1_PI_F;
@@ -535,7 +535,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
             ldir = vsub(rp, so);
             ldist = length3(ldir);
             if (ldist > 1.0e-6f) {
-                ldir = vscale(ldir, 1.0f / ldist);
+                ldir = vscale(ldir, rcp_(ldist));
                 float costa = dot3(vneg(ldir), lnrm);
                 if (costa > 1.0e-6f) {
                     lem = vscale(lemi, (float)nl);
@@ -578,7 +578,7 @@ RTW_DEV bool shade_b(const uint32_t depth, const uint32_t max_depth, Rng<KIND>& 
         float p = __builtin_fmaxf(__builtin_fmaxf(T.x, T.y), T.z);
         if (cap_rr) p = __builtin_fminf(p, 1.0f);
         if (p < g.rr_draw()) return false;
-        T = vscale(T, 1.0f / p);
+        T = vscale(T, rcp_(p));
     }
     return depth + 1u < max_depth;
 }
@@ -1675,6 +1675,44 @@ __global__ void __launch_bounds__(kBlock) k_debug_intersect(const DScene sc, con
                                  gather_time ? gather_time[i] : 0.f, g, tm, t, prim);
     out_t[i] = t;
     out_prim[i] = prim;
+}
+
+// rtw_debug_math: every 32-bit pattern through one short form of rtw_math.h and through the compiler's form, side by side.
+// The range test is evaluated per lane and the short form taken without the wave vote (the vote only chooses between the two
+// forms compared here). tally[0] = patterns whose results differ (NaN equals NaN), tally[1] = patterns inside the window,
+// tally[2] = the lowest differing pattern (preset to ~0 by the host). Thread i of T takes patterns i, i + T, ...
+// op (include/rtw.h): 0 1.0f / x, 1 sqrtf(x), 2 1.0f / sqrtf(x) as shipped; 3 / 4 the reciprocal with one / two steps, 5 / 6 the
+// root without / with the coupled step, whatever the header's switches say.
+__global__ void __launch_bounds__(kBlock) k_debug_math(int op, unsigned long long* __restrict__ tally) {
+    const uint32_t T = gridDim.x * blockDim.x;
+    uint32_t differ = 0, fast = 0, first = 0xffffffffu;
+    for (uint64_t p = blockIdx.x * blockDim.x + threadIdx.x; p < (1ull << 32); p += T) {
+        const uint32_t bits = (uint32_t)p;
+        const float x = __uint_as_float(bits);
+        float want, got;
+        bool in;
+        if (op == 0) {
+            want = 1.0f / x; in = rtwmath::rcp_window(x); got = rtwmath::rcp_short<MathHw>(x);
+        } else if (op == 1) {
+            want = __builtin_sqrtf(x); in = rtwmath::sqrt_window(x); got = rtwmath::sqrt_short<MathHw>(x);
+        } else if (op == 2) {
+            want = 1.0f / __builtin_sqrtf(x); in = rtwmath::sqrt_window(x); got = rtwmath::rcp_sqrt_short<MathHw>(x);
+        } else if (op == 3) {
+            want = 1.0f / x; in = rtwmath::rcp_window(x); got = rtwmath::rcp_short<MathHw, 1>(x);
+        } else if (op == 4) {
+            want = 1.0f / x; in = rtwmath::rcp_window(x); got = rtwmath::rcp_short<MathHw, 2>(x);
+        } else if (op == 5) {
+            want = __builtin_sqrtf(x); in = rtwmath::sqrt_window(x); got = rtwmath::sqrt_short<MathHw, 0>(x);
+        } else {
+            want = __builtin_sqrtf(x); in = rtwmath::sqrt_window(x); got = rtwmath::sqrt_short<MathHw, 1>(x);
+        }
+        if (!in) continue;
+        fast++;
+        const bool same = __float_as_uint(got) == __float_as_uint(want) || (got != got && want != want);
+        if (!same) { differ++; first = bits < first ? bits : first; }
+    }
+    atomicAdd(&tally[1], (unsigned long long)fast);
+    if (differ) { atomicAdd(&tally[0], (unsigned long long)differ); atomicMin(&tally[2], (unsigned long long)first); }
 }
 
 #endif  // RTW_TEMPLATES_ONLY

@@ -1,12 +1,24 @@
 #!/bin/bash
-# usage: scripts/isa_phases.sh [extra flags] : static instruction counts of k_path<PHILOX,false> per phase (between the phase-fence comments)
+# usage: scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0> per phase (between the
+# phase-fence comments). Compiles rtw_inst_path.hip the way __graft_entry__.build() does (HIP_FLAGS + that unit's UNIT_FLAGS) and
+# prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
+# divisions (v_div_fixup_f32, fallbacks of the short forms included), sqrt = its roots (v_sqrt_f32), rcp_short / rsq_short = the
+# short forms of rtw_math.h (a v_rcp_f32 without a v_div_fixup_f32; v_rsq_f32). Exits 1 when the kernel is not found.
 R=$(cd "$(dirname "$0")/.." && pwd)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -DRTW_MIN_WAVES=4 "$@" -S --cuda-device-only -o /tmp/rtw.s $R/raytracing_weekend_amd/csrc/rtw_hip.hip 2>&1 | grep -E "error" 
-awk '/^_ZN4rtwk6k_pathILi0ELi0EEEvNS_5KArgsE:/{f=1} f{print} /s_endpgm/{if(f){exit}}' /tmp/rtw.s > /tmp/kpath.s
-python3 - <<'PY'
-import re,collections
+T=$(mktemp -d)
+trap 'rm -rf "$T"' EXIT
+FLAGS=$(cd "$R" && python3 -c "
+import __graft_entry__ as g
+print(' '.join([f for f in g.HIP_FLAGS if f != '-shared'] + ['-DRTW_SPLIT_BUILD'] + g.UNIT_FLAGS['rtw_inst_path.hip']))") || exit 1
+${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS "$@" -S --cuda-device-only -o "$T/rtw.s" "$R/raytracing_weekend_amd/csrc/rtw_inst_path.hip" || exit 1
+awk '/^_ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE:/{f=1} f{print} /s_endpgm/{if(f){exit}}' "$T/rtw.s" > "$T/kpath.s"
+if [ ! -s "$T/kpath.s" ]; then echo "isa_phases: no k_pathILi0ELi0ELi0ELi0EEE in the assembly" >&2; exit 1; fi
+awk '/\.amdhsa_kernel _ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE/{f=1} f&&/amdhsa_next_free_vgpr|amdhsa_private_segment_fixed_size/{print} /\.end_amdhsa_kernel/{f=0}' "$T/rtw.s"
+awk '/^_ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE:/{f=1} f&&/^; codeLenInByte/{print; exit}' "$T/rtw.s"
+python3 - "$T/kpath.s" <<'PY'
+import re,collections,sys
 cur="pre"; cnt=collections.OrderedDict()
-for l in open('/tmp/kpath.s'):
+for l in open(sys.argv[1]):
     l=l.strip()
     m=re.match(r"; MARK (\w+)",l)
     if m: cur=m.group(1); continue
@@ -24,5 +36,14 @@ for l in open('/tmp/kpath.s'):
     if op.startswith(('v_readlane','v_writelane')): c['lane']+=1
     if op.startswith('v_cndmask'): c['cndmask']+=1
     if op.startswith('v_cmp'): c['cmp']+=1
-for k,v in cnt.items(): print(k, dict(v))
+    if op.startswith('v_div_fixup_f32'): c['div']+=1
+    if op.startswith('v_sqrt_f32'): c['sqrt']+=1
+    if op.startswith('v_rcp_f32'): c['rcp']+=1
+    if op.startswith('v_rsq_f32'): c['rsq_short']+=1
+tot=collections.Counter()
+for k,v in cnt.items():
+    v['rcp_short']=v.pop('rcp',0)-v.get('div',0)
+    tot.update(v)
+    print(k, dict(v))
+print('total', dict(tot))
 PY

@@ -254,7 +254,9 @@ typedef struct rtw_stats {
     /* per kernel kind, measured with HIP events recorded on the launch stream around every launch */
     double kernel_seconds[RTW_K_COUNT];
     uint64_t kernel_launches[RTW_K_COUNT];
-    uint64_t kernel_segments[RTW_K_COUNT]; /* radiance segments shaded by that kernel (k_trace: path slots traced = a radiance ray and / or its queued probe) */
+    uint64_t kernel_segments[RTW_K_COUNT]; /* radiance segments shaded by that kernel (k_trace: path slots traced = a radiance ray and / or its queued probe).
+                                            * Segments the host counts without a kernel - the one-segment samples of pixels that certainly see nothing,
+                                            * see RTW_CULL below - are in `segments` and in no entry here. */
 } rtw_stats;
 
 typedef struct rtw_ctx rtw_ctx;
@@ -287,7 +289,10 @@ int rtw_render(rtw_ctx* ctx, const rtw_params* params, float* rgba_out, rtw_stat
  * written on it. NULL (which is also HIP's legacy default stream handle) selects the context's own non-blocking stream,
  * which is NOT ordered with the default stream: pass a stream of your own (or hipStreamLegacy / hipStreamPerThread) when
  * d_rgba has pending work. Returns when done. rtw_stats.kernel_seconds is filled from HIP events recorded on the launch
- * streams around every kernel (only when stats != NULL; RTW_KERNEL_TIMING=0 turns the events off). */
+ * streams around every kernel (only when stats != NULL; RTW_KERNEL_TIMING=0 turns the events off).
+ * Tuning knobs are environment variables read per call (csrc/rtw_plan.h lists them); none changes the image or the counts.
+ * RTW_CULL=0 makes renders of scenes without a sky light trace the pixels whose camera rays cannot reach any primitive
+ * as well (by default such pixels are black and their samples counted without being traced). */
 int rtw_render_device(rtw_ctx* ctx, const rtw_params* params, void* d_rgba, void* hip_stream,
                       rtw_stats* stats);
 

@@ -94,6 +94,8 @@ struct rtw_ctx {
     DScene sc{};
     void* d_scene = nullptr;   // one allocation holding all scene tables
     int stack_depth = 0;
+    bool cull_ok = false;               // cull_bmin / cull_bmax hold the bounds the empty-pixel cull projects (rtw_plan.h cull_bounds)
+    float cull_bmin[3] = {0, 0, 0}, cull_bmax[3] = {0, 0, 0};
     size_t lds_bytes = 0;
     size_t n_tree_nodes = 0, n_tree_leaves = 0;  // 4-wide nodes and leaf records of the uploaded scene's tree
     // render pool
@@ -768,6 +770,7 @@ int impl_upload_scene(rtw_ctx* c, const void* blob, size_t bytes) {
         const float pad = 0.01f * std::sqrt(diag) + 1.0f;
         for (int a = 0; a < 3; a++) { sc.bmin[a] = all.mn[a] - pad; sc.bmax[a] = all.mx[a] + pad; }
     }
+    c->cull_ok = cull_bounds(prims.data(), h.n_prims, xforms.data(), h.camera, c->cull_bmin, c->cull_bmax);
     sc.sky_light = h.sky_light;
     sc.use_bvh = use_bvh ? 1 : 0;
     sc.has_motion = has_motion;
@@ -826,6 +829,7 @@ KArgs shard_args(const DScene& sc, const rtw_params* P, size_t npix) {
     a.max_depth = (uint32_t)P->max_depth;
     a.stack_stride = kBlock;
     a.spp = (uint32_t)P->spp;
+    a.cull_x0 = 0; a.cull_x1 = P->width; a.cull_y0 = 0; a.cull_y1 = P->height;  // nothing culled (render_path sets the rectangle)
     return a;
 }
 
@@ -840,6 +844,7 @@ struct CallLog {
     size_t ev_used = 0;
     hipEvent_t begin = nullptr, end = nullptr;
     uint64_t launches = 0;
+    uint64_t culled_segments = 0;  // render_path: one segment per sample of the pixels no kernel was given (rtw_plan.h cull_rect)
 
     hipError_t event(hipEvent_t& e) {
         if (ev_used == c->ev_pool.size()) {
@@ -875,17 +880,28 @@ struct CallLog {
 };
 
 // ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
-int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
-    const size_t npix = base.npix;
+int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base_in, float4* out, hipStream_t s, CallLog& log) {
+    const size_t npix = base_in.npix;
     int rc = ensure_pool(c, 0, 0, npix, 0);
     if (rc) return rc;
+    // groups of 64 pixels that certainly see nothing get no job: a miss adds +0 (no sky light), so their pixels stay at accum = 0
+    // and their samples - one segment each, as the oracle counts them - are added to the call's counts on the host
+    KArgs base = base_in;
+    size_t live_groups = ~(size_t)0, culled_pixels = 0;
+    if (tune.cull && c->cull_ok) {
+        const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->cull_bmin, c->cull_bmax, P->width, P->height);
+        base.cull_x0 = r.x0; base.cull_x1 = r.x1; base.cull_y0 = r.y0; base.cull_y1 = r.y1;
+        live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &culled_pixels);
+    }
+    log.culled_segments = (uint64_t)culled_pixels * (uint64_t)P->spp;
+    const ResolveCull rcull{base.cull_x0, base.cull_x1, base.cull_y0, base.cull_y1, base.width, base.row0, base.row_stride, base.divw_m, base.divw_s1, base.divw_s2};
     int wg_per_cu = tune.path_grid_mult;
     if (wg_per_cu <= 0) {
         int nb = 0;
         const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), kBlock, 0);
         wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
     }
-    const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu);
+    const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, live_groups);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     if (plan.n_groups > c->order_groups) {
         if (c->d_order) (void)hipFree(c->d_order);
@@ -911,6 +927,7 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     }
     const unsigned pix_grid = pixel_grid(c, npix);
     for (const PathPass& ps : plan.passes) {
+        if (live_groups == 0) break;  // the frame looks past everything: black, nothing to launch
         HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
         HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
         hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
@@ -947,9 +964,9 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
         // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
         if (plan.unit_sums)
             hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
-                               (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse));
+                               (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse), rcull);
         else
-            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0);
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0, rcull);
     }
     hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
     return RTW_OK;
@@ -1175,7 +1192,7 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
         for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];
         stats->bounce_launches = log.launches;
         stats->samples = (uint64_t)npix * (uint64_t)P->spp;
-        stats->segments = hs[0];
+        stats->segments = hs[0] + log.culled_segments;  // (kernel_segments above: what the kernels shaded themselves)
         stats->shadow_rays = hs[1];
         stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
     }

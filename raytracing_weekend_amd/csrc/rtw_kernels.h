@@ -97,6 +97,9 @@ struct KArgs {
     const uint32_t* order_counts;  // lengths of the lists of classes 2, 1, 0
     // (the k_path / k_first instantiations with LIST = 1, rtw_render_adaptive's passes, read `order` as the list of active pixels:
     // order[0] = its length n, order[1 + i] = the shard-local pixel of list position i; every other field keeps its meaning)
+    // k_classify: pixels outside [cull_x0, cull_x1) x [cull_y0, cull_y1) (full-image coordinates) certainly see nothing (rtw_plan.h
+    // cull_rect; the whole frame when nothing may be culled). Last in the struct: no kernel argument k_path reads moves.
+    int32_t cull_x0, cull_x1, cull_y0, cull_y1;
 };
 
 struct Path {
@@ -1278,6 +1281,9 @@ RTW_DEV uint32_t order_lookup(const KArgs& A, uint32_t gi) {
 //   class 2  a quarter of the group's pixel-centre camera rays meet a specular surface first (metal, dielectric: long chains)
 //   class 1  some ray can reach the scene
 //   class 0  every ray stays outside the scene bounds (one-segment paths)
+//   (none)   every pixel of the group lies outside the cull rectangle (KArgs cull_*: no ray of theirs can reach a primitive and a miss
+//            adds +0): the group is written to no list, gets no job, and the host counts its samples (rtw_plan.h cull_live_groups
+//            finds the same groups with the same integers: the job count is live groups x ranges)
 // order[] holds three lists (class 2 at 0, class 1 at n_groups, class 0 at 2 n_groups) and counters[] their lengths; the
 // queue serves them in that order. Measured on the metric workload's 1/8 shard: the launch's fixed cost (tail) fell from
 // 5.6 ms to [see DESIGN.md].
@@ -1292,10 +1298,11 @@ __global__ void __launch_bounds__(kBlock) k_classify(const KArgs A, uint32_t* __
     const uint32_t waves = gridDim.x * (kBlock / 64u);
     for (uint32_t g = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); g < n_groups; g += waves) {
         const uint32_t p_local = g * 64u + lane;
-        bool may = false, specular = false;
+        bool may = false, specular = false, inside = false;
         if (p_local < A.npix) {
             const uint32_t yl = fastdiv(p_local, A.divw_m, A.divw_s1, A.divw_s2);
             const uint32_t x = p_local - yl * A.width, y = A.row0 + yl * A.row_stride;
+            inside = (int32_t)x >= A.cull_x0 && (int32_t)x < A.cull_x1 && (int32_t)y >= A.cull_y0 && (int32_t)y < A.cull_y1;
             const rtw_camera& cam = A.sc.cam;
             if (A.sc.cam_type != RTW_CAM_PERSPECTIVE || cam.lens_radius != 0.0f) {
                 may = true;  // (no cheap classification: everything counts as ordinary)
@@ -1315,6 +1322,7 @@ __global__ void __launch_bounds__(kBlock) k_classify(const KArgs A, uint32_t* __
                 }
             }
         }
+        if (__ballot(inside) == 0ull) continue;  // (wave-uniform)
         const bool any = __ballot(may) != 0ull;
         const uint32_t n_spec = (uint32_t)__popcll(__ballot(specular));
         if (lane == 0) {
@@ -1572,9 +1580,15 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
 // per-pixel sums of one k_path pass in the arithmetic spec's order (rtw.h: samples in order inside blocks, block sums in order
 // inside aligned units of kSumUnitBlocks blocks, unit sums in order). slots: n_unit_slots whole unit sums [unit][pixel], then
 // n_block_slots block sums [block][pixel] whose first block (index first_block of the render call) is unit-aligned.
+// Pixels outside the cull rectangle are left alone: their sums are +0 where k_path wrote them (accum + 0 = accum) and were never
+// written where their whole group was culled.
+struct ResolveCull { int32_t x0, x1, y0, y1; uint32_t width, row0, row_stride, divw_m, divw_s1, divw_s2; };
 __global__ void __launch_bounds__(kBlock) k_resolve_blocks(const float4* __restrict__ slots, float4* __restrict__ accum, uint32_t npix, uint32_t n_unit_slots,
-                                                           uint32_t n_block_slots, uint32_t first_block) {
+                                                           uint32_t n_block_slots, uint32_t first_block, const ResolveCull R) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        const uint32_t yl = fastdiv(i, R.divw_m, R.divw_s1, R.divw_s2);
+        const int32_t x = (int32_t)(i - yl * R.width), y = (int32_t)(R.row0 + yl * R.row_stride);
+        if (x < R.x0 || x >= R.x1 || y < R.y0 || y >= R.y1) continue;
         float4 a = accum[i];
         for (uint32_t u = 0; u < n_unit_slots; u++) {
             const float4 l = slots[(size_t)u * npix + i];

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <vector>
@@ -62,6 +63,8 @@ inline void magic_div(uint32_t d, uint32_t& m, uint32_t& s1, uint32_t& s2) {
 //   RTW_PATH_GRID_MULT   k_path workgroups per CU (default: what the occupancy query admits)
 //   RTW_BLOCKSUM_BYTES   cap of the k_path block-sum buffer (default 16 GiB); larger renders run in passes over the samples
 //   RTW_KERNEL_TIMING    0: no per-launch events even when the caller asks for rtw_stats (kernel_seconds stay 0)
+//   RTW_CULL             0: k_path is handed every 64-pixel group, also those no camera ray of which can reach a primitive (default 1:
+//                        such groups get no job and their pixels are black, see cull_rect below; same image and counts either way)
 // Two measured-slower alternatives were removed from the code: k_path_tree for tree scenes and the paired batch
 // schedule; their knobs are no longer read.
 struct Tuning {
@@ -93,6 +96,7 @@ struct Tuning {
     int path_grid_mult = 0;
     size_t blocksum_bytes = (size_t)16 << 30;
     bool kernel_timing = true;
+    bool cull = true;
     bool verbose = false;  // RTW_VERBOSE=1: table sizes at upload (stderr)
 };
 inline Tuning read_tuning() {
@@ -125,6 +129,7 @@ inline Tuning read_tuning() {
     if (geti("RTW_PATH_GRID_MULT", v)) t.path_grid_mult = (int)std::max<long long>(1, std::min<long long>(16, v));
     if (geti("RTW_BLOCKSUM_BYTES", v) && v >= (1 << 16)) t.blocksum_bytes = (size_t)v;
     if (geti("RTW_KERNEL_TIMING", v)) t.kernel_timing = v != 0;
+    if (geti("RTW_CULL", v)) t.cull = v != 0;
     if (geti("RTW_VERBOSE", v)) t.verbose = v != 0;
     return t;
 }
@@ -156,10 +161,13 @@ struct PathPlan {
     std::vector<PathPass> passes;
 };
 
-inline PathPlan plan_path(const Tuning& tune, size_t npix, int spp, int n_cu, int wg_per_cu) {
+// live_groups: the groups that get jobs (cull_live_groups; default: all of them). It sets the job count and the grid; the unit size
+// keeps following the full pixel count (blocks_per_lane below), so a culled render is planned like the uncut one with fewer jobs.
+inline PathPlan plan_path(const Tuning& tune, size_t npix, int spp, int n_cu, int wg_per_cu, size_t live_groups = ~(size_t)0) {
     PathPlan p{};
     const size_t n_blocks = ((size_t)spp + kSumBlock - 1) / kSumBlock;
     const size_t n_groups = (npix + 63) / 64;
+    live_groups = std::min(live_groups, n_groups);
     p.n_blocks = n_blocks;
     p.n_groups = n_groups;
     // A launch ends when its slowest unit ends, and a unit through a glass sphere runs several milliseconds. So the bulk of
@@ -208,13 +216,137 @@ inline PathPlan plan_path(const Tuning& tune, size_t npix, int spp, int n_cu, in
             const size_t n_units = (l.count + l.unit_blocks - 1) / l.unit_blocks;    // units per pixel in this launch
             l.jb = std::min<size_t>((size_t)tune.path_job_blocks, n_units);        // units per pixel and job
             l.n_ranges = (n_units + l.jb - 1) / l.jb;
-            l.n_jobs = n_groups * l.n_ranges;
+            l.n_jobs = live_groups * l.n_ranges;
             if (l.n_jobs > 0xfffffff0ull) p.too_many_jobs = true;
             l.grid = (int)std::min<size_t>((size_t)n_cu * (size_t)wg_per_cu, (l.n_jobs + 3) / 4);
         }
         p.passes.push_back(ps);
     }
     return p;
+}
+
+// ---- pixels that certainly see nothing (k_path renders of scenes without a sky light: DESIGN.md 4.1)
+// A camera ray that meets no primitive adds +0 to its pixel when the scene has no sky light, so a pixel none of whose rays can
+// meet one is black without being traced. cull_bounds: world bounds of every primitive, generous enough for the float arithmetic of
+// the primitive tests; cull_rect: the pixel rectangle outside which every pixel is certainly empty; cull_group_live /
+// cull_live_groups: the 64-pixel groups of a shard that have a pixel inside it (k_classify drops the others from the job order
+// with the same integer predicate; k_path itself knows nothing of this).
+struct CullRect { int32_t x0, x1, y0, y1; };  // every pixel outside [x0, x1) x [y0, y1) (full-image coordinates) is certainly empty
+
+// Union of the primitives' world bounds (rtw_bvh.h world_bounds: the reference's boxes + 1e-4 relative), spheres grown by what their
+// discriminant can get wrong: fma(b, b, -(a * cc)) carries an error of a few 2^-23 |o - c|^2 |d|^2, so a ray passing the centre at
+// distance m can be reported as a hit while m^2 < r^2 + ~2^-21 |o - c|^2. They are grown to sqrt(r^2 + 2^-19 D^2), D = |o - c| + r in
+// object space, times the transform's Frobenius norm. Returns false (nothing may be culled) when there is no primitive, a moving
+// sphere (a ray time outside the sphere's own keys moves it out of its swept box) or something not finite.
+inline bool cull_bounds(const rtw_prim* prims, size_t n_prims, const rtw_xform* xforms, const rtw_camera& cam, float bmin[3], float bmax[3]) {
+    rtwbvh::Box all;
+    for (size_t i = 0; i < n_prims; i++) {
+        const rtw_prim& p = prims[i];
+        const rtw_xform& xf = xforms[p.xform];
+        if (p.type == RTW_PRIM_MOVING_SPHERE) return false;
+        rtwbvh::Box wb = rtwbvh::world_bounds(p, xf);
+        if (p.type == RTW_PRIM_SPHERE || p.type == RTW_PRIM_VOLUME_SPHERE) {
+            double oo[3], frob = 0.0, grow = 0.0;
+            for (int a = 0; a < 3; a++) oo[a] = (double)xf.inv[4 * a] * cam.origin[0] + (double)xf.inv[4 * a + 1] * cam.origin[1] + (double)xf.inv[4 * a + 2] * cam.origin[2] + xf.inv[4 * a + 3];
+            for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) frob += (double)xf.m[4 * a + b] * xf.m[4 * a + b];
+            const double r = std::fabs((double)p.p[3]);
+            const float* c = p.p;
+            const double D = std::sqrt((oo[0] - c[0]) * (oo[0] - c[0]) + (oo[1] - c[1]) * (oo[1] - c[1]) + (oo[2] - c[2]) * (oo[2] - c[2])) + r;
+            grow = std::sqrt(r * r + D * D / 524288.0) - r;
+            const float g = (float)(grow * std::sqrt(frob) * 1.000001);
+            for (int a = 0; a < 3; a++) { wb.mn[a] -= g; wb.mx[a] += g; }
+        }
+        all.add(wb);
+    }
+    bool ok = n_prims > 0;
+    for (int a = 0; a < 3; a++) {
+        bmin[a] = all.mn[a]; bmax[a] = all.mx[a];
+        ok = ok && std::isfinite(bmin[a]) && std::isfinite(bmax[a]) && bmin[a] <= bmax[a];
+    }
+    return ok;
+}
+
+// The rectangle for a frame of width x height pixels. raygen (rtw_kernels.h) builds d = lower_left + s horizontal + t vertical - origin
+// with s = (x + r0) / width, t = (y + r1) / height, r in [0, 1): pixel (x, y) covers s in [x, x + 1] / width ((float)x + r0 may round up
+// to x + 1), t likewise. The eight corners of the bounds, grown by 2^-13 of the largest coordinate around (bounds and camera origin: the
+// primitive tests' float error is some 2^-20 of it), are projected onto (s, t) in double precision: corner - origin = a horizontal +
+// b vertical + c (lower_left - origin), s = a / c, t = b / c. With every c > 0 the bounds' projection is the convex hull of the eight
+// points, inside their bounding rectangle. That rectangle is widened to whole pixels and by ONE MORE pixel on every side, which pays for
+// the rounding of raygen's own arithmetic: s and the two fused multiply-adds and the subtraction leave component k of d off by at most
+// eps_k = 4 * 2^-24 max(|origin_k|, |lower_left_k| + |horizontal_k| + |vertical_k|), which moves (s, t) by at most err_s, err_t computed
+// below - the rectangle is only used when both are below half a pixel (else: whole frame). Whole frame also for a sky light, any camera
+// but the perspective one without a lens, a corner not strictly in front of the camera, a singular camera frame, anything not finite.
+inline CullRect cull_rect(const rtw_camera& cam, int cam_type, int sky_light, const float bmin[3], const float bmax[3], int width, int height) {
+    const CullRect whole{0, width, 0, height};
+    if (sky_light != 0 || cam_type != RTW_CAM_PERSPECTIVE || cam.lens_radius != 0.0f || width <= 0 || height <= 0) return whole;
+    double m[3][3], big = 0.0, eps[3];  // columns: horizontal, vertical, lower_left - origin
+    for (int a = 0; a < 3; a++) {
+        m[a][0] = cam.horizontal[a]; m[a][1] = cam.vertical[a]; m[a][2] = (double)cam.lower_left[a] - (double)cam.origin[a];
+        if (!(bmin[a] <= bmax[a])) return whole;
+        big = std::max(big, std::max(std::fabs((double)bmin[a]), std::max(std::fabs((double)bmax[a]), std::fabs((double)cam.origin[a]))));
+        eps[a] = std::max(std::fabs((double)cam.origin[a]), std::fabs((double)cam.lower_left[a]) + std::fabs(m[a][0]) + std::fabs(m[a][1])) * (4.0 / 16777216.0);
+        if (!std::isfinite(eps[a])) return whole;
+    }
+    if (!std::isfinite(big)) return whole;
+    double inv[3][3];
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    if (!std::isfinite(det) || det == 0.0) return whole;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;  // inv[i][j] = cofactor(j, i) / det
+            inv[i][j] = (m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0]) / det;
+        }
+    // raygen's rounding: a direction error e moves s = a / c (c = 1 on the image plane) by |inv_a e - s inv_c e|, |s| <= 1 + a pixel
+    double err_s = 0.0, err_t = 0.0;
+    for (int k = 0; k < 3; k++) {
+        err_s += (std::fabs(inv[0][k]) + 1.01 * std::fabs(inv[2][k])) * eps[k];
+        err_t += (std::fabs(inv[1][k]) + 1.01 * std::fabs(inv[2][k])) * eps[k];
+    }
+    if (!(err_s * width <= 0.5 && err_t * height <= 0.5)) return whole;
+    const double pad = big / 8192.0;
+    double smin = HUGE_VAL, smax = -HUGE_VAL, tmin = HUGE_VAL, tmax = -HUGE_VAL, cmin = HUGE_VAL, cmax = 0.0;
+    for (int k = 0; k < 8; k++) {
+        double q[3], abc[3];
+        for (int a = 0; a < 3; a++) q[a] = (((k >> a) & 1) ? (double)bmax[a] + pad : (double)bmin[a] - pad) - (double)cam.origin[a];
+        for (int i = 0; i < 3; i++) abc[i] = inv[i][0] * q[0] + inv[i][1] * q[1] + inv[i][2] * q[2];
+        if (!(abc[2] > 0.0)) return whole;
+        cmin = std::min(cmin, abc[2]); cmax = std::max(cmax, abc[2]);
+        smin = std::min(smin, abc[0] / abc[2]); smax = std::max(smax, abc[0] / abc[2]);
+        tmin = std::min(tmin, abc[1] / abc[2]); tmax = std::max(tmax, abc[1] / abc[2]);
+    }
+    if (!(cmin > 1.0e-6 * cmax) || !std::isfinite(smin) || !std::isfinite(smax) || !std::isfinite(tmin) || !std::isfinite(tmax)) return whole;
+    auto lo = [](double v, int n) { return (int32_t)std::max(0.0, std::min((double)n, std::floor(v * n) - 1.0)); };
+    auto hi = [](double v, int n) { return (int32_t)std::max(0.0, std::min((double)n, std::floor(v * n) + 2.0)); };
+    CullRect r{lo(smin, width), hi(smax, width), lo(tmin, height), hi(tmax, height)};
+    if (r.x0 >= r.x1 || r.y0 >= r.y1) r = CullRect{0, 0, 0, 0};  // the frame looks past everything
+    return r;
+}
+
+// Group g of a shard: its shard-local pixels [64 g, 64 g + 64) below npix, local pixel p at x = p % width, y = row0 + (p / width) row_stride.
+// Live = one of them lies inside the rectangle. k_classify decides the same with the same integers (one pixel per lane, a ballot).
+inline bool cull_group_live(const CullRect& r, size_t g, size_t npix, uint32_t width, uint32_t row0, uint32_t row_stride) {
+    const size_t p0 = g * 64, p1 = std::min(npix, p0 + 64);
+    for (size_t yl = p0 / width; yl * width < p1; yl++) {
+        const int64_t y = (int64_t)row0 + (int64_t)(yl * row_stride);
+        if (y < r.y0 || y >= r.y1) continue;
+        const int64_t xa = (int64_t)(std::max(p0, yl * width) - yl * width), xb = (int64_t)(std::min(p1, (yl + 1) * width) - yl * width);  // [xa, xb)
+        if (xa < r.x1 && xb > r.x0) return true;
+    }
+    return false;
+}
+// live groups of the shard and (culled_pixels) the pixels of the others: those k_path never sees
+inline size_t cull_live_groups(const CullRect& r, size_t npix, uint32_t width, uint32_t row0, uint32_t row_stride, size_t* culled_pixels = nullptr) {
+    const size_t n_groups = (npix + 63) / 64;
+    size_t live = 0, dead_pix = 0;
+    if (npix == 0 || width == 0) { if (culled_pixels) *culled_pixels = 0; return 0; }
+    if (r.x0 <= 0 && r.y0 <= 0 && r.x1 >= (int64_t)width && (int64_t)row0 + (int64_t)((npix + width - 1) / width - 1) * row_stride < r.y1) live = n_groups;  // nothing culled
+    else
+        for (size_t g = 0; g < n_groups; g++) {
+            if (cull_group_live(r, g, npix, width, row0, row_stride)) live++;
+            else dead_pix += std::min(npix, g * 64 + 64) - g * 64;
+        }
+    if (culled_pixels) *culled_pixels = dead_pix;
+    return live;
 }
 
 // ---- wavefront pipeline (tree scenes; RTW_PATH=0)

@@ -18,6 +18,7 @@
 
 #define RTW_MATH_FN RTW_DEV
 #include "rtw_math.h"
+#include "rtw_scene.h"  // the host-built records the kernels read: HitRec, BruteGroup, BruteRec, kWalkMaxWords
 
 // One switch per translation unit. 1: reciprocals and roots of one float take the short forms of rtw_math.h (same bits, proved over
 // every input: tests/test_gpu_math_forms.py). 0 (-DRTW_SHORT_FORMS=0, e.g. through __graft_entry__'s RTW_BUILD_FLAGS_<UNIT>): the
@@ -315,42 +316,8 @@ struct Rng<RTW_RNG_PHILOX> {
 // ------------------------------------------------------------------ device scene
 // The tree: 64-byte nodes of the 4-wide tree with quantised child boxes, 32-byte leaf records in tree order (rtw_bvh.h
 // Q4Node, LeafRec). A reference is idx << 2 | count (count 0 = inner node, 1-2 = leaf of that many records).
-// Per-primitive hit record baked at upload (96 B, fetched with a burst of 16-byte loads once
-// the closest hit is known): material + its constant texture colour (texture/constantTexture.cu:5-10,
-// nullTexture.cu:7-12) and everything the shading normal needs, so that no primitive / transform
-// record has to be re-read per lane after traversal.
-enum { HK_CONST_NORMAL = 0, HK_SPHERE = 1, HK_MOVING_SPHERE = 2, HK_SPHERE_XFORM = 3 };
-struct HitRec {
-    int32_t mat_type;   // rtw_material_type
-    int32_t bsdf_eval;
-    float param;        // fuzz or eta
-    int32_t kind;       // HK_* | listed light << 7 | (index of a non-constant texture + 1) << 8
-    float r, g, b;      // texture colour
-    float inv_r;        // spheres: 1/radius (IEEE division, done once on the host)
-    float nx, ny, nz;   // HK_CONST_NORMAL: world shading normal (rectangles, volumes); spheres: centre
-    int32_t xform;
-    // HK_CONST_NORMAL: the orthonormal basis onb::buildFromW(normal) of lib/onb.cuh:20-32, computed once on the
-    // host with the same fp32 operations (u = cross(w,v), v = normalize(cross(w,a)), w = normalize(n))
-    float ux, uy, uz; int32_t tex_dyn;  // (filled by load_hitrec from kind's high bits; -1 = constant colour in r, g, b)
-    float vx, vy, vz; int32_t listed;    // (from kind bit 7) an emitting rectangle a light definition describes
-    float wx, wy, wz, pad2;
-};
-
-// Small-scene candidate lists, built at upload (rtw_upload_scene). 32-byte records so that one
-// s_load_dwordx8 brings a whole candidate into SGPRs; rectangles are sorted by axis inside a group so
-// the inner loops contain no per-candidate kind dispatch at all.
-struct BruteGroup {
-    int32_t xform;
-    int32_t first;                 // first record of the group in recs[]
-    int32_t n_rx, n_ry, n_rz, n_sph;
-    int32_t pad0, pad1;
-};
-struct BruteRec {
-    float a, b, c, d, e;           // rect: a0,a1,b0,b1,k   sphere: cx,cy,cz,r,-
-    int32_t prim;
-    int32_t pad0, pad1;
-};
-
+// The per-primitive hit records (HitRec) and the small scenes' candidate lists (BruteGroup, BruteRec) are plain host-built records:
+// rtw_scene.h.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -972,7 +939,6 @@ RTW_DEV void traverse_brute(const DScene& sc, v3 o, v3 d, float tmin, float tmax
 //   closest hit, ties to the lowest primitive index: (t, prim + 1) < (best_t, best_prim + 1) as ONE unsigned 64-bit
 //                        compare of (bits(t) << 32 | prim + 1): t > 0 where it matters, so bits(t) orders like t
 //   any hit              no running minimum at all: occluded |= hit & (t < tmax)
-constexpr int kWalkMaxWords = 400;  // 6.4 KB of LDS; scenes whose lists are larger use the wavefront kernels
 struct WalkRec { u32x4 q0, q1; };
 RTW_DEV bool in_range(float a, uint32_t lo, uint32_t hi) { return __builtin_amdgcn_fmed3f(a, __uint_as_float(lo), __uint_as_float(hi)) == a; }
 

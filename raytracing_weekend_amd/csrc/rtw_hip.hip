@@ -22,6 +22,8 @@
 //
 // render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
 // (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU).
+// rtw_upload_scene prepares the blob once on the host (rtw_scene.h prepare_scene: validation, hit records, candidate lists, tree, one
+// staged image, likewise checked on the CPU) and copies the image to each device.
 //
 // No OptiX, no CUDA shims, no Triton, no MFMA (divergent scalar fp32). Results do not depend on
 // scheduling: every path owns a counter-based RNG stream and every (pixel, block) its own sum.
@@ -43,6 +45,7 @@
 
 #include "../../include/rtw.h"
 #include "rtw_bvh.h"
+#include "rtw_scene.h"
 #include "rtw_device.h"
 #include "rtw_plan.h"
 #include "rtw_kernels.h"
@@ -93,11 +96,7 @@ struct rtw_ctx {
     bool has_scene = false;
     DScene sc{};
     void* d_scene = nullptr;   // one allocation holding all scene tables
-    int stack_depth = 0;
-    bool cull_ok = false;               // cull_bmin / cull_bmax hold the bounds the empty-pixel cull projects (rtw_plan.h cull_bounds)
-    float cull_bmin[3] = {0, 0, 0}, cull_bmax[3] = {0, 0, 0};
-    size_t lds_bytes = 0;
-    size_t n_tree_nodes = 0, n_tree_leaves = 0;  // 4-wide nodes and leaf records of the uploaded scene's tree
+    SceneInfo info{};          // its host-side facts, overwritten as a whole by every upload (rtw_scene.h)
     // render pool
     // Two independent "lanes" (stream + path pool): consecutive batches alternate between them so that the
     // bandwidth-bound kernels of one batch overlap the compute- and latency-bound kernels of the other.
@@ -458,340 +457,61 @@ int impl_destroy(rtw_ctx* c) {
     return RTW_OK;
 }
 
-int impl_upload_scene(rtw_ctx* c, const void* blob, size_t bytes) {
-    if (!c) return RTW_ERR_INVALID_ARG;
-    if (!c->kids.empty()) {  // group: every device gets its own copy of the scene tables and the tree
-        c->has_scene = false;
-        for (rtw_ctx* k : c->kids) {
-            const int rc = impl_upload_scene(k, blob, bytes);
-            if (rc) return fail(c, rc, k->err);
-        }
-        c->has_scene = true;
-        return RTW_OK;
-    }
-    if (!blob || bytes < sizeof(rtw_scene_header)) return fail(c, RTW_ERR_BAD_SCENE, "scene blob too small");
-    rtw_scene_header h;
-    memcpy(&h, blob, sizeof h);
-    if (h.magic != RTW_SCENE_MAGIC || h.version != RTW_SCENE_VERSION || h.total_bytes > bytes)
-        return fail(c, RTW_ERR_BAD_SCENE, "bad scene header (magic/version/size)");
-    auto in_range = [&](uint32_t off, uint32_t n, size_t sz) { return (size_t)off + (size_t)n * sz <= bytes; };
-    if (!in_range(h.off_prims, h.n_prims, sizeof(rtw_prim)) || !in_range(h.off_xforms, h.n_xforms, sizeof(rtw_xform)) ||
-        !in_range(h.off_materials, h.n_materials, sizeof(rtw_material)) || !in_range(h.off_textures, h.n_textures, sizeof(rtw_texture)) ||
-        !in_range(h.off_lights, h.n_lights, sizeof(rtw_light)) || h.n_xforms < 1)
-        return fail(c, RTW_ERR_BAD_SCENE, "scene table out of range");
-    if (h.camera_type < RTW_CAM_PERSPECTIVE || h.camera_type > RTW_CAM_ORTHOGRAPHIC) return fail(c, RTW_ERR_BAD_SCENE, "unknown camera type");
-    if ((h.off_prims | h.off_xforms | h.off_materials | h.off_textures | h.off_lights | h.off_texdata) & 15u)
-        return fail(c, RTW_ERR_BAD_SCENE, "scene table not 16-byte aligned");
-    const char* b = (const char*)blob;
-    std::vector<rtw_prim> prims(h.n_prims);
-    std::vector<rtw_xform> xforms(h.n_xforms);
-    std::vector<rtw_material> mats(h.n_materials);
-    std::vector<rtw_texture> texs(h.n_textures);
-    std::vector<rtw_light> lights(h.n_lights);
-    if (h.n_prims) memcpy(prims.data(), b + h.off_prims, h.n_prims * sizeof(rtw_prim));
-    memcpy(xforms.data(), b + h.off_xforms, h.n_xforms * sizeof(rtw_xform));
-    if (h.n_materials) memcpy(mats.data(), b + h.off_materials, h.n_materials * sizeof(rtw_material));
-    if (h.n_textures) memcpy(texs.data(), b + h.off_textures, h.n_textures * sizeof(rtw_texture));
-    if (h.n_lights) memcpy(lights.data(), b + h.off_lights, h.n_lights * sizeof(rtw_light));
-
-    for (const rtw_xform& x : xforms)
-        for (int k = 0; k < 12; k++) if (!std::isfinite(x.m[k]) || !std::isfinite(x.inv[k])) return fail(c, RTW_ERR_BAD_SCENE, "transform not finite");
-    for (const rtw_material& m : mats)
-        if (m.texture >= (int32_t)h.n_textures) return fail(c, RTW_ERR_BAD_SCENE, "material texture out of range");
-    // texture data section and texture records (the test-side checker applies the same rules)
-    std::vector<uint32_t> texdata;
-    if (h.off_texdata) {
-        if ((h.off_texdata & 3u) || (size_t)h.off_texdata + (size_t)h.texdata_bytes > bytes) return fail(c, RTW_ERR_BAD_SCENE, "texture data section out of range");
-        texdata.resize(h.texdata_bytes / 4u);
-        if (!texdata.empty()) memcpy(texdata.data(), b + h.off_texdata, texdata.size() * 4u);
-    }
-    for (uint32_t i = 0; i < h.n_textures; i++) {
-        const rtw_texture& t = texs[i];
-        if (t.type == RTW_TEX_CHECKER) {
-            if (t.odd < 0 || t.even < 0 || (uint32_t)t.odd >= h.n_textures || (uint32_t)t.even >= h.n_textures ||
-                texs[t.odd].type == RTW_TEX_CHECKER || texs[t.even].type == RTW_TEX_CHECKER)
-                return fail(c, RTW_ERR_BAD_SCENE, "checker texture children out of range or nested");
-        } else if (t.type == RTW_TEX_NOISE) {
-            if ((size_t)t.data + 1536u > texdata.size()) return fail(c, RTW_ERR_BAD_SCENE, "noise texture tables out of range");
-        } else if (t.type == RTW_TEX_IMAGE) {
-            if ((size_t)t.data + 2u > texdata.size()) return fail(c, RTW_ERR_BAD_SCENE, "image texture out of range");
-            const uint32_t iw = texdata[t.data], ih = texdata[t.data + 1];
-            if (iw == 0 || ih == 0 || iw > 32768u || ih > 32768u || (size_t)t.data + 2u + (size_t)iw * ih > texdata.size())
-                return fail(c, RTW_ERR_BAD_SCENE, "image texture out of range");
-        } else if (t.type != RTW_TEX_CONSTANT && t.type != RTW_TEX_NULL) {
-            return fail(c, RTW_ERR_BAD_SCENE, "unknown texture type");
-        }
-    }
-    // RTW_EST_CORRECTED: light definitions moved onto the emitting rectangles they describe, and which primitives those
-    // are (same matching rule as the CPU checker: same normal axis and in-plane extent, plane within 1 % of the longer edge)
-    std::vector<rtw_light> clights(lights);
-    std::vector<uint8_t> listed(h.n_prims, 0);
-    for (size_t i = 0; i < clights.size(); i++) {
-        rtw_light& lt = clights[i];
-        for (uint32_t j = 0; j < h.n_prims; j++) {
-            const rtw_prim& pr = prims[j];
-            if (pr.type < RTW_PRIM_RECT_X || pr.type > RTW_PRIM_RECT_Z || pr.xform != 0) continue;
-            if (pr.material < 0 || (uint32_t)pr.material >= h.n_materials || mats[pr.material].type != RTW_MAT_DIFFUSE_LIGHT) continue;
-            const int ax = pr.type - RTW_PRIM_RECT_X, aa = ax == 0 ? 1 : 0, ab = ax == 2 ? 1 : 2;
-            const float ea = pr.p[1] - pr.p[0], eb = pr.p[3] - pr.p[2];
-            float u[3] = {0.f, 0.f, 0.f}, v[3] = {0.f, 0.f, 0.f};
-            u[aa] = ea; v[ab] = eb;
-            bool same = lt.position[aa] == pr.p[0] && lt.position[ab] == pr.p[2];
-            for (int k = 0; k < 3; k++) if (lt.vec_u[k] != u[k] || lt.vec_v[k] != v[k]) same = false;
-            if (!same || !(std::fabs(lt.position[ax] - pr.p[4]) <= 0.01f * std::fmax(ea, eb))) continue;
-            lt.position[ax] = pr.p[4];
-            listed[j] = 1;
-            break;
-        }
-    }
-    std::vector<HitRec> shade(h.n_prims);
-    std::vector<int32_t> order;
-    int has_motion = 0, has_tex = 0;
-    for (uint32_t i = 0; i < h.n_prims; i++) {
-        const rtw_prim& p = prims[i];
-        if (p.type < RTW_PRIM_SPHERE || p.type > RTW_PRIM_VOLUME_SPHERE) return fail(c, RTW_ERR_BAD_SCENE, "unknown primitive type");
-        if (p.xform < 0 || (uint32_t)p.xform >= h.n_xforms) return fail(c, RTW_ERR_BAD_SCENE, "primitive xform out of range");
-        if (p.material < 0 || (uint32_t)p.material >= h.n_materials) return fail(c, RTW_ERR_BAD_SCENE, "primitive material out of range");
-        for (int k = 0; k < 12; k++) if (!std::isfinite(p.p[k])) return fail(c, RTW_ERR_BAD_SCENE, "primitive parameter not finite");
-        if (p.type == RTW_PRIM_MOVING_SPHERE) has_motion = 1;
-        const rtw_material& m = mats[p.material];
-        HitRec s{};
-        s.mat_type = m.type; s.bsdf_eval = m.bsdf_eval; s.param = m.fuzz_or_eta; s.xform = p.xform;
-        {
-            // shading-normal data, same fp32 operations and order as the device/oracle would use per hit
-            const rtw_xform& xf = xforms[p.xform];
-            auto xfn = [&](float nx, float ny, float nz, float* o3) {
-                float v[3] = {std::fmaf(xf.inv[0], nx, std::fmaf(xf.inv[4], ny, xf.inv[8] * nz)),
-                              std::fmaf(xf.inv[1], nx, std::fmaf(xf.inv[5], ny, xf.inv[9] * nz)),
-                              std::fmaf(xf.inv[2], nx, std::fmaf(xf.inv[6], ny, xf.inv[10] * nz))};
-                float dd = std::fmaf(v[2], v[2], std::fmaf(v[1], v[1], v[0] * v[0]));
-                float inv = 1.0f / std::sqrt(dd);
-                o3[0] = v[0] * inv; o3[1] = v[1] * inv; o3[2] = v[2] * inv;
-            };
-            if (p.type == RTW_PRIM_SPHERE || p.type == RTW_PRIM_MOVING_SPHERE) {
-                s.kind = p.type == RTW_PRIM_MOVING_SPHERE ? HK_MOVING_SPHERE : (p.xform != 0 ? HK_SPHERE_XFORM : HK_SPHERE);
-                s.nx = p.p[0]; s.ny = p.p[1]; s.nz = p.p[2];
-                s.inv_r = 1.0f / p.p[3];
-            } else {
-                s.kind = HK_CONST_NORMAL;
-                float n[3] = {0.f, 0.f, 0.f};
-                if (p.type == RTW_PRIM_RECT_X) n[0] = 1.f;
-                else if (p.type == RTW_PRIM_RECT_Y) n[1] = 1.f;
-                else if (p.type == RTW_PRIM_RECT_Z) n[2] = 1.f;
-                else n[0] = 1.f;  // volumes report (1,0,0)
-                if (p.flip && !rtwbvh::is_volume(p.type)) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
-                if (p.xform != 0) { float w[3]; xfn(n[0], n[1], n[2], w); n[0] = w[0]; n[1] = w[1]; n[2] = w[2]; }
-                s.nx = n[0]; s.ny = n[1]; s.nz = n[2];
-                // onb::buildFromW (lib/onb.cuh:20-32) with the device's fp32 operation order
-                auto nrm = [](const float* a3, float* o3) {
-                    float dd = std::fmaf(a3[2], a3[2], std::fmaf(a3[1], a3[1], a3[0] * a3[0]));
-                    float inv = 1.0f / std::sqrt(dd);
-                    o3[0] = a3[0] * inv; o3[1] = a3[1] * inv; o3[2] = a3[2] * inv;
-                };
-                auto crs = [](const float* a3, const float* b3, float* o3) {
-                    o3[0] = std::fmaf(a3[1], b3[2], -(a3[2] * b3[1]));
-                    o3[1] = std::fmaf(a3[2], b3[0], -(a3[0] * b3[2]));
-                    o3[2] = std::fmaf(a3[0], b3[1], -(a3[1] * b3[0]));
-                };
-                float w3[3], a3[3], t3[3], v3_[3], u3[3];
-                nrm(n, w3);
-                if (w3[0] > 0.9f || w3[0] < -0.9f) { a3[0] = 0.f; a3[1] = 1.f; a3[2] = 0.f; } else { a3[0] = 1.f; a3[1] = 0.f; a3[2] = 0.f; }
-                crs(w3, a3, t3);
-                nrm(t3, v3_);
-                crs(w3, v3_, u3);
-                s.ux = u3[0]; s.uy = u3[1]; s.uz = u3[2];
-                s.vx = v3_[0]; s.vy = v3_[1]; s.vz = v3_[2];
-                s.wx = w3[0]; s.wy = w3[1]; s.wz = w3[2];
-            }
-        }
-        if (m.texture >= 0) {
-            if ((uint32_t)m.texture >= h.n_textures) return fail(c, RTW_ERR_BAD_SCENE, "material texture out of range");
-            const rtw_texture& t = texs[m.texture];
-            if (t.type == RTW_TEX_CONSTANT) { s.r = t.color[0]; s.g = t.color[1]; s.b = t.color[2]; }
-            else if (t.type != RTW_TEX_NULL) { s.kind |= (m.texture + 1) << 8; has_tex = 1; }  // checker / noise / image: evaluated per hit
-        }
-        if (listed[i]) s.kind |= 0x80;
-        shade[i] = s;
-    }
-    const Tuning tune = read_tuning();
-    const bool use_bvh = (int)h.n_prims > tune.brute_max;
-    // order[]: volumes (index order), then -- small scenes only -- the moving spheres, which keep the generic test
-    for (uint32_t i = 0; i < h.n_prims; i++) if (rtwbvh::is_volume(prims[i].type)) order.push_back((int32_t)i);
-    const int n_vol = (int)order.size();
-    if (!use_bvh)
-        for (uint32_t i = 0; i < h.n_prims; i++) if (prims[i].type == RTW_PRIM_MOVING_SPHERE) order.push_back((int32_t)i);
-    const int n_generic = (int)order.size() - n_vol;
-
-    // small scenes: regroup the remaining primitives by instance transform, rectangles by axis
-    std::vector<BruteGroup> groups;
-    std::vector<BruteRec> recs;
-    if (!use_bvh) {
-        std::vector<int> xf_seen;
-        for (uint32_t i = 0; i < h.n_prims; i++) {
-            const int t = prims[i].type;
-            if (rtwbvh::is_volume(t) || t == RTW_PRIM_MOVING_SPHERE) continue;
-            if (std::find(xf_seen.begin(), xf_seen.end(), prims[i].xform) == xf_seen.end()) xf_seen.push_back(prims[i].xform);
-        }
-        for (int xf : xf_seen) {
-            BruteGroup g{};
-            g.xform = xf;
-            g.first = (int32_t)recs.size();
-            const int kinds[4] = {RTW_PRIM_RECT_X, RTW_PRIM_RECT_Y, RTW_PRIM_RECT_Z, RTW_PRIM_SPHERE};
-            int32_t* counts[4] = {&g.n_rx, &g.n_ry, &g.n_rz, &g.n_sph};
-            for (int k = 0; k < 4; k++)
-                for (uint32_t i = 0; i < h.n_prims; i++) {
-                    const rtw_prim& p = prims[i];
-                    if (p.type != kinds[k] || p.xform != xf) continue;
-                    BruteRec r{};
-                    if (k < 3) { r.a = p.p[0]; r.b = p.p[1]; r.c = p.p[2]; r.d = p.p[3]; r.e = p.p[4]; }
-                    else { r.a = p.p[0]; r.b = p.p[1]; r.c = p.p[2]; r.d = p.p[3]; }
-                    r.prim = (int32_t)i;
-                    recs.push_back(r);
-                    (*counts[k])++;
-                }
-            groups.push_back(g);
-        }
-    }
-    // k_path's LDS image of the same lists (rtw_device.h walk_lds): groups, their world->object matrices, records
-    std::vector<uint32_t> walk;
-    if (!use_bvh && n_generic == 0 && !groups.empty()) {
-        static_assert(sizeof(BruteGroup) == 32 && sizeof(BruteRec) == 32, "walk image layout");
-        const size_t ng = groups.size();
-        walk.resize((5 * ng + 2 * recs.size() + 4) * 4, 0u);  // + 4 words: the reader fetches up to two records ahead
-        memcpy(walk.data(), groups.data(), ng * sizeof(BruteGroup));
-        for (size_t g = 0; g < ng; g++) memcpy(walk.data() + (2 * ng + 3 * g) * 4, xforms[groups[g].xform].inv, 12 * sizeof(float));
-        if (!recs.empty()) memcpy(walk.data() + 5 * ng * 4, recs.data(), recs.size() * sizeof(BruteRec));
-        for (size_t i = 0; i < recs.size(); i++) walk[(5 * ng + 2 * i) * 4 + 5] = (uint32_t)recs[i].prim + 1u;  // the walk's tie key
-        // (a rectangle with lo > hi can never be hit under either form of the range test, so none needs removing)
-        if (walk.size() / 4 > (size_t)kWalkMaxWords) walk.clear();
-    }
-    rtwbvh::Bvh bvh;
-    if (use_bvh) {
-        bvh = rtwbvh::build_bvh(prims.data(), h.n_prims, xforms.data());
-        if (bvh.stack_need > 95) return fail(c, RTW_ERR_UNSUPPORTED, "tree deeper than the LDS traversal stack");
-        if (bvh.max_exp > 60) return fail(c, RTW_ERR_UNSUPPORTED, "scene extent beyond 1e20");
-    }
-
-    // one device allocation, 256-byte aligned sub-tables
-    auto al = [](size_t v) { return (v + 255u) & ~size_t(255); };
-    size_t o_prims = 0;
-    size_t o_xf = al(o_prims + prims.size() * sizeof(rtw_prim));
-    size_t o_shade = al(o_xf + xforms.size() * sizeof(rtw_xform));
-    size_t o_lights = al(o_shade + shade.size() * sizeof(HitRec));
-    size_t o_clights = al(o_lights + std::max<size_t>(1, lights.size()) * sizeof(rtw_light));
-    size_t o_nodes = al(o_clights + std::max<size_t>(1, lights.size()) * sizeof(rtw_light));
-    // the wave-coherent walk's nodes: fp32 child boxes, padded for its plane arithmetic. It computes a plane's distance as
-    // fma(plane, 1/d, -(o * 1/d)): the rounding of o * 1/d displaces a plane by about ulp(|o|) in space, so the boxes grow by
-    // 2^-19 of the largest coordinate around (scene bounds, camera origin; the primitives' own bounds carry 1e-4 already)
-    if (use_bvh) {
-        float big = 1.0f;
-        for (uint32_t i = 0; i < h.n_prims; i++) {
-            const rtwbvh::Box wb = rtwbvh::world_bounds(prims[i], xforms[prims[i].xform]);
-            for (int a = 0; a < 3; a++) big = std::max(big, std::max(std::fabs(wb.mn[a]), std::fabs(wb.mx[a])));
-        }
-        for (int a = 0; a < 3; a++) big = std::max(big, std::fabs(h.camera.origin[a]) + std::fabs(h.camera.lens_radius));
-        const float pad = 1.0e-4f + big * (1.0f / 524288.0f);
-        for (rtwbvh::WNode& w : bvh.wq4)
-            for (int k = 0; k < 4; k++)
-                if (w.ref[k] != rtwbvh::kQ4Empty)
-                    for (int a = 0; a < 3; a++) { w.box[k][a] -= pad; w.box[k][3 + a] += pad; }
-    }
-    size_t o_wnodes = al(o_nodes + std::max<size_t>(1, bvh.q4.size()) * sizeof(rtwbvh::Q4Node));
-    size_t o_tree = al(o_wnodes + std::max<size_t>(1, bvh.wq4.size()) * sizeof(rtwbvh::WNode));
-    size_t o_order = al(o_tree + std::max<size_t>(1, bvh.leaves.size()) * sizeof(rtwbvh::LeafRec));
-    size_t o_groups = al(o_order + std::max<size_t>(1, order.size()) * sizeof(int32_t));
-    size_t o_recs = al(o_groups + std::max<size_t>(1, groups.size()) * sizeof(BruteGroup));
-    size_t o_texs = al(o_recs + (recs.size() + 1) * sizeof(BruteRec));  // + 1: traverse_brute reads one record ahead
-    size_t o_texdata = al(o_texs + std::max<size_t>(1, texs.size()) * sizeof(rtw_texture));
-    size_t o_walk = al(o_texdata + std::max<size_t>(1, texdata.size()) * sizeof(uint32_t));
-    size_t total = al(o_walk + std::max<size_t>(1, walk.size()) * sizeof(uint32_t));
-    std::vector<char> stage(total, 0);
-    if (!prims.empty()) memcpy(stage.data() + o_prims, prims.data(), prims.size() * sizeof(rtw_prim));
-    memcpy(stage.data() + o_xf, xforms.data(), xforms.size() * sizeof(rtw_xform));
-    if (!shade.empty()) memcpy(stage.data() + o_shade, shade.data(), shade.size() * sizeof(HitRec));
-    if (!lights.empty()) memcpy(stage.data() + o_lights, lights.data(), lights.size() * sizeof(rtw_light));
-    if (!clights.empty()) memcpy(stage.data() + o_clights, clights.data(), clights.size() * sizeof(rtw_light));
-    if (!bvh.q4.empty()) memcpy(stage.data() + o_nodes, bvh.q4.data(), bvh.q4.size() * sizeof(rtwbvh::Q4Node));
-    if (!bvh.wq4.empty()) memcpy(stage.data() + o_wnodes, bvh.wq4.data(), bvh.wq4.size() * sizeof(rtwbvh::WNode));
-    if (!bvh.leaves.empty()) memcpy(stage.data() + o_tree, bvh.leaves.data(), bvh.leaves.size() * sizeof(rtwbvh::LeafRec));
-    if (!order.empty()) memcpy(stage.data() + o_order, order.data(), order.size() * sizeof(int32_t));
-    if (!groups.empty()) memcpy(stage.data() + o_groups, groups.data(), groups.size() * sizeof(BruteGroup));
-    if (!recs.empty()) memcpy(stage.data() + o_recs, recs.data(), recs.size() * sizeof(BruteRec));
-    if (!texs.empty()) memcpy(stage.data() + o_texs, texs.data(), texs.size() * sizeof(rtw_texture));
-    if (!texdata.empty()) memcpy(stage.data() + o_texdata, texdata.data(), texdata.size() * sizeof(uint32_t));
-    if (!walk.empty()) memcpy(stage.data() + o_walk, walk.data(), walk.size() * sizeof(uint32_t));
-
+// one device's share of an upload: the staged image copied, DScene bound to it
+int upload_prepared(rtw_ctx* c, const PreparedScene& ps) {
     test_fault("upload");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_scene) { (void)hipFree(c->d_scene); c->d_scene = nullptr; }
     c->has_scene = false;
-    HIP_TRY(c, hipMalloc(&c->d_scene, total));
-    HIP_TRY(c, hipMemcpy(c->d_scene, stage.data(), total, hipMemcpyHostToDevice));
-    char* d = (char*)c->d_scene;
+    HIP_TRY(c, hipMalloc(&c->d_scene, ps.image.size()));
+    HIP_TRY(c, hipMemcpy(c->d_scene, ps.image.data(), ps.image.size(), hipMemcpyHostToDevice));
+    const char* d = (const char*)c->d_scene;
+    const SceneScalars& v = ps.sc;
+    const SceneFacts& f = ps.info.facts;
     DScene sc{};
-    sc.prims = (const rtw_prim*)(d + o_prims);
-    sc.xforms = (const rtw_xform*)(d + o_xf);
-    sc.hitrec = (const HitRec*)(d + o_shade);
-    sc.lights = (const rtw_light*)(d + o_lights);
-    sc.clights = (const rtw_light*)(d + o_clights);
+    sc.prims = (const rtw_prim*)(d + ps.off[ST_PRIMS]);
+    sc.xforms = (const rtw_xform*)(d + ps.off[ST_XFORMS]);
+    sc.hitrec = (const HitRec*)(d + ps.off[ST_HITREC]);
+    sc.lights = (const rtw_light*)(d + ps.off[ST_LIGHTS]);
+    sc.clights = (const rtw_light*)(d + ps.off[ST_CLIGHTS]);
+    sc.nodes = (const u32x4*)(d + ps.off[ST_NODES]);
+    sc.wnodes = (const u32x4*)(d + ps.off[ST_WNODES]);
+    sc.leaves = (const u32x4*)(d + ps.off[ST_LEAVES]);
+    sc.order = (const int32_t*)(d + ps.off[ST_ORDER]);
+    sc.groups = (const BruteGroup*)(d + ps.off[ST_GROUPS]);
+    sc.recs = (const BruteRec*)(d + ps.off[ST_RECS]);
+    sc.texs = (const rtw_texture*)(d + ps.off[ST_TEXS]);
+    sc.texdata = (const uint32_t*)(d + ps.off[ST_TEXDATA]);
+    sc.walk = (const u32x4*)(d + ps.off[ST_WALK]);
+    sc.n_prims = v.n_prims; sc.n_tree = v.n_tree; sc.n_lights = v.n_lights; sc.sky_light = v.sky_light; sc.has_motion = v.has_motion;
+    sc.n_groups = v.n_groups; sc.n_generic = v.n_generic; sc.n_walk_words = v.n_walk_words; sc.n_lds_nodes = v.n_lds_nodes; sc.has_tex = v.has_tex;
+    sc.noise_lds_data = v.noise_lds_data; sc.n_lds_leaves = v.n_lds_leaves; sc.cam_type = v.cam_type;
+    sc.use_bvh = f.use_bvh ? 1 : 0; sc.n_vol = f.n_vol; sc.stack_depth = f.stack_depth; sc.stack_wide = f.stack_wide ? 1 : 0; sc.n_nodes = (int32_t)f.n_tree_nodes;
     sc.estimator = RTW_EST_REFERENCE; sc.ray_tmin = 1e-6f; sc.probe_eps = 500 * 1.0e-7f;  // set per render
-    sc.nodes = (const u32x4*)(d + o_nodes);
-    sc.leaves = (const u32x4*)(d + o_tree);
-    sc.wnodes = (const u32x4*)(d + o_wnodes);
-    sc.order = (const int32_t*)(d + o_order);
-    sc.groups = (const BruteGroup*)(d + o_groups);
-    sc.recs = (const BruteRec*)(d + o_recs);
-    sc.texs = (const rtw_texture*)(d + o_texs);
-    sc.texdata = (const uint32_t*)(d + o_texdata);
-    sc.walk = (const u32x4*)(d + o_walk);
-    sc.n_walk_words = (int32_t)(walk.size() / 4);
-    sc.noise_lds_data = -1;  // the first noise texture some primitive shows gets its tables staged in LDS
-    for (uint32_t i = 0; i < h.n_prims && sc.noise_lds_data < 0; i++) {
-        int ti = mats[prims[i].material].texture;
-        if (ti < 0) continue;
-        if (texs[ti].type == RTW_TEX_CHECKER) ti = texs[texs[ti].odd].type == RTW_TEX_NOISE ? texs[ti].odd : texs[ti].even;
-        if (texs[ti].type == RTW_TEX_NOISE) sc.noise_lds_data = (int32_t)texs[ti].data;
-    }
-    // selects the kernel instantiations that contain the cold features: textures, media, (k_path) moving spheres in the brute lists,
-    // camera kinds other than the reference's lens-free perspective camera
-    sc.has_tex = (has_tex || n_vol > 0 || n_generic > 0 || h.camera_type != RTW_CAM_PERSPECTIVE || h.camera.lens_radius != 0.0f) ? 1 : 0;
-    sc.n_groups = (int)groups.size();
-    sc.n_generic = n_generic;
-    sc.n_prims = (int)h.n_prims;
-    sc.n_vol = n_vol;
-    sc.n_tree = (int)bvh.prim_order.size();
-    sc.n_lights = (int)h.n_lights;
-    {   // generous bounds of the whole scene (volumes and motion sweeps included), padded by 1 % of the diagonal
-        rtwbvh::Box all;
-        for (uint32_t i = 0; i < h.n_prims; i++) all.add(rtwbvh::world_bounds(prims[i], xforms[prims[i].xform]));
-        float diag = 0.f;
-        for (int a = 0; a < 3; a++) diag += (all.mx[a] - all.mn[a]) * (all.mx[a] - all.mn[a]);
-        const float pad = 0.01f * std::sqrt(diag) + 1.0f;
-        for (int a = 0; a < 3; a++) { sc.bmin[a] = all.mn[a] - pad; sc.bmax[a] = all.mx[a] + pad; }
-    }
-    c->cull_ok = cull_bounds(prims.data(), h.n_prims, xforms.data(), h.camera, c->cull_bmin, c->cull_bmax);
-    sc.sky_light = h.sky_light;
-    sc.use_bvh = use_bvh ? 1 : 0;
-    sc.has_motion = has_motion;
-    sc.cam = h.camera;
-    sc.pdf = h.pdf;
-    sc.cam_type = h.camera_type;
-    // LDS per block: the traversal stacks (16-bit entries when every reference fits), then as many leading (breadth-first)
-    // tree nodes and, behind them, leaf records as fit the budget
-    c->stack_depth = use_bvh ? bvh.stack_need + 2 : 0;  // + the two rows under the stack that end a walk
-    sc.stack_depth = c->stack_depth;
-    sc.n_lds_nodes = 0; sc.n_lds_leaves = 0; sc.stack_wide = 0;
-    c->lds_bytes = 0;
-    if (use_bvh) {
-        sc.stack_wide = (std::max(bvh.q4.size(), (size_t)bvh.n_slots) << 2) >= 0x7ff0u ? 1 : 0;  // 16-bit entries are read sign-extended
-        c->n_tree_nodes = bvh.q4.size(); c->n_tree_leaves = bvh.n_slots;
-        sc.n_nodes = (int32_t)bvh.q4.size();
-        c->lds_bytes = tree_lds_layout(c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, sc.stack_wide != 0, kBlock, tune.lds_kb * 1024, sc.n_lds_nodes, sc.n_lds_leaves);
-        if (tune.verbose) fprintf(stderr, "[rtw] tree (SAH bins %d, collapse %d, sample-walk cost %.3f): %zu nodes, %zu leaf records, stack %d x %d bit; LDS %zu B: %d nodes, %d leaf records\n", bvh.bins, bvh.collapse_kind, bvh.cost,
-                                  bvh.q4.size(), (size_t)bvh.n_slots, c->stack_depth, sc.stack_wide ? 32 : 16, c->lds_bytes, sc.n_lds_nodes, sc.n_lds_leaves);
-    }
+    for (int a = 0; a < 3; a++) { sc.bmin[a] = v.bmin[a]; sc.bmax[a] = v.bmax[a]; }
+    sc.cam = v.cam;
+    sc.pdf = v.pdf;
     c->sc = sc;
+    c->info = ps.info;
+    c->has_scene = true;
+    return RTW_OK;
+}
+
+// The blob is prepared once on the host (rtw_scene.h: nothing of the context changes when it is refused); every device of a group
+// then gets its own copy of the staged image.
+int impl_upload_scene(rtw_ctx* c, const void* blob, size_t bytes) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (!c->kids.empty()) c->has_scene = false;
+    PreparedScene ps;
+    std::string err;
+    const int prc = prepare_scene(blob, bytes, read_tuning(), ps, err);
+    if (prc) return fail(c, prc, err);
+    if (c->kids.empty()) return upload_prepared(c, ps);
+    for (rtw_ctx* k : c->kids) {
+        const int rc = upload_prepared(k, ps);
+        if (rc) return fail(c, rc, k->err);
+    }
     c->has_scene = true;
     return RTW_OK;
 }
@@ -888,8 +608,8 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     // and their samples - one segment each, as the oracle counts them - are added to the call's counts on the host
     KArgs base = base_in;
     size_t live_groups = ~(size_t)0, culled_pixels = 0;
-    if (tune.cull && c->cull_ok) {
-        const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->cull_bmin, c->cull_bmax, P->width, P->height);
+    if (tune.cull && c->info.cull_ok) {
+        const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->info.cull_bmin, c->info.cull_bmax, P->width, P->height);
         base.cull_x0 = r.x0; base.cull_x1 = r.x1; base.cull_y0 = r.y0; base.cull_y1 = r.y1;
         live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &culled_pixels);
     }
@@ -976,7 +696,7 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
 // pixel; list: of each listed pixel), then the plan's schedule. a: the batch's arguments (the render's, with sample0 of the batch)
 int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a, rtw_ctx::Lane& L, size_t paths, size_t Sb, hipEvent_t ready,
                 CallLog& log, bool list) {
-    const size_t lds = c->lds_bytes;
+    const size_t lds = c->info.lds_bytes;
     const uint32_t regions = w.grid_for(paths);
     HIP_TRY(c, hipStreamWaitEvent(L.st, ready, 0));
     HIP_TRY(c, hipMemsetAsync(L.cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
@@ -997,7 +717,7 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
     a.depth = 0; a.n_iter = 1;
     log.launches++;
     // every compacting launch uses exactly this grid: workgroup b owns region b
-    HIP_TRY(c, log.launch(L.st, RTW_K_FIRST, a, (int)regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->stack_depth * sizeof(uint32_t) : 0, kBlock, list));
+    HIP_TRY(c, log.launch(L.st, RTW_K_FIRST, a, (int)regions, c->sc.use_bvh ? (size_t)(kBlock / 64) * (size_t)c->info.facts.stack_depth * sizeof(uint32_t) : 0, kBlock, list));
     for (const Step& st : w.sched) {
         a.in = L.buf[cur];
         a.hit = L.hit[cur];
@@ -1029,7 +749,7 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
 // ---- wavefront pipeline (tree scenes; RTW_PATH=0): batches of S samples per pixel alternate between the lanes
 int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
     const size_t npix = base.npix;
-    const SceneFacts sf{c->sc.use_bvh != 0, c->sc.n_vol, c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, c->sc.stack_wide != 0};
+    const SceneFacts& sf = c->info.facts;
     WavefrontPlan w;
     for (;;) {
         w = plan_wavefront(tune, npix, P->spp, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, sf);
@@ -1453,7 +1173,7 @@ int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune,
                             size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
     const size_t npix = base.npix;
     const size_t step = (size_t)(n_to - n_from);
-    const SceneFacts sf{c->sc.use_bvh != 0, c->sc.n_vol, c->n_tree_nodes, c->n_tree_leaves, c->stack_depth, c->sc.stack_wide != 0};
+    const SceneFacts& sf = c->info.facts;
     WavefrontPlan w;
     for (;;) {
         size_t S = P->samples_per_pass > 0 ? (size_t)P->samples_per_pass : std::max<size_t>(1, std::min(tune.pool_paths, c->pool_cap) / (size_t)tune.lanes / npix);
@@ -1695,7 +1415,7 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
         if (e == hipSuccess) e = hipEventRecord(ev[0], d->stream);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_guides, dim3(pixel_grid(d, npix)), dim3(kBlock), d->lds_bytes, d->stream, a, g);
+        hipLaunchKernelGGL(k_guides, dim3(pixel_grid(d, npix)), dim3(kBlock), d->info.lds_bytes, d->stream, a, g);
         e = hipGetLastError();
     }
     if (e == hipSuccess && stats) e = hipEventRecord(ev[1], d->stream);
@@ -1750,7 +1470,7 @@ int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, c
     HIP_TRY_D(hipMemcpy(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
     if (ray_time) { HIP_TRY_D(hipMalloc(&d_rt, (size_t)n * sizeof(float))); HIP_TRY_D(hipMemcpy(d_rt, ray_time, (size_t)n * sizeof(float), hipMemcpyHostToDevice)); }
     if (gather_time) { HIP_TRY_D(hipMalloc(&d_gt, (size_t)n * sizeof(float))); HIP_TRY_D(hipMemcpy(d_gt, gather_time, (size_t)n * sizeof(float), hipMemcpyHostToDevice)); }
-    const size_t lds = c->lds_bytes;
+    const size_t lds = c->info.lds_bytes;
     hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, c->stream, c->sc, (const float*)d_rays,
                        (const float*)d_rt, (const float*)d_gt, n, d_t, d_p, (uint32_t)kBlock);
     HIP_TRY_D(hipGetLastError());

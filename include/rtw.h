@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RTW_ABI_VERSION 4   /* entry points and the structs they take (rtw_params, rtw_stats, rtw_guides, rtw_adaptive) */
+#define RTW_ABI_VERSION 5   /* entry points and the structs they take (rtw_params, rtw_stats, rtw_guides, rtw_adaptive, rtw_accum_info) */
 #define RTW_SCENE_VERSION 1 /* layout of the scene blob (rtw_scene_header.version) */
 #define RTW_SCENE_MAGIC 0x57545221u /* "!RTW" */
 /* Summation order of a pixel's samples (part of the arithmetic contract). Three levels, all counted from
@@ -388,6 +388,62 @@ typedef struct rtw_adaptive {
 
 int rtw_render_adaptive(rtw_ctx* ctx, const rtw_params* params, const rtw_adaptive* ad, float* rgba_out, int32_t* spp_out,
                         float* error_out, rtw_stats* stats);
+
+/* Accumulation sessions: a device-resident running sum of a shard's samples that the caller adds to as often as it likes, reads
+ * whenever it likes and saves to or restores from host memory - progressive previews, checkpoints, "another 256 spp". The frame
+ * after n samples is rtw_render's frame with spp = n, bit for bit, whatever the schedule of adds: the session keeps the summation
+ * order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS (blocks of 16, units of 128 counted from sample_offset, units in order) by carrying
+ * the open unit from add to add.
+ *   One session per context. Groups (n_devices > 1): the session runs on device_ids[0], as rtw_render_guides does.
+ *   rtw_accum_begin: params means what it means for rtw_render (rows, row_stride, seed, rng_kind, sample_offset, estimator,
+ *     samples_per_pass), except that params->spp is the CAP, the most samples per pixel the session may ever hold: a positive
+ *     multiple of RTW_SUM_BLOCK with sample_offset + cap <= INT32_MAX (the cap costs nothing: the state does not depend on it).
+ *     flags: 0 or RTW_ACCUM_ERROR (keep the batch-means moments, 16 more bytes per pixel, so that a read can return the error map;
+ *     every block sum then reaches memory, as in rtw_render_adaptive's passes). The state starts at zero samples.
+ *     Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for bad params or flags, an empty shard, or a session that is
+ *     already active.
+ *   rtw_accum_add: renders samples [sample_offset + done, sample_offset + done + spp) of every pixel of the shard into the state and
+ *     returns when done. spp is a positive multiple of RTW_SUM_BLOCK with done + spp <= cap, else RTW_ERR_INVALID_ARG (and the session
+ *     is as it was). The launches are rtw_render's (tuning knobs as there). stats (may be NULL) describes this add alone; samples,
+ *     segments and shadow_rays summed over the adds equal the counts of the one-shot render (rtw_accum_status keeps the sums).
+ *     An add that fails on the device ends the session.
+ *   rtw_accum_read / rtw_accum_read_device: the frame of the done samples - rtw_render's / rtw_render_device's output with spp = done,
+ *     same layout, bit for bit; read_device is ordered on hip_stream as rtw_render_device is (NULL: the context's own stream) and
+ *     returns when the frame is written. Reading changes nothing: add, read, add is fine. error_out (may be NULL; rows*width float)
+ *     is rtw_render_adaptive's error_out for spp = min_spp = done (one checkpoint), bit for bit: the same formula over the same block
+ *     sums in the same fp64 order. Errors: RTW_ERR_INVALID_ARG without a session, at done = 0, with a NULL frame pointer, and for
+ *     error_out on a session without RTW_ACCUM_ERROR or with done < 2 * RTW_SUM_BLOCK.
+ *   rtw_accum_status: fills *out; without a session active = 0 and everything else is 0. Never fails on a valid context.
+ *   rtw_accum_save: copies the session into blob (host memory), bytes == state_bytes of rtw_accum_status: a 128-byte header (magic,
+ *     version, flags, the params of begin, done, the three running counts, a 64-bit FNV-1a fingerprint of the uploaded scene blob)
+ *     followed by the per-pixel arrays: the closed units' sums, the open unit's sums (rows*width float4 each) and, with
+ *     RTW_ACCUM_ERROR, the moments (rows*width pairs of doubles). Native byte order. The session goes on.
+ *   rtw_accum_restore: starts a session from such a blob, in this or any other context or process: it needs an uploaded scene with
+ *     the same fingerprint and no active session. The restored session continues exactly. RTW_ERR_INVALID_ARG for a blob that is
+ *     not a saved session (magic, version), whose size, params or counts do not fit together, or that belongs to another scene; the
+ *     context then stays usable and without a session.
+ *   rtw_accum_end: frees the session (RTW_ERR_INVALID_ARG when there is none). rtw_upload_scene and rtw_destroy end it too.
+ *   Independence: the session owns its state. Between two adds rtw_render, rtw_render_device, rtw_render_guides, rtw_render_adaptive
+ *     and rtw_denoise* on the same context work as before and do not change it. */
+enum { RTW_ACCUM_ERROR = 1 };
+typedef struct rtw_accum_info {
+    int32_t active;       /* 1: a session exists                                                    */
+    int32_t done;         /* samples per pixel it holds                                             */
+    int32_t cap;          /* params.spp of begin                                                    */
+    uint32_t flags;
+    uint64_t state_bytes; /* what rtw_accum_save writes                                             */
+    uint64_t samples, segments, shadow_rays; /* summed over the adds (restored sessions: and over those before the save) */
+    rtw_params params;    /* as given to begin                                                      */
+} rtw_accum_info;      /* 96 B */
+
+int rtw_accum_begin(rtw_ctx* ctx, const rtw_params* params, uint32_t flags);
+int rtw_accum_add(rtw_ctx* ctx, int32_t spp, rtw_stats* stats);
+int rtw_accum_read(rtw_ctx* ctx, float* rgba_out, float* error_out);
+int rtw_accum_read_device(rtw_ctx* ctx, void* d_rgba, void* hip_stream);
+int rtw_accum_status(rtw_ctx* ctx, rtw_accum_info* out);
+int rtw_accum_save(rtw_ctx* ctx, void* blob, size_t bytes);
+int rtw_accum_restore(rtw_ctx* ctx, const void* blob, size_t bytes);
+int rtw_accum_end(rtw_ctx* ctx);
 
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.

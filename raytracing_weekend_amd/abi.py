@@ -14,7 +14,7 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 HOST_LIB = os.path.join(PKG_DIR, "host", "librtw_host.so")
 HIP_LIB = os.environ.get("RTW_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "librtw_hip.so")
 
-RTW_ABI_VERSION = 4
+RTW_ABI_VERSION = 5
 RTW_SCENE_VERSION = 1
 RTW_SCENE_MAGIC = 0x57545221
 RTW_RNG_PHILOX = 0
@@ -104,9 +104,17 @@ class Adaptive(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("step_spp", C.c_int32), ("threshold", C.c_float), ("dilate", C.c_int32)]
 
 
+class AccumInfo(C.Structure):
+    """rtw_accum_info (include/rtw.h): what rtw_accum_status reports."""
+    _fields_ = [("active", C.c_int32), ("done", C.c_int32), ("cap", C.c_int32), ("flags", C.c_uint32), ("state_bytes", C.c_uint64),
+                ("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64), ("params", Params)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
-               "rtw_render_adaptive", "rtw_debug_math"]
+               "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
+               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end"]
+RTW_ACCUM_ERROR = 1  # rtw_accum_begin's flag: keep the moments, so that accum_read can return the error map
 MATH_OPS = {"rcp": 0, "sqrt": 1, "rcp_sqrt": 2, "rcp_one_step": 3, "rcp_two_steps": 4, "sqrt_residual_only": 5, "sqrt_coupled": 6}  # rtw_debug_math's op
 GUIDES = ("albedo", "normal", "depth", "prim")
 # Default edge-stopping sigmas of Renderer.denoise_guided (see there)
@@ -164,6 +172,22 @@ def load_hip():
         lib.rtw_debug_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.rtw_debug_math.restype = C.c_int
         lib.rtw_debug_math.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        lib.rtw_accum_begin.restype = C.c_int
+        lib.rtw_accum_begin.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32]
+        lib.rtw_accum_add.restype = C.c_int
+        lib.rtw_accum_add.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Stats)]
+        lib.rtw_accum_read.restype = C.c_int
+        lib.rtw_accum_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rtw_accum_read_device.restype = C.c_int
+        lib.rtw_accum_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rtw_accum_status.restype = C.c_int
+        lib.rtw_accum_status.argtypes = [C.c_void_p, C.POINTER(AccumInfo)]
+        lib.rtw_accum_save.restype = C.c_int
+        lib.rtw_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.rtw_accum_restore.restype = C.c_int
+        lib.rtw_accum_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.rtw_accum_end.restype = C.c_int
+        lib.rtw_accum_end.argtypes = [C.c_void_p]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -342,6 +366,49 @@ class Renderer:
         self._check(self.lib.rtw_render_adaptive(self.ctx, C.byref(params), C.byref(ad), img.ctypes.data, spp.ctypes.data,
                                                  err.ctypes.data, C.byref(st)), "rtw_render_adaptive")
         return img, spp, err, st
+
+    # ---- accumulation sessions (include/rtw.h rtw_accum_*): begin, add samples as often as you like, read whenever you like
+    def accum_begin(self, params, error=False):
+        """Start the context's session: params as for render, params.spp = the cap (a multiple of 16). error=True keeps the
+        moments, so that accum_read(error=True) works."""
+        self._check(self.lib.rtw_accum_begin(self.ctx, C.byref(params), RTW_ACCUM_ERROR if error else 0), "rtw_accum_begin")
+
+    def accum_add(self, spp):
+        """Render the next spp samples (a multiple of 16) of every pixel into the session; the Stats of this add alone."""
+        st = Stats()
+        self._check(self.lib.rtw_accum_add(self.ctx, spp, C.byref(st)), "rtw_accum_add")
+        return st
+
+    def accum_read(self, error=False):
+        """The frame of the samples added so far: bit for bit render(spp = done). error=True: (img, err), err the (rows, w)
+        float32 error map of render_adaptive(spp = min_spp = done)."""
+        info = self.accum_status()
+        rows, w = local_rows(info.params), info.params.width
+        img = np.empty((rows, w, 4), dtype=np.float32)
+        err = np.empty((rows, w), dtype=np.float32) if error else None
+        self._check(self.lib.rtw_accum_read(self.ctx, img.ctypes.data, err.ctypes.data if error else None), "rtw_accum_read")
+        return (img, err) if error else img
+
+    def accum_read_device(self, device_ptr, stream_ptr=0):
+        self._check(self.lib.rtw_accum_read_device(self.ctx, C.c_void_p(device_ptr), C.c_void_p(stream_ptr)), "rtw_accum_read_device")
+
+    def accum_status(self):
+        info = AccumInfo()
+        self._check(self.lib.rtw_accum_status(self.ctx, C.byref(info)), "rtw_accum_status")
+        return info
+
+    def accum_save(self):
+        """The session as bytes (header + per-pixel state); the session goes on."""
+        buf = C.create_string_buffer(self.accum_status().state_bytes)
+        self._check(self.lib.rtw_accum_save(self.ctx, buf, len(buf)), "rtw_accum_save")
+        return buf.raw
+
+    def accum_restore(self, blob):
+        """Start a session from accum_save's bytes: same scene uploaded, no session active. It continues exactly."""
+        self._check(self.lib.rtw_accum_restore(self.ctx, bytes(blob), len(blob)), "rtw_accum_restore")
+
+    def accum_end(self):
+        self._check(self.lib.rtw_accum_end(self.ctx), "rtw_accum_end")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

@@ -20,6 +20,9 @@
 //   k_finish (once)               mean radiance -> float4 framebuffer tile
 //   n_devices > 1: one host thread + context per device, interleaved row shards, peer-copy gather, k_interleave
 //
+//   accumulation sessions (rtw_accum_*): the same launches over a range of samples, resolved into a state the session owns
+//     (rtw_accum.h) that keeps the summation unit open between adds; splitting and the saved form: rtw_accum_state.h
+//
 // render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
 // (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU).
 // rtw_upload_scene prepares the blob once on the host (rtw_scene.h prepare_scene: validation, hit records, candidate lists, tree, one
@@ -48,9 +51,11 @@
 #include "rtw_scene.h"
 #include "rtw_device.h"
 #include "rtw_plan.h"
+#include "rtw_accum_state.h"
 #include "rtw_kernels.h"
 #include "rtw_guides.h"
 #include "rtw_adaptive.h"
+#include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
 #endif
@@ -138,6 +143,22 @@ struct rtw_ctx {
     // two active lists (a length word, then the pixels) and the compaction's masks and offsets (one per 64 pixels)
     void* adapt = nullptr;
     size_t adapt_pix = 0;
+    // the accumulation session (rtw.h rtw_accum_*; a group's lives in kids[0]). It owns its per-pixel state, one allocation: accum,
+    // upart, part (rtw_accum.h), with RTW_ACCUM_ERROR mom and the error map a read computes. An add borrows the context's scratch
+    // (blocksum, job order, queue, lanes, stats rows: all dead again when the add returns), never its accum / upart / part / adapt.
+    struct Accum {
+        bool active = false;
+        rtw_params P{};
+        uint32_t flags = 0;
+        int32_t done = 0;
+        uint64_t samples = 0, segments = 0, shadow_rays = 0;
+        size_t npix = 0;
+        void* slab = nullptr;
+        float4 *accum = nullptr, *upart = nullptr, *part = nullptr;
+        double2* mom = nullptr;
+        float* err = nullptr;
+    } acc;
+    uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
 
 // One persistent host thread per kid context of a group (n_devices > 1). The caller's thread hands it one shard per render
@@ -361,6 +382,7 @@ int guarded(rtw_ctx* c, F&& f) noexcept {
 }
 
 int impl_destroy(rtw_ctx* c);
+void accum_free(rtw_ctx* c);
 int impl_render_device(rtw_ctx* c, const rtw_params* P, void* d_rgba, void* hip_stream, rtw_stats* stats);
 void worker_main(rtw_ctx* kc);
 
@@ -433,6 +455,7 @@ int impl_destroy(rtw_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    accum_free(c);
     free_pool(c);
     for (auto& L : c->lane) {
         if (L.ev_done) (void)hipEventDestroy(L.ev_done);
@@ -464,6 +487,7 @@ int upload_prepared(rtw_ctx* c, const PreparedScene& ps) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_scene) { (void)hipFree(c->d_scene); c->d_scene = nullptr; }
     c->has_scene = false;
+    accum_free(c);  // a session belongs to the scene it was begun with
     HIP_TRY(c, hipMalloc(&c->d_scene, ps.image.size()));
     HIP_TRY(c, hipMemcpy(c->d_scene, ps.image.data(), ps.image.size(), hipMemcpyHostToDevice));
     const char* d = (const char*)c->d_scene;
@@ -507,6 +531,7 @@ int impl_upload_scene(rtw_ctx* c, const void* blob, size_t bytes) {
     std::string err;
     const int prc = prepare_scene(blob, bytes, read_tuning(), ps, err);
     if (prc) return fail(c, prc, err);
+    c->scene_fp = accum_fingerprint(blob, bytes);
     if (c->kids.empty()) return upload_prepared(c, ps);
     for (rtw_ctx* k : c->kids) {
         const int rc = upload_prepared(k, ps);
@@ -1333,6 +1358,400 @@ int impl_render_adaptive(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* AD
     return rc;
 }
 
+// ---- accumulation sessions (rtw.h rtw_accum_*): the uniform launches of render_path / render_wavefront over samples [done, done + spp),
+// resolved into the session's own state by the kernels of rtw_accum.h, which keep the summation unit open from add to add
+void accum_free(rtw_ctx* c) {
+    if (c->acc.slab) {
+        (void)hipSetDevice(c->device);
+        (void)hipFree(c->acc.slab);
+    }
+    c->acc = rtw_ctx::Accum{};
+}
+
+// the session's allocation for npix pixels: accum, upart, part, with RTW_ACCUM_ERROR mom and err
+int accum_alloc(rtw_ctx* c, size_t npix, uint32_t flags) {
+    rtw_ctx::Accum& A = c->acc;
+    const bool em = (flags & RTW_ACCUM_ERROR) != 0;
+    const size_t sz[5] = {npix * 16, npix * 16, npix * 16, em ? npix * 16 : 0, em ? npix * 4 : 0};
+    size_t off[6] = {0};
+    for (int k = 0; k < 5; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMalloc(&A.slab, off[5]));
+    char* b = (char*)A.slab;
+    A.accum = (float4*)(b + off[0]); A.upart = (float4*)(b + off[1]); A.part = (float4*)(b + off[2]);
+    A.mom = em ? (double2*)(b + off[3]) : nullptr;
+    A.err = em ? (float*)(b + off[4]) : nullptr;
+    A.npix = npix;
+    A.flags = flags;
+    const hipError_t e = hipMemsetAsync(A.slab, 0, off[5], c->stream);
+    if (e != hipSuccess) { accum_free(c); return fail(c, RTW_ERR_DEVICE, std::string("rtw_accum: ") + hipGetErrorString(e)); }
+    return RTW_OK;
+}
+
+// k_path over samples [n_from, n_to) of every pixel (both multiples of kSumBlock, counted from sample_offset): render_path's launches -
+// k_classify's job order, the cull, the bulk launch and the end-game launch beside it, unit sums where plan_path picks 8-block units -
+// split where a unit-sum launch would not start on a unit boundary (rtw_accum_state.h accum_split)
+int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_from, int n_to, hipStream_t s, CallLog& log) {
+    const rtw_ctx::Accum& A = c->acc;
+    const rtw_params* P = &A.P;
+    const size_t npix = base_in.npix;
+    int rc = ensure_pool(c, 0, 0, npix, 0);
+    if (rc) return rc;
+    KArgs base = base_in;
+    size_t live_groups = ~(size_t)0, culled_pixels = 0;
+    if (tune.cull && c->info.cull_ok) {
+        const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->info.cull_bmin, c->info.cull_bmax, P->width, P->height);
+        base.cull_x0 = r.x0; base.cull_x1 = r.x1; base.cull_y0 = r.y0; base.cull_y1 = r.y1;
+        live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &culled_pixels);
+    }
+    log.culled_segments = (uint64_t)culled_pixels * (uint64_t)(n_to - n_from);
+    const ResolveCull rcull{base.cull_x0, base.cull_x1, base.cull_y0, base.cull_y1, base.width, base.row0, base.row_stride, base.divw_m, base.divw_s1, base.divw_s2};
+    int wg_per_cu = tune.path_grid_mult;
+    if (wg_per_cu <= 0) {
+        int nb = 0;
+        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), kBlock, 0);
+        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+    }
+    const size_t n_groups = (npix + 63) / 64;
+    if (n_groups > c->order_groups) {
+        if (c->d_order) (void)hipFree(c->d_order);
+        c->d_order = nullptr; c->order_groups = 0;
+        HIP_TRY(c, hipMalloc(&c->d_order, 3 * n_groups * sizeof(uint32_t)));
+        c->order_groups = n_groups;
+    }
+    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    if (live_groups == 0) return RTW_OK;  // the frame looks past everything: the state stays black
+    {   // job order: longest units first (k_classify), once per add
+        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
+        const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
+        if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
+        else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
+    }
+    const unsigned pix_grid = pixel_grid(c, npix);
+    // one plan per run (rtw_accum_state.h accum_runs: the head on its own, the whole units and the open tail behind them together),
+    // all planned before the first launch so that the sums' buffer is sized once, as render_path sizes it
+    const AccumRuns runs = accum_runs(accum_split(n_from, n_to, A.mom != nullptr), A.mom != nullptr);
+    PathPlan plans[2];
+    size_t need_slots = 0;
+    for (int k = 0; k < runs.n; k++) {
+        Tuning t = tune;  // every block's sum must reach memory (adaptive_path_pass): no lane unit may be a whole summation unit
+        if (!runs.run[k].units_ok && t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
+        plans[k] = plan_path(t, npix, runs.run[k].n_to - runs.run[k].n_from, c->n_cu, wg_per_cu, live_groups);
+        if (plans[k].too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
+        if (plans[k].unit_sums && !runs.run[k].units_ok) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_accum_add: unit sums off a unit boundary");
+        need_slots = std::max(need_slots, plans[k].need_slots);
+    }
+    if (need_slots * npix > c->blocksum_elems) {
+        if (c->blocksum) (void)hipFree(c->blocksum);
+        c->blocksum = nullptr; c->blocksum_elems = 0;
+        HIP_TRY(c, hipMalloc(&c->blocksum, need_slots * npix * sizeof(float4)));
+        c->blocksum_elems = need_slots * npix;
+    }
+    for (int k = 0; k < runs.n; k++) {
+        const int r_from = runs.run[k].n_from, r_to = runs.run[k].n_to;
+        const PathPlan& plan = plans[k];
+        const uint32_t blk0 = (uint32_t)r_from / kSumBlock;
+        for (const PathPass& ps : plan.passes) {
+            HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
+            HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
+            hipEvent_t ev_a = nullptr, ev_b = nullptr;
+            HIP_TRY(c, log.event(ev_a));
+            HIP_TRY(c, log.event(ev_b));
+            HIP_TRY(c, hipEventRecord(ev_a, s));
+            CallLog::Timed tp;
+            HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
+            for (int part = 0; part < 2; part++) {  // as in render_path: the bulk launch and the end-game launch beside it
+                const PathLaunch& l = ps.part[part];
+                if (l.count == 0) continue;
+                KArgs a = base;
+                a.stats = c->d_stats;
+                a.sample0 = (uint32_t)P->sample_offset;
+                a.spp = (uint32_t)r_to;
+                a.queue = c->d_queue + (part == 0 ? 0 : 4);
+                a.order = c->d_order;
+                a.order_counts = c->d_queue + 1;
+                a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * npix;
+                a.unit_sums = (part == 0 && plan.unit_sums) ? 1u : 0u;
+                a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
+                a.block0 = blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
+                hipStream_t ls = part == 0 ? s : c->stream2;
+                if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
+                launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls);
+                log.launches++;
+                if (part == 1) {
+                    HIP_TRY(c, hipEventRecord(ev_b, ls));
+                    HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
+                }
+            }
+            HIP_TRY(c, log.close(tp, s));
+            // coarse region: whole unit sums (unit_sums) or block sums from block b0 of the run on; fine region: block sums
+            const uint32_t n_unit = plan.unit_sums ? (uint32_t)ps.slots_coarse : 0u;
+            const uint32_t n_blk = plan.unit_sums ? (uint32_t)(ps.nb - ps.nb_coarse) : (uint32_t)ps.nb;
+            const uint32_t first = blk0 + (uint32_t)(plan.unit_sums ? ps.b0 + ps.nb_coarse : ps.b0);
+            hipLaunchKernelGGL(k_accum_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, (uint32_t)npix, n_unit, n_blk, first,
+                               A.accum, A.upart, A.mom, rcull);
+        }
+    }
+    return RTW_OK;
+}
+
+// the wavefront pipeline over samples [n_from, n_to) of every pixel: render_wavefront's batches, resolved into the session's state
+int accum_add_wavefront(rtw_ctx* c, const Tuning& tune, const KArgs& base, int n_from, int n_to, hipStream_t s, CallLog& log) {
+    const rtw_ctx::Accum& A = c->acc;
+    const rtw_params* P = &A.P;
+    const size_t npix = base.npix;
+    const size_t step = (size_t)(n_to - n_from);
+    const SceneFacts& sf = c->info.facts;
+    WavefrontPlan w;
+    for (;;) {
+        w = plan_wavefront(tune, npix, (int)step, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, sf);
+        if (w.trace_lds > 48 * 1024) {
+            DScene ts = c->sc;
+            ts.n_lds_nodes = w.trace_nodes;
+            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
+            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
+        }
+        const int rc = ensure_pool(c, w.n_lanes, (size_t)w.regions_max * w.region_cap_max, npix, w.cnt_words, c->sc.n_lights > 0);
+        if (rc == RTW_OK) break;
+        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || w.S <= 1) return rc;
+        free_pool(c);  // as in render_wavefront: half as many paths in flight, the same image
+        (void)hipGetLastError();
+        c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * w.S * (size_t)tune.lanes / 2);
+    }
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    const unsigned pix_grid = pixel_grid(c, npix);
+    hipEvent_t ev_ready = nullptr;
+    if (P->max_depth > 0) {
+        HIP_TRY(c, log.event(ev_ready));
+        HIP_TRY(c, hipEventRecord(ev_ready, s));
+    }
+    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < step; b++) {
+        const size_t Sb = w.batch_size(b, s0);
+        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
+        KArgs a = base;
+        a.sample0 = (uint32_t)(P->sample_offset + n_from + (int)s0);
+        const int rc = issue_batch(c, w, tune, a, L, npix * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, false);
+        if (rc) return rc;
+        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
+        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+        hipLaunchKernelGGL(k_accum_resolve_samples, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, (uint32_t)npix, (uint32_t)Sb,
+                           (uint32_t)(n_from + (int)s0), A.accum, A.upart, A.part, A.mom);
+        HIP_TRY(c, hipEventRecord(L.ev_free, s));
+        s0 += Sb;
+    }
+    return RTW_OK;
+}
+
+// one device (a group's first): one add, its counts and times
+int accum_add_single(rtw_ctx* c, int32_t spp, rtw_stats* stats) {
+    rtw_ctx::Accum& A = c->acc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t npix = A.npix;
+    const Tuning tune = read_tuning();
+    CallLog log{c, A.P.rng_kind, stats != nullptr && tune.kernel_timing};
+    HIP_TRY(c, log.event(log.begin));
+    HIP_TRY(c, log.event(log.end));
+    const KArgs base = render_args(c, &A.P, npix);
+    const bool use_path = path_pipeline(c, &A.P, tune);
+    const int n_from = A.done, n_to = A.done + spp;
+    int rc = use_path ? accum_add_path(c, tune, base, n_from, n_to, s, log) : accum_add_wavefront(c, tune, base, n_from, n_to, s, log);
+    if (rc) return rc;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(log.end, s));
+    HIP_TRY(c, hipEventSynchronize(log.end));
+    unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    {
+        unsigned long long rows_[kStatRows * 8];
+        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < kStatRows; r++)
+            for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
+    }
+    const uint64_t samples = (uint64_t)npix * (uint64_t)spp, segments = hs[0] + log.culled_segments;
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
+        stats->seconds = (double)ms * 1e-3;
+        stats->bounce_seconds = stats->seconds;
+        for (const CallLog::Timed& t : log.timed) {
+            float m = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
+            stats->kernel_seconds[t.kind] += (double)m * 1e-3;
+            stats->kernel_launches[t.kind]++;
+        }
+        for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];
+        stats->bounce_launches = log.launches;
+        stats->samples = samples;
+        stats->segments = segments;
+        stats->shadow_rays = hs[1];
+        stats->algorithmic_bytes = 128ull * segments + 32ull * samples;
+    }
+    A.done = n_to;
+    A.samples += samples; A.segments += segments; A.shadow_rays += hs[1];
+    return RTW_OK;
+}
+
+// the context that holds the session: a group's first kid
+rtw_ctx* accum_ctx(rtw_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
+// an error of the session's context, reported on the caller's
+int accum_up(rtw_ctx* c, rtw_ctx* d, int rc) { return rc && d != c ? fail(c, rc, d->err) : rc; }
+
+int impl_accum_begin(rtw_ctx* c, const rtw_params* P, uint32_t flags) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, "rtw_accum_begin before rtw_upload_scene");
+    if (!P) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_begin: null params");
+    if (const char* why = accum_check_params(*P, flags)) return fail(c, RTW_ERR_INVALID_ARG, std::string("rtw_accum_begin: ") + why);
+    rtw_ctx* d = accum_ctx(c);
+    if (d->acc.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_begin: a session is active (rtw_accum_end it first)");
+    const size_t npix = shard_rows(P) * (size_t)P->width;
+    if (npix == 0) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_begin: the shard has no rows");
+    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_accum_begin: tile too large");
+    int rc = accum_alloc(d, npix, flags);
+    if (rc == RTW_OK && hipStreamSynchronize(d->stream) != hipSuccess) rc = fail(d, RTW_ERR_DEVICE, "rtw_accum_begin: clearing the state failed");
+    if (rc) { accum_free(d); return accum_up(c, d, rc); }
+    d->acc.P = *P;
+    d->acc.active = true;
+    return RTW_OK;
+}
+
+int impl_accum_add(rtw_ctx* c, int32_t spp, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, "rtw_accum_add before rtw_upload_scene");
+    rtw_ctx* d = accum_ctx(c);
+    if (!d->acc.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_add: no active session");
+    if (spp <= 0 || spp % (int)kSumBlock != 0) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_add: spp must be a positive multiple of RTW_SUM_BLOCK");
+    if ((int64_t)d->acc.done + spp > (int64_t)d->acc.P.spp) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_add: more samples than the session's cap");
+    const int rc = accum_add_single(d, spp, stats);
+    if (rc) {  // some of the add may have reached the state: the session is not to be continued
+        (void)hipStreamSynchronize(d->stream);
+        (void)hipGetLastError();
+        accum_free(d);
+    }
+    return accum_up(c, d, rc);
+}
+
+// the frame of the done samples into d_rgba on stream s (and the error map into the session's err); returns when it is written
+int accum_read_single(rtw_ctx* c, float4* d_rgba, bool want_err, hipStream_t s) {
+    const rtw_ctx::Accum& A = c->acc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!s) s = c->stream;
+    const unsigned pix_grid = pixel_grid(c, A.npix);
+    hipLaunchKernelGGL(k_accum_read, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)A.accum, (const float4*)A.upart, d_rgba, (uint32_t)A.npix, (float)A.done);
+    if (want_err) hipLaunchKernelGGL(k_accum_error, dim3(pix_grid), dim3(kBlock), 0, s, (const double2*)A.mom, A.err, (uint32_t)A.npix, (uint32_t)A.done / kSumBlock);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RTW_OK;
+}
+
+int accum_read_check(rtw_ctx* c, rtw_ctx* d, const void* frame, bool want_err) {
+    if (!d->acc.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_read: no active session");
+    if (!frame) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_read: null output");
+    if (d->acc.done <= 0) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_read: the session holds no samples yet");
+    if (want_err && !d->acc.mom) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_read: the session was begun without RTW_ACCUM_ERROR");
+    if (want_err && d->acc.done < 2 * (int)kSumBlock) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_read: the error map needs 2 * RTW_SUM_BLOCK samples");
+    return RTW_OK;
+}
+
+int impl_accum_read_device(rtw_ctx* c, void* d_rgba, void* hip_stream) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_ctx* d = accum_ctx(c);
+    int rc = accum_read_check(c, d, d_rgba, false);
+    if (rc) return rc;
+    return accum_up(c, d, accum_read_single(d, (float4*)d_rgba, false, (hipStream_t)hip_stream));
+}
+
+int impl_accum_read(rtw_ctx* c, float* rgba_out, float* error_out) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_ctx* d = accum_ctx(c);
+    int rc = accum_read_check(c, d, rgba_out, error_out != nullptr);
+    if (rc) return rc;
+    const size_t npix = d->acc.npix;
+    HIP_TRY(c, hipSetDevice(d->device));
+    if (npix > d->out_pix) {
+        if (d->d_out) (void)hipFree(d->d_out);
+        d->d_out = nullptr; d->out_pix = 0;
+        HIP_TRY(c, hipMalloc(&d->d_out, npix * sizeof(float4)));
+        d->out_pix = npix;
+    }
+    rc = accum_read_single(d, d->d_out, error_out != nullptr, nullptr);
+    if (rc) return accum_up(c, d, rc);
+    HIP_TRY(c, hipMemcpy(rgba_out, d->d_out, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (error_out) HIP_TRY(c, hipMemcpy(error_out, d->acc.err, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+int impl_accum_status(rtw_ctx* c, rtw_accum_info* out) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (!out) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_status: null output");
+    memset(out, 0, sizeof *out);
+    const rtw_ctx::Accum& A = accum_ctx(c)->acc;
+    if (!A.active) return RTW_OK;
+    out->active = 1; out->done = A.done; out->cap = A.P.spp; out->flags = A.flags;
+    out->state_bytes = (uint64_t)accum_state_bytes(A.npix, A.flags);
+    out->samples = A.samples; out->segments = A.segments; out->shadow_rays = A.shadow_rays;
+    out->params = A.P;
+    return RTW_OK;
+}
+
+int impl_accum_save(rtw_ctx* c, void* blob, size_t bytes) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_ctx* d = accum_ctx(c);
+    const rtw_ctx::Accum& A = d->acc;
+    if (!A.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_save: no active session");
+    if (!blob || bytes != accum_state_bytes(A.npix, A.flags)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_save: the blob must be state_bytes long");
+    const AccumHeader h = accum_pack(A.P, A.flags, A.done, A.samples, A.segments, A.shadow_rays, c->scene_fp);
+    memcpy(blob, &h, sizeof h);
+    char* at = (char*)blob + sizeof h;
+    const size_t arr = A.npix * 16;
+    HIP_TRY(c, hipSetDevice(d->device));
+    HIP_TRY(c, hipMemcpy(at, A.accum, arr, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(at + arr, A.upart, arr, hipMemcpyDeviceToHost));
+    if (A.mom) HIP_TRY(c, hipMemcpy(at + 2 * arr, A.mom, arr, hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+int impl_accum_restore(rtw_ctx* c, const void* blob, size_t bytes) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, "rtw_accum_restore before rtw_upload_scene");
+    rtw_ctx* d = accum_ctx(c);
+    if (d->acc.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_restore: a session is active (rtw_accum_end it first)");
+    AccumHeader h;
+    std::string why;
+    if (!accum_validate(blob, bytes, c->scene_fp, h, why)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_restore: " + why);
+    const size_t npix = (size_t)h.npix;
+    if (npix == 0) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_restore: the shard has no rows");
+    if (npix > 0xffffffffull / 2) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_accum_restore: tile too large");
+    int rc = accum_alloc(d, npix, h.flags);
+    if (rc) { accum_free(d); return accum_up(c, d, rc); }
+    rtw_ctx::Accum& A = d->acc;
+    const char* at = (const char*)blob + sizeof h;
+    const size_t arr = npix * 16;
+    hipError_t e = hipStreamSynchronize(d->stream);  // (the allocation's clear)
+    if (e == hipSuccess) e = hipMemcpy(A.accum, at, arr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(A.upart, at + arr, arr, hipMemcpyHostToDevice);
+    if (e == hipSuccess && A.mom) e = hipMemcpy(A.mom, at + 2 * arr, arr, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        accum_free(d);
+        return fail(c, RTW_ERR_DEVICE, std::string("rtw_accum_restore: ") + hipGetErrorString(e));
+    }
+    A.P = h.params; A.done = h.done;
+    A.samples = h.samples; A.segments = h.segments; A.shadow_rays = h.shadow_rays;
+    A.active = true;
+    return RTW_OK;
+}
+
+int impl_accum_end(rtw_ctx* c) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_ctx* d = accum_ctx(c);
+    if (!d->acc.active) return fail(c, RTW_ERR_INVALID_ARG, "rtw_accum_end: no active session");
+    accum_free(d);
+    return RTW_OK;
+}
+
 // rtw_denoise and rtw_denoise_guided on the context's device: the colour image (and the guides) in, `iterations` a-trous passes
 // that ping-pong between two buffers, the result out. pass(grid, in, out, albedo, normal, step, inv_sigma2) issues one pass.
 template <class Pass>
@@ -1540,5 +1959,13 @@ int rtw_denoise_guided(rtw_ctx* c, const float* rgba_in, const float* albedo, co
                        int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
     return guarded(c, [&] { return impl_denoise_guided(c, rgba_in, albedo, normal, rgba_out, width, height, iterations, sigma, sigma_albedo, sigma_normal); });
 }
+int rtw_accum_begin(rtw_ctx* c, const rtw_params* P, uint32_t flags) { return guarded(c, [&] { return impl_accum_begin(c, P, flags); }); }
+int rtw_accum_add(rtw_ctx* c, int32_t spp, rtw_stats* stats) { return guarded(c, [&] { return impl_accum_add(c, spp, stats); }); }
+int rtw_accum_read(rtw_ctx* c, float* rgba_out, float* error_out) { return guarded(c, [&] { return impl_accum_read(c, rgba_out, error_out); }); }
+int rtw_accum_read_device(rtw_ctx* c, void* d_rgba, void* hip_stream) { return guarded(c, [&] { return impl_accum_read_device(c, d_rgba, hip_stream); }); }
+int rtw_accum_status(rtw_ctx* c, rtw_accum_info* out) { return guarded(c, [&] { return impl_accum_status(c, out); }); }
+int rtw_accum_save(rtw_ctx* c, void* blob, size_t bytes) { return guarded(c, [&] { return impl_accum_save(c, blob, bytes); }); }
+int rtw_accum_restore(rtw_ctx* c, const void* blob, size_t bytes) { return guarded(c, [&] { return impl_accum_restore(c, blob, bytes); }); }
+int rtw_accum_end(rtw_ctx* c) { return guarded(c, [&] { return impl_accum_end(c); }); }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Director.cpp — see Director.h. Reference call sites replaced:
 //   Director::init          Director.cpp:33-64    -> rtw_create
 //   Director::createScene   Director.cpp:951-969  -> ioScene::init + marshalScene + rtw_upload_scene
-//   Director::renderFrame   Director.cpp:971-1008 -> rtw_render (optixLaunch + D2H copy; no AI denoiser)
+//   Director::renderFrame   Director.cpp:971-1008 -> rtw_render (optixLaunch + D2H copy; no AI denoiser), or an accumulation
+//                                                    session (rtw_accum_*: what the accum_buffer left commented out at :485-488 was for)
 //   Director::printPPM      Director.cpp:1010-1031
 //   Director::destroy       Director.cpp:66-104   -> rtw_destroy
 #include "Director.h"
@@ -11,7 +12,10 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <iterator>
+#include <string>
 
+#include "../csrc/rtw_accum_state.h"  // kAccumCapMax (host-only, no HIP)
 #include "../csrc/rtw_plan.h"  // adaptive_checkpoints (host-only planning, no HIP)
 #include "PfmWriter.h"
 #include "SceneMarshal.h"
@@ -66,7 +70,13 @@ void Director::renderFrame() {
     p.rng_kind = m_rngKind;
     p.estimator = m_estimator;
     int rc = RTW_OK;
-    if (m_adaptive) {
+    if (m_session) {
+        if (m_adaptive) {
+            std::cerr << "ERROR: -progressive / -checkpoint / -resume do not combine with -adaptive" << std::endl;
+            std::exit(EXIT_FAILURE);
+        }
+        renderSession(p);
+    } else if (m_adaptive) {
         const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
         std::vector<int32_t> spp(npix);
         m_errMap.assign(npix, 0.f);
@@ -130,6 +140,88 @@ void Director::renderFrame() {
                   << " shadow rays in " << m_stats.seconds << " s on the GPU = " << m_stats.samples / s / 1e6 << " Msamples/s, "
                   << m_stats.algorithmic_bytes / s / 1e9 << " GB/s algorithmic" << std::endl;
     }
+}
+
+// The frame through an accumulation session (rtw.h rtw_accum_*): adds of m_progStep samples (or one add), the frame read back after
+// each, the state loaded from / written to a file. The session's cap is the largest there is (it costs nothing), so that a
+// checkpoint can be resumed to any total.
+void Director::renderSession(const rtw_params& frame) {
+    auto bad = [](const std::string& what) {
+        std::cerr << "ERROR: " << what << std::endl;
+        std::exit(EXIT_FAILURE);
+    };
+    if (m_Ns % RTW_SUM_BLOCK != 0 || m_progStep < 0 || m_progStep % RTW_SUM_BLOCK != 0)
+        bad("-progressive / -checkpoint / -resume need -ns (and the -progressive step) to be multiples of " + std::to_string(RTW_SUM_BLOCK));
+    if (m_devices.size() > 1)
+        std::cerr << "WARNING: -progressive / -checkpoint / -resume render on the first of the " << m_devices.size()
+                  << " devices alone (a session is not sharded across devices)" << std::endl;
+    rtw_params p = frame;
+    p.spp = rtwk::kAccumCapMax;
+    rtw_accum_info info{};
+    int rc = RTW_OK;
+    if (!m_resume.empty()) {
+        std::ifstream f(m_resume, std::ios::binary);
+        std::vector<char> blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        if (!f || blob.empty()) bad("cannot read the checkpoint " + m_resume);
+        rc = rtw_accum_restore(m_ctx, blob.data(), blob.size());
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_restore", rc);
+        rc = rtw_accum_status(m_ctx, &info);
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_status", rc);
+        const rtw_params& q = info.params;
+        if (q.width != p.width || q.height != p.height || q.max_depth != p.max_depth || q.seed != p.seed || q.row0 != p.row0 || q.row1 != p.row1 ||
+            q.rng_kind != p.rng_kind || q.sample_offset != p.sample_offset || q.row_stride != p.row_stride || q.estimator != p.estimator || info.flags != 0)
+            bad("the checkpoint " + m_resume + " was rendered with other parameters (" + std::to_string(q.width) + "x" + std::to_string(q.height) + ", depth " +
+                std::to_string(q.max_depth) + ", seed " + std::to_string(q.seed) + ", rng " + std::to_string(q.rng_kind) + ", estimator " +
+                std::to_string(q.estimator) + ")");
+        if (info.done > m_Ns) bad("the checkpoint " + m_resume + " holds " + std::to_string(info.done) + " samples per pixel, more than -ns " + std::to_string(m_Ns));
+        if (_verbose) std::cerr << "INFO: resumed " << m_resume << " at " << info.done << " spp" << std::endl;
+    } else {
+        rc = rtw_accum_begin(m_ctx, &p, 0);
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_begin", rc);
+    }
+    m_stats = rtw_stats{};
+    int done = info.done;
+    bool fresh = false;  // m_hostBuffer holds the frame of `done` samples
+    while (done < m_Ns) {
+        const int n = m_progStep > 0 ? std::min(m_progStep, m_Ns - done) : m_Ns - done;
+        rtw_stats st{};
+        rc = rtw_accum_add(m_ctx, n, &st);
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_add", rc);
+        done += n;
+        m_stats.samples += st.samples; m_stats.segments += st.segments; m_stats.shadow_rays += st.shadow_rays;
+        m_stats.algorithmic_bytes += st.algorithmic_bytes; m_stats.bounce_launches += st.bounce_launches;
+        m_stats.seconds += st.seconds; m_stats.bounce_seconds += st.bounce_seconds;
+        for (int k = 0; k < RTW_K_COUNT; k++) {
+            m_stats.kernel_seconds[k] += st.kernel_seconds[k]; m_stats.kernel_launches[k] += st.kernel_launches[k];
+            m_stats.kernel_segments[k] += st.kernel_segments[k];
+        }
+        fresh = false;
+        if (m_progStep > 0) {
+            rc = rtw_accum_read(m_ctx, m_hostBuffer.data(), nullptr);
+            if (rc != RTW_OK) die(m_ctx, "rtw_accum_read", rc);
+            fresh = true;
+            if (_verbose) std::cerr << "INFO: progressive: " << done << " of " << m_Ns << " spp" << std::endl;
+            if (m_onFrame) m_onFrame(done);
+        }
+    }
+    if (!fresh) {
+        if (done <= 0) bad("nothing to render");
+        rc = rtw_accum_read(m_ctx, m_hostBuffer.data(), nullptr);
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_read", rc);
+    }
+    if (!m_checkpoint.empty()) {
+        rc = rtw_accum_status(m_ctx, &info);
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_status", rc);
+        std::vector<char> blob(static_cast<size_t>(info.state_bytes));
+        rc = rtw_accum_save(m_ctx, blob.data(), blob.size());
+        if (rc != RTW_OK) die(m_ctx, "rtw_accum_save", rc);
+        std::ofstream f(m_checkpoint, std::ios::binary);
+        f.write(blob.data(), static_cast<std::streamsize>(blob.size()));
+        if (!f) bad("cannot write the checkpoint " + m_checkpoint);
+        if (_verbose) std::cerr << "INFO: checkpoint " << m_checkpoint << ": " << done << " spp, " << blob.size() << " bytes" << std::endl;
+    }
+    rc = rtw_accum_end(m_ctx);
+    if (rc != RTW_OK) die(m_ctx, "rtw_accum_end", rc);
 }
 
 // P3 ASCII PPM on stdout, rows top to bottom, gamma 2 then int(255.99*clamp) — Director.cpp:1010-1031.

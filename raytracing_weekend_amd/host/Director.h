@@ -4,6 +4,7 @@
 // SBT, launch params, denoiser) is replaced by calls into the C ABI of include/rtw.h.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -49,6 +50,14 @@ public:
     // adaptive sampling (rtw_render_adaptive): renderFrame renders until every pixel's error estimate is below `threshold` or it has
     // the -ns cap; minSpp samples first, then checkpoints `stepSpp` apart (0: half of what a pixel has); dilate 1
     void setAdaptive(float threshold, int minSpp, int stepSpp) { m_adaptive = true; m_adThreshold = threshold; m_adMinSpp = minSpp; m_adStepSpp = stepSpp; }
+    // accumulation session (rtw_accum_*): renderFrame renders in adds of `step` samples (0: one add) and calls onFrame(done) with the
+    // frame of the samples so far in hostBuffer() after every add; the final frame is the one-shot frame, bit for bit. -ns must be
+    // a multiple of 16.
+    void setProgressive(int step, std::function<void(int)> onFrame) { m_session = true; m_progStep = step; m_onFrame = std::move(onFrame); }
+    // the session's state is written to `path` when the render ends / the render starts from the state in `path` (-ns is then the
+    // new total, at least what the state holds; scene, size and parameters must be the checkpoint's)
+    void setCheckpoint(const std::string& path) { m_session = true; m_checkpoint = path; }
+    void setResume(const std::string& path) { m_session = true; m_resume = path; }
     // PREFIX_albedo.pfm, PREFIX_normal.pfm (PF, rgb) and PREFIX_depth.pfm (Pf), rows bottom-up as writePFM; after an adaptive
     // frame also PREFIX_spp.pfm and PREFIX_error.pfm (Pf: each pixel's sample count and error estimate)
     bool writeGuides(const std::string& prefix) const;
@@ -57,6 +66,7 @@ public:
 
 private:
     void marshalAndUpload();  // createSBT + initLaunchParams of the reference
+    void renderSession(const rtw_params& p);  // renderFrame's render through an accumulation session
 
     int m_Nx = 0, m_Ny = 0, m_Ns = 0;
     int m_maxRayDepth = 20;
@@ -75,6 +85,10 @@ private:
     float m_adThreshold = 0.f;
     int m_adMinSpp = 64, m_adStepSpp = 0;
     std::vector<float> m_sppMap, m_errMap;  // the last adaptive frame's sample counts and error estimates
+    bool m_session = false;
+    int m_progStep = 0;
+    std::function<void(int)> m_onFrame;
+    std::string m_checkpoint, m_resume;
     rtw_ctx* m_ctx = nullptr;
     rtwhost::ioScene m_scene;
     std::vector<float> m_hostBuffer;

@@ -2,6 +2,7 @@
 //   -s scene  -ns samples  -dx width  -dy height  -h  -v  -g
 // plus what the benchmark configurations need and the reference hard-wires:
 //   -d depth (reference: 20, Director.cpp:42)   -seed N   -rng philox|lcg   -gpu id   -gpus N   -o file.ppm|file.png|file.pfm
+//   -progressive N   -checkpoint file   -resume file   (accumulation sessions: previews, checkpoints, resumed renders)
 // The reference's resolution / sample clamps (main.cpp:21-27) are widened so that 200x200 and
 // 7680x4320 are reachable, and its scene range bug (only scene 4 selectable, main.cpp:69) is not kept.
 #include <chrono>
@@ -69,6 +70,11 @@ int main(int argc, char* argv[]) {
                    -ns becomes the cap (a multiple of 16). With -aov also PREFIX_spp.pfm and PREFIX_error.pfm (Pf)
     -min_spp N     With -adaptive: samples every pixel gets first (default 64; a multiple of 16, at least 32)
     -step N        With -adaptive: samples added per checkpoint (default: half of what a pixel has, rounded up to 16)
+    -progressive N Render in adds of N samples (a multiple of 16, as -ns must then be) and rewrite the -o file after every add;
+                   the final file is the file of the same command without the flag
+    -checkpoint F  Write the accumulation session's state to F when the render ends (-ns a multiple of 16)
+    -resume F      Start from the state in F instead of from zero: -ns is the new total (at least what F holds); scene, size
+                   and parameters must be those F was rendered with
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -143,6 +149,32 @@ int main(int argc, char* argv[]) {
         director.setAdaptive(thr, minSpp, step);
     }
 
+    const std::string& outPath = cl_input.getCmdOption("-o");
+    auto writeOutput = [&]() {
+        auto ends = [&](const char* ext) { return outPath.size() > 4 && outPath.compare(outPath.size() - 4, 4, ext) == 0; };
+        return ends(".pfm") ? director.writePFM(outPath) : ends(".png") ? director.writePNG(outPath) : director.writeBinaryPPM(outPath);
+    };
+    if (cl_input.cmdOptionExists("-progressive")) {
+        int step = 0;
+        if (!intOption(cl_input, "-progressive", "progressive step (-progressive)", step) || step <= 0) {
+            std::cerr << "ERROR: -progressive needs a sample count (a positive multiple of 16)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        director.setProgressive(step, [&](int) {
+            if (!outPath.empty() && !writeOutput()) std::cerr << "WARNING: cannot write " << outPath << std::endl;
+        });
+    }
+    if (cl_input.cmdOptionExists("-checkpoint")) {
+        const std::string& f = cl_input.getCmdOption("-checkpoint");
+        if (f.empty()) { std::cerr << "ERROR: -checkpoint needs a file name" << std::endl; return EXIT_FAILURE; }
+        director.setCheckpoint(f);
+    }
+    if (cl_input.cmdOptionExists("-resume")) {
+        const std::string& f = cl_input.getCmdOption("-resume");
+        if (f.empty()) { std::cerr << "ERROR: -resume needs a file name" << std::endl; return EXIT_FAILURE; }
+        director.setResume(f);
+    }
+
     auto start = std::chrono::system_clock::now();
     director.init(Nx, Ny, Ns);
     if (Qverbose) {
@@ -155,13 +187,10 @@ int main(int argc, char* argv[]) {
     auto stop = std::chrono::system_clock::now();
     std::cerr << "INFO: Took " << std::chrono::duration<float>(stop - start).count() << " seconds." << std::endl;
 
-    const std::string& outPath = cl_input.getCmdOption("-o");
     if (outPath.empty()) {
         director.printPPM();
     } else {
-        auto ends = [&](const char* ext) { return outPath.size() > 4 && outPath.compare(outPath.size() - 4, 4, ext) == 0; };
-        const bool ok = ends(".pfm") ? director.writePFM(outPath) : ends(".png") ? director.writePNG(outPath) : director.writeBinaryPPM(outPath);
-        if (!ok) {
+        if (!writeOutput()) {
             std::cerr << "ERROR: cannot write " << outPath << std::endl;
             director.destroy();
             return EXIT_FAILURE;

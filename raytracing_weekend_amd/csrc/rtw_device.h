@@ -613,8 +613,12 @@ RTW_DEV uint32_t bvh_pop(const TravMem& tm, int& sp) {
 // entered, the others are pushed. Returns the next reference (inner or leaf), or kBvhDone when nothing is left.
 // The boxes only cull (exact hits are decided by the primitive tests), so everything here may be approximate as long as
 // it errs towards "hit": planes are p + q * step on the node's grid (rounded outwards by the builder, and the primitive
-// bounds under them are padded by 1e-4), plane distances q * (step / d) + (p - o) / d with the reciprocal clamped to
-// +-1e18 (a zero direction component then gives huge finite distances of the right sign instead of inf - inf).
+// bounds under them are padded by 1e-4), plane distances q * (step / d) + (p - o) / d with an INFINITE reciprocal replaced by
+// +-1e18 (a zero direction component then gives huge finite distances of the right sign instead of inf - inf). A finite
+// reciprocal stays as it is, however large: clamping it as well (as this did until the edge-ray tests) scales one axis' distances
+// and not the others', so that rays whose direction components are below 1e-18 lost hits that lie beyond t = 1e18. Where a
+// product overflows instead, inf keeps its sign and inf - inf is a NaN that fminf / fmaxf drop: the axis stops culling.
+RTW_DEV float slab_inv(float r) { return __builtin_isinf(r) ? __builtin_copysignf(1.0e18f, r) : r; }
 RTW_DEV uint32_t bvh_inner_step(const DScene& sc, const TravMem& tm, const v3 o, const v3 inv, float tmin, float best_t, uint32_t cur, int& sp) {
     const uint32_t i = cur >> 2;
     u32x4 q0, q1, q2, q3;
@@ -625,8 +629,7 @@ RTW_DEV uint32_t bvh_inner_step(const DScene& sc, const TravMem& tm, const v3 o,
         q0 = q[0]; q1 = q[1]; q2 = q[2]; q3 = q[3];
     }
     // q0 = p.x p.y p.z step.x, q1 = lo.x lo.y lo.z hi.x, q2 = hi.y hi.z step.y step.z, q3 = the references
-    const float ix = __builtin_amdgcn_fmed3f(inv.x, -1.0e18f, 1.0e18f), iy = __builtin_amdgcn_fmed3f(inv.y, -1.0e18f, 1.0e18f),
-                iz = __builtin_amdgcn_fmed3f(inv.z, -1.0e18f, 1.0e18f);
+    const float ix = slab_inv(inv.x), iy = slab_inv(inv.y), iz = slab_inv(inv.z);
     const float ax = (__uint_as_float(q0.x) - o.x) * ix, ay = (__uint_as_float(q0.y) - o.y) * iy, az = (__uint_as_float(q0.z) - o.z) * iz;
     const float bx = __uint_as_float(q0.w) * ix, by = __uint_as_float(q2.z) * iy, bz = __uint_as_float(q2.w) * iz;
     // the plane a ray meets first on an axis is lo when it travels upwards
@@ -689,8 +692,7 @@ RTW_DEV void bvh_step16(const DScene& sc, const TravMem& tm, const v3 o, const v
         const RTW_CONST u32x4* q = (const RTW_CONST u32x4*)(uint64_t)(sc.nodes + 4u * i);
         q0 = q[0]; q1 = q[1]; q2 = q[2]; q3 = q[3];
     }
-    const float ix = __builtin_amdgcn_fmed3f(inv.x, -1.0e18f, 1.0e18f), iy = __builtin_amdgcn_fmed3f(inv.y, -1.0e18f, 1.0e18f),
-                iz = __builtin_amdgcn_fmed3f(inv.z, -1.0e18f, 1.0e18f);
+    const float ix = slab_inv(inv.x), iy = slab_inv(inv.y), iz = slab_inv(inv.z);
     const float ax = (__uint_as_float(q0.x) - o.x) * ix, ay = (__uint_as_float(q0.y) - o.y) * iy, az = (__uint_as_float(q0.z) - o.z) * iz;
     const float bx = __uint_as_float(q0.w) * ix, by = __uint_as_float(q2.z) * iy, bz = __uint_as_float(q2.w) * iz;
     const uint32_t nx = ix < 0.0f ? q1.w : q1.x, fx = ix < 0.0f ? q1.x : q1.w;
@@ -1099,8 +1101,7 @@ RTW_DEV void traverse_wave(const DScene& sc, uint32_t* wave_stack, const uint32_
                            const float ray_time, const float gather_time, float& best_t, int& best_prim, bool best_is_vol) {
     if (sc.n_tree <= 0) return;
     const v3 inv = recip3(d);
-    const float ix = __builtin_amdgcn_fmed3f(inv.x, -1.0e18f, 1.0e18f), iy = __builtin_amdgcn_fmed3f(inv.y, -1.0e18f, 1.0e18f),
-                iz = __builtin_amdgcn_fmed3f(inv.z, -1.0e18f, 1.0e18f);
+    const float ix = slab_inv(inv.x), iy = slab_inv(inv.y), iz = slab_inv(inv.z);
     const float nx = -(o.x * ix), ny = -(o.y * iy), nz = -(o.z * iz);
     TravMem tm0;  // leaf records come through the scalar cache here, not from the workgroup's LDS image
     tm0.stack16 = nullptr; tm0.stack32 = nullptr; tm0.stride = 0; tm0.nodes = nullptr; tm0.n_nodes = 0; tm0.leaves = nullptr; tm0.n_leaves = 0; tm0.wide = false;

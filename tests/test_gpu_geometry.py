@@ -1,0 +1,332 @@
+"""GPU suite: closest hits and texture coordinates of the kernels against geometry_ref.py (a float64 second reading of the
+reference, independent of the oracle), and the rays random tests never draw - zero direction components, origins on planes,
+faces and split planes, rays in a rectangle's plane, degenerate intervals, NaN and inf - against the oracle's index-order scan,
+through rtw_debug_intersect's generic walk and through the render kernels."""
+import functools
+
+import numpy as np
+import pytest
+
+import geometry_ref as G
+import guides_ref
+import oracle
+from raytracing_weekend_amd import abi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    r = abi.Renderer(0)
+    yield r
+    r.close()
+
+
+UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}, "no_lds": {"RTW_LDS_KB": "0"}}  # both knobs are read at upload
+
+
+def upload(gpu, monkeypatch, blob, how):
+    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in UPLOADS[how].items():
+        monkeypatch.setenv(k, v)
+    gpu.upload_scene(blob)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+# ---------------------------------------------------------------- (a) closest hits against the float64 reference
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(blob, rays, ray times, gather times, float64 reference, oracle t, oracle prim) of one scene, computed once."""
+    blob = G.SCENES[name]()
+    rays, rt, gt = G.scene_rays(blob, G.RAY_SEED)
+    return (blob, rays, rt, gt, G.closest_hit(blob, rays, rt, gt)) + oracle.intersect(blob, rays, rt, gt)
+
+
+@pytest.mark.parametrize("how", list(UPLOADS))
+@pytest.mark.parametrize("name", list(G.SCENES))
+def test_closest_hit_matches_float64_reference(gpu, monkeypatch, name, how):
+    blob, rays, rt, gt, ref, t_cpu, prim_cpu = case(name)
+    upload(gpu, monkeypatch, blob, how)
+    t, prim = gpu.debug_intersect(rays, rt, gt)
+    print(G.check_against(f"{name} ({how})", ref, t, prim))
+    # ... and the oracle's bits, so that a failure above says which side moved
+    assert np.array_equal(prim, prim_cpu) and same_bits(t, t_cpu)
+
+
+# ---------------------------------------------------------------- (b) edge rays against the oracle, bit for bit
+def edge_rays(blob, seed, first_pass):
+    """About 20 000 rays (n, 8) of the families random draws never produce, with their ray and gather times.
+    first_pass(rays) -> t: hit distances of a first pass, for the family whose tmax is its own hit distance."""
+    rng = np.random.default_rng(seed)
+    prims, xforms = G.scene_tables(blob)
+    cen, rad, _ = G.bounding_spheres(blob)
+    lo, hi = (cen - rad[:, None]).min(0), (cen + rad[:, None]).max(0)
+    f32 = np.float32
+
+    def rand_o(n):
+        return rng.uniform(lo - 0.1 * (hi - lo), hi + 0.1 * (hi - lo), (n, 3)).astype(f32)
+
+    def rand_d(n):
+        d = rng.normal(size=(n, 3))
+        return (d * rng.uniform(0.2, 12.0, (n, 1)) / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32)
+
+    def to_world(xi, p):  # fp32, the way a hit point is made
+        m = xforms["m"][xi].reshape(3, 4)
+        if np.array_equal(m, np.eye(3, 4, dtype=f32)):
+            return p.astype(f32)
+        return (p.astype(f32) @ m[:, :3].T + m[:, 3]).astype(f32)
+
+    def vec_world(xi, v):
+        return (v.astype(f32) @ xforms["m"][xi].reshape(3, 4)[:, :3].T).astype(f32)
+    rects = np.nonzero((prims["type"] >= abi.PRIM_RECT_X) & (prims["type"] <= abi.PRIM_RECT_Z))[0]
+    spheres = np.nonzero(prims["type"] == abi.PRIM_SPHERE)[0]
+    out = []
+
+    def add(o, d, tmin=1e-6, tmax=1e27):
+        n = len(o)
+        r = np.empty((n, 8), f32)
+        r[:, 0:3], r[:, 3:6], r[:, 6], r[:, 7] = o, d, tmin, tmax
+        out.append(r)
+
+    def rect_points(n, mode):
+        """n points of random rectangles in object space, with the rectangle's index, transform and axes: mode 'in' anywhere
+        inside, 'corner' a corner, 'edge' on an edge."""
+        pi = rng.choice(rects, n)
+        p = prims["p"][pi]
+        fa, fb = rng.uniform(0, 1, n), rng.uniform(0, 1, n)
+        if mode == "corner":
+            fa, fb = np.rint(fa), np.rint(fb)
+        elif mode == "edge":
+            fa = np.rint(fa)
+        pts = np.zeros((n, 3), f32)
+        axes = np.array([G.RECT_AXES[int(t)] for t in prims["type"][pi]])
+        rows = np.arange(n)
+        pts[rows, axes[:, 0]] = p[:, 4]
+        pts[rows, axes[:, 1]] = np.where(fa == 0, p[:, 0], np.where(fa == 1, p[:, 1], (p[:, 0] + fa * (p[:, 1] - p[:, 0])).astype(f32)))
+        pts[rows, axes[:, 2]] = np.where(fb == 0, p[:, 2], np.where(fb == 1, p[:, 3], (p[:, 2] + fb * (p[:, 3] - p[:, 2])).astype(f32)))
+        return pi, prims["xform"][pi], axes, pts
+
+    def per_xform(xi, pts, fn):
+        res = np.empty_like(pts)
+        for x in np.unique(xi):
+            res[xi == x] = fn(int(x), pts[xi == x])
+        return res
+    # 1. directions with one or two components exactly +0.0 / -0.0
+    n = 3000
+    d = rand_d(n)
+    pat = np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 0], [1, 0, 1], [0, 1, 1]], bool)[np.arange(n) % 6]
+    d[pat] = np.where(np.arange(n) % 2 == 0, f32(0.0), f32(-0.0))[:, None].repeat(3, 1)[pat]
+    add(rand_o(n), d)
+    # 2. origins exactly on a rectangle's plane / a transformed box's face (tmin 1e-6 and 0), random and axis-parallel directions
+    n = 2400
+    _, xi, axes, pts = rect_points(n, "in")
+    d = rand_d(n)
+    axis_d = np.zeros((n, 3), f32)
+    axis_d[np.arange(n), rng.integers(0, 3, n)] = rng.choice([-1.0, 1.0, 3.0], n)
+    d[::3] = per_xform(xi, axis_d, vec_world)[::3]
+    add(per_xform(xi, pts, to_world), d, tmin=np.where(np.arange(n) % 2 == 0, 1e-6, 0.0))
+    # 3. origins on a sphere's surface: the fp32 point c + r n
+    if spheres.size:
+        n = 1200
+        si = rng.choice(spheres, n)
+        nrm = rng.normal(size=(n, 3))
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        p = prims["p"][si]
+        pts = (p[:, 0:3] + p[:, 3:4] * nrm.astype(f32)).astype(f32)
+        add(per_xform(prims["xform"][si], pts, to_world), rand_d(n), tmin=np.where(np.arange(n) % 2 == 0, 1e-6, 0.0))
+    # 4. origins on coordinates taken from the primitives' bounds (the tree's split planes are among them)
+    n = 3000
+    ident = prims["xform"] == 0
+    coords = []
+    for ax in range(3):
+        vals = [cen[:, ax] - rad, cen[:, ax] + rad]  # bounding spheres of everything, transformed primitives included
+        for ty, (ik, ia, ib) in G.RECT_AXES.items():
+            m = ident & (prims["type"] == ty)
+            vals += [prims["p"][m, 4]] if ik == ax else []
+            vals += [prims["p"][m, 0], prims["p"][m, 1]] if ia == ax else []
+            vals += [prims["p"][m, 2], prims["p"][m, 3]] if ib == ax else []
+        m = ident & (prims["type"] == abi.PRIM_SPHERE)
+        vals += [prims["p"][m, ax] - prims["p"][m, 3], prims["p"][m, ax] + prims["p"][m, 3], prims["p"][m, ax]]
+        coords.append(np.unique(np.concatenate(vals).astype(f32)))
+    o = np.stack([rng.choice(coords[ax], n) for ax in range(3)], axis=1)
+    rnd = rand_o(n)
+    keep_random = rng.uniform(size=(n, 3)) < 0.4  # one or two coordinates stay off the planes
+    o[keep_random] = rnd[keep_random]
+    d = rand_d(n)
+    axis_d = np.zeros((n, 3), f32)
+    axis_d[np.arange(n), rng.integers(0, 3, n)] = rng.choice([-1.0, 1.0], n)
+    d[::2] = axis_d[::2]
+    add(o, d)
+    # 5. rays lying in a rectangle's plane (d_k = 0 in its object space), starting on the plane inside, outside and far away
+    n = 1500
+    _, xi, axes, pts = rect_points(n, "in")
+    d_obj = rand_d(n)
+    d_obj[np.arange(n), axes[:, 0]] = 0.0
+    shift = (rng.choice([0.0, -1.5, 40.0], n)[:, None] * d_obj).astype(f32)
+    add(per_xform(xi, (pts + shift).astype(f32), to_world), per_xform(xi, d_obj, vec_world))
+    # 6. rays through rectangle corners and along edges
+    n = 2400
+    _, xi, axes, pts = rect_points(n, "corner")
+    rows = np.arange(n)
+    d_obj = np.zeros((n, 3), f32)                  # a third: along the normal, exactly through the corner
+    d_obj[rows, axes[:, 0]] = rng.choice([-2.0, 1.0], n)
+    o_obj = (pts - 5.0 * d_obj).astype(f32)
+    k3 = rows % 3 == 1                             # a third: along an edge, starting before the corner
+    d_obj[k3] = 0.0
+    d_obj[rows[k3], axes[k3, 1]] = 1.0
+    o_obj[k3] = (pts[k3] - 7.0 * d_obj[k3]).astype(f32)
+    o_w, d_w = per_xform(xi, o_obj, to_world), per_xform(xi, d_obj, vec_world)
+    k3 = rows % 3 == 2                             # a third: from anywhere, aimed at the corner
+    o_w[k3] = rand_o(int(k3.sum()))
+    d_w[k3] = (per_xform(xi, pts, to_world)[k3] - o_w[k3]).astype(f32)
+    add(o_w, d_w)
+    # 7. denormal components and components of 1e-30
+    n = 2000
+    o, d = rand_o(n), rand_d(n)
+    tiny = np.array([1e-30, -1e-30, 1e-40, -1e-40, 1.4e-45], f32)
+    col = rng.integers(0, 3, n)
+    d[np.arange(n)[: n // 2], col[: n // 2]] = rng.choice(tiny, n // 2)
+    o[np.arange(n)[n // 2:], col[n // 2:]] = rng.choice(tiny, n - n // 2)
+    add(o, d)
+    # 8. direction lengths of 1e-18 and 1e18
+    n = 2000
+    d = rand_d(n)
+    d = (d * np.where(np.arange(n) % 2 == 0, f32(1e-18), f32(1e18))[:, None]).astype(f32)
+    o = rand_o(n)
+    o[: n // 2] = ((lo + hi) / 2).astype(f32)
+    add(o, d)
+    # 9. tmax equal to the hit distance of the same ray (and one ulp above it); tmin == tmax; tmin > tmax; tmax = inf
+    n = 2000
+    o, d = rand_o(n), rand_d(n)
+    probe = np.concatenate([o, d, np.full((n, 1), 1e-6, f32), np.full((n, 1), 1e27, f32)], axis=1).astype(f32)
+    t_hit = np.asarray(first_pass(probe), f32)
+    add(o, d, tmax=np.where(np.arange(n) % 2 == 0, t_hit, np.nextafter(t_hit, f32(np.inf))))
+    add(o[:600], d[:600], tmin=t_hit[:600], tmax=t_hit[:600])
+    add(o[600:1000], d[600:1000], tmin=5.0, tmax=1.0)
+    add(o[1000:], d[1000:], tmax=np.inf)
+    # 10. NaN and inf components (paths do produce them; the walks end whatever the ray holds, see the test below)
+    n = 600
+    o, d = rand_o(n), rand_d(n)
+    bad = np.array([np.nan, np.inf, -np.inf], f32)
+    col = rng.integers(0, 3, n)
+    o[np.arange(n)[:200], col[:200]] = rng.choice(bad, 200)
+    d[np.arange(n)[200:400], col[200:400]] = rng.choice(bad, 200)
+    tmax = np.full(n, 1e27, f32)
+    tmax[400:500] = np.nan
+    d[500:] = 0.0  # the null direction: 0 / 0 everywhere
+    add(o, d, tmax=tmax)
+    rays = np.concatenate(out)
+    return rays, rng.uniform(0, 1, len(rays)).astype(f32), rng.uniform(0, 1, len(rays)).astype(f32)
+
+
+EDGE_SCENES = {
+    "cornell": (lambda: abi.build_scene(0, 32, 32), ("as_uploaded", "forced_tree")),
+    "cluttered_cornell": (lambda: oracle.cluttered_cornell(32, 32), ("forced_tree",)),
+    "random19": (lambda: oracle.random_scene(19, 32, 32, n_prims=300), ("forced_tree",)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name):
+    blob = EDGE_SCENES[name][0]()
+    rays, rt, gt = edge_rays(blob, 77, lambda probe: oracle.intersect(blob, probe)[0])
+    return (blob, rays, rt, gt) + oracle.intersect(blob, rays, rt, gt)
+
+
+@pytest.mark.parametrize("name,how", [(n, h) for n, (_, hows) in EDGE_SCENES.items() for h in hows])
+def test_edge_rays_match_the_oracle_bit_for_bit(gpu, monkeypatch, name, how):
+    """NaN and inf rays are in: the walks of the tree end whatever a ray holds. Every step of traverse<> either enters a child
+    of the node it stands at or pops the stack, the stack is sized for the worst walk the tree's shape allows
+    (rtw_bvh.h stack_need), and no loop condition compares ray data; the list walk runs over counts alone."""
+    blob, rays, rt, gt, t_cpu, prim_cpu = edge_case(name)
+    assert 15_000 <= len(rays) <= 25_000
+    finite = np.isfinite(rays[:, :6]).all(1)
+    assert (prim_cpu[finite] >= 0).mean() > 0.2
+    upload(gpu, monkeypatch, blob, how)
+    t, prim = gpu.debug_intersect(rays, rt, gt)
+    wrong = np.nonzero((prim != prim_cpu) | (t.view(np.uint32) != t_cpu.view(np.uint32)))[0]
+    assert wrong.size == 0, (f"{wrong.size} rays differ, first {wrong[:5]}: rays {rays[wrong[:5]]}, gpu {list(zip(t[wrong[:5]], prim[wrong[:5]]))}, "
+                             f"oracle {list(zip(t_cpu[wrong[:5]], prim_cpu[wrong[:5]]))}")
+
+
+# ---------------------------------------------------------------- (c) the same edge geometry through the render kernels
+def ortho_views():
+    """Orthographic cameras (rtw.h: origin = lower_left + s horizontal + t vertical + camera origin, direction = -normalize(w))
+    whose rays are axis-parallel and lie IN planes of the Cornell box: one image axis is collapsed, so that every pixel column
+    (or row) falls on the plane of a wall, the floor, the ceiling or the top face of a box. (name, w, lower_left, horizontal, vertical)."""
+    z_in, x_in, y_in = (0.0, 0.0, -1.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0)  # w of views along +z, +x, -y (the last two start inside the box)
+    v = [("whole box along z", z_in, (-10.0, -10.0, -800.0), (575.0, 0.0, 0.0), (0.0, 575.0, 0.0))]
+    for x in (0.0, 555.0, 213.0):
+        v.append((f"along z in x = {x:g}", z_in, (x, 0.0, -800.0), (0.0, 0.0, 0.0), (0.0, 555.0, 0.0)))
+    for y in (0.0, 555.0, 330.0, 165.0):  # floor, ceiling, the tops of the tall and of the short box
+        v.append((f"along z in y = {y:g}", z_in, (0.0, y, -800.0), (555.0, 0.0, 0.0), (0.0, 0.0, 0.0)))
+    v.append(("along x in z = 555", x_in, (1.0, 0.0, 555.0), (0.0, 0.0, 0.0), (0.0, 555.0, 0.0)))
+    v.append(("along x in y = 330", x_in, (1.0, 330.0, 0.0), (0.0, 0.0, 555.0), (0.0, 0.0, 0.0)))
+    v.append(("along -y in x = 555", y_in, (555.0, 550.0, 0.0), (0.0, 0.0, 0.0), (0.0, 0.0, 555.0)))
+    v.append(("along -y in z = 555", y_in, (0.0, 550.0, 555.0), (555.0, 0.0, 0.0), (0.0, 0.0, 0.0)))
+    return v
+
+
+def with_ortho(blob, w, h, view):
+    """blob with build_scene(200)'s orthographic camera (as guides_ref.with_camera takes it over), then placed by `view`."""
+    _, wv, ll, hz, vt = view
+    parts = dict(abi.parse_scene(guides_ref.with_camera(blob, 200, w, h)))
+    hdr = abi.SceneHeader.from_buffer_copy(bytes(parts["header"]))
+    assert hdr.camera_type == abi.RTW_CAM_ORTHOGRAPHIC
+    for i in range(3):
+        hdr.camera.origin[i] = 0.0  # (the origin enters the ray origin once more: zero keeps the planes exact)
+        hdr.camera.w[i], hdr.camera.lower_left[i], hdr.camera.horizontal[i], hdr.camera.vertical[i] = wv[i], ll[i], hz[i], vt[i]
+    parts["header"] = hdr
+    return abi.assemble_scene(parts)
+
+
+@functools.lru_cache(maxsize=None)
+def ortho_case(scene, rng, k):
+    w, h = 64, 48
+    base = abi.build_scene(0, w, h) if scene == "cornell" else oracle.cluttered_cornell(w, h)
+    n = len(abi.parse_scene(base)["prims"])
+    cols = [((i + 1) / 256.0, 0.5, 0.25) for i in range(n)]  # test_prim_identity's colours
+    blob = with_ortho(guides_ref.all_emitters(base, cols), w, h, ortho_views()[k])
+    p = abi.make_params(w, h, 4, 1, rng_kind=rng)
+    img, st = oracle.render(blob, p, threads=4)
+    return blob, img, (st.samples, st.segments, st.shadow_rays)
+
+
+@pytest.mark.parametrize("rng", [abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG])
+@pytest.mark.parametrize("path", ["1", "0"])  # k_path (the default) / the wavefront kernels
+@pytest.mark.parametrize("scene", ["cornell", "cluttered_cornell"])  # candidate lists / k_first's whole-wave tree walk
+def test_axis_parallel_camera_rays_in_planes_render_like_the_oracle(gpu, monkeypatch, scene, path, rng):
+    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("RTW_PATH", path)
+    seen = 0
+    for k, view in enumerate(ortho_views()):
+        blob, img_cpu, counts = ortho_case(scene, rng, k)
+        gpu.upload_scene(blob)
+        img, st = gpu.render(abi.make_params(64, 48, 4, 1, rng_kind=rng))
+        assert same_bits(img, img_cpu), f"{view[0]}: {(img != img_cpu).any(-1).sum()} pixels differ"
+        assert (st.samples, st.segments, st.shadow_rays) == counts, view[0]
+        seen += int((img_cpu[..., 1] != 0).sum())
+    assert seen > 64 * 48  # the views do see the box
+
+
+# ---------------------------------------------------------------- (d) texture coordinates against the float64 reference
+@pytest.mark.parametrize("how", ["as_uploaded", "forced_tree"])
+@pytest.mark.parametrize("rng", [abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG])
+def test_texture_coordinates_match_float64_reference(gpu, monkeypatch, rng, how):
+    """The albedo guide of an emitter is the texture value at the first hit: red must be the reference's u and green its v,
+    within the range over the pixel plus one 8-bit step (sphere and rectangle conventions, image row 0 at v = 0, texel centres
+    at (i + 0.5) / width; the transformed sphere's texture turns twice)."""
+    blob = G.texture_scene()
+    exp = G.uv_expectation(blob)
+    upload(gpu, monkeypatch, blob, how)
+    p = abi.make_params(G.TEX_W, G.TEX_H, 1, 1, rng_kind=rng)
+    g = gpu.render_guides(p, which=("albedo", "prim"))
+    G.check_uv(exp, g["albedo"], f"albedo guide ({how})")
+    assert np.array_equal(g["prim"][exp["checked"]], exp["prim"][exp["checked"]])
+    img, _ = gpu.render(p)
+    G.check_uv(exp, img, f"beauty ({how})")

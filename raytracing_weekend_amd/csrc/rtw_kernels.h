@@ -25,6 +25,7 @@
 // (raygen.cu:60) is preserved bit for bit. A "zombie" is a path that ended (roulette / depth) with a
 // shadow probe still queued: it survives one more trace pass, collects the contribution and retires.
 #pragma once
+#include "rtw_ahead.h"
 #include "rtw_device.h"
 #include "rtw_plan.h"
 
@@ -1410,6 +1411,16 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
     const PathConsts* pc_cam = TEX ? nullptr : &s_pc;
     __shared__ u32x4 s_walk[TEX ? 1 : kWalkMaxWords];
     if (!TEX) for (uint32_t i = tid; i < (uint32_t)A.sc.n_walk_words; i += kBlock) s_walk[i] = A.sc.walk[i];
+    // The reserve of camera rays (rtw_ahead.h), hot instantiation with Philox only: there a new path's state beside the direction is
+    // constant (origin = the camera's, T = 1, L = 0, generator word 0), so an entry is the unnormalised direction raygen produces.
+    // Each lane reads and writes its own column, slot = sample mod K; the count of valid entries rides in blk_end's high bits.
+#if RTW_PATH_AHEAD > 0
+    constexpr bool AHEAD = !TEX && KIND == RTW_RNG_PHILOX;
+    constexpr uint32_t AK = RTW_PATH_AHEAD;
+    __shared__ float s_ray[AHEAD ? AK : 1][3][AHEAD ? kBlock : 1];
+#else
+    constexpr bool AHEAD = false;
+#endif
     __syncthreads();
     const uint32_t lane = tid & 63u;
     // wave-uniform: the job stream
@@ -1479,6 +1490,33 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
         const bool busy = !need;
         const uint32_t px = pxy & 0xffffu, py = pxy >> 16;
         Rng<KIND> g;
+#if RTW_PATH_AHEAD > 0
+        if constexpr (AHEAD) {
+            // The fill phase runs only when some lane starts a path with an empty reserve, and then every busy lane with room generates
+            // the entry of its first uncached sample (the same raygen call a regeneration made: same operations, same bits), never one
+            // outside its unit. Between the fills a regeneration is three LDS reads.
+            const uint32_t cnt = ahead_count(blk_end);
+            if (__ballot(ahead_starved(busy, alive, cnt)) != 0ull) {
+                const PathConsts* kc = &s_pc;  // (launch constants from the LDS page: see PathConsts)
+                const uint32_t first = ahead_first_uncached(s_cur, alive, cnt);
+                if (busy && ahead_room(cnt, AK, first, ahead_unit_end(kc->block0, ahead_blk_end(blk_end), kc->spp))) {
+                    Path p;
+                    Rng<KIND> gf;
+                    raygen<KIND, true>(A, px, py, A.sample0 + first, 0u, p, gf, pc_cam);
+                    const uint32_t sl = ahead_slot(first, AK);
+                    s_ray[sl][0][tid] = p.d.x; s_ray[sl][1][tid] = p.d.y; s_ray[sl][2][tid] = p.d.z;
+                    blk_end = ahead_pushed(blk_end);
+                }
+            }
+            if (busy && !alive) {  // regeneration from the reserve: the lane's entry of sample s_cur
+                const uint32_t sl = ahead_slot(s_cur, AK);
+                d = V(s_ray[sl][0][tid], s_ray[sl][1][tid], s_ray[sl][2][tid]);
+                blk_end = ahead_popped(blk_end);
+                o = ld3(s_pc.cam_o); T = V(1.f, 1.f, 1.f); L = V(0.f, 0.f, 0.f); rng_a = 0u;
+                depth = 0; alive = true;
+            }
+        } else
+#endif
         if (busy && !alive) {  // regeneration: the next camera path of this lane's unit
             Path p;
             raygen<KIND, !TEX>(A, px, py, A.sample0 + s_cur, 0u, p, g, pc_cam);
@@ -1496,8 +1534,16 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
         // closest hit (raygen.cu:41-54). Camera rays of neighbouring pixels that all look past the scene skip the walk.
         float th = 1.e27f;
         int prim = -1;
+#if RTW_PATH_GATE_BOUNDS
+        // The bounds test counts only through the ballot, and one busy lane past depth 0 makes the wave walk whatever it says: it runs
+        // in the iterations where it decides (all busy lanes on camera rays: the start of a launch, frames that look past the scene)
+        bool walk_any = !bounds_test_decides(__ballot(busy && depth > 0u));
+        if (!walk_any) walk_any = __ballot(busy && may_hit_scene(A.sc, o, d)) != 0ull;
+        if (walk_any) {
+#else
         const bool walk = busy && (depth > 0u || may_hit_scene(A.sc, o, d));
         if (__ballot(walk) != 0ull) {
+#endif
             if (busy) {
                 if (TEX) traverse_brute<Rng<KIND>, false, false>(A.sc, o, d, A.sc.ray_tmin, 1.e27f, ray_time, gt, g, th, prim);
                 else walk_lds<false>(s_walk, A.sc.n_groups, o, d, A.sc.ray_tmin, 1.e27f, th, prim);
@@ -1544,7 +1590,7 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                     const uint32_t pix = LIST ? __float_as_uint(s_usum[0][tid]) : yl_ * c_width + px;
                     const uint32_t b_done = blk;
                     blk++;
-                    need = blk >= blk_end || s_cur >= A.spp;
+                    need = blk >= (AHEAD ? ahead_blk_end(blk_end) : blk_end) || s_cur >= A.spp;
                     float4* const bsum_base = (float4*)(((uint64_t)kc->bs_hi << 32) | kc->bs_lo);
                     // the spec's second level: block sums add up in order inside aligned units of kSumUnitBlocks blocks (the launch's
                     // first block is unit-aligned). A launch whose lane units are whole summation units (A.unit_sums: shift 3) keeps

@@ -445,6 +445,56 @@ int rtw_accum_save(rtw_ctx* ctx, void* blob, size_t bytes);
 int rtw_accum_restore(rtw_ctx* ctx, const void* blob, size_t bytes);
 int rtw_accum_end(rtw_ctx* ctx);
 
+/* Ray queries: closest-hit and occlusion queries on the caller's own rays, in batches (what an OptiX user does with a raygen
+ * program of their own over optixTrace: visibility and ambient-occlusion passes, picking, range and lidar simulation, form
+ * factors). Nothing here starts from the scene's camera.
+ *   Rays: `rays` holds n*8 floats (ox, oy, oz, dx, dy, dz, tmin, tmax), rtw_debug_intersect's layout. Directions need not be
+ *     normalised: t is the ray parameter. ray_time and gather_time hold n floats each or are NULL (0 for every ray); they mean what
+ *     they mean for rtw_debug_intersect: the ray time places a moving sphere's motion transform, the gather time its centre.
+ *     Participating media are transparent, as they are for the guides (volume primitives are skipped: a medium's hit is a random draw).
+ *   Outputs: every pointer of rtw_hits holds n entries, or is NULL for an output the caller does not want. Outputs may not alias
+ *     the inputs or each other.
+ *   RTW_CAST_CLOSEST: the candidates are the non-volume primitives with tmin < t < tmax, the hit is the minimum over (t, primitive
+ *     index). t[i] and prim[i] carry the bits rtw_debug_intersect returns for that ray: t = tmax and prim = -1 on a miss.
+ *     material[i] = prims[prim].material, -1 on a miss. normal[i].xyz is the world-space shading normal, exactly the vector the
+ *     closest-hit code hands to the materials: rectangles +-axis by their flip flag, taken to world space, unit length; spheres
+ *     (P_world - C_object) / r through the inverse transpose, NOT normalised; moving spheres with the centre at the
+ *     gather time. normal[i].w = 1.0f when dot(normal, d) < 0 (the shading code's front-face rule), else 0.0f. uv[i] are the texture
+ *     coordinates the image textures are fetched at (spheres from the shading normal, rectangles from the object-space hit point).
+ *     On a miss normal = (0, 0, 0, 0) and uv = (0, 0).
+ *   RTW_CAST_ANY: prim[i] = -1 when no candidate lies in the interval, else the index of a non-volume primitive that does - which
+ *     one is unspecified, but it is the same from call to call for one uploaded scene and one set of upload knobs. t[i] = tmax.
+ *     material, normal and uv must be NULL (RTW_ERR_INVALID_ARG otherwise). Guarantee: prim[i] >= 0 exactly when RTW_CAST_CLOSEST
+ *     returns a hit for the same ray - the two walks are identical up to the first accepted candidate - NaN and inf rays included.
+ *   The result for ray i depends on ray i alone: not on n, the launch geometry or how rtw_cast cuts the batch into chunks.
+ *   rtw_cast: host pointers. The rays are staged through device buffers the context keeps and grows (no allocation per call once
+ *     they are large enough), in chunks of at most RTW_CAST_CHUNK rays (an environment variable read per call, csrc/rtw_plan.h).
+ *   rtw_cast_device: device pointers on the context's device; rays and normal 16-byte aligned, uv 8-byte aligned. Ordered on
+ *     hip_stream exactly as rtw_render_device is; returns when the results are written. NULL selects the context's own
+ *     non-blocking stream, NOT the legacy default stream (whose handle NULL also is): a caller whose rays are still being written
+ *     on stream 0 passes hipStreamLegacy, or a stream of its own, or synchronises first. It allocates nothing per call. One persistent launch: the grid is what the device holds at once, lanes stride over
+ *     64-bit ray indices.
+ *   Groups (n_devices > 1): the query runs on device_ids[0], as rtw_render_guides does; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   stats (may be NULL): segments = n (closest) or shadow_rays = n (any), samples = 0, seconds = device time from the call's first
+ *     event to its last; the per-kernel arrays are 0.
+ *   Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for a mode other than the two, n > 2^31 - 1, with n > 0 a NULL
+ *     rays or out or an rtw_hits whose pointers are all NULL, outputs RTW_CAST_ANY does not have, and (rtw_cast_device) a
+ *     misaligned rays, normal or uv. n = 0 is RTW_OK and launches nothing. The context stays usable after an error. */
+enum { RTW_CAST_CLOSEST = 0, RTW_CAST_ANY = 1 };
+typedef struct rtw_hits {
+    float* t;          /* n floats                                                   */
+    int32_t* prim;     /* n int32                                                    */
+    int32_t* material; /* n int32                                                    */
+    float* normal;     /* n float4: xyz shading normal, w = 1.0f front face / 0.0f   */
+    float* uv;         /* n float2                                                   */
+} rtw_hits;            /* 40 B */
+
+int rtw_cast(rtw_ctx* ctx, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode,
+             const rtw_hits* out, rtw_stats* stats);
+int rtw_cast_device(rtw_ctx* ctx, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode,
+                    const rtw_hits* out, void* hip_stream, rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

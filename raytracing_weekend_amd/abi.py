@@ -110,10 +110,18 @@ class AccumInfo(C.Structure):
                 ("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64), ("params", Params)]
 
 
+class Hits(C.Structure):
+    """rtw_hits (include/rtw.h): the output pointers of rtw_cast / rtw_cast_device, NULL for an output nobody wants."""
+    _fields_ = [("t", C.c_void_p), ("prim", C.c_void_p), ("material", C.c_void_p), ("normal", C.c_void_p), ("uv", C.c_void_p)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
-               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end"]
+               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device"]
+CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
+# rtw_hits' outputs: name -> (numpy dtype, trailing shape)
+CAST_OUTPUTS = {"t": (np.float32, ()), "prim": (np.int32, ()), "material": (np.int32, ()), "normal": (np.float32, (4,)), "uv": (np.float32, (2,))}
 RTW_ACCUM_ERROR = 1  # rtw_accum_begin's flag: keep the moments, so that accum_read can return the error map
 MATH_OPS = {"rcp": 0, "sqrt": 1, "rcp_sqrt": 2, "rcp_one_step": 3, "rcp_two_steps": 4, "sqrt_residual_only": 5, "sqrt_coupled": 6}  # rtw_debug_math's op
 GUIDES = ("albedo", "normal", "depth", "prim")
@@ -188,6 +196,11 @@ def load_hip():
         lib.rtw_accum_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.rtw_accum_end.restype = C.c_int
         lib.rtw_accum_end.argtypes = [C.c_void_p]
+        lib.rtw_cast.restype = C.c_int
+        lib.rtw_cast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Hits), C.POINTER(Stats)]
+        lib.rtw_cast_device.restype = C.c_int
+        lib.rtw_cast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Hits), C.c_void_p,
+                                        C.POINTER(Stats)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -279,6 +292,7 @@ class Renderer:
         self.lib = load_hip()
         self.ctx = C.c_void_p()
         ids = list(device) if isinstance(device, (list, tuple)) else [device]
+        self.devices = ids  # a group's queries (guides, adaptive, sessions, casts) run on ids[0]
         dev = (C.c_int * len(ids))(*ids)
         rc = self.lib.rtw_create(C.byref(self.ctx), len(ids), dev)
         if rc != 0:
@@ -409,6 +423,55 @@ class Renderer:
 
     def accum_end(self):
         self._check(self.lib.rtw_accum_end(self.ctx), "rtw_accum_end")
+
+    # ---- ray queries on the caller's own rays (include/rtw.h rtw_cast / rtw_cast_device)
+    @staticmethod
+    def cast_outputs(mode, want):
+        """The outputs a cast returns: `want` in rtw_hits' order, without the ones the mode does not have."""
+        if mode not in CAST_MODES:
+            raise ValueError(f"cast: mode {mode!r} is neither 'closest' nor 'any'")
+        want = tuple(want)
+        bad = [k for k in want if k not in CAST_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"cast: unknown or no output names {bad or want}")
+        names = [k for k in CAST_OUTPUTS if k in want and (mode == "closest" or k in ("t", "prim"))]
+        if not names:
+            raise ValueError(f"cast: mode 'any' has t and prim only, not {want}")
+        return names
+
+    def cast(self, rays, ray_time=None, gather_time=None, mode="closest", want=("t", "prim", "material", "normal", "uv"), stats=None):
+        """rtw_cast on (n, 8) float32 rays (origin, direction, tmin, tmax) with optional (n,) ray and gather times: a dict of the
+        requested outputs as numpy arrays - t (n,) float32, prim and material (n,) int32, normal (n, 4) float32 (w = 1 front face),
+        uv (n, 2) float32. mode "any" answers occlusion: prim >= 0 where something lies in (tmin, tmax); it has t and prim only (the
+        other names of the default `want` are dropped). `stats`: a Stats to fill, or None."""
+        names = self.cast_outputs(mode, want)
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"cast: rays of shape {rays.shape}, expected (n, 8)")
+        n = rays.shape[0]
+
+        def times(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (n,):
+                raise ValueError(f"cast: times of shape {a.shape} for {n} rays")
+            return a
+        rt, gt = times(ray_time), times(gather_time)
+        out = {k: np.empty((n,) + CAST_OUTPUTS[k][1], CAST_OUTPUTS[k][0]) for k in names}
+        h = Hits(**{k: v.ctypes.data for k, v in out.items()})
+        self._check(self.lib.rtw_cast(self.ctx, rays.ctypes.data, None if rt is None else rt.ctypes.data,
+                                      None if gt is None else gt.ctypes.data, n, CAST_MODES[mode], C.byref(h),
+                                      None if stats is None else C.byref(stats)), "rtw_cast")
+        return out
+
+    def cast_device(self, n, rays_ptr, out_ptrs, ray_time_ptr=0, gather_time_ptr=0, mode="closest", stream_ptr=0, stats=None):
+        """rtw_cast_device on raw device pointers, as render_device takes them: n rays at rays_ptr (16-byte aligned), out_ptrs a
+        dict name -> device pointer of the outputs wanted, stream_ptr a hipStream_t (0: the context's own stream)."""
+        h = Hits(**{k: C.c_void_p(v) for k, v in out_ptrs.items()})
+        self._check(self.lib.rtw_cast_device(self.ctx, C.c_void_p(rays_ptr), C.c_void_p(ray_time_ptr), C.c_void_p(gather_time_ptr), n,
+                                             CAST_MODES[mode], C.byref(h), C.c_void_p(stream_ptr),
+                                             None if stats is None else C.byref(stats)), "rtw_cast_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

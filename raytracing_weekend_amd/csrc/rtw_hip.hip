@@ -54,10 +54,12 @@
 #include "rtw_accum_state.h"
 #include "rtw_kernels.h"
 #include "rtw_guides.h"
+#include "rtw_cast.h"
 #include "rtw_adaptive.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
+#include "rtw_cast.hip"    // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -158,6 +160,9 @@ struct rtw_ctx {
         double2* mom = nullptr;
         float* err = nullptr;
     } acc;
+    // rtw_cast's staging (the host variant): one allocation of cast_rays rays' inputs and outputs, grown on demand, kept until rtw_destroy
+    void* cast_buf = nullptr;
+    size_t cast_rays = 0;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
 
@@ -474,6 +479,7 @@ int impl_destroy(rtw_ctx* c) {
     if (c->stage) (void)hipFree(c->stage);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_out) (void)hipFree(c->d_out);
+    if (c->cast_buf) (void)hipFree(c->cast_buf);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1901,6 +1907,136 @@ int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, c
     return RTW_OK;
 }
 
+// ---- rtw_cast / rtw_cast_device (rtw.h): the caller's rays through k_cast
+typedef void (*CastKernel)(const DScene, const CastArgs);
+
+// one persistent launch of n rays on stream s of device context d (device pointers): as many workgroups as the device holds at once
+// (the occupancy query with the scene's dynamic LDS x the CU count), never more than the rays fill
+hipError_t cast_launch(rtw_ctx* d, int32_t mode, const CastArgs& a, hipStream_t s) {
+    const bool attr = a.material || a.normal || a.uv;
+    const CastKernel k = mode == RTW_CAST_ANY ? k_cast<true, false> : attr ? k_cast<false, true> : k_cast<false, false>;
+    const size_t lds = d->info.lds_bytes;
+    int nb = 0;
+    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
+    // workgroups per CU: what the query admits (registers allow 6 or 7 of these 4-wave workgroups, a tree's LDS image up to 10); the
+    // cap of 8 and the 4 taken when the query fails are render_path's for k_path (a failed query only costs occupancy: the launch is
+    // grid-stride, any grid computes the same)
+    size_t per_cu = (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
+    if (const int mult = read_tuning().cast_grid_mult) per_cu = (size_t)mult;  // RTW_CAST_GRID_MULT (rtw_plan.h)
+    const size_t grid = std::min<size_t>(((size_t)a.n + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, d->sc, a);
+    return hipGetLastError();
+}
+
+// the checks the two variants share (c: the context the caller holds; a group's has_scene covers its devices)
+int cast_check(rtw_ctx* c, const char* what, const float* rays, size_t n, int32_t mode, const rtw_hits* out) {
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, std::string(what) + " before rtw_upload_scene");
+    if (mode != RTW_CAST_CLOSEST && mode != RTW_CAST_ANY) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad mode");
+    if (n > 0x7fffffffull) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": more than 2^31 - 1 rays");
+    if (n == 0) return RTW_OK;
+    if (!rays || !out) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null rays or outputs");
+    if (!out->t && !out->prim && !out->material && !out->normal && !out->uv) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": no output buffer");
+    if (mode == RTW_CAST_ANY && (out->material || out->normal || out->uv))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": RTW_CAST_ANY has no material, normal or uv");
+    return RTW_OK;
+}
+
+// two timing events of the context's pool (no event is created once a context has timed anything)
+hipError_t cast_events(rtw_ctx* d, hipEvent_t ev[2]) {
+    while (d->ev_pool.size() < 2) {
+        hipEvent_t n = nullptr;
+        const hipError_t e = hipEventCreate(&n);
+        if (e != hipSuccess) return e;
+        d->ev_pool.push_back(n);
+    }
+    ev[0] = d->ev_pool[0]; ev[1] = d->ev_pool[1];
+    return hipSuccess;
+}
+
+void cast_stats(rtw_stats* stats, size_t n, int32_t mode, float ms) {
+    memset(stats, 0, sizeof *stats);
+    (mode == RTW_CAST_ANY ? stats->shadow_rays : stats->segments) = (uint64_t)n;
+    stats->seconds = (double)ms * 1e-3;
+}
+
+int impl_cast_device(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
+                     void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    const int rc = cast_check(c, "rtw_cast_device", rays, n, mode, out);
+    if (rc) return rc;
+    if (n > 0 && (((uintptr_t)rays & 15) || ((uintptr_t)out->normal & 15) || ((uintptr_t)out->uv & 7)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_cast_device: rays and normal must be 16-byte aligned, uv 8-byte aligned");
+    if (stats) cast_stats(stats, n, mode, 0.f);  // (after every refusal: a refused call leaves *stats alone)
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    const CastArgs a{(const float4*)rays, ray_time, gather_time, (uint64_t)n, out->t, out->prim, out->material, (float4*)out->normal, (float2*)out->uv};
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, cast_launch(d, mode, a, s));
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        stats->seconds = (double)ms * 1e-3;
+    }
+    return RTW_OK;
+}
+
+int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
+              rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    const int rc = cast_check(c, "rtw_cast", rays, n, mode, out);
+    if (rc) return rc;
+    if (stats) cast_stats(stats, n, mode, 0.f);
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const size_t chunk = std::min(n, read_tuning().cast_chunk);
+    // the staging slab: per ray 32 B of ray, two times, and the five outputs (4 + 4 + 4 + 16 + 8 B), every section 256-byte aligned
+    const size_t width[8] = {32, 4, 4, 4, 4, 4, 16, 8};
+    if (chunk > d->cast_rays) {
+        if (d->cast_buf) (void)hipFree(d->cast_buf);
+        d->cast_buf = nullptr; d->cast_rays = 0;
+        size_t bytes = 0;
+        for (size_t w : width) bytes += (chunk * w + 255) & ~(size_t)255;
+        HIP_TRY(c, hipMalloc(&d->cast_buf, bytes));
+        d->cast_rays = chunk;
+    }
+    char* sec[8];
+    {
+        size_t off = 0;
+        for (int k = 0; k < 8; k++) { sec[k] = (char*)d->cast_buf + off; off += (d->cast_rays * width[k] + 255) & ~(size_t)255; }
+    }
+    void* const dst[5] = {out->t, out->prim, out->material, out->normal, out->uv};
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        HIP_TRY(c, hipMemcpyAsync(sec[0], rays + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
+        if (ray_time) HIP_TRY(c, hipMemcpyAsync(sec[1], ray_time + i0, m * 4, hipMemcpyHostToDevice, d->stream));
+        if (gather_time) HIP_TRY(c, hipMemcpyAsync(sec[2], gather_time + i0, m * 4, hipMemcpyHostToDevice, d->stream));
+        CastArgs a{(const float4*)sec[0], ray_time ? (const float*)sec[1] : nullptr, gather_time ? (const float*)sec[2] : nullptr, (uint64_t)m,
+                   dst[0] ? (float*)sec[3] : nullptr, dst[1] ? (int32_t*)sec[4] : nullptr, dst[2] ? (int32_t*)sec[5] : nullptr,
+                   dst[3] ? (float4*)sec[6] : nullptr, dst[4] ? (float2*)sec[7] : nullptr};
+        HIP_TRY(c, cast_launch(d, mode, a, d->stream));
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        for (int k = 0; k < 5; k++)
+            if (dst[k]) HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * width[3 + k], sec[3 + k], m * width[3 + k], hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
+    }
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        stats->seconds = (double)ms * 1e-3;
+    }
+    return RTW_OK;
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -1967,5 +2103,12 @@ int rtw_accum_status(rtw_ctx* c, rtw_accum_info* out) { return guarded(c, [&] { 
 int rtw_accum_save(rtw_ctx* c, void* blob, size_t bytes) { return guarded(c, [&] { return impl_accum_save(c, blob, bytes); }); }
 int rtw_accum_restore(rtw_ctx* c, const void* blob, size_t bytes) { return guarded(c, [&] { return impl_accum_restore(c, blob, bytes); }); }
 int rtw_accum_end(rtw_ctx* c) { return guarded(c, [&] { return impl_accum_end(c); }); }
+int rtw_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_cast(c, rays, ray_time, gather_time, n, mode, out, stats); });
+}
+int rtw_cast_device(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
+                    void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_cast_device(c, rays, ray_time, gather_time, n, mode, out, hip_stream, stats); });
+}
 
 }  // extern "C"

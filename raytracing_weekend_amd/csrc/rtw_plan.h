@@ -65,6 +65,10 @@ inline void magic_div(uint32_t d, uint32_t& m, uint32_t& s1, uint32_t& s2) {
 //   RTW_KERNEL_TIMING    0: no per-launch events even when the caller asks for rtw_stats (kernel_seconds stay 0)
 //   RTW_CULL             0: k_path is handed every 64-pixel group, also those no camera ray of which can reach a primitive (default 1:
 //                        such groups get no job and their pixels are black, see cull_rect below; same image and counts either way)
+//   RTW_CAST_CHUNK       rays rtw_cast (the host variant) stages and casts at a time (default 2^20: 76 MB of staging at all five outputs;
+//                        1 .. 2^31 - 1). The results do not depend on it.
+//   RTW_CAST_GRID_MULT   k_cast workgroups per CU (default: what the occupancy query admits, the persistent launch; larger values queue
+//                        workgroups behind the resident ones - for measurements). The results do not depend on it.
 // Two measured-slower alternatives were removed from the code: k_path_tree for tree scenes and the paired batch
 // schedule; their knobs are no longer read.
 struct Tuning {
@@ -97,6 +101,8 @@ struct Tuning {
     size_t blocksum_bytes = (size_t)16 << 30;
     bool kernel_timing = true;
     bool cull = true;
+    size_t cast_chunk = (size_t)1 << 20;  // rtw_cast: rays per staged chunk
+    int cast_grid_mult = 0;               // k_cast workgroups per CU; 0 = the occupancy query's answer
     bool verbose = false;  // RTW_VERBOSE=1: table sizes at upload (stderr)
 };
 inline Tuning read_tuning() {
@@ -130,6 +136,8 @@ inline Tuning read_tuning() {
     if (geti("RTW_BLOCKSUM_BYTES", v) && v >= (1 << 16)) t.blocksum_bytes = (size_t)v;
     if (geti("RTW_KERNEL_TIMING", v)) t.kernel_timing = v != 0;
     if (geti("RTW_CULL", v)) t.cull = v != 0;
+    if (geti("RTW_CAST_CHUNK", v)) t.cast_chunk = (size_t)std::max<long long>(1, std::min<long long>(0x7fffffffll, v));
+    if (geti("RTW_CAST_GRID_MULT", v)) t.cast_grid_mult = (int)std::max<long long>(0, std::min<long long>(4096, v));
     if (geti("RTW_VERBOSE", v)) t.verbose = v != 0;
     return t;
 }

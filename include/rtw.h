@@ -495,6 +495,57 @@ int rtw_cast(rtw_ctx* ctx, const float* rays, const float* ray_time, const float
 int rtw_cast_device(rtw_ctx* ctx, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode,
                     const rtw_hits* out, void* hip_stream, rtw_stats* stats);
 
+/* Radiance queries: the light arriving along the caller's own rays, estimated by whole paths, in batches (what an OptiX user does
+ * with a raygen program of their own: irradiance and light probes, lightmap texels, cameras the library does not know, foveated or
+ * importance-driven pixel sets, radiance fields with the tensors left on the device). A radiance query is a camera path of rtw_render
+ * whose camera ray is replaced: everything after the camera ray - traversal (media included), closest-hit and miss programs, light
+ * sampling with its shadow probe, removeNaNs, Russian roulette - is rtw_render's, operation for operation.
+ *   Rays: `rays` holds n*8 floats in rtw_cast's layout (ox, oy, oz, dx, dy, dz, tmin, tmax); directions of any length. tmin and tmax
+ *     bound the FIRST segment only; later segments use the estimator's own start distance (1e-6, or 1e-3 for estimators other than
+ *     RTW_EST_REFERENCE) and 1e27f, as a render does. A first segment that finds nothing inside (tmin, tmax) is a miss (sky or black).
+ *   Draws: sample s of ray i consumes exactly what a perspective camera path of rtw_render consumes for the pixel with stream key
+ *     k = key_offset + i (mod 2^32; a render's key is width*y + x) and sample index sample_offset + s. Philox: block (k, sample, 0, 0),
+ *     whose words 0-3 (jitter, lens) are drawn and unused and whose low bytes give the gather-time draw, then stream 1 from draw 0 and
+ *     ray times from stream 2. TEA+LCG: tea<64>(k, sample), four LCG draws discarded, the path's two generator words, then the
+ *     gather-time draw. Gather time and ray times span the uploaded scene's camera.time0 / time1.
+ *     Hence: a scene whose header carries ray i as a perspective camera with horizontal = vertical = 0 and lens_radius = 0 (origin = o,
+ *     lower_left with lower_left - o = d in float32), rendered by rtw_render at a pixel with stream key k, gives ray i's result, bit for bit.
+ *   Output: rgba_out[i] = the sum of the samples' radiance in the summation order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from
+ *     sample_offset, divided by (float)spp, alpha 1.0f. The result for ray i depends on its ray, its key and the params alone: not on
+ *     n, the launch geometry, how the batch is cut into chunks or ranges, or tuning knobs.
+ *   rtw_radiance: host pointers. The rays are staged through a slab the context keeps and grows, in chunks of at most
+ *     RTW_RADIANCE_CHUNK rays (an environment variable read per call, csrc/rtw_plan.h); chunk c runs with the key of its first ray.
+ *   rtw_radiance_device: device pointers on the context's device, both 16-byte aligned. Ordered on hip_stream exactly as
+ *     rtw_cast_device is; returns when the results are written. NULL selects the context's own non-blocking stream, NOT the legacy
+ *     default stream: a caller whose rays are still being written on stream 0 passes hipStreamLegacy, or a stream of its own, or
+ *     synchronises first. Persistent launches: the grid is what the device holds at once, waves take jobs of consecutive (ray,
+ *     128-sample unit) pairs from a queue. Calls of at most 128 spp write the means directly; longer ones keep one 16-byte sum per ray
+ *     and unit in a scratch slab of the context (n * ceil(spp / 128) * 16 B, capped by RTW_RADIANCE_SLAB_BYTES: a larger batch runs as
+ *     consecutive ray ranges) and add them in order. It allocates nothing per call once the context's scratch is large enough.
+ *   Groups (n_devices > 1): the query runs on device_ids[0], as rtw_render_guides does; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   stats (may be NULL): samples = n*spp, segments and shadow_rays as counted by the kernel (a render's counts of the same paths),
+ *     seconds = device time from the call's first event to its last, algorithmic_bytes = 128*segments + 32*samples; the per-kernel
+ *     arrays are 0.
+ *   Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for NULL params, spp <= 0, max_depth < 0, a bad rng_kind or
+ *     estimator, sample_offset < 0 or sample_offset + spp > INT32_MAX, reserved != 0, n > 2^31 - 1, with n > 0 a NULL rays or output,
+ *     and (rtw_radiance_device) a misaligned rays or output. n = 0 is RTW_OK and launches nothing. The context stays usable after an
+ *     error. */
+typedef struct rtw_radiance_params {
+    int32_t spp;            /* samples per ray, > 0                                          */
+    int32_t max_depth;      /* as rtw_params.max_depth (0: every ray returns 0)              */
+    uint32_t seed;
+    int32_t rng_kind;       /* rtw_rng_kind                                                  */
+    int32_t sample_offset;  /* first sample index; sample_offset + spp <= INT32_MAX          */
+    int32_t estimator;      /* rtw_estimator                                                 */
+    uint32_t key_offset;    /* ray i draws from the stream of "pixel" key_offset + i (mod 2^32) */
+    uint32_t reserved;      /* 0, else RTW_ERR_INVALID_ARG                                   */
+} rtw_radiance_params;      /* 32 B */
+
+int rtw_radiance(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_params* params, float* rgba_out, rtw_stats* stats);
+int rtw_radiance_device(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_params* params, void* d_rgba, void* hip_stream,
+                        rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

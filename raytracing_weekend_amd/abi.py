@@ -115,10 +115,17 @@ class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("prim", C.c_void_p), ("material", C.c_void_p), ("normal", C.c_void_p), ("uv", C.c_void_p)]
 
 
+class RadianceParams(C.Structure):
+    """rtw_radiance_params (include/rtw.h): the sampling of rtw_radiance / rtw_radiance_device."""
+    _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint32), ("rng_kind", C.c_int32),
+                ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("key_offset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
-               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device"]
+               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
+               "rtw_radiance", "rtw_radiance_device"]
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
 CAST_OUTPUTS = {"t": (np.float32, ()), "prim": (np.int32, ()), "material": (np.int32, ()), "normal": (np.float32, (4,)), "uv": (np.float32, (2,))}
@@ -201,6 +208,11 @@ def load_hip():
         lib.rtw_cast_device.restype = C.c_int
         lib.rtw_cast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Hits), C.c_void_p,
                                         C.POINTER(Stats)]
+        lib.rtw_radiance.restype = C.c_int
+        lib.rtw_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_radiance_device.restype = C.c_int
+        lib.rtw_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -276,6 +288,13 @@ def make_params(width, height, spp, max_depth, seed=0x6314759, row0=0, row1=None
     p.row_stride = row_stride
     p.estimator = estimator
     return p
+
+
+def make_radiance_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0):
+    """rtw_radiance_params; spp must be a positive integer (the library checks the rest)."""
+    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp <= 0:
+        raise ValueError(f"radiance: spp = {spp!r}, expected a positive integer")
+    return RadianceParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, 0)
 
 
 def local_rows(params):
@@ -472,6 +491,30 @@ class Renderer:
         self._check(self.lib.rtw_cast_device(self.ctx, C.c_void_p(rays_ptr), C.c_void_p(ray_time_ptr), C.c_void_p(gather_time_ptr), n,
                                              CAST_MODES[mode], C.byref(h), C.c_void_p(stream_ptr),
                                              None if stats is None else C.byref(stats)), "rtw_cast_device")
+
+    # ---- path-traced radiance along the caller's own rays (include/rtw.h rtw_radiance / rtw_radiance_device)
+    def radiance(self, rays, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, stats=None):
+        """rtw_radiance on (n, 8) float32 rays (origin, direction, tmin, tmax: tmin and tmax bound the first segment): the (n, 4)
+        float32 mean radiance of spp paths along every ray, alpha 1. Ray i draws from the stream of key_offset + i, samples
+        sample_offset ... sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
+        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32:
+            raise ValueError("radiance: rays must be a float32 numpy array")
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"radiance: rays of shape {rays.shape}, expected (n, 8)")
+        rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
+        rays = np.ascontiguousarray(rays)
+        out = np.empty((rays.shape[0], 4), dtype=np.float32)
+        self._check(self.lib.rtw_radiance(self.ctx, rays.ctypes.data, rays.shape[0], C.byref(rp), out.ctypes.data,
+                                          None if stats is None else C.byref(stats)), "rtw_radiance")
+        return out
+
+    def radiance_device(self, n, rays_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
+                        key_offset=0, stream_ptr=0, stats=None):
+        """rtw_radiance_device on raw device pointers, as cast_device takes them: n rays at rays_ptr, n float4 means written at out_ptr
+        (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
+        rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
+        self._check(self.lib.rtw_radiance_device(self.ctx, C.c_void_p(rays_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
+                                                 None if stats is None else C.byref(stats)), "rtw_radiance_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

@@ -55,11 +55,14 @@
 #include "rtw_kernels.h"
 #include "rtw_guides.h"
 #include "rtw_cast.h"
+#include "rtw_radiance.h"
+#include "rtw_radiance_plan.h"
 #include "rtw_adaptive.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
 #include "rtw_cast.hip"    // (likewise)
+#include "rtw_radiance.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -163,6 +166,13 @@ struct rtw_ctx {
     // rtw_cast's staging (the host variant): one allocation of cast_rays rays' inputs and outputs, grown on demand, kept until rtw_destroy
     void* cast_buf = nullptr;
     size_t cast_rays = 0;
+    // rtw_radiance's scratch, grown on demand and kept until rtw_destroy: the unit sums [unit][ray] of calls beyond 128 spp, the host
+    // variant's staging (rad_rays rays and their means) and the control words (kStatRows rows of 8 counters, then the queue word)
+    void* rad_slab = nullptr;
+    size_t rad_slab_bytes = 0;
+    void* rad_stage = nullptr;
+    size_t rad_rays = 0;
+    unsigned long long* rad_ctl = nullptr;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
 
@@ -480,6 +490,9 @@ int impl_destroy(rtw_ctx* c) {
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->cast_buf) (void)hipFree(c->cast_buf);
+    if (c->rad_slab) (void)hipFree(c->rad_slab);
+    if (c->rad_stage) (void)hipFree(c->rad_stage);
+    if (c->rad_ctl) (void)hipFree(c->rad_ctl);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2037,6 +2050,169 @@ int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float*
     return RTW_OK;
 }
 
+// ---- rtw_radiance / rtw_radiance_device (rtw.h): whole paths along the caller's rays through k_radiance
+typedef void (*RadianceKernel)(const DScene, const RadianceArgs);
+
+// launch()'s rule: generator x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator)
+RadianceKernel radiance_kernel(int rng_kind, int feat) {
+#define RTW_RK(R_) (feat == 2 ? k_radiance<R_, 2> : feat == 1 ? k_radiance<R_, 1> : k_radiance<R_, 0>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(RTW_RNG_TEA_LCG) : RTW_RK(RTW_RNG_PHILOX);
+#undef RTW_RK
+}
+
+// the checks the two variants share (c: the context the caller holds; a group's has_scene covers its devices)
+int radiance_check(rtw_ctx* c, const char* what, const float* rays, size_t n, const rtw_radiance_params* RP, const void* out) {
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, std::string(what) + " before rtw_upload_scene");
+    if (!RP) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null params");
+    if (RP->spp <= 0 || RP->max_depth < 0) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad spp or max_depth");
+    if (RP->rng_kind != RTW_RNG_PHILOX && RP->rng_kind != RTW_RNG_TEA_LCG) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad rng_kind");
+    if (RP->estimator < RTW_EST_REFERENCE || RP->estimator > RTW_EST_MIXTURE) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad estimator");
+    if (RP->sample_offset < 0 || (int64_t)RP->sample_offset + (int64_t)RP->spp > (int64_t)INT32_MAX)
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": sample_offset + spp beyond INT32_MAX");
+    if (RP->reserved != 0u) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": reserved must be 0");
+    if (n > 0x7fffffffull) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": more than 2^31 - 1 rays");
+    if (n > 0 && (!rays || !out)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null rays or output");
+    return RTW_OK;
+}
+
+int radiance_ctl(rtw_ctx* c, rtw_ctx* d) {
+    if (!d->rad_ctl) HIP_TRY(c, hipMalloc((void**)&d->rad_ctl, (kStatRows * 8 + 2) * sizeof(unsigned long long)));
+    return RTW_OK;
+}
+
+// n rays at d_rays (device) -> their means at d_out, issued on stream s of device context d and not waited for: one k_radiance launch
+// per ray range (rtw_radiance_plan.h: all the rays unless the unit-sum slab would pass its cap), ray i on the stream of key_offset + i.
+// The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
+int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_rays, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
+                   float4* d_out, hipStream_t s) {
+    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    if (RP->max_depth == 0) {  // no segment is traced: every mean is 0
+        hipLaunchKernelGGL(k_radiance_resolve, dim3(pixel_grid(d, n)), dim3(kBlock), 0, s, (const float4*)nullptr, d_out, (uint32_t)n, 0u, (float)RP->spp);
+        HIP_TRY(c, hipGetLastError());
+        return RTW_OK;
+    }
+    DScene sc = d->sc;
+    if (RP->estimator != RTW_EST_REFERENCE) {  // render_args' override: the corrected estimators live in the cold-feature instantiations
+        sc.estimator = RP->estimator; sc.has_tex = RP->estimator == RTW_EST_MIXTURE ? 2 : 1;
+        sc.ray_tmin = 1.0e-3f; sc.probe_eps = 1.0e-3f;
+    }
+    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex);
+    const size_t lds = d->info.lds_bytes;
+    int nb = 0;
+    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
+    // workgroups per CU: what the query admits, capped and defaulted as cast_launch does (any grid computes the same)
+    const size_t per_cu = (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
+    const uint32_t units = radiance_units(RP->spp);
+    const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
+    if (units > 1) {
+        const uint64_t need = radiance_slab_bytes(per, RP->spp);
+        if (need > d->rad_slab_bytes) {
+            HIP_TRY(c, hipStreamSynchronize(s));
+            if (d->rad_slab) (void)hipFree(d->rad_slab);
+            d->rad_slab = nullptr; d->rad_slab_bytes = 0;
+            HIP_TRY(c, hipMalloc(&d->rad_slab, (size_t)need));
+            d->rad_slab_bytes = (size_t)need;
+        }
+    }
+    for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
+        const RadianceRange rg = radiance_range(n, per, r);
+        RadianceArgs a{};
+        a.rays = (const float4*)d_rays + 2 * rg.first;
+        a.out = units > 1 ? (float4*)d->rad_slab : d_out + rg.first;
+        a.queue = queue;
+        a.stats = d->rad_ctl;
+        a.n = (uint32_t)rg.count; a.units_per_ray = units; a.n_units = (uint32_t)(rg.count * units);
+        const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
+        a.job_units = radiance_job_units(RP->spp, a.n_units, grid * (kBlock / 64));
+        a.n_jobs = (uint32_t)radiance_n_jobs(a.n_units, a.job_units);
+        magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
+        a.spp = (uint32_t)RP->spp; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
+        a.key0 = radiance_key(key_offset, rg.first);
+        HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+        HIP_TRY(c, hipGetLastError());
+        if (units > 1) {
+            hipLaunchKernelGGL(k_radiance_resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first, a.n, units,
+                               (float)RP->spp);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    return RTW_OK;
+}
+
+// after the call's last event: the counters of the rows and the device time
+int radiance_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, size_t n, const rtw_radiance_params* RP, hipEvent_t ev[2]) {
+    if (!stats) return RTW_OK;
+    unsigned long long rows_[kStatRows * 8];
+    HIP_TRY(c, hipMemcpy(rows_, d->rad_ctl, sizeof rows_, hipMemcpyDeviceToHost));
+    memset(stats, 0, sizeof *stats);
+    for (uint32_t r = 0; r < kStatRows; r++) { stats->segments += rows_[r * 8]; stats->shadow_rays += rows_[r * 8 + 1]; }
+    stats->samples = (uint64_t)n * (uint64_t)RP->spp;
+    stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    stats->seconds = (double)ms * 1e-3;
+    return RTW_OK;
+}
+
+int impl_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = radiance_check(c, "rtw_radiance_device", rays, n, RP, d_rgba);
+    if (rc) return rc;
+    if (n > 0 && (((uintptr_t)rays & 15) || ((uintptr_t)d_rgba & 15)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_radiance_device: rays and the output must be 16-byte aligned");
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    if ((rc = radiance_issue(c, d, read_tuning(), rays, n, RP, RP->key_offset, (float4*)d_rgba, s)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    return radiance_stats(c, d, stats, n, RP, ev);
+}
+
+int impl_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, float* rgba_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = radiance_check(c, "rtw_radiance", rays, n, RP, rgba_out);
+    if (rc) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const Tuning tune = read_tuning();
+    const size_t chunk = std::min(n, tune.radiance_chunk);
+    // the staging slab: per ray 32 B of ray and 16 B of mean, both sections 256-byte aligned
+    if (chunk > d->rad_rays) {
+        if (d->rad_stage) (void)hipFree(d->rad_stage);
+        d->rad_stage = nullptr; d->rad_rays = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, ((chunk * 32 + 255) & ~(size_t)255) + chunk * 16));
+        d->rad_rays = chunk;
+    }
+    float* const st_rays = (float*)d->rad_stage;
+    float4* const st_out = (float4*)((char*)d->rad_stage + ((d->rad_rays * 32 + 255) & ~(size_t)255));
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        HIP_TRY(c, hipMemcpyAsync(st_rays, rays + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
+        // chunk c runs with the key of its first ray: the bits do not depend on the chunk size
+        if ((rc = radiance_issue(c, d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, d->stream)) != RTW_OK) return rc;
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
+    }
+    return radiance_stats(c, d, stats, n, RP, ev);
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -2109,6 +2285,12 @@ int rtw_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float* 
 int rtw_cast_device(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
                     void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_cast_device(c, rays, ray_time, gather_time, n, mode, out, hip_stream, stats); });
+}
+int rtw_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, float* rgba_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_radiance(c, rays, n, RP, rgba_out, stats); });
+}
+int rtw_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_radiance_device(c, rays, n, RP, d_rgba, hip_stream, stats); });
 }
 
 }  // extern "C"

@@ -1,0 +1,167 @@
+"""CPU suite of the radiance queries (include/rtw.h rtw_radiance / rtw_radiance_device): the additive ABI, the Python surface's
+argument handling, radiance_ref.py (the oracle as the referee of a user ray) on the oracle alone, and the launch planning of
+csrc/rtw_radiance_plan.h under the sanitizers."""
+import ast
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+import radiance_ref as R
+from raytracing_weekend_amd import abi
+
+
+# ---------------------------------------------------------------- ABI
+def header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(abi.REPO_DIR, "include", "rtw.h")).read(), flags=re.S)
+
+
+def test_header_declares_both_entry_points_and_the_struct():
+    text = " ".join(header().split())
+    assert ("int rtw_radiance(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_params* params, float* rgba_out, "
+            "rtw_stats* stats);") in text
+    assert ("int rtw_radiance_device(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_params* params, void* d_rgba, "
+            "void* hip_stream, rtw_stats* stats);") in text
+    fields = re.search(r"typedef struct rtw_radiance_params \{(.*?)\} rtw_radiance_params;", text).group(1)
+    decl = [f.split() for f in fields.split(";") if f.strip()]
+    assert [d[-1] for d in decl] == ["spp", "max_depth", "seed", "rng_kind", "sample_offset", "estimator", "key_offset", "reserved"]
+    assert [d[0] for d in decl] == ["int32_t", "int32_t", "uint32_t", "int32_t", "int32_t", "int32_t", "uint32_t", "uint32_t"]
+    assert "#define RTW_ABI_VERSION 5" in text  # additive: the version and the older structs stay
+
+
+def test_params_mirror_the_struct_and_the_older_structs_keep_their_sizes():
+    assert C.sizeof(abi.RadianceParams) == 32
+    assert [f for f, _ in abi.RadianceParams._fields_] == ["spp", "max_depth", "seed", "rng_kind", "sample_offset", "estimator", "key_offset", "reserved"]
+    assert abi.RTW_ABI_VERSION == 5 and C.sizeof(abi.Stats) == 184 and C.sizeof(abi.Params) == 48 and C.sizeof(abi.Hits) == 40
+
+
+def test_symbols_are_listed_and_exported():
+    assert "rtw_radiance" in abi.HIP_SYMBOLS and "rtw_radiance_device" in abi.HIP_SYMBOLS
+    lib = abi.load_hip()
+    assert hasattr(lib, "rtw_radiance") and hasattr(lib, "rtw_radiance_device") and lib.rtw_abi_version() == 5
+
+
+def test_null_context_is_an_error_not_a_crash():
+    lib = abi.load_hip()
+    rays, out = np.zeros((4, 8), np.float32), np.zeros((4, 4), np.float32)
+    rp = abi.make_radiance_params(4, 4)
+    for n in (0, 4):
+        assert lib.rtw_radiance(None, rays.ctypes.data, n, C.byref(rp), out.ctypes.data, None) < 0
+        assert lib.rtw_radiance_device(None, rays.ctypes.data, n, C.byref(rp), out.ctypes.data, None, None) < 0
+    assert lib.rtw_radiance(None, None, 0, None, None, None) < 0
+    assert not out.any()
+
+
+def test_the_knobs_are_listed_with_the_others():
+    plan = open(os.path.join(abi.PKG_DIR, "csrc", "rtw_plan.h")).read()
+    for knob in ("RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES"):
+        assert re.search(r"//\s+" + knob + r"\s", plan) and f'geti("{knob}"' in plan
+
+
+def test_the_kernel_is_a_unit_of_the_build_with_the_common_flags():
+    entry = open(os.path.join(abi.REPO_DIR, "__graft_entry__.py")).read()
+    assert '("rtw_radiance.hip", "rtw_radiance.o", [])' in entry and '"rtw_radiance.hip"' not in entry.split("UNIT_FLAGS = ")[1].split("\n")[0]
+    assert '"-ffp-contract=off"' in entry.split("HIP_FLAGS = ")[1].split("]")[0]
+    hip = open(os.path.join(abi.PKG_DIR, "csrc", "rtw_hip.hip")).read()
+    assert '#include "rtw_radiance.hip"' in hip.split("#ifndef RTW_SPLIT_BUILD")[1].split("#endif")[0]  # the single-file variant build
+    assert hip.count("return guarded(c, [&] { return impl_radiance") == 2
+
+
+# ---------------------------------------------------------------- the Python surface
+class NoLibrary:
+    """A Renderer that must refuse before it reaches the library."""
+    ctx = None
+
+    class lib:
+        @staticmethod
+        def rtw_radiance(*a):
+            raise AssertionError("the library was called")
+
+
+def test_python_side_argument_validation():
+    call = abi.Renderer.radiance
+    good = np.zeros((5, 8), np.float32)
+    for rays in (np.zeros((5, 7), np.float32), np.zeros(8, np.float32), np.zeros((5, 8, 1), np.float32),  # shape
+                 np.zeros((5, 8), np.float64), np.zeros((5, 8), np.int32), [[0.0] * 8]):                   # dtype
+        with pytest.raises(ValueError):
+            call(NoLibrary, rays, 4, 4)
+    for spp in (0, -3, 1.5, None, True):
+        with pytest.raises(ValueError):
+            call(NoLibrary, good, spp, 4)
+    rp = abi.make_radiance_params(7, 3, seed=9, rng_kind=1, sample_offset=16, estimator=2, key_offset=2 ** 32 - 3)
+    assert (rp.spp, rp.max_depth, rp.seed, rp.rng_kind, rp.sample_offset, rp.estimator, rp.key_offset, rp.reserved) == (7, 3, 9, 1, 16, 2, 2 ** 32 - 3, 0)
+
+
+def test_torch_is_imported_inside_the_function_only():
+    tree = ast.parse(open(os.path.join(abi.PKG_DIR, "torch_radiance.py")).read())
+    top = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+    names = {a.name.split(".")[0] for n in top if isinstance(n, ast.Import) for a in n.names} | {(n.module or "").split(".")[0] for n in top if isinstance(n, ast.ImportFrom)}
+    assert "torch" not in names
+    from raytracing_weekend_amd import torch_radiance
+    assert callable(torch_radiance.radiance_torch)
+
+
+# ---------------------------------------------------------------- radiance_ref on the oracle alone
+def test_make_rays_carries_the_camera_rays_bits():
+    o = np.array([[278.0, 273.0, -800.0], [0.1, 0.2, 0.3]], np.float32)
+    ll = np.array([[100.5, 33.25, 7.0], [0.30000001, -5.0, 1e-3]], np.float32)
+    r0, r1 = R.make_rays(o, ll), R.make_rays(o, ll, estimator=2)
+    assert r0.dtype == np.float32 and r0.shape == (2, 8)
+    assert np.array_equal(r0[:, :3], o) and np.array_equal(r0[:, 3:6], ll - o)
+    assert np.array_equal(r0[:, 6:], np.array([[1e-6, 1e27]] * 2, np.float32)) and np.array_equal(r1[:, 6], np.array([1e-3] * 2, np.float32))
+    blob = R.scene("scene0")
+    h0, h = abi.SceneHeader.from_buffer_copy(blob[:R._HDR]), abi.SceneHeader.from_buffer_copy(R.ray_blob(blob, o[1], ll[1])[:R._HDR])
+    assert list(h.camera.origin) == list(o[1]) and list(h.camera.lower_left) == list(ll[1])
+    assert not any(h.camera.horizontal) and not any(h.camera.vertical) and h.camera.lens_radius == 0.0 and h.camera_type == 0
+    assert (h.camera.time0, h.camera.time1) == (h0.camera.time0, h0.camera.time1) and R.ray_blob(blob, o[1], ll[1])[R._HDR:] == blob[R._HDR:]
+
+
+@pytest.mark.parametrize("rng_kind", [abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG])
+def test_expect_is_trace_pixel_per_sample_summed_in_block_order(rng_kind):
+    """One ray at spp 48 (three blocks): the rendered one-pixel frame equals the per-sample radiances summed in float32 in block
+    order and divided - also with the samples taken at the 65536-wide addressing of the same key, the route of keys from 2^31 - 1 on."""
+    blob = R.scene("scene0")
+    o, ll = R.pairs(blob, R.N)
+    i, key = 2, 77
+    pix, seg, shadow = R.expect(blob, o[i:i + 1], ll[i:i + 1], 48, 8, rng_kind=rng_kind, key_offset=key)
+    assert pix.shape == (1, 4) and pix[0, 3] == 1.0 and seg >= 48 and shadow >= 0
+    lib = oracle.load()
+    rb = R.ray_blob(blob, o[i], ll[i])
+    p = abi.make_params(1, key + 1, 48, 8, rng_kind=rng_kind, row0=key, row1=key + 1)
+    smp = np.zeros((48, 3), np.float32)
+    for s in range(48):
+        assert lib.rtwo_trace_pixel(rb, len(rb), C.byref(p), 0, key, s, smp[s].ctypes.data) == 0
+    assert smp.any()
+    assert np.array_equal(R.sum_in_order(smp, 48).view(np.uint32), pix[0, :3].view(np.uint32))
+    assert np.array_equal(R.trace_samples(blob, o[i], ll[i], key, 48, 8, 0x6314759, rng_kind, 0, 0).view(np.uint32), smp.view(np.uint32))
+    # a second unit and a sample offset: spp 144 from sample 16 on
+    pix2, _, _ = R.expect(blob, o[i:i + 1], ll[i:i + 1], 144, 4, rng_kind=rng_kind, key_offset=key, sample_offset=16)
+    smp2 = R.trace_samples(blob, o[i], ll[i], key, 144, 4, 0x6314759, rng_kind, 16, 0)
+    assert np.array_equal(R.sum_in_order(smp2, 144).view(np.uint32), pix2[0, :3].view(np.uint32))
+
+
+def test_keys_beyond_a_one_pixel_wide_image_have_pixels_but_no_counts():
+    blob = R.scene("scene0")
+    o, ll = R.pairs(blob, 4)
+    pix, seg, shadow = R.expect(blob, o, ll, 4, 4, key_offset=2 ** 32 - 2)  # keys 2^32 - 2, 2^32 - 1, 0, 1
+    assert seg is None and shadow is None and np.isfinite(pix).all() and (pix[:, 3] == 1.0).all()
+    small, seg2, _ = R.expect(blob, o[2:], ll[2:], 4, 4, key_offset=0)
+    assert seg2 >= 8 and np.array_equal(small.view(np.uint32), pix[2:].view(np.uint32))
+
+
+def test_special_origins_lie_inside_the_glass_and_the_media():
+    assert len(R.special_origins(R.scene("scene0"))) >= 1 and len(R.special_origins(R.scene("scene3"))) >= 2
+    assert len(R.special_origins(R.scene("random_volumes_motion"))) >= 2
+
+
+# ---------------------------------------------------------------- the planning header, under the sanitizers
+def test_plan_header_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "radiance_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                           "-Werror", "-o", exe, os.path.join(abi.REPO_DIR, "tests", "native", "radiance_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "radiance_check ok" in out.stdout, out.stdout + out.stderr[-2000:]

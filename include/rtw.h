@@ -546,6 +546,61 @@ int rtw_radiance(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_p
 int rtw_radiance_device(rtw_ctx* ctx, const float* rays, size_t n, const rtw_radiance_params* params, void* d_rgba, void* hip_stream,
                         rtw_stats* stats);
 
+/* Probes: irradiance and ambient occlusion at surface points, integrated by the library (what a lightmap baker, an irradiance cache
+ * or an ambient-occlusion pass calls). rtw_cast and rtw_radiance take one fixed ray per index; a probe takes a different direction
+ * for every sample, drawn on the device from the sample's own random stream.
+ *   Probes: `probes` holds n*8 floats (px, py, pz, nx, ny, nz, tmin, tmax): rtw_cast's ray layout with the normal (any non-zero
+ *     length) in the direction's place, so a tensor built from rtw_cast's hit points and normals is a probe tensor.
+ *   Direction: for sample s of probe i take the stream key k = key_offset + i (mod 2^32) and the sample index S = sample_offset + s.
+ *     r1 and r2 are the first two raygen uniforms of that path, the ones rtw_radiance consumes and drops - Philox: the 24-bit
+ *     uniforms of words 0 and 1 of block (k, S, 0, 0) under key (seed, 0); TEA+LCG: the first two lcg_rnd values of tea<64>(k, S).
+ *     The direction is the Lambertian material's own basis and lobe in its corrected (cosine-weighted) form, operation for operation
+ *     as the closest-hit code writes it:
+ *       w = normalize3(n); a = (w.x > 0.9f || w.x < -0.9f) ? (0,1,0) : (1,0,0); v = normalize3(cross3(w, a)); u = cross3(w, v);
+ *       sincos2pi(r1, sn, cs); sq = sqrt(r2); lx = cs * sq; ly = sn * sq; lz = sqrt(1 - r2);
+ *       d = normalize3(fma(lz, w, fma(ly, v, lx * u)))
+ *     whichever estimator is chosen (the stray factor 2 of the reference estimator is not part of a probe). A degenerate normal
+ *     gives whatever the equivalent ray gives: there is no special case.
+ *   RTW_PROBE_IRRADIANCE: the sample's value is the radiance of the rtw_radiance sample of ray (p, d, tmin, tmax) at key k, sample
+ *     index S and the same seed, generator, estimator and max_depth: the path after the first direction, its draws, media, light
+ *     sampling, removeNaNs and roulette are unchanged. rgb = (sum / (float)spp) * 3.14159265f, alpha 1.0f, the sum taken in the
+ *     order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from sample_offset. The density is cos / pi, so this is the irradiance.
+ *     max_depth = 0 gives zeros. stats: samples = n*spp, segments and shadow_rays as the kernel counts them, algorithmic_bytes and
+ *     seconds as rtw_radiance reports them.
+ *   RTW_PROBE_OCCLUSION: sample s is unoccluded when RTW_CAST_ANY finds nothing for ray (p, d, tmin, tmax) with NULL ray and gather
+ *     times (volumes are skipped, as in rtw_cast). rgb = (float)unoccluded / (float)spp in all three channels, alpha 1.0f: an
+ *     integer count, so no summation order is involved; counts are combined with integer arithmetic only. max_depth and estimator
+ *     are validated but unused. stats: samples = shadow_rays = n*spp, segments = 0, seconds as above.
+ *   The result for probe i depends on its probe, its key and the params alone: not on n, the launch geometry, how the batch is cut
+ *     into chunks or ranges, or tuning knobs.
+ *   rtw_probe: host pointers, staged as rtw_radiance stages its rays (the same slab, in chunks of at most RTW_RADIANCE_CHUNK probes;
+ *     chunk c runs with the key of its first probe).
+ *   rtw_probe_device: device pointers on the context's device, both 16-byte aligned. Ordered on hip_stream exactly as
+ *     rtw_radiance_device is; returns when the results are written. NULL selects the context's own non-blocking stream, NOT the
+ *     legacy default stream. Calls beyond 128 spp keep their unit sums (or unit counts) in rtw_radiance's scratch slab, capped by
+ *     RTW_RADIANCE_SLAB_BYTES in the same way: a larger batch runs as consecutive probe ranges.
+ *   Groups (n_devices > 1): the query runs on device_ids[0]; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   Errors: rtw_radiance's list (RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for NULL params, spp <= 0, max_depth < 0, a
+ *     bad rng_kind or estimator, sample_offset < 0 or sample_offset + spp > INT32_MAX, n > 2^31 - 1, with n > 0 a NULL probes or
+ *     output, and (rtw_probe_device) a misaligned probes or output) and a mode other than the two. A refused call writes nothing and
+ *     leaves *stats alone. n = 0 is RTW_OK and launches nothing. The context stays usable after an error. */
+enum { RTW_PROBE_IRRADIANCE = 0, RTW_PROBE_OCCLUSION = 1 };
+typedef struct rtw_probe_params {
+    int32_t spp;            /* samples per probe, > 0                                        */
+    int32_t max_depth;      /* as rtw_radiance_params.max_depth (irradiance only)            */
+    uint32_t seed;
+    int32_t rng_kind;       /* rtw_rng_kind                                                  */
+    int32_t sample_offset;  /* first sample index; sample_offset + spp <= INT32_MAX          */
+    int32_t estimator;      /* rtw_estimator (irradiance only)                               */
+    uint32_t key_offset;    /* probe i draws from the stream of key_offset + i (mod 2^32)    */
+    int32_t mode;           /* RTW_PROBE_IRRADIANCE or RTW_PROBE_OCCLUSION                   */
+} rtw_probe_params;         /* 32 B */
+
+int rtw_probe(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_params* params, float* rgba_out, rtw_stats* stats);
+int rtw_probe_device(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_params* params, void* d_rgba, void* hip_stream,
+                     rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

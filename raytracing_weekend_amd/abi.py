@@ -121,11 +121,18 @@ class RadianceParams(C.Structure):
                 ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("key_offset", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ProbeParams(C.Structure):
+    """rtw_probe_params (include/rtw.h): the sampling and the mode of rtw_probe / rtw_probe_device."""
+    _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint32), ("rng_kind", C.c_int32),
+                ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("key_offset", C.c_uint32), ("mode", C.c_int32)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
                "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
-               "rtw_radiance", "rtw_radiance_device"]
+               "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device"]
+PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
 CAST_OUTPUTS = {"t": (np.float32, ()), "prim": (np.int32, ()), "material": (np.int32, ()), "normal": (np.float32, (4,)), "uv": (np.float32, (2,))}
@@ -213,6 +220,10 @@ def load_hip():
         lib.rtw_radiance_device.restype = C.c_int
         lib.rtw_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats)]
+        lib.rtw_probe.restype = C.c_int
+        lib.rtw_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_probe_device.restype = C.c_int
+        lib.rtw_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -295,6 +306,15 @@ def make_radiance_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX
     if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp <= 0:
         raise ValueError(f"radiance: spp = {spp!r}, expected a positive integer")
     return RadianceParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, 0)
+
+
+def make_probe_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, mode="irradiance"):
+    """rtw_probe_params; spp must be a positive integer and mode "irradiance" or "occlusion" (the library checks the rest)."""
+    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp <= 0:
+        raise ValueError(f"probe: spp = {spp!r}, expected a positive integer")
+    if mode not in PROBE_MODES:
+        raise ValueError(f"probe: mode {mode!r} is neither 'irradiance' nor 'occlusion'")
+    return ProbeParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, PROBE_MODES[mode])
 
 
 def local_rows(params):
@@ -515,6 +535,32 @@ class Renderer:
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
         self._check(self.lib.rtw_radiance_device(self.ctx, C.c_void_p(rays_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                                  None if stats is None else C.byref(stats)), "rtw_radiance_device")
+
+    # ---- irradiance and ambient occlusion at surface points (include/rtw.h rtw_probe / rtw_probe_device)
+    def probe(self, probes, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
+              mode="irradiance", stats=None):
+        """rtw_probe on (n, 8) float32 probes (position, normal, tmin, tmax): the (n, 4) float32 result of spp samples per probe, alpha
+        1 - mode "irradiance": the irradiance (cosine-weighted paths, mean radiance times pi); mode "occlusion": the fraction of the
+        same directions that reach tmax unoccluded, in all three channels. Probe i draws from the stream of key_offset + i, samples
+        sample_offset ... sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
+        if not isinstance(probes, np.ndarray) or probes.dtype != np.float32:
+            raise ValueError("probe: probes must be a float32 numpy array")
+        if probes.ndim != 2 or probes.shape[1] != 8:
+            raise ValueError(f"probe: probes of shape {probes.shape}, expected (n, 8)")
+        pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
+        probes = np.ascontiguousarray(probes)
+        out = np.empty((probes.shape[0], 4), dtype=np.float32)
+        self._check(self.lib.rtw_probe(self.ctx, probes.ctypes.data, probes.shape[0], C.byref(pp), out.ctypes.data,
+                                       None if stats is None else C.byref(stats)), "rtw_probe")
+        return out
+
+    def probe_device(self, n, probes_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
+                     key_offset=0, mode="irradiance", stream_ptr=0, stats=None):
+        """rtw_probe_device on raw device pointers, as radiance_device takes them: n probes at probes_ptr, n float4 results written at
+        out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
+        pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
+        self._check(self.lib.rtw_probe_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
+                                              None if stats is None else C.byref(stats)), "rtw_probe_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

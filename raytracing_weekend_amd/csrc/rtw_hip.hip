@@ -57,12 +57,14 @@
 #include "rtw_cast.h"
 #include "rtw_radiance.h"
 #include "rtw_radiance_plan.h"
+#include "rtw_probe.h"
 #include "rtw_adaptive.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
 #include "rtw_cast.hip"    // (likewise)
 #include "rtw_radiance.hip"  // (likewise)
+#include "rtw_probe.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -2050,17 +2052,23 @@ int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float*
     return RTW_OK;
 }
 
-// ---- rtw_radiance / rtw_radiance_device (rtw.h): whole paths along the caller's rays through k_radiance
+// ---- rtw_radiance / rtw_radiance_device and rtw_probe / rtw_probe_device (rtw.h): whole paths along the caller's rays through
+// k_radiance, or from the caller's probes through k_probe / k_probe_occlusion. The two families share everything on the host but
+// the kernels: `query` says which one a call serves.
 typedef void (*RadianceKernel)(const DScene, const RadianceArgs);
+typedef void (*RadianceResolve)(const float4*, float4*, uint32_t, uint32_t, float);
+typedef void (*OcclusionKernel)(const DScene, const OcclusionArgs);
+constexpr int kQueryRadiance = -1;  // (else rtw_probe's mode: RTW_PROBE_IRRADIANCE or RTW_PROBE_OCCLUSION)
 
 // launch()'s rule: generator x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator)
-RadianceKernel radiance_kernel(int rng_kind, int feat) {
-#define RTW_RK(R_) (feat == 2 ? k_radiance<R_, 2> : feat == 1 ? k_radiance<R_, 1> : k_radiance<R_, 0>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(RTW_RNG_TEA_LCG) : RTW_RK(RTW_RNG_PHILOX);
+RadianceKernel radiance_kernel(int rng_kind, int feat, bool probe) {
+#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
+    if (probe) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe, RTW_RNG_TEA_LCG) : RTW_RK(k_probe, RTW_RNG_PHILOX);
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_radiance, RTW_RNG_TEA_LCG) : RTW_RK(k_radiance, RTW_RNG_PHILOX);
 #undef RTW_RK
 }
 
-// the checks the two variants share (c: the context the caller holds; a group's has_scene covers its devices)
+// the checks the variants share (c: the context the caller holds; a group's has_scene covers its devices)
 int radiance_check(rtw_ctx* c, const char* what, const float* rays, size_t n, const rtw_radiance_params* RP, const void* out) {
     if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, std::string(what) + " before rtw_upload_scene");
     if (!RP) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null params");
@@ -2080,11 +2088,68 @@ int radiance_ctl(rtw_ctx* c, rtw_ctx* d) {
     return RTW_OK;
 }
 
-// n rays at d_rays (device) -> their means at d_out, issued on stream s of device context d and not waited for: one k_radiance launch
-// per ray range (rtw_radiance_plan.h: all the rays unless the unit-sum slab would pass its cap), ray i on the stream of key_offset + i.
-// The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
+// the context's unit slab, at least `need` bytes: grown after the stream's pending work, which may still read the old one
+int radiance_slab(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
+    if (need <= d->rad_slab_bytes) return RTW_OK;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (d->rad_slab) (void)hipFree(d->rad_slab);
+    d->rad_slab = nullptr; d->rad_slab_bytes = 0;
+    HIP_TRY(c, hipMalloc(&d->rad_slab, (size_t)need));
+    d->rad_slab_bytes = (size_t)need;
+    return RTW_OK;
+}
+
+// workgroups per CU of a persistent launch of k: what the occupancy query admits, capped and defaulted as cast_launch does (any
+// grid computes the same)
+template <class K>
+size_t radiance_per_cu(K k, size_t lds) {
+    int nb = 0;
+    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
+    return (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
+}
+
+// RTW_PROBE_OCCLUSION: n probes at d_probes (device) -> their unoccluded fractions at d_out, issued on stream s and not waited for.
+// One k_probe_occlusion launch per probe range; the ranges are rtw_radiance_plan.h's (the counts [unit][probe] of a call beyond 128
+// spp take 4 of the 16 bytes the plan reserves per unit in the context's slab).
+int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_probes, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
+                    float4* d_out, hipStream_t s) {
+    const OcclusionKernel k = RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion<RTW_RNG_TEA_LCG> : k_probe_occlusion<RTW_RNG_PHILOX>;
+    const size_t lds = d->info.lds_bytes;
+    const size_t per_cu = radiance_per_cu(k, lds);
+    const uint32_t units = radiance_units(RP->spp);
+    const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
+    if (units > 1) {
+        const int rc = radiance_slab(c, d, radiance_slab_bytes(per, RP->spp), s);
+        if (rc != RTW_OK) return rc;
+    }
+    for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
+        const RadianceRange rg = radiance_range(n, per, r);
+        OcclusionArgs a{};
+        a.probes = (const float4*)d_probes + 2 * rg.first;
+        a.out = d_out + rg.first;
+        a.counts = (uint32_t*)d->rad_slab;
+        a.n = (uint32_t)rg.count; a.units_per_probe = units; a.n_units = (uint32_t)(rg.count * units);
+        magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
+        a.spp = (uint32_t)RP->spp; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed;
+        a.key0 = radiance_key(key_offset, rg.first);
+        const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, d->sc, a);
+        HIP_TRY(c, hipGetLastError());
+        if (units > 1) {
+            hipLaunchKernelGGL(k_probe_occlusion_resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, d_out + rg.first, a.n,
+                               units, (float)RP->spp);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    return RTW_OK;
+}
+
+// n rays (or probes) at d_rays (device) -> their means at d_out, issued on stream s of device context d and not waited for: one
+// k_radiance (k_probe) launch per ray range (rtw_radiance_plan.h: all the rays unless the unit-sum slab would pass its cap), ray i on
+// the stream of key_offset + i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
 int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_rays, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
-                   float4* d_out, hipStream_t s) {
+                   float4* d_out, hipStream_t s, int query) {
+    if (query == RTW_PROBE_OCCLUSION) return occlusion_issue(c, d, tune, d_rays, n, RP, key_offset, d_out, s);
     uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
     if (RP->max_depth == 0) {  // no segment is traced: every mean is 0
         hipLaunchKernelGGL(k_radiance_resolve, dim3(pixel_grid(d, n)), dim3(kBlock), 0, s, (const float4*)nullptr, d_out, (uint32_t)n, 0u, (float)RP->spp);
@@ -2096,23 +2161,16 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         sc.estimator = RP->estimator; sc.has_tex = RP->estimator == RTW_EST_MIXTURE ? 2 : 1;
         sc.ray_tmin = 1.0e-3f; sc.probe_eps = 1.0e-3f;
     }
-    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex);
+    const bool probe = query == RTW_PROBE_IRRADIANCE;
+    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe);
+    const RadianceResolve resolve = probe ? k_probe_resolve : k_radiance_resolve;
     const size_t lds = d->info.lds_bytes;
-    int nb = 0;
-    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
-    // workgroups per CU: what the query admits, capped and defaulted as cast_launch does (any grid computes the same)
-    const size_t per_cu = (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
+    const size_t per_cu = radiance_per_cu(k, lds);
     const uint32_t units = radiance_units(RP->spp);
     const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
     if (units > 1) {
-        const uint64_t need = radiance_slab_bytes(per, RP->spp);
-        if (need > d->rad_slab_bytes) {
-            HIP_TRY(c, hipStreamSynchronize(s));
-            if (d->rad_slab) (void)hipFree(d->rad_slab);
-            d->rad_slab = nullptr; d->rad_slab_bytes = 0;
-            HIP_TRY(c, hipMalloc(&d->rad_slab, (size_t)need));
-            d->rad_slab_bytes = (size_t)need;
-        }
+        const int rc = radiance_slab(c, d, radiance_slab_bytes(per, RP->spp), s);
+        if (rc != RTW_OK) return rc;
     }
     for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
         const RadianceRange rg = radiance_range(n, per, r);
@@ -2132,7 +2190,7 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
         HIP_TRY(c, hipGetLastError());
         if (units > 1) {
-            hipLaunchKernelGGL(k_radiance_resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first, a.n, units,
+            hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first, a.n, units,
                                (float)RP->spp);
             HIP_TRY(c, hipGetLastError());
         }
@@ -2141,26 +2199,31 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
 }
 
 // after the call's last event: the counters of the rows and the device time
-int radiance_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, size_t n, const rtw_radiance_params* RP, hipEvent_t ev[2]) {
+int radiance_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, size_t n, const rtw_radiance_params* RP, hipEvent_t ev[2], int query) {
     if (!stats) return RTW_OK;
-    unsigned long long rows_[kStatRows * 8];
-    HIP_TRY(c, hipMemcpy(rows_, d->rad_ctl, sizeof rows_, hipMemcpyDeviceToHost));
     memset(stats, 0, sizeof *stats);
-    for (uint32_t r = 0; r < kStatRows; r++) { stats->segments += rows_[r * 8]; stats->shadow_rays += rows_[r * 8 + 1]; }
     stats->samples = (uint64_t)n * (uint64_t)RP->spp;
-    stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    if (query == RTW_PROBE_OCCLUSION) {  // every sample is one occlusion ray, nothing else is traced
+        stats->shadow_rays = stats->samples;
+    } else {
+        unsigned long long rows_[kStatRows * 8];
+        HIP_TRY(c, hipMemcpy(rows_, d->rad_ctl, sizeof rows_, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < kStatRows; r++) { stats->segments += rows_[r * 8]; stats->shadow_rays += rows_[r * 8 + 1]; }
+        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    }
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
     stats->seconds = (double)ms * 1e-3;
     return RTW_OK;
 }
 
-int impl_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
-    if (!c) return RTW_ERR_INVALID_ARG;
-    int rc = radiance_check(c, "rtw_radiance_device", rays, n, RP, d_rgba);
+// the device variant of either family: `what` names the entry point in messages
+int query_device(rtw_ctx* c, const char* what, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream,
+                 rtw_stats* stats, int query) {
+    int rc = radiance_check(c, what, rays, n, RP, d_rgba);
     if (rc) return rc;
     if (n > 0 && (((uintptr_t)rays & 15) || ((uintptr_t)d_rgba & 15)))
-        return fail(c, RTW_ERR_INVALID_ARG, "rtw_radiance_device: rays and the output must be 16-byte aligned");
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": rays and the output must be 16-byte aligned");
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n == 0) return RTW_OK;
     rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
@@ -2171,15 +2234,15 @@ int impl_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radi
     if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
     HIP_TRY(c, hipEventRecord(ev[0], s));
     HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
-    if ((rc = radiance_issue(c, d, read_tuning(), rays, n, RP, RP->key_offset, (float4*)d_rgba, s)) != RTW_OK) return rc;
+    if ((rc = radiance_issue(c, d, read_tuning(), rays, n, RP, RP->key_offset, (float4*)d_rgba, s, query)) != RTW_OK) return rc;
     HIP_TRY(c, hipEventRecord(ev[1], s));
     HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return radiance_stats(c, d, stats, n, RP, ev);
+    return radiance_stats(c, d, stats, n, RP, ev, query);
 }
 
-int impl_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, float* rgba_out, rtw_stats* stats) {
-    if (!c) return RTW_ERR_INVALID_ARG;
-    int rc = radiance_check(c, "rtw_radiance", rays, n, RP, rgba_out);
+// the host variant of either family
+int query_host(rtw_ctx* c, const char* what, const float* rays, size_t n, const rtw_radiance_params* RP, float* rgba_out, rtw_stats* stats, int query) {
+    int rc = radiance_check(c, what, rays, n, RP, rgba_out);
     if (rc) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTW_OK;
@@ -2205,12 +2268,48 @@ int impl_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_pa
         const size_t m = std::min(chunk, n - i0);
         HIP_TRY(c, hipMemcpyAsync(st_rays, rays + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
         // chunk c runs with the key of its first ray: the bits do not depend on the chunk size
-        if ((rc = radiance_issue(c, d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, d->stream)) != RTW_OK) return rc;
+        if ((rc = radiance_issue(c, d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, d->stream, query)) != RTW_OK) return rc;
         if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
         HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
     }
-    return radiance_stats(c, d, stats, n, RP, ev);
+    return radiance_stats(c, d, stats, n, RP, ev, query);
+}
+
+int impl_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    return query_device(c, "rtw_radiance_device", rays, n, RP, d_rgba, hip_stream, stats, kQueryRadiance);
+}
+
+int impl_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, float* rgba_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    return query_host(c, "rtw_radiance", rays, n, RP, rgba_out, stats, kQueryRadiance);
+}
+
+// rtw_probe_params is rtw_radiance_params with the mode in the reserved word's place: the sampling fields go through
+// rtw_radiance's checks as they are, the mode through its own
+static_assert(sizeof(rtw_probe_params) == sizeof(rtw_radiance_params) && offsetof(rtw_probe_params, mode) == offsetof(rtw_radiance_params, reserved),
+              "rtw_probe_params mirrors rtw_radiance_params");
+const rtw_radiance_params* probe_sampling(const rtw_probe_params* PP, rtw_radiance_params& rp) {
+    if (!PP) return nullptr;
+    memcpy(&rp, PP, sizeof rp);
+    rp.reserved = 0u;
+    return &rp;
+}
+bool probe_mode_ok(const rtw_probe_params* PP) { return !PP || PP->mode == RTW_PROBE_IRRADIANCE || PP->mode == RTW_PROBE_OCCLUSION; }
+
+int impl_probe_device(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (c->has_scene && !probe_mode_ok(PP)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_probe_device: bad mode");
+    rtw_radiance_params rp;
+    return query_device(c, "rtw_probe_device", probes, n, probe_sampling(PP, rp), d_rgba, hip_stream, stats, PP ? PP->mode : 0);
+}
+
+int impl_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, float* rgba_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    if (c->has_scene && !probe_mode_ok(PP)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_probe: bad mode");
+    rtw_radiance_params rp;
+    return query_host(c, "rtw_probe", probes, n, probe_sampling(PP, rp), rgba_out, stats, PP ? PP->mode : 0);
 }
 
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
@@ -2291,6 +2390,12 @@ int rtw_radiance(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_par
 }
 int rtw_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_radiance_device(c, rays, n, RP, d_rgba, hip_stream, stats); });
+}
+int rtw_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, float* rgba_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_probe(c, probes, n, PP, rgba_out, stats); });
+}
+int rtw_probe_device(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_probe_device(c, probes, n, PP, d_rgba, hip_stream, stats); });
 }
 
 }  // extern "C"

@@ -1,0 +1,33 @@
+"""rtw_probe_device on torch tensors: probes in, irradiance or ambient occlusion out, everything stays on the device (include/rtw.h
+rtw_probe_device)."""
+from . import abi
+
+
+def probe_torch(renderer, probes, spp, max_depth, seed=0x6314759, rng_kind=abi.RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
+                mode="irradiance", stats=None):
+    """Irradiance (mode "irradiance") or unoccluded fraction (mode "occlusion") of an abi.Renderer at an (n, 8) float32 CUDA tensor of
+    probes (position, normal, tmin, tmax): the (n, 4) float32 tensor of spp samples per probe (alpha 1) on the probes' device,
+    allocated here, written on torch's current stream; the call returns when it is written. The tensor must be contiguous and live on
+    the renderer's device. No host copy is made. torch's default stream has the null handle, which rtw_probe_device reads as "the
+    context's own stream" - a stream that does not wait for the default stream's pending work - so under the default stream that
+    work is waited for here, before the call."""
+    import torch
+
+    if probes.dim() != 2 or probes.shape[1] != 8:
+        raise ValueError(f"probe_torch: probes of shape {tuple(probes.shape)}, expected (n, 8)")
+    n = probes.shape[0]
+    if not probes.is_cuda or probes.device.index != renderer.devices[0]:
+        raise ValueError(f"probe_torch: probes on {probes.device}, the renderer answers on cuda:{renderer.devices[0]}")
+    if probes.dtype != torch.float32 or not probes.is_contiguous():
+        raise ValueError("probe_torch: probes must be a contiguous float32 CUDA tensor")
+    abi.make_probe_params(spp, max_depth, mode=mode)  # (spp and mode are checked even when there is nothing to trace)
+    with torch.cuda.device(probes.device):
+        out = torch.empty((n, 4), dtype=torch.float32, device=probes.device)
+        stream = torch.cuda.current_stream()
+        if n and stream.cuda_stream == 0:
+            stream.synchronize()
+        if n:
+            renderer.probe_device(n, probes.data_ptr(), out.data_ptr(), spp, max_depth, seed=seed, rng_kind=rng_kind,
+                                  sample_offset=sample_offset, estimator=estimator, key_offset=key_offset, mode=mode,
+                                  stream_ptr=stream.cuda_stream, stats=stats)
+    return out

@@ -19,7 +19,7 @@ constexpr int32_t kAccumCapMax = 0x7ffffff0;                       // the larges
 // k_path stores ONE sum per summation unit where the planner picks 8-block lane units (rtw_plan.h plan_path: unit_sums), and such a
 // launch must start on a unit boundary: slot [block / 8] is then a whole unit of the render. So:
 //   head   [n_from, next unit boundary or n_to)  when n_from is inside a unit: every block's sum is stored (planned the way
-//          adaptive_path_pass plans a pass) and joins the unit the session holds open
+//          rtw_render_adaptive plans a pass) and joins the unit the session holds open
 //   body   the whole units that follow: unit sums allowed
 //   tail   [last unit boundary, n_to)  when n_to is inside a unit: block sums; the unit stays open in the session
 // every_block (sessions with RTW_ACCUM_ERROR: the moments are taken over block sums, so every block's sum must reach memory): one

@@ -24,7 +24,8 @@
 //     (rtw_accum.h) that keeps the summation unit open between adds; splitting and the saved form: rtw_accum_state.h
 //
 // render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
-// (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU).
+// (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU), through the
+// schedules they share with the adaptive renderer and the sessions (issue_path_pass, run_batches).
 // rtw_upload_scene prepares the blob once on the host (rtw_scene.h prepare_scene: validation, hit records, candidate lists, tree, one
 // staged image, likewise checked on the CPU) and copies the image to each device.
 //
@@ -595,7 +596,7 @@ KArgs shard_args(const DScene& sc, const rtw_params* P, size_t npix) {
     a.max_depth = (uint32_t)P->max_depth;
     a.stack_stride = kBlock;
     a.spp = (uint32_t)P->spp;
-    a.cull_x0 = 0; a.cull_x1 = P->width; a.cull_y0 = 0; a.cull_y1 = P->height;  // nothing culled (render_path sets the rectangle)
+    a.cull_x0 = 0; a.cull_x1 = P->width; a.cull_y0 = 0; a.cull_y1 = P->height;  // nothing culled (path_cull sets the rectangle)
     return a;
 }
 
@@ -610,7 +611,7 @@ struct CallLog {
     size_t ev_used = 0;
     hipEvent_t begin = nullptr, end = nullptr;
     uint64_t launches = 0;
-    uint64_t culled_segments = 0;  // render_path: one segment per sample of the pixels no kernel was given (rtw_plan.h cull_rect)
+    uint64_t culled_segments = 0;  // k_path renders: one segment per sample of the pixels no kernel was given (rtw_plan.h cull_rect)
 
     hipError_t event(hipEvent_t& e) {
         if (ev_used == c->ev_pool.size()) {
@@ -645,96 +646,118 @@ struct CallLog {
     }
 };
 
-// ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
-int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base_in, float4* out, hipStream_t s, CallLog& log) {
-    const size_t npix = base_in.npix;
-    int rc = ensure_pool(c, 0, 0, npix, 0);
-    if (rc) return rc;
-    // groups of 64 pixels that certainly see nothing get no job: a miss adds +0 (no sky light), so their pixels stay at accum = 0
-    // and their samples - one segment each, as the oracle counts them - are added to the call's counts on the host
-    KArgs base = base_in;
-    size_t live_groups = ~(size_t)0, culled_pixels = 0;
+// ---- the launch schedules that rtw_render, rtw_render_adaptive and rtw_accum_add share. Each renderer plans its own launches (rtw_plan.h)
+// and resolves them with its own kernel; how a planned pass or batch is issued, how the pool is fitted and how a call's counters
+// become rtw_stats is written once, here.
+
+// Workgroups per CU of a persistent launch of `kernel` with `lds` bytes of dynamic LDS: `override` where it is set (> 0), else what the
+// occupancy query admits, at most 8, and 4 where the query fails (that only costs occupancy: these launches draw from a queue or stride
+// over the grid, any grid computes the same)
+int path_wg_per_cu(const void* kernel, size_t lds, int override) {
+    if (override > 0) return override;
+    int nb = 0;
+    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, lds);
+    return (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+}
+
+// k_path's unit sums of one pass, at least `elems` of them
+int grow_blocksum(rtw_ctx* c, size_t elems) {
+    if (elems <= c->blocksum_elems) return RTW_OK;
+    if (c->blocksum) (void)hipFree(c->blocksum);
+    c->blocksum = nullptr; c->blocksum_elems = 0;
+    HIP_TRY(c, hipMalloc(&c->blocksum, elems * sizeof(float4)));
+    c->blocksum_elems = elems;
+    return RTW_OK;
+}
+// k_classify's three job lists, for at least n_groups groups of 64 pixels
+int grow_order(rtw_ctx* c, size_t n_groups) {
+    if (n_groups <= c->order_groups) return RTW_OK;
+    if (c->d_order) (void)hipFree(c->d_order);
+    c->d_order = nullptr; c->order_groups = 0;
+    HIP_TRY(c, hipMalloc(&c->d_order, 3 * n_groups * sizeof(uint32_t)));
+    c->order_groups = n_groups;
+    return RTW_OK;
+}
+
+// Groups of 64 pixels that certainly see nothing get no job: a miss adds +0 (no sky light), so their pixels stay at 0 and their
+// samples - one segment each, as the oracle counts them - are added to the call's counts on the host (culled_pixels x samples).
+// Sets base.cull_*; rcull is the same rectangle for the resolve kernels.
+struct PathCull { size_t live_groups, culled_pixels; ResolveCull rcull; };
+PathCull path_cull(const rtw_ctx* c, const rtw_params* P, const Tuning& tune, KArgs& base, size_t npix) {
+    PathCull pc{~(size_t)0, 0, {}};
     if (tune.cull && c->info.cull_ok) {
         const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->info.cull_bmin, c->info.cull_bmax, P->width, P->height);
         base.cull_x0 = r.x0; base.cull_x1 = r.x1; base.cull_y0 = r.y0; base.cull_y1 = r.y1;
-        live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &culled_pixels);
+        pc.live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &pc.culled_pixels);
     }
-    log.culled_segments = (uint64_t)culled_pixels * (uint64_t)P->spp;
-    const ResolveCull rcull{base.cull_x0, base.cull_x1, base.cull_y0, base.cull_y1, base.width, base.row0, base.row_stride, base.divw_m, base.divw_s1, base.divw_s2};
-    int wg_per_cu = tune.path_grid_mult;
-    if (wg_per_cu <= 0) {
-        int nb = 0;
-        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), kBlock, 0);
-        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
-    }
-    const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, live_groups);
-    if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
-    if (plan.n_groups > c->order_groups) {
-        if (c->d_order) (void)hipFree(c->d_order);
-        c->d_order = nullptr; c->order_groups = 0;
-        HIP_TRY(c, hipMalloc(&c->d_order, 3 * plan.n_groups * sizeof(uint32_t)));
-        c->order_groups = plan.n_groups;
-    }
-    if (plan.need_slots * npix > c->blocksum_elems) {
-        if (c->blocksum) (void)hipFree(c->blocksum);
-        c->blocksum = nullptr; c->blocksum_elems = 0;
-        HIP_TRY(c, hipMalloc(&c->blocksum, plan.need_slots * npix * sizeof(float4)));
-        c->blocksum_elems = plan.need_slots * npix;
-    }
-    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));  // low priority: it fills the slots the bulk launch vacates
-    HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
-    {   // job order: longest units first (k_classify)
-        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
-        const dim3 cg((unsigned)std::min<size_t>((plan.n_groups + 3) / 4, (size_t)c->n_cu * 8));
-        if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)plan.n_groups);
-        else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)plan.n_groups);
-    }
-    const unsigned pix_grid = pixel_grid(c, npix);
-    for (const PathPass& ps : plan.passes) {
-        if (live_groups == 0) break;  // the frame looks past everything: black, nothing to launch
-        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
-        HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
-        HIP_TRY(c, log.event(ev_a));
-        HIP_TRY(c, log.event(ev_b));
-        HIP_TRY(c, hipEventRecord(ev_a, s));
-        // the two launches of a pass overlap, so they are timed as one: from before the first to after both (on s, which waits
-        // for the second stream's launch below); rocprofv3 lists them as two dispatches whose durations both span the pass
-        CallLog::Timed tp;
-        HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
-        for (int part = 0; part < 2; part++) {
-            const PathLaunch& l = ps.part[part];
-            if (l.count == 0) continue;
-            KArgs a = base;
-            a.stats = c->d_stats;
-            a.sample0 = (uint32_t)P->sample_offset;
-            a.queue = c->d_queue + (part == 0 ? 0 : 4);
-            a.order = c->d_order;
-            a.order_counts = c->d_queue + 1;
-            a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * npix;
-            a.unit_sums = (part == 0 && plan.unit_sums) ? 1u : 0u;
-            a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
-            a.block0 = (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
-            hipStream_t ls = part == 0 ? s : c->stream2;
-            if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
-            launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls);
-            log.launches++;
-            if (part == 1) {
-                HIP_TRY(c, hipEventRecord(ev_b, ls));
-                HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
-            }
+    pc.rcull = ResolveCull{base.cull_x0, base.cull_x1, base.cull_y0, base.cull_y1, base.width, base.row0, base.row_stride, base.divw_m, base.divw_s1, base.divw_s2};
+    return pc;
+}
+
+// job order: longest units first (k_classify), into c->d_order with the lists' lengths at c->d_queue + 1
+int classify_jobs(rtw_ctx* c, const KArgs& base, size_t n_groups, hipStream_t s) {
+    HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
+    const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
+    if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
+    else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
+    return RTW_OK;
+}
+
+// what one k_path pass runs over: the shard's pixels in k_classify's order, or the pixels of an active list (rtw_adaptive.h)
+struct PathTarget {
+    size_t n_items;                // pixels of the shard, or of the list: the stride of the sums' buffer
+    const uint32_t* order;         // the job order (c->d_order), or the list
+    const uint32_t* order_counts;  // the lengths of the order's three lists; null for a list
+    bool list;                     // k_path's LIST = 1 twin
+    uint32_t blk0;                 // absolute index of the plan's block 0 (the samples before it are done: adaptive passes, accum adds)
+    uint32_t spp_end;              // KArgs::spp: the last sample of the range, counted from sample0
+    int rng_kind;
+    uint32_t sample0;
+};
+
+// One pass of a PathPlan: the bulk launch on s and the fine-grained end-game launch beside it on stream2, which starts after what s held
+// before the pass and which s waits for. The caller resolves c->blocksum on s afterwards. unit_sums: the plan's, for the bulk launch.
+int issue_path_pass(rtw_ctx* c, CallLog& log, const KArgs& base, const PathPass& ps, bool unit_sums, const PathTarget& target, hipStream_t s) {
+    // render_path and accum_add_path have d_queue from ensure_pool before they point target.order_counts into it; only the list caller,
+    // whose order_counts is null, can arrive here without one. A caller that needs the counts must allocate d_queue first.
+    if (!c->d_queue) HIP_TRY(c, hipMalloc(&c->d_queue, 64));
+    // low priority: it fills the slots the bulk launch vacates. Created by a context's first pass, after the call's begin event: that
+    // one call's stats.seconds includes the stream's creation
+    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
+    HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
+    HIP_TRY(c, log.event(ev_a));
+    HIP_TRY(c, log.event(ev_b));
+    HIP_TRY(c, hipEventRecord(ev_a, s));
+    // the two launches of a pass overlap, so they are timed as one: from before the first to after both (on s, which waits
+    // for the second stream's launch below); rocprofv3 lists them as two dispatches whose durations both span the pass
+    CallLog::Timed tp;
+    HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
+    for (int part = 0; part < 2; part++) {
+        const PathLaunch& l = ps.part[part];
+        if (l.count == 0) continue;
+        KArgs a = base;
+        a.stats = c->d_stats;
+        a.sample0 = target.sample0;
+        a.spp = target.spp_end;
+        a.queue = c->d_queue + (part == 0 ? 0 : 4);
+        a.order = target.order;
+        a.order_counts = target.order_counts;
+        a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * target.n_items;
+        a.unit_sums = (part == 0 && unit_sums) ? 1u : 0u;
+        a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
+        a.block0 = target.blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
+        hipStream_t ls = part == 0 ? s : c->stream2;
+        if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
+        launch(RTW_K_PATH, target.rng_kind, a, l.grid, 0, ls, kBlock, target.list);
+        log.launches++;
+        if (part == 1) {
+            HIP_TRY(c, hipEventRecord(ev_b, ls));
+            HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
         }
-        HIP_TRY(c, log.close(tp, s));
-        // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
-        if (plan.unit_sums)
-            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
-                               (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse), rcull);
-        else
-            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0, rcull);
     }
-    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
+    HIP_TRY(c, log.close(tp, s));
     return RTW_OK;
 }
 
@@ -791,23 +814,21 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
     }
     return RTW_OK;
 }
-
-// ---- wavefront pipeline (tree scenes; RTW_PATH=0): batches of S samples per pixel alternate between the lanes
-int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
-    const size_t npix = base.npix;
-    const SceneFacts& sf = c->info.facts;
-    WavefrontPlan w;
+// Plans the wavefront batches (plan_fn: the caller's plan_wavefront call, which reads c->pool_cap) and sizes the pool for them: paths_fn(w)
+// paths per lane, counters and accumulators for npix pixels. A trace launch beyond the default dynamic-LDS limit gets its attribute raised.
+template <class PlanFn, class PathsFn>
+int fit_wavefront_pool(rtw_ctx* c, const Tuning& tune, int samples_per_pass, size_t npix, PlanFn plan_fn, PathsFn paths_fn, WavefrontPlan& w) {
     for (;;) {
-        w = plan_wavefront(tune, npix, P->spp, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, sf);
+        w = plan_fn();
         if (w.trace_lds > 48 * 1024) {  // beyond the default dynamic-LDS limit of a launch
             DScene ts = c->sc;
             ts.n_lds_nodes = w.trace_nodes;
             const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
             HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
         }
-        const int rc = ensure_pool(c, w.n_lanes, (size_t)w.regions_max * w.region_cap_max, npix, w.cnt_words, c->sc.n_lights > 0);
-        if (rc == RTW_OK) break;
-        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || w.S <= 1) return rc;
+        const int rc = ensure_pool(c, w.n_lanes, paths_fn(w), npix, w.cnt_words, c->sc.n_lights > 0);
+        if (rc == RTW_OK) return RTW_OK;
+        if (rc != RTW_ERR_OOM || samples_per_pass > 0 || w.S <= 1) return rc;
         // The pool is sized for an MI355X to itself (2^29 paths: up to 120 GiB). A device with less to give - another process on
         // it, a smaller part - gets half as many paths in flight, and half again, until the allocation fits: smaller batches,
         // the same image (a path's draws and a pixel's summation order do not depend on the batch size).
@@ -815,7 +836,116 @@ int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const 
         (void)hipGetLastError();
         c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * w.S * (size_t)tune.lanes / 2);
     }
+}
 
+// The batches of `step` samples per item (a pixel of the shard; list: a pixel of the list) alternate between the lanes; batch b holds
+// samples [s0, s0 + Sb) of the step and draws from first_sample + s0 on. The lanes start after what s holds now; resolve(L, Sb, s0)
+// launches the caller's resolve kernel for lane L's batch on s, in batch order.
+template <class Resolve>
+int run_batches(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, const KArgs& base, size_t items, size_t step, int first_sample,
+                const uint32_t* list, hipStream_t s, CallLog& log, Resolve resolve) {
+    if (base.max_depth == 0) return RTW_OK;  // no segment is traced: nothing to launch
+    hipEvent_t ev_ready = nullptr;
+    HIP_TRY(c, log.event(ev_ready));
+    HIP_TRY(c, hipEventRecord(ev_ready, s));
+    for (size_t s0 = 0, b = 0; s0 < step; b++) {
+        const size_t Sb = w.batch_size(b, s0);
+        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
+        KArgs a = base;
+        a.sample0 = (uint32_t)(first_sample + (int)s0);
+        if (list) a.order = list;
+        // this lane's pool is free again once the resolve of its previous batch has run on the main stream
+        const int rc = issue_batch(c, w, tune, a, L, items * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, list != nullptr);
+        if (rc) return rc;
+        // batches are resolved in order, on the main stream
+        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
+        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+        resolve(L, Sb, s0);
+        HIP_TRY(c, hipEventRecord(L.ev_free, s));
+        s0 += Sb;
+    }
+    return RTW_OK;
+}
+
+// hs: the column sums of the kStatRows rows of 8 counters at d_rows (segments, shadow rays, then the segments by kernel kind)
+int sum_stat_rows(rtw_ctx* c, const unsigned long long* d_rows, unsigned long long hs[8]) {
+    unsigned long long rows_[kStatRows * 8];
+    HIP_TRY(c, hipMemcpy(rows_, d_rows, sizeof rows_, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 8; k++) hs[k] = 0;
+    for (uint32_t r = 0; r < kStatRows; r++)
+        for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
+    return RTW_OK;
+}
+
+// a finished call's rtw_stats (zeroed by the caller): its times from the log's events, its counts from the summed rows
+int fill_stats(rtw_ctx* c, const CallLog& log, const unsigned long long hs[8], uint64_t samples, uint64_t segments, rtw_stats* stats) {
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
+    stats->seconds = (double)ms * 1e-3;
+    stats->bounce_seconds = stats->seconds;  // the lanes overlap: the loop time is the elapsed time of the call
+    for (const CallLog::Timed& t : log.timed) {
+        float m = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
+        stats->kernel_seconds[t.kind] += (double)m * 1e-3;
+        stats->kernel_launches[t.kind]++;
+    }
+    for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];  // (what the kernels shaded themselves)
+    stats->bounce_launches = log.launches;
+    stats->samples = samples;
+    stats->segments = segments;
+    stats->shadow_rays = hs[1];
+    stats->algorithmic_bytes = 128ull * segments + 32ull * samples;
+    return RTW_OK;
+}
+
+// the corrected estimators live in the cold-feature instantiations
+void apply_estimator(DScene& sc, int estimator) {
+    if (estimator == RTW_EST_REFERENCE) return;
+    sc.estimator = estimator; sc.has_tex = estimator == RTW_EST_MIXTURE ? 2 : 1;
+    sc.ray_tmin = 1.0e-3f; sc.probe_eps = 1.0e-3f;
+}
+
+// ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
+int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base_in, float4* out, hipStream_t s, CallLog& log) {
+    const size_t npix = base_in.npix;
+    int rc = ensure_pool(c, 0, 0, npix, 0);
+    if (rc) return rc;
+    KArgs base = base_in;
+    const PathCull cull = path_cull(c, P, tune, base, npix);
+    log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)P->spp;
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), 0, tune.path_grid_mult);
+    const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, cull.live_groups);
+    if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
+    if ((rc = grow_order(c, plan.n_groups)) != RTW_OK) return rc;
+    if ((rc = grow_blocksum(c, plan.need_slots * npix)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(log.begin, s));
+    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    if ((rc = classify_jobs(c, base, plan.n_groups, s)) != RTW_OK) return rc;
+    const unsigned pix_grid = pixel_grid(c, npix);
+    const PathTarget target{npix, c->d_order, c->d_queue + 1, false, 0u, (uint32_t)P->spp, P->rng_kind, (uint32_t)P->sample_offset};
+    for (const PathPass& ps : plan.passes) {
+        if (cull.live_groups == 0) break;  // the frame looks past everything: black, nothing to launch
+        if ((rc = issue_path_pass(c, log, base, ps, plan.unit_sums, target, s)) != RTW_OK) return rc;
+        // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
+        if (plan.unit_sums)
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
+                               (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse), cull.rcull);
+        else
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0, cull.rcull);
+    }
+    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
+    return RTW_OK;
+}
+
+// ---- wavefront pipeline (tree scenes; RTW_PATH=0): batches of S samples per pixel alternate between the lanes
+int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, float4* out, hipStream_t s, CallLog& log) {
+    const size_t npix = base.npix;
+    WavefrontPlan w;
+    int rc = fit_wavefront_pool(c, tune, P->samples_per_pass, npix,
+                                [&] { return plan_wavefront(tune, npix, P->spp, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, c->info.facts); },
+                                [](const WavefrontPlan& p) { return (size_t)p.regions_max * p.region_cap_max; }, w);
+    if (rc) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
     HIP_TRY(c, hipMemsetAsync(c->part, 0, npix * sizeof(float4), s));
@@ -823,27 +953,10 @@ int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const 
     HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
     const unsigned pix_grid = pixel_grid(c, npix);
     // the lanes start once the accumulators are cleared
-    hipEvent_t ev_ready = nullptr;
-    if (P->max_depth > 0) {
-        HIP_TRY(c, log.event(ev_ready));
-        HIP_TRY(c, hipEventRecord(ev_ready, s));
-    }
-    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < (size_t)P->spp; b++) {
-        // batch b on its lane: samples [s0, s0 + Sb) of every pixel
-        const size_t Sb = w.batch_size(b, s0);
-        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
-        // this lane's pool is free again once the resolve of its previous batch has run on the main stream
-        KArgs a = base;
-        a.sample0 = (uint32_t)(P->sample_offset + (int)s0);
-        const int rc = issue_batch(c, w, tune, a, L, npix * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, false);
-        if (rc) return rc;
-        // batches are resolved into the accumulators in order, on the main stream
-        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
-        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+    rc = run_batches(c, w, tune, base, npix, (size_t)P->spp, P->sample_offset, nullptr, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
         hipLaunchKernelGGL(k_resolve, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, c->accum, c->upart, c->part, (uint32_t)npix, (uint32_t)Sb, (uint32_t)s0);
-        HIP_TRY(c, hipEventRecord(L.ev_free, s));
-        s0 += Sb;
-    }
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)c->upart, (const float4*)c->part, out, (uint32_t)npix, (float)P->spp);
     return RTW_OK;
 }
@@ -900,10 +1013,7 @@ int print_diagnostics(rtw_ctx* c, bool path, const unsigned long long* hs) {
 // the kernel arguments of a render: shard_args, and the corrected estimators' settings
 KArgs render_args(const rtw_ctx* c, const rtw_params* P, size_t npix) {
     KArgs base = shard_args(c->sc, P, npix);
-    if (P->estimator != RTW_EST_REFERENCE) {  // the corrected estimators live in the cold-feature instantiations
-        base.sc.estimator = P->estimator; base.sc.has_tex = P->estimator == RTW_EST_MIXTURE ? 2 : 1;
-        base.sc.ray_tmin = 1.0e-3f; base.sc.probe_eps = 1.0e-3f;
-    }
+    apply_estimator(base.sc, P->estimator);
     return base;
 }
 // k_path: scenes walked with the brute lists; it packs a unit's pixel as x | y << 16, so frames wider or taller than 65535
@@ -935,33 +1045,11 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
     HIP_TRY(c, hipEventRecord(log.end, s));
     HIP_TRY(c, hipEventSynchronize(log.end));
 
-    unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        unsigned long long rows_[kStatRows * 8];
-        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < kStatRows; r++)
-            for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
-    }
+    unsigned long long hs[8];
+    if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
     rc = print_diagnostics(c, use_path, hs);
     if (rc) return rc;
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
-        stats->seconds = (double)ms * 1e-3;
-        stats->bounce_seconds = stats->seconds;  // the lanes overlap: the loop time is the elapsed time of the call
-        for (const CallLog::Timed& t : log.timed) {
-            float m = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
-            stats->kernel_seconds[t.kind] += (double)m * 1e-3;
-            stats->kernel_launches[t.kind]++;
-        }
-        for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];
-        stats->bounce_launches = log.launches;
-        stats->samples = (uint64_t)npix * (uint64_t)P->spp;
-        stats->segments = hs[0] + log.culled_segments;  // (kernel_segments above: what the kernels shaded themselves)
-        stats->shadow_rays = hs[1];
-        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
-    }
+    if (stats) return fill_stats(c, log, hs, (uint64_t)npix * (uint64_t)P->spp, hs[0] + log.culled_segments, stats);
     return RTW_OK;
 }
 
@@ -1157,55 +1245,15 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
     // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
     Tuning t = tune;
     if (t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
-    int wg_per_cu = t.path_grid_mult;
-    if (wg_per_cu <= 0) {
-        int nb = 0;
-        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol, true), kBlock, 0);
-        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
-    }
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol, true), 0, t.path_grid_mult);
     const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
-    if (plan.need_slots * n_list > c->blocksum_elems) {
-        if (c->blocksum) (void)hipFree(c->blocksum);
-        c->blocksum = nullptr; c->blocksum_elems = 0;
-        HIP_TRY(c, hipMalloc(&c->blocksum, plan.need_slots * n_list * sizeof(float4)));
-        c->blocksum_elems = plan.need_slots * n_list;
-    }
-    if (!c->d_queue) HIP_TRY(c, hipMalloc(&c->d_queue, 64));
-    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
+    int rc = grow_blocksum(c, plan.need_slots * n_list);
+    if (rc) return rc;
     const uint32_t blk0 = (uint32_t)n_from / kSumBlock;
+    const PathTarget target{n_list, list, nullptr, true, blk0, (uint32_t)n_to, P->rng_kind, (uint32_t)P->sample_offset};
     for (const PathPass& ps : plan.passes) {
-        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
-        HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;
-        HIP_TRY(c, log.event(ev_a));
-        HIP_TRY(c, log.event(ev_b));
-        HIP_TRY(c, hipEventRecord(ev_a, s));
-        CallLog::Timed tp;
-        HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
-        for (int part = 0; part < 2; part++) {  // as in render_path: the bulk launch and the end-game launch beside it
-            const PathLaunch& l = ps.part[part];
-            if (l.count == 0) continue;
-            KArgs a = base;
-            a.stats = c->d_stats;
-            a.sample0 = (uint32_t)P->sample_offset;
-            a.spp = (uint32_t)n_to;
-            a.queue = c->d_queue + (part == 0 ? 0 : 4);
-            a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * n_list;
-            a.unit_sums = 0u;
-            a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
-            a.block0 = blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
-            a.order = list;
-            hipStream_t ls = part == 0 ? s : c->stream2;
-            if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
-            launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls, kBlock, true);
-            log.launches++;
-            if (part == 1) {
-                HIP_TRY(c, hipEventRecord(ev_b, ls));
-                HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
-            }
-        }
-        HIP_TRY(c, log.close(tp, s));
+        if ((rc = issue_path_pass(c, log, base, ps, false, target, s)) != RTW_OK) return rc;
         hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(c, n_list)), dim3(kBlock), 0, s, (const float4*)c->blocksum, list, (uint32_t)n_list,
                            (uint32_t)ps.nb, blk0 + (uint32_t)ps.b0, st.accum, st.upart, st.mom);
     }
@@ -1219,47 +1267,22 @@ int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune,
                             size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
     const size_t npix = base.npix;
     const size_t step = (size_t)(n_to - n_from);
-    const SceneFacts& sf = c->info.facts;
     WavefrontPlan w;
-    for (;;) {
-        size_t S = P->samples_per_pass > 0 ? (size_t)P->samples_per_pass : std::max<size_t>(1, std::min(tune.pool_paths, c->pool_cap) / (size_t)tune.lanes / npix);
-        S = std::min(S, step);
-        while (S > 1 && npix * S > 0xfffffff0ull) S--;
-        w = plan_wavefront(tune, n_list, (int)step, (int)S, P->max_depth, c->pool_cap, c->n_cu, sf);
-        if (w.trace_lds > 48 * 1024) {
-            DScene ts = c->sc;
-            ts.n_lds_nodes = w.trace_nodes;
-            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
-            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
-        }
-        const size_t paths = std::max((size_t)w.regions_max * w.region_cap_max, w.S * npix);
-        const int rc = ensure_pool(c, w.n_lanes, paths, npix, w.cnt_words, c->sc.n_lights > 0);
-        if (rc == RTW_OK) break;
-        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || S <= 1) return rc;
-        free_pool(c);  // as in render_wavefront: half as many paths in flight, the same image
-        (void)hipGetLastError();
-        c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * S * (size_t)tune.lanes / 2);
-    }
-    hipEvent_t ev_ready = nullptr;
-    HIP_TRY(c, log.event(ev_ready));
-    HIP_TRY(c, hipEventRecord(ev_ready, s));  // after the previous checkpoint's decision (the list) on s
+    int rc = fit_wavefront_pool(c, tune, P->samples_per_pass, npix,
+                                [&] {  // the batch size is chosen here, over npix, and handed to the plan (whose w.S is then this S)
+                                    size_t S = P->samples_per_pass > 0 ? (size_t)P->samples_per_pass : std::max<size_t>(1, std::min(tune.pool_paths, c->pool_cap) / (size_t)tune.lanes / npix);
+                                    S = std::min(S, step);
+                                    while (S > 1 && npix * S > 0xfffffff0ull) S--;
+                                    return plan_wavefront(tune, n_list, (int)step, (int)S, P->max_depth, c->pool_cap, c->n_cu, c->info.facts);
+                                },
+                                [&](const WavefrontPlan& p) { return std::max((size_t)p.regions_max * p.region_cap_max, p.S * npix); }, w);
+    if (rc) return rc;
     const unsigned grid = pixel_grid(c, n_list);
-    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < step; b++) {
-        const size_t Sb = w.batch_size(b, s0);
-        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
-        KArgs a = base;
-        a.sample0 = (uint32_t)(P->sample_offset + n_from + (int)s0);
-        a.order = list;
-        const int rc = issue_batch(c, w, tune, a, L, n_list * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, true);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
-        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+    // the lanes start after the previous checkpoint's decision (the list) on s
+    return run_batches(c, w, tune, base, n_list, step, P->sample_offset + n_from, list, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
         hipLaunchKernelGGL(k_adapt_resolve_samples, dim3(grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, list, (uint32_t)n_list, (uint32_t)npix,
                            (uint32_t)Sb, (uint32_t)(n_from + (int)s0), st.accum, st.upart, st.part, st.mom);
-        HIP_TRY(c, hipEventRecord(L.ev_free, s));
-        s0 += Sb;
-    }
-    return RTW_OK;
+    });
 }
 
 // one device (a group's first): the checkpoints, a pass and a decision per checkpoint, the final image
@@ -1340,27 +1363,9 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
                 passes[k].n_to, passes[k].active, smp, ms * 1e-3, smp / std::max(ms * 1e-3, 1e-12) / 1e6);
     }
     if (stats) {
-        unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        unsigned long long rows_[kStatRows * 8];
-        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < kStatRows; r++)
-            for (int q = 0; q < 8; q++) hs[q] += rows_[r * 8 + q];
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
-        stats->seconds = (double)ms * 1e-3;
-        stats->bounce_seconds = stats->seconds;
-        for (const CallLog::Timed& t : log.timed) {
-            float m = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
-            stats->kernel_seconds[t.kind] += (double)m * 1e-3;
-            stats->kernel_launches[t.kind]++;
-        }
-        for (int q = 0; q < RTW_K_COUNT; q++) stats->kernel_segments[q] = hs[2 + q];
-        stats->bounce_launches = log.launches;
-        stats->samples = samples;
-        stats->segments = hs[0];
-        stats->shadow_rays = hs[1];
-        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+        unsigned long long hs[8];
+        if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
+        return fill_stats(c, log, hs, samples, hs[0], stats);
     }
     return RTW_OK;
 }
@@ -1419,37 +1424,15 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     int rc = ensure_pool(c, 0, 0, npix, 0);
     if (rc) return rc;
     KArgs base = base_in;
-    size_t live_groups = ~(size_t)0, culled_pixels = 0;
-    if (tune.cull && c->info.cull_ok) {
-        const CullRect r = cull_rect(c->sc.cam, c->sc.cam_type, c->sc.sky_light, c->info.cull_bmin, c->info.cull_bmax, P->width, P->height);
-        base.cull_x0 = r.x0; base.cull_x1 = r.x1; base.cull_y0 = r.y0; base.cull_y1 = r.y1;
-        live_groups = cull_live_groups(r, npix, base.width, base.row0, base.row_stride, &culled_pixels);
-    }
-    log.culled_segments = (uint64_t)culled_pixels * (uint64_t)(n_to - n_from);
-    const ResolveCull rcull{base.cull_x0, base.cull_x1, base.cull_y0, base.cull_y1, base.width, base.row0, base.row_stride, base.divw_m, base.divw_s1, base.divw_s2};
-    int wg_per_cu = tune.path_grid_mult;
-    if (wg_per_cu <= 0) {
-        int nb = 0;
-        const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), kBlock, 0);
-        wg_per_cu = (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
-    }
+    const PathCull cull = path_cull(c, P, tune, base, npix);
+    log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)(n_to - n_from);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), 0, tune.path_grid_mult);
     const size_t n_groups = (npix + 63) / 64;
-    if (n_groups > c->order_groups) {
-        if (c->d_order) (void)hipFree(c->d_order);
-        c->d_order = nullptr; c->order_groups = 0;
-        HIP_TRY(c, hipMalloc(&c->d_order, 3 * n_groups * sizeof(uint32_t)));
-        c->order_groups = n_groups;
-    }
-    if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
+    if ((rc = grow_order(c, n_groups)) != RTW_OK) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));
     HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
-    if (live_groups == 0) return RTW_OK;  // the frame looks past everything: the state stays black
-    {   // job order: longest units first (k_classify), once per add
-        HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
-        const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
-        if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
-        else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
-    }
+    if (cull.live_groups == 0) return RTW_OK;  // the frame looks past everything: the state stays black
+    if ((rc = classify_jobs(c, base, n_groups, s)) != RTW_OK) return rc;  // once per add
     const unsigned pix_grid = pixel_grid(c, npix);
     // one plan per run (rtw_accum_state.h accum_runs: the head on its own, the whole units and the open tail behind them together),
     // all planned before the first launch so that the sums' buffer is sized once, as render_path sizes it
@@ -1459,60 +1442,24 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     for (int k = 0; k < runs.n; k++) {
         Tuning t = tune;  // every block's sum must reach memory (adaptive_path_pass): no lane unit may be a whole summation unit
         if (!runs.run[k].units_ok && t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
-        plans[k] = plan_path(t, npix, runs.run[k].n_to - runs.run[k].n_from, c->n_cu, wg_per_cu, live_groups);
+        plans[k] = plan_path(t, npix, runs.run[k].n_to - runs.run[k].n_from, c->n_cu, wg_per_cu, cull.live_groups);
         if (plans[k].too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
         if (plans[k].unit_sums && !runs.run[k].units_ok) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_accum_add: unit sums off a unit boundary");
         need_slots = std::max(need_slots, plans[k].need_slots);
     }
-    if (need_slots * npix > c->blocksum_elems) {
-        if (c->blocksum) (void)hipFree(c->blocksum);
-        c->blocksum = nullptr; c->blocksum_elems = 0;
-        HIP_TRY(c, hipMalloc(&c->blocksum, need_slots * npix * sizeof(float4)));
-        c->blocksum_elems = need_slots * npix;
-    }
+    if ((rc = grow_blocksum(c, need_slots * npix)) != RTW_OK) return rc;
     for (int k = 0; k < runs.n; k++) {
-        const int r_from = runs.run[k].n_from, r_to = runs.run[k].n_to;
         const PathPlan& plan = plans[k];
-        const uint32_t blk0 = (uint32_t)r_from / kSumBlock;
+        const uint32_t blk0 = (uint32_t)runs.run[k].n_from / kSumBlock;
+        const PathTarget target{npix, c->d_order, c->d_queue + 1, false, blk0, (uint32_t)runs.run[k].n_to, P->rng_kind, (uint32_t)P->sample_offset};
         for (const PathPass& ps : plan.passes) {
-            HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
-            HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
-            hipEvent_t ev_a = nullptr, ev_b = nullptr;
-            HIP_TRY(c, log.event(ev_a));
-            HIP_TRY(c, log.event(ev_b));
-            HIP_TRY(c, hipEventRecord(ev_a, s));
-            CallLog::Timed tp;
-            HIP_TRY(c, log.open(tp, RTW_K_PATH, s));
-            for (int part = 0; part < 2; part++) {  // as in render_path: the bulk launch and the end-game launch beside it
-                const PathLaunch& l = ps.part[part];
-                if (l.count == 0) continue;
-                KArgs a = base;
-                a.stats = c->d_stats;
-                a.sample0 = (uint32_t)P->sample_offset;
-                a.spp = (uint32_t)r_to;
-                a.queue = c->d_queue + (part == 0 ? 0 : 4);
-                a.order = c->d_order;
-                a.order_counts = c->d_queue + 1;
-                a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * npix;
-                a.unit_sums = (part == 0 && plan.unit_sums) ? 1u : 0u;
-                a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
-                a.block0 = blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
-                hipStream_t ls = part == 0 ? s : c->stream2;
-                if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
-                launch(RTW_K_PATH, P->rng_kind, a, l.grid, 0, ls);
-                log.launches++;
-                if (part == 1) {
-                    HIP_TRY(c, hipEventRecord(ev_b, ls));
-                    HIP_TRY(c, hipStreamWaitEvent(s, ev_b, 0));
-                }
-            }
-            HIP_TRY(c, log.close(tp, s));
+            if ((rc = issue_path_pass(c, log, base, ps, plan.unit_sums, target, s)) != RTW_OK) return rc;
             // coarse region: whole unit sums (unit_sums) or block sums from block b0 of the run on; fine region: block sums
             const uint32_t n_unit = plan.unit_sums ? (uint32_t)ps.slots_coarse : 0u;
             const uint32_t n_blk = plan.unit_sums ? (uint32_t)(ps.nb - ps.nb_coarse) : (uint32_t)ps.nb;
             const uint32_t first = blk0 + (uint32_t)(plan.unit_sums ? ps.b0 + ps.nb_coarse : ps.b0);
             hipLaunchKernelGGL(k_accum_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, (uint32_t)npix, n_unit, n_blk, first,
-                               A.accum, A.upart, A.mom, rcull);
+                               A.accum, A.upart, A.mom, cull.rcull);
         }
     }
     return RTW_OK;
@@ -1524,46 +1471,18 @@ int accum_add_wavefront(rtw_ctx* c, const Tuning& tune, const KArgs& base, int n
     const rtw_params* P = &A.P;
     const size_t npix = base.npix;
     const size_t step = (size_t)(n_to - n_from);
-    const SceneFacts& sf = c->info.facts;
     WavefrontPlan w;
-    for (;;) {
-        w = plan_wavefront(tune, npix, (int)step, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, sf);
-        if (w.trace_lds > 48 * 1024) {
-            DScene ts = c->sc;
-            ts.n_lds_nodes = w.trace_nodes;
-            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
-            HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
-        }
-        const int rc = ensure_pool(c, w.n_lanes, (size_t)w.regions_max * w.region_cap_max, npix, w.cnt_words, c->sc.n_lights > 0);
-        if (rc == RTW_OK) break;
-        if (rc != RTW_ERR_OOM || P->samples_per_pass > 0 || w.S <= 1) return rc;
-        free_pool(c);  // as in render_wavefront: half as many paths in flight, the same image
-        (void)hipGetLastError();
-        c->pool_cap = std::max<size_t>((size_t)tune.lanes * npix, npix * w.S * (size_t)tune.lanes / 2);
-    }
+    const int rc = fit_wavefront_pool(c, tune, P->samples_per_pass, npix,
+                                      [&] { return plan_wavefront(tune, npix, (int)step, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, c->info.facts); },
+                                      [](const WavefrontPlan& p) { return (size_t)p.regions_max * p.region_cap_max; }, w);
+    if (rc) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));
     HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
     const unsigned pix_grid = pixel_grid(c, npix);
-    hipEvent_t ev_ready = nullptr;
-    if (P->max_depth > 0) {
-        HIP_TRY(c, log.event(ev_ready));
-        HIP_TRY(c, hipEventRecord(ev_ready, s));
-    }
-    for (size_t s0 = 0, b = 0; P->max_depth > 0 && s0 < step; b++) {
-        const size_t Sb = w.batch_size(b, s0);
-        rtw_ctx::Lane& L = c->lane[b % (size_t)w.n_lanes];
-        KArgs a = base;
-        a.sample0 = (uint32_t)(P->sample_offset + n_from + (int)s0);
-        const int rc = issue_batch(c, w, tune, a, L, npix * Sb, Sb, b < (size_t)w.n_lanes ? ev_ready : L.ev_free, log, false);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(L.ev_done, L.st));
-        HIP_TRY(c, hipStreamWaitEvent(s, L.ev_done, 0));
+    return run_batches(c, w, tune, base, npix, step, P->sample_offset + n_from, nullptr, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
         hipLaunchKernelGGL(k_accum_resolve_samples, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, (uint32_t)npix, (uint32_t)Sb,
                            (uint32_t)(n_from + (int)s0), A.accum, A.upart, A.part, A.mom);
-        HIP_TRY(c, hipEventRecord(L.ev_free, s));
-        s0 += Sb;
-    }
-    return RTW_OK;
+    });
 }
 
 // one device (a group's first): one add, its counts and times
@@ -1584,32 +1503,10 @@ int accum_add_single(rtw_ctx* c, int32_t spp, rtw_stats* stats) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(log.end, s));
     HIP_TRY(c, hipEventSynchronize(log.end));
-    unsigned long long hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        unsigned long long rows_[kStatRows * 8];
-        HIP_TRY(c, hipMemcpy(rows_, c->d_stats, sizeof rows_, hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < kStatRows; r++)
-            for (int k = 0; k < 8; k++) hs[k] += rows_[r * 8 + k];
-    }
+    unsigned long long hs[8];
+    if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
     const uint64_t samples = (uint64_t)npix * (uint64_t)spp, segments = hs[0] + log.culled_segments;
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, log.begin, log.end));
-        stats->seconds = (double)ms * 1e-3;
-        stats->bounce_seconds = stats->seconds;
-        for (const CallLog::Timed& t : log.timed) {
-            float m = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&m, t.a, t.b));
-            stats->kernel_seconds[t.kind] += (double)m * 1e-3;
-            stats->kernel_launches[t.kind]++;
-        }
-        for (int k = 0; k < RTW_K_COUNT; k++) stats->kernel_segments[k] = hs[2 + k];
-        stats->bounce_launches = log.launches;
-        stats->samples = samples;
-        stats->segments = segments;
-        stats->shadow_rays = hs[1];
-        stats->algorithmic_bytes = 128ull * segments + 32ull * samples;
-    }
+    if (stats && (rc = fill_stats(c, log, hs, samples, segments, stats)) != RTW_OK) return rc;
     A.done = n_to;
     A.samples += samples; A.segments += segments; A.shadow_rays += hs[1];
     return RTW_OK;
@@ -1931,13 +1828,9 @@ hipError_t cast_launch(rtw_ctx* d, int32_t mode, const CastArgs& a, hipStream_t 
     const bool attr = a.material || a.normal || a.uv;
     const CastKernel k = mode == RTW_CAST_ANY ? k_cast<true, false> : attr ? k_cast<false, true> : k_cast<false, false>;
     const size_t lds = d->info.lds_bytes;
-    int nb = 0;
-    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
-    // workgroups per CU: what the query admits (registers allow 6 or 7 of these 4-wave workgroups, a tree's LDS image up to 10); the
-    // cap of 8 and the 4 taken when the query fails are render_path's for k_path (a failed query only costs occupancy: the launch is
-    // grid-stride, any grid computes the same)
-    size_t per_cu = (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
-    if (const int mult = read_tuning().cast_grid_mult) per_cu = (size_t)mult;  // RTW_CAST_GRID_MULT (rtw_plan.h)
+    // workgroups per CU: what the query admits (registers allow 6 or 7 of these 4-wave workgroups, a tree's LDS image up to 10), or
+    // RTW_CAST_GRID_MULT (rtw_plan.h)
+    const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, read_tuning().cast_grid_mult);
     const size_t grid = std::min<size_t>(((size_t)a.n + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, d->sc, a);
     return hipGetLastError();
@@ -2099,15 +1992,6 @@ int radiance_slab(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
     return RTW_OK;
 }
 
-// workgroups per CU of a persistent launch of k: what the occupancy query admits, capped and defaulted as cast_launch does (any
-// grid computes the same)
-template <class K>
-size_t radiance_per_cu(K k, size_t lds) {
-    int nb = 0;
-    const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBlock, lds);
-    return (qe == hipSuccess && nb > 0) ? (size_t)std::min(nb, 8) : 4;
-}
-
 // RTW_PROBE_OCCLUSION: n probes at d_probes (device) -> their unoccluded fractions at d_out, issued on stream s and not waited for.
 // One k_probe_occlusion launch per probe range; the ranges are rtw_radiance_plan.h's (the counts [unit][probe] of a call beyond 128
 // spp take 4 of the 16 bytes the plan reserves per unit in the context's slab).
@@ -2115,7 +1999,7 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
                     float4* d_out, hipStream_t s) {
     const OcclusionKernel k = RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion<RTW_RNG_TEA_LCG> : k_probe_occlusion<RTW_RNG_PHILOX>;
     const size_t lds = d->info.lds_bytes;
-    const size_t per_cu = radiance_per_cu(k, lds);
+    const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, 0);
     const uint32_t units = radiance_units(RP->spp);
     const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
     if (units > 1) {
@@ -2157,15 +2041,12 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         return RTW_OK;
     }
     DScene sc = d->sc;
-    if (RP->estimator != RTW_EST_REFERENCE) {  // render_args' override: the corrected estimators live in the cold-feature instantiations
-        sc.estimator = RP->estimator; sc.has_tex = RP->estimator == RTW_EST_MIXTURE ? 2 : 1;
-        sc.ray_tmin = 1.0e-3f; sc.probe_eps = 1.0e-3f;
-    }
+    apply_estimator(sc, RP->estimator);
     const bool probe = query == RTW_PROBE_IRRADIANCE;
     const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe);
     const RadianceResolve resolve = probe ? k_probe_resolve : k_radiance_resolve;
     const size_t lds = d->info.lds_bytes;
-    const size_t per_cu = radiance_per_cu(k, lds);
+    const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, 0);
     const uint32_t units = radiance_units(RP->spp);
     const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
     if (units > 1) {
@@ -2206,9 +2087,10 @@ int radiance_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, size_t n, const rtw
     if (query == RTW_PROBE_OCCLUSION) {  // every sample is one occlusion ray, nothing else is traced
         stats->shadow_rays = stats->samples;
     } else {
-        unsigned long long rows_[kStatRows * 8];
-        HIP_TRY(c, hipMemcpy(rows_, d->rad_ctl, sizeof rows_, hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < kStatRows; r++) { stats->segments += rows_[r * 8]; stats->shadow_rays += rows_[r * 8 + 1]; }
+        unsigned long long hs[8];
+        const int rc = sum_stat_rows(c, d->rad_ctl, hs);
+        if (rc) return rc;
+        stats->segments = hs[0]; stats->shadow_rays = hs[1];
         stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
     }
     float ms = 0.f;

@@ -1,6 +1,6 @@
 // rtw_plan.h — what a render launches, decided on the host from sizes alone: the tuning knobs, the k_path passes and launches
 // (plan_path) and the wavefront pipeline's batches, trace workgroup and schedule (plan_wavefront). No HIP in here: rtw_hip.hip's
-// render_path / render_wavefront issue what these plans say, and tests/native/plan_check.cpp pins them with g++.
+// issue_path_pass / run_batches issue what these plans say, for every renderer, and tests/native/plan_check.cpp pins them with g++.
 #pragma once
 #include <stdint.h>
 

@@ -73,7 +73,7 @@ int main(int argc, char** argv) {
     if (!prims.empty()) memcpy(prims.data(), blob.data() + h.off_prims, prims.size() * sizeof(rtw_prim));
     memcpy(xforms.data(), blob.data() + h.off_xforms, xforms.size() * sizeof(rtw_xform));
 
-    // what render_path does
+    // what rtw_hip.hip's path_cull does
     float bmin[3], bmax[3];
     CullRect r{0, width, 0, height};
     if (cull_bounds(prims.data(), prims.size(), xforms.data(), h.camera, bmin, bmax)) r = cull_rect(h.camera, h.camera_type, h.sky_light, bmin, bmax, width, height);

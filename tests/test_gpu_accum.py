@@ -11,6 +11,7 @@ import torch  # (before the HIP library is loaded, as in a run of the whole suit
 
 from raytracing_weekend_amd import abi
 from test_gpu_adaptive import CASES
+from test_gpu_cull import K_PATH, aimed_aside
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,6 +120,30 @@ def test_unit_sum_and_multi_pass_regimes(gpu, monkeypatch, regime):
     for schedule in schedules:
         tot = _run(gpu, p, schedule, knobbed)
         assert tot == [st_ref.samples, st_ref.segments, st_ref.shadow_rays], (schedule, tot)
+
+
+def test_adds_to_a_frame_aimed_past_the_scene(gpu):
+    """Every group of pixels is culled: an add launches no k_path, the state stays black, and each sample counts as one segment on the host"""
+    gpu.upload_scene(aimed_aside(abi.build_scene(0, W, H)))
+    p = abi.make_params(W, H, 64, DEPTH)
+    refs = Refs(gpu, p)
+    gpu.accum_begin(p)
+    done, tot = 0, [0, 0, 0]
+    try:
+        for n in (16, 48):
+            st = gpu.accum_add(n)
+            done += n
+            assert st.samples == st.segments == W * H * n and st.shadow_rays == 0 and st.kernel_segments[K_PATH] == 0
+            for k, v in enumerate((st.samples, st.segments, st.shadow_rays)):
+                tot[k] += v
+            img, ref = gpu.accum_read(), refs(done)[0]
+            assert _same(img, ref), f"at {done}: {np.count_nonzero(_bits(img) != _bits(ref))} words differ"
+        info = gpu.accum_status()
+        assert (info.active, info.done, info.cap) == (1, done, p.spp)
+        st_ref = refs(64)[1]
+        assert [info.samples, info.segments, info.shadow_rays] == tot == [st_ref.samples, st_ref.segments, st_ref.shadow_rays]
+    finally:
+        gpu.accum_end()
 
 
 @pytest.mark.parametrize("case", ["scene0_path_hot", "tree_wavefront"])

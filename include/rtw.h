@@ -601,6 +601,40 @@ int rtw_probe(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_param
 int rtw_probe_device(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_params* params, void* d_rgba, void* hip_stream,
                      rtw_stats* stats);
 
+/* Spherical-harmonic light probes at free points: the radiance arriving at a point from every direction, projected onto the nine
+ * real spherical harmonics of bands 0 to 2 (an irradiance volume's probe; what lights things that move through a baked scene).
+ * rtw_probe needs a normal and returns one number per channel; this needs none and returns nine coefficients per channel, which
+ * the caller evaluates for any normal at run time.
+ *   Points: `points` holds n*8 floats (px, py, pz, -, -, -, tmin, tmax): rtw_cast's layout, so a probe tensor is a valid point
+ *     tensor. Floats 3..5 are loaded and never used: a NaN there changes nothing. tmin and tmax bound the first segment only.
+ *   Direction: sample s of point i uses the key k = key_offset + i (mod 2^32), the sample index S = sample_offset + s and rtw_probe's
+ *     two raygen uniforms r1, r2 of that path. The direction is uniform over the whole sphere, in world axes, in fp32 without
+ *     contraction:
+ *       z = 1.0f - 2.0f * r2 (exact); s2 = fma(-z, z, 1.0f); sq = sqrt(s2); sincos2pi(r1, sn, cs); d = (cs * sq, sn * sq, z),
+ *     not normalised.
+ *   Basis: with (x, y, z) = d, one rounding per operation, parenthesised as written:
+ *       Y0 = 0.282094792f
+ *       Y1 = 0.488602512f * y        Y2 = 0.488602512f * z        Y3 = 0.488602512f * x
+ *       Y4 = 1.092548431f * (x * y)  Y5 = 1.092548431f * (y * z)
+ *       Y6 = 0.315391565f * (3.0f * (z * z) - 1.0f)
+ *       Y7 = 1.092548431f * (x * z)  Y8 = 0.546274215f * ((x * x) - (y * y))
+ *   Sample value: L is the radiance of the rtw_radiance sample of ray (p, d, tmin, tmax) at key k, sample index S and the same
+ *     seed, generator, estimator and max_depth, after removeNaNs; the sample adds Y_j * L_c to coefficient j, channel c.
+ *   Output: sh_out[i * 9 + j] is a float4: rgb = (sum / (float)spp) * 12.5663706f (the float nearest 4 pi; the density is
+ *     1 / (4 pi)), each of the 27 sums taken on its own in the order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from
+ *     sample_offset; w = 0.0f. max_depth = 0 gives zeros. The result for point i depends on its point, its key and the params
+ *     alone: not on n, the launch geometry, how the batch is cut into chunks or ranges, or tuning knobs.
+ *   Everything else is rtw_radiance's: the same params and validation (reserved == 0) and the same refusals, which write nothing
+ *     and leave *stats alone; n = 0 is RTW_OK; rtw_probe_sh takes host pointers and stages in chunks of RTW_RADIANCE_CHUNK points,
+ *     rtw_probe_sh_device takes 16-byte aligned device pointers (d_sh: n * 9 float4) and the same stream rule (NULL selects the
+ *     context's own non-blocking stream). Calls beyond 128 spp keep nine 16-byte sums per point and unit in rtw_radiance's scratch
+ *     slab (n * ceil(spp / 128) * 144 B, capped by RTW_RADIANCE_SLAB_BYTES: a larger batch runs as consecutive point ranges).
+ *     Groups answer on device_ids[0]; an accumulation session is not disturbed. stats: samples = n*spp, segments and shadow_rays
+ *     those of the same paths, algorithmic_bytes and seconds as rtw_radiance reports them. */
+int rtw_probe_sh(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance_params* params, float* sh_out, rtw_stats* stats);
+int rtw_probe_sh_device(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance_params* params, void* d_sh, void* hip_stream,
+                        rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

@@ -131,7 +131,8 @@ HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render"
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
                "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
-               "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device"]
+               "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
+               "rtw_probe_sh", "rtw_probe_sh_device"]
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -224,6 +225,10 @@ def load_hip():
         lib.rtw_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_probe_device.restype = C.c_int
         lib.rtw_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_probe_sh.restype = C.c_int
+        lib.rtw_probe_sh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_probe_sh_device.restype = C.c_int
+        lib.rtw_probe_sh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -561,6 +566,31 @@ class Renderer:
         pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
         self._check(self.lib.rtw_probe_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                               None if stats is None else C.byref(stats)), "rtw_probe_device")
+
+    # ---- spherical-harmonic light probes at free points (include/rtw.h rtw_probe_sh / rtw_probe_sh_device)
+    def probe_sh(self, points, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, stats=None):
+        """rtw_probe_sh on (n, 8) float32 points (position, three unused floats, tmin, tmax): the (n, 9, 4) float32 coefficients of the
+        radiance arriving at every point on the nine real spherical harmonics of bands 0 to 2, spp samples per point, w = 0
+        (bake.sh_irradiance evaluates them for a normal). Point i draws from the stream of key_offset + i, samples sample_offset ...
+        sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
+        if not isinstance(points, np.ndarray) or points.dtype != np.float32:
+            raise ValueError("probe_sh: points must be a float32 numpy array")
+        if points.ndim != 2 or points.shape[1] != 8:
+            raise ValueError(f"probe_sh: points of shape {points.shape}, expected (n, 8)")
+        rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
+        points = np.ascontiguousarray(points)
+        out = np.empty((points.shape[0], 9, 4), dtype=np.float32)
+        self._check(self.lib.rtw_probe_sh(self.ctx, points.ctypes.data, points.shape[0], C.byref(rp), out.ctypes.data,
+                                          None if stats is None else C.byref(stats)), "rtw_probe_sh")
+        return out
+
+    def probe_sh_device(self, n, points_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
+                        key_offset=0, stream_ptr=0, stats=None):
+        """rtw_probe_sh_device on raw device pointers, as radiance_device takes them: n points at points_ptr, n * 9 float4 coefficients
+        written at out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
+        rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
+        self._check(self.lib.rtw_probe_sh_device(self.ctx, C.c_void_p(points_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
+                                                 None if stats is None else C.byref(stats)), "rtw_probe_sh_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

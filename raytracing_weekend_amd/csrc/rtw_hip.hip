@@ -59,6 +59,7 @@
 #include "rtw_radiance.h"
 #include "rtw_radiance_plan.h"
 #include "rtw_probe.h"
+#include "rtw_probe_sh.h"
 #include "rtw_adaptive.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
@@ -66,6 +67,7 @@
 #include "rtw_cast.hip"    // (likewise)
 #include "rtw_radiance.hip"  // (likewise)
 #include "rtw_probe.hip"  // (likewise)
+#include "rtw_probe_sh.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -170,11 +172,11 @@ struct rtw_ctx {
     void* cast_buf = nullptr;
     size_t cast_rays = 0;
     // rtw_radiance's scratch, grown on demand and kept until rtw_destroy: the unit sums [unit][ray] of calls beyond 128 spp, the host
-    // variant's staging (rad_rays rays and their means) and the control words (kStatRows rows of 8 counters, then the queue word)
+    // variant's staging (rad_stage_bytes: a chunk's rays and their results) and the control words (kStatRows rows of 8 counters, then the queue word)
     void* rad_slab = nullptr;
     size_t rad_slab_bytes = 0;
     void* rad_stage = nullptr;
-    size_t rad_rays = 0;
+    size_t rad_stage_bytes = 0;
     unsigned long long* rad_ctl = nullptr;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
@@ -1946,16 +1948,21 @@ int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float*
 }
 
 // ---- rtw_radiance / rtw_radiance_device and rtw_probe / rtw_probe_device (rtw.h): whole paths along the caller's rays through
-// k_radiance, or from the caller's probes through k_probe / k_probe_occlusion. The two families share everything on the host but
-// the kernels: `query` says which one a call serves.
+// k_radiance, or from the caller's probes through k_probe / k_probe_occlusion, or from the caller's points through k_probe_sh
+// (rtw_probe_sh / rtw_probe_sh_device). The families share everything on the host but the kernels and the size of a result:
+// `query` says which one a call serves.
 typedef void (*RadianceKernel)(const DScene, const RadianceArgs);
 typedef void (*RadianceResolve)(const float4*, float4*, uint32_t, uint32_t, float);
 typedef void (*OcclusionKernel)(const DScene, const OcclusionArgs);
 constexpr int kQueryRadiance = -1;  // (else rtw_probe's mode: RTW_PROBE_IRRADIANCE or RTW_PROBE_OCCLUSION)
+constexpr int kQueryProbeSh = -2;   // rtw_probe_sh: nine float4 per point
+// float4 of one result: the output stride of a query
+constexpr size_t query_stride(int query) { return query == kQueryProbeSh ? 9 : 1; }
 
 // launch()'s rule: generator x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator)
-RadianceKernel radiance_kernel(int rng_kind, int feat, bool probe) {
+RadianceKernel radiance_kernel(int rng_kind, int feat, bool probe, bool sh = false) {
 #define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
+    if (sh) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe_sh, RTW_RNG_TEA_LCG) : RTW_RK(k_probe_sh, RTW_RNG_PHILOX);
     if (probe) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe, RTW_RNG_TEA_LCG) : RTW_RK(k_probe, RTW_RNG_PHILOX);
     return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_radiance, RTW_RNG_TEA_LCG) : RTW_RK(k_radiance, RTW_RNG_PHILOX);
 #undef RTW_RK
@@ -2030,11 +2037,24 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
 
 // n rays (or probes) at d_rays (device) -> their means at d_out, issued on stream s of device context d and not waited for: one
 // k_radiance (k_probe) launch per ray range (rtw_radiance_plan.h: all the rays unless the unit-sum slab would pass its cap), ray i on
-// the stream of key_offset + i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
+// the stream of key_offset + i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s. A result is `stride` float4
+// (query_stride: nine for rtw_probe_sh, whose slab and ranges are the plan's 144-byte variants).
 int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_rays, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
                    float4* d_out, hipStream_t s, int query) {
     if (query == RTW_PROBE_OCCLUSION) return occlusion_issue(c, d, tune, d_rays, n, RP, key_offset, d_out, s);
     uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    const bool sh = query == kQueryProbeSh;
+    const size_t stride = query_stride(query);
+    if (RP->max_depth == 0 && sh) {  // no segment is traced: every coefficient is 0 (n <= 2^31 - 1: the launch goes by ranges as well)
+        const uint64_t per = probe_sh_range_points(n, 1, 0);
+        for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
+            const RadianceRange rg = radiance_range(n, per, r);
+            hipLaunchKernelGGL(k_probe_sh_resolve, dim3(pixel_grid(d, rg.count * stride)), dim3(kBlock), 0, s, (const float4*)nullptr, d_out + rg.first * stride,
+                               (uint32_t)rg.count, 0u, (float)RP->spp);
+            HIP_TRY(c, hipGetLastError());
+        }
+        return RTW_OK;
+    }
     if (RP->max_depth == 0) {  // no segment is traced: every mean is 0
         hipLaunchKernelGGL(k_radiance_resolve, dim3(pixel_grid(d, n)), dim3(kBlock), 0, s, (const float4*)nullptr, d_out, (uint32_t)n, 0u, (float)RP->spp);
         HIP_TRY(c, hipGetLastError());
@@ -2043,21 +2063,21 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
     DScene sc = d->sc;
     apply_estimator(sc, RP->estimator);
     const bool probe = query == RTW_PROBE_IRRADIANCE;
-    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe);
-    const RadianceResolve resolve = probe ? k_probe_resolve : k_radiance_resolve;
+    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe, sh);
+    const RadianceResolve resolve = sh ? k_probe_sh_resolve : probe ? k_probe_resolve : k_radiance_resolve;
     const size_t lds = d->info.lds_bytes;
     const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, 0);
     const uint32_t units = radiance_units(RP->spp);
-    const uint64_t per = radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
+    const uint64_t per = sh ? probe_sh_range_points(n, RP->spp, tune.radiance_slab_bytes) : radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
     if (units > 1) {
-        const int rc = radiance_slab(c, d, radiance_slab_bytes(per, RP->spp), s);
+        const int rc = radiance_slab(c, d, sh ? probe_sh_slab_bytes(per, RP->spp) : radiance_slab_bytes(per, RP->spp), s);
         if (rc != RTW_OK) return rc;
     }
     for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
         const RadianceRange rg = radiance_range(n, per, r);
         RadianceArgs a{};
         a.rays = (const float4*)d_rays + 2 * rg.first;
-        a.out = units > 1 ? (float4*)d->rad_slab : d_out + rg.first;
+        a.out = units > 1 ? (float4*)d->rad_slab : d_out + rg.first * stride;
         a.queue = queue;
         a.stats = d->rad_ctl;
         a.n = (uint32_t)rg.count; a.units_per_ray = units; a.n_units = (uint32_t)(rg.count * units);
@@ -2071,7 +2091,7 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
         HIP_TRY(c, hipGetLastError());
         if (units > 1) {
-            hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first, a.n, units,
+            hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count * stride)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first * stride, a.n, units,
                                (float)RP->spp);
             HIP_TRY(c, hipGetLastError());
         }
@@ -2132,15 +2152,17 @@ int query_host(rtw_ctx* c, const char* what, const float* rays, size_t n, const 
     HIP_TRY(c, hipSetDevice(d->device));
     const Tuning tune = read_tuning();
     const size_t chunk = std::min(n, tune.radiance_chunk);
-    // the staging slab: per ray 32 B of ray and 16 B of mean, both sections 256-byte aligned
-    if (chunk > d->rad_rays) {
+    // the staging slab: per ray 32 B of ray and 16 B of result per float4 of the query's stride, both sections 256-byte aligned
+    const size_t stride = query_stride(query);
+    const size_t rays_bytes = (chunk * 32 + 255) & ~(size_t)255, stage_bytes = rays_bytes + chunk * 16 * stride;
+    if (stage_bytes > d->rad_stage_bytes) {
         if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_rays = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, ((chunk * 32 + 255) & ~(size_t)255) + chunk * 16));
-        d->rad_rays = chunk;
+        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
+        d->rad_stage_bytes = stage_bytes;
     }
     float* const st_rays = (float*)d->rad_stage;
-    float4* const st_out = (float4*)((char*)d->rad_stage + ((d->rad_rays * 32 + 255) & ~(size_t)255));
+    float4* const st_out = (float4*)((char*)d->rad_stage + rays_bytes);
     hipEvent_t ev[2];
     HIP_TRY(c, cast_events(d, ev));
     if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
@@ -2152,7 +2174,7 @@ int query_host(rtw_ctx* c, const char* what, const float* rays, size_t n, const 
         // chunk c runs with the key of its first ray: the bits do not depend on the chunk size
         if ((rc = radiance_issue(c, d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, d->stream, query)) != RTW_OK) return rc;
         if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * stride * i0, st_out, m * 16 * stride, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
     }
     return radiance_stats(c, d, stats, n, RP, ev, query);
@@ -2192,6 +2214,17 @@ int impl_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params
     if (c->has_scene && !probe_mode_ok(PP)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_probe: bad mode");
     rtw_radiance_params rp;
     return query_host(c, "rtw_probe", probes, n, probe_sampling(PP, rp), rgba_out, stats, PP ? PP->mode : 0);
+}
+
+// rtw_probe_sh takes rtw_radiance's params as they are (reserved == 0 included)
+int impl_sh_probe_device(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, void* d_sh, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    return query_device(c, "rtw_probe_sh_device", points, n, RP, d_sh, hip_stream, stats, kQueryProbeSh);
+}
+
+int impl_sh_probe(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, float* sh_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    return query_host(c, "rtw_probe_sh", points, n, RP, sh_out, stats, kQueryProbeSh);
 }
 
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
@@ -2278,6 +2311,12 @@ int rtw_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params*
 }
 int rtw_probe_device(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_probe_device(c, probes, n, PP, d_rgba, hip_stream, stats); });
+}
+int rtw_probe_sh(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, float* sh_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_sh_probe(c, points, n, RP, sh_out, stats); });
+}
+int rtw_probe_sh_device(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, void* d_sh, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_sh_probe_device(c, points, n, RP, d_sh, hip_stream, stats); });
 }
 
 }  // extern "C"

@@ -5,6 +5,9 @@
 // source. It is a macro and not a function so that k_radiance's text, and with it its generated code, stays what it was before
 // k_probe existed (as a function inlined into both kernels the same statements were scheduled differently: a few lines of ISA in
 // 15 000 moved; profiles/probe_rates.txt).
+// A third value of the macro's argument, 2, makes k_probe_sh's body (rtw_probe_sh.hip): the first direction is uniform over the sphere
+// and every sample adds Y_j(d) * L to nine coefficients. Every statement of that kernel alone stands under a compile-time
+// (int)(PROBE_) == 2, so the two older kernels' generated code does not move.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +16,7 @@
 #include "rtw_kernels.h"
 #include "rtw_radiance.h"
 #include "rtw_probe.h"
+#include "rtw_probe_sh.h"
 
 namespace rtwk {
 
@@ -59,12 +63,43 @@ RTW_DEV v3 probe_direction(const v3 n, const float r1, const float r2) {
                         fma_(lz, w.z, fma_(ly, v.z, lx * u.z))));
 }
 
+// A spherical-harmonic probe's direction (rtw.h rtw_probe_sh): uniform over the sphere, in world axes, from the same two uniforms
+RTW_DEV v3 probe_sh_direction(const float r1, const float r2) {
+    const float z = 1.0f - 2.0f * r2;  // exact: r2 is a multiple of 2^-24 in [0, 1)
+    const float s2 = fma_(-z, z, 1.0f);
+    const float sq = sqrt_(s2);  // (s2 may be 0: the full-range root)
+    float sn, cs;
+    sincos2pi(r1, sn, cs);
+    return V(cs * sq, sn * sq, z);
+}
+
+// The nine real spherical harmonics of bands 0 to 2 at d (rtw.h rtw_probe_sh, "Basis"): one rounding per operation, as written
+RTW_DEV void probe_sh_basis(const v3 d, float* Y) {
+    const float x = d.x, y = d.y, z = d.z;
+    Y[0] = 0.282094792f;
+    Y[1] = 0.488602512f * y;
+    Y[2] = 0.488602512f * z;
+    Y[3] = 0.488602512f * x;
+    Y[4] = 1.092548431f * (x * y);
+    Y[5] = 1.092548431f * (y * z);
+    Y[6] = 0.315391565f * (3.0f * (z * z) - 1.0f);
+    Y[7] = 1.092548431f * (x * z);
+    Y[8] = 0.546274215f * ((x * x) - (y * y));
+}
+
+// k_probe_sh's per-lane LDS rows (stride kBlock): the 27 sums of the open block of 16 samples, coefficient-major, then the first
+// direction of the lane's current path. Both are touched once per path (a path is hundreds of instructions) and would otherwise
+// have to live in VGPRs across the segment loop, which is full at 128. The unit sums - touched once per 16 paths - run in the words
+// that receive them in the end: the lane's nine float4 of the output (at most 128 spp) or of the slab [unit][point][9].
+constexpr uint32_t kShSums = 27, kShRows = kShSums + 3;
+
 // The kernels' body; sc and a are the kernel's parameters, KIND and TEX its template parameters. s_usum: the running sum of the lane's
 // summation unit (the sums of its finished blocks, in order): touched once per 16 samples.
 #define RTW_RADIANCE_BODY(PROBE_) \
     extern __shared__ uint32_t s_stack[]; \
     RTW_NOISE_SHARED \
     __shared__ float s_usum[3][kBlock]; \
+    __shared__ float s_sh[kShRows][kBlock];  /* (never referenced, and dropped, in the two older kernels; s_usum in k_probe_sh) */ \
     const uint32_t tid = threadIdx.x; \
     const uint32_t* noise_lds = stage_noise<(TEX != 0)>(sc, s_noise); \
     /* it holds a barrier: every thread, before the loop; the branch is uniform (a property of the scene) */ \
@@ -105,6 +140,9 @@ RTW_DEV v3 probe_direction(const v3 n, const float r1, const float r2) {
                 s_cur = unit * (kSumBlock * kSumUnitBlocks); \
                 s_end = min(s_cur + kSumBlock * kSumUnitBlocks, a.spp); \
                 bsum = V(0.f, 0.f, 0.f); \
+                if ((int)(PROBE_) == 2) { \
+                    _Pragma("unroll") for (uint32_t j = 0; j < kShSums; j++) s_sh[j][tid] = 0.f; \
+                } \
                 need = false; \
                 alive = false; \
             } \
@@ -119,7 +157,13 @@ RTW_DEV v3 probe_direction(const v3 n, const float r1, const float r2) {
             const float4 r0 = a.rays[2 * (size_t)ray], r1 = a.rays[2 * (size_t)ray + 1];  /* two 16-byte loads */ \
             o = V(r0.x, r0.y, r0.z); d = V(r0.w, r1.x, r1.y); \
             seg_tmin = r1.z; seg_tmax = r1.w;  /* the caller's interval bounds the first segment only */ \
-            if (PROBE_) { \
+            if ((int)(PROBE_) == 2) { \
+                /* floats 3..5 are loaded and unused; the direction waits in LDS for the path's end, where the basis is taken */ \
+                float jitter[2]; \
+                radiance_raygen<KIND, true>(sc, a.seed, key, sample, g, gt, ray_time, jitter); \
+                d = probe_sh_direction(jitter[0], jitter[1]); \
+                s_sh[kShSums][tid] = d.x; s_sh[kShSums + 1][tid] = d.y; s_sh[kShSums + 2][tid] = d.z; \
+            } else if (PROBE_) { \
                 /* a probe keeps nothing between its samples: the basis is rebuilt from the normal that the two loads above bring anyway */ \
                 float jitter[2]; \
                 radiance_raygen<KIND, true>(sc, a.seed, key, sample, g, gt, ray_time, jitter); \
@@ -154,6 +198,34 @@ RTW_DEV v3 probe_direction(const v3 n, const float r1, const float r2) {
                 ray_time = (KIND == RTW_RNG_TEA_LCG || sc.has_motion) ? g.ray_time(depth) : 0.0f; \
                 rng_b = g.b; \
                 seg_tmin = sc.ray_tmin; seg_tmax = 1.e27f;  /* later segments: the estimator's start distance, as a render */ \
+            } else if ((int)(PROBE_) == 2) { \
+                /* removeNaNs, then Y_j * L_c joins each of the block's 27 running sums, in sample order */ \
+                const v3 Ln = V((L.x == L.x) ? L.x : 0.f, (L.y == L.y) ? L.y : 0.f, (L.z == L.z) ? L.z : 0.f); \
+                float Y[9]; \
+                probe_sh_basis(V(s_sh[kShSums][tid], s_sh[kShSums + 1][tid], s_sh[kShSums + 2][tid]), Y); \
+                _Pragma("unroll") for (uint32_t j = 0; j < 9; j++) { \
+                    s_sh[3 * j][tid] += Y[j] * Ln.x; s_sh[3 * j + 1][tid] += Y[j] * Ln.y; s_sh[3 * j + 2][tid] += Y[j] * Ln.z; \
+                } \
+                s_cur++; \
+                if ((s_cur % kSumBlock) == 0u || s_cur >= s_end) {  /* a block is complete: its sums join the unit's */ \
+                    const uint32_t b_done = (s_cur - 1u) / kSumBlock; \
+                    const bool first = (b_done % kSumUnitBlocks) == 0u, last = s_cur >= s_end; \
+                    const bool mean = last && a.units_per_ray == 1u;  /* at most 128 spp: the unit sum is the total */ \
+                    float4* const dst = a.out + 9u * (a.units_per_ray == 1u ? (size_t)ray : (size_t)(b_done / kSumUnitBlocks) * a.n + ray); \
+                    const float nf = (float)a.spp; \
+                    _Pragma("unroll") for (uint32_t j = 0; j < 9; j++) { \
+                        v3 prev = V(0.f, 0.f, 0.f); \
+                        if (!first) { const float4 p = dst[j]; prev = V(p.x, p.y, p.z); } \
+                        v3 u = vadd(prev, V(s_sh[3 * j][tid], s_sh[3 * j + 1][tid], s_sh[3 * j + 2][tid])); \
+                        s_sh[3 * j][tid] = 0.f; s_sh[3 * j + 1][tid] = 0.f; s_sh[3 * j + 2][tid] = 0.f; \
+                        if (mean) { \
+                            u = vadd(V(0.f, 0.f, 0.f), u); \
+                            u = V((u.x / nf) * kProbeSh4Pi, (u.y / nf) * kProbeSh4Pi, (u.z / nf) * kProbeSh4Pi); \
+                        } \
+                        dst[j] = make_float4(u.x, u.y, u.z, 0.f); \
+                    } \
+                    if (last) need = true; \
+                } \
             } else { \
                 /* removeNaNs (raygen.cu:17-24), then the block's running sum, in sample order */ \
                 bsum = vadd(bsum, V((L.x == L.x) ? L.x : 0.f, (L.y == L.y) ? L.y : 0.f, (L.z == L.z) ? L.z : 0.f)); \

@@ -34,6 +34,21 @@ inline uint64_t radiance_range_rays(uint64_t n, int32_t spp, uint64_t cap_bytes)
     return std::min<uint64_t>(std::max<uint64_t>(rays, 1), std::max<uint64_t>(n, 1));
 }
 
+// rtw_probe_sh keeps nine float4 - 144 bytes - per point and unit where a radiance query keeps one: the same three rules at that
+// size. A launch's float4 index (unit * n + point) * 9 + j stays below 2^31 as well, hence a ninth of the units per launch.
+constexpr uint64_t kProbeShUnitBytes = 9ull * 16ull;
+constexpr uint64_t kProbeShMaxLaunchUnits = kRadianceMaxLaunchUnits / 9ull;
+inline uint64_t probe_sh_slab_bytes(uint64_t n, int32_t spp) {
+    const uint64_t u = radiance_units(spp);
+    return u <= 1 ? 0ull : n * u * kProbeShUnitBytes;
+}
+inline uint64_t probe_sh_range_points(uint64_t n, int32_t spp, uint64_t cap_bytes) {
+    const uint64_t u = radiance_units(spp);
+    uint64_t points = kProbeShMaxLaunchUnits / u;
+    if (u > 1) points = std::min<uint64_t>(points, cap_bytes / (u * kProbeShUnitBytes));
+    return std::min<uint64_t>(std::max<uint64_t>(points, 1), std::max<uint64_t>(n, 1));
+}
+
 // range r of the cut of [0, n) into ranges of `per` rays: [first, first + count); count = 0 past the end
 struct RadianceRange { uint64_t first, count; };
 inline uint64_t radiance_n_ranges(uint64_t n, uint64_t per) { return (n + per - 1) / per; }

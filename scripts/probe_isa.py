@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """ISA line and scratch-instruction counts of the radiance and probe kernels, from `hipcc -S` with the build's flags (no GPU needed).
 
-usage: scripts/probe_isa.py [unit.hip ...]      default: rtw_radiance.hip rtw_probe.hip of raytracing_weekend_amd/csrc
+usage: scripts/probe_isa.py [unit.hip ...]      default: rtw_radiance.hip rtw_probe.hip rtw_probe_sh.hip of raytracing_weekend_amd/csrc
 Prints one line per kernel: ISA lines (instructions: lines that are neither labels, directives nor comments), scratch_ instructions,
-and the VGPR / scratch figures of the kernel's .amdhsa block. profiles/probe_rates.txt keeps the output of the parent's
-rtw_radiance.hip beside this tree's."""
+and the VGPR / scratch / static LDS figures of the kernel's .amdhsa block. profiles/probe_rates.txt keeps the output of the parent's
+rtw_radiance.hip beside this tree's, profiles/probe_sh_rates.txt the seven older kernels' beside k_probe_sh's."""
 import os
 import re
 import subprocess
@@ -30,14 +30,16 @@ def counts(unit):
         scratch = sum(1 for ln in inst if ln.split()[0].startswith("scratch_"))
         vgpr = re.search(r"\.amdhsa_next_free_vgpr (\d+)", body)
         priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body)
+        lds = re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body)
         demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0]
-        rows.append((demangled, len(inst), scratch, int(vgpr.group(1)) if vgpr else -1, int(priv.group(1)) if priv else -1))
+        rows.append((demangled, len(inst), scratch, int(vgpr.group(1)) if vgpr else -1, int(priv.group(1)) if priv else -1,
+                     int(lds.group(1)) if lds else -1))
     return rows
 
 
 if __name__ == "__main__":
-    units = sys.argv[1:] or [os.path.join(entry.CSRC, u) for u in ("rtw_radiance.hip", "rtw_probe.hip")]
+    units = sys.argv[1:] or [os.path.join(entry.CSRC, u) for u in ("rtw_radiance.hip", "rtw_probe.hip", "rtw_probe_sh.hip")]
     for u in units:
         print(f"# {os.path.basename(u)}")
-        for name, n, scratch, vgpr, priv in counts(u):
-            print(f"{name:64s} {n:7d} ISA lines  {scratch:4d} scratch instructions  next_free_vgpr {vgpr:4d}  scratch bytes {priv:5d}")
+        for name, n, scratch, vgpr, priv, lds in counts(u):
+            print(f"{name:64s} {n:7d} ISA lines  {scratch:4d} scratch instructions  next_free_vgpr {vgpr:4d}  scratch bytes {priv:5d}  static LDS {lds:6d}")

@@ -1,0 +1,187 @@
+"""CPU suite of the spherical-harmonic probes (include/rtw.h rtw_probe_sh / rtw_probe_sh_device): the additive ABI, the Python
+surface's argument handling, sh_ref.directions and sh_ref.basis (the restated formulas the GPU tests referee with), bake.probe_grid,
+bake.sh_basis and bake.sh_irradiance, and the planning functions under the sanitizers."""
+import ast
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import sh_ref as S
+from raytracing_weekend_amd import abi, bake
+
+BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
+
+
+# ---------------------------------------------------------------- ABI
+def header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(abi.REPO_DIR, "include", "rtw.h")).read(), flags=re.S)
+
+
+def test_header_declares_both_entry_points_and_stays_at_version_5():
+    text = " ".join(header().split())
+    assert ("int rtw_probe_sh(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance_params* params, float* sh_out, "
+            "rtw_stats* stats);") in text
+    assert ("int rtw_probe_sh_device(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance_params* params, void* d_sh, "
+            "void* hip_stream, rtw_stats* stats);") in text
+    assert "#define RTW_ABI_VERSION 5" in text
+    assert abi.RTW_ABI_VERSION == 5 and C.sizeof(abi.Stats) == 184 and C.sizeof(abi.Params) == 48
+    assert C.sizeof(abi.RadianceParams) == 32 and C.sizeof(abi.ProbeParams) == 32
+
+
+def test_symbols_are_listed_and_exported():
+    assert "rtw_probe_sh" in abi.HIP_SYMBOLS and "rtw_probe_sh_device" in abi.HIP_SYMBOLS
+    lib = abi.load_hip()
+    assert hasattr(lib, "rtw_probe_sh") and hasattr(lib, "rtw_probe_sh_device") and lib.rtw_abi_version() == 5
+
+
+def test_null_context_is_an_error_not_a_crash():
+    lib = abi.load_hip()
+    points, out = np.zeros((4, 8), np.float32), np.zeros((4, 9, 4), np.float32)
+    rp = abi.make_radiance_params(4, 4)
+    for n in (0, 4):
+        assert lib.rtw_probe_sh(None, points.ctypes.data, n, C.byref(rp), out.ctypes.data, None) < 0
+        assert lib.rtw_probe_sh_device(None, points.ctypes.data, n, C.byref(rp), out.ctypes.data, None, None) < 0
+    assert lib.rtw_probe_sh(None, None, 0, None, None, None) < 0
+    assert not out.any()
+
+
+def test_the_kernels_are_a_unit_of_the_build_and_share_the_body():
+    entry = open(os.path.join(abi.REPO_DIR, "__graft_entry__.py")).read()
+    assert '("rtw_probe_sh.hip", "rtw_probe_sh.o", [])' in entry and '"rtw_probe_sh.hip"' not in entry.split("UNIT_FLAGS = ")[1].split("\n")[0]
+    csrc = os.path.join(abi.PKG_DIR, "csrc")
+    hip, body, sh = (open(os.path.join(csrc, f)).read() for f in ("rtw_hip.hip", "rtw_radiance_body.h", "rtw_probe_sh.hip"))
+    assert '#include "rtw_probe_sh.hip"' in hip.split("#ifndef RTW_SPLIT_BUILD")[1].split("#endif")[0]  # the single-file variant build
+    assert hip.count("return guarded(c, [&] { return impl_sh_probe") == 2
+    assert "RTW_RADIANCE_BODY(2)" in sh and "shade_a<" not in sh and "shade_b<" not in sh
+    assert body.count("shade_a<KIND, TEX>") == 1 and body.count("shade_b<KIND>") == 1
+
+
+# ---------------------------------------------------------------- the Python surface
+class NoLibrary:
+    """A Renderer that must refuse before it reaches the library."""
+    ctx = None
+
+    class lib:
+        @staticmethod
+        def rtw_probe_sh(*a):
+            raise AssertionError("the library was called")
+
+
+def test_python_side_argument_validation():
+    call = abi.Renderer.probe_sh
+    good = np.zeros((5, 8), np.float32)
+    for points in (np.zeros((5, 7), np.float32), np.zeros(8, np.float32), np.zeros((5, 8, 1), np.float32),  # shape
+                   np.zeros((5, 8), np.float64), np.zeros((5, 8), np.int32), [[0.0] * 8]):                   # dtype
+        with pytest.raises(ValueError):
+            call(NoLibrary, points, 4, 4)
+    for spp in (0, -3, 1.5, None, True):
+        with pytest.raises(ValueError):
+            call(NoLibrary, good, spp, 4)
+
+
+def test_torch_is_imported_inside_the_function_only():
+    for name in ("torch_probe_sh.py", "bake.py"):
+        tree = ast.parse(open(os.path.join(abi.PKG_DIR, name)).read())
+        top = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+        names = {a.name.split(".")[0] for n in top if isinstance(n, ast.Import) for a in n.names} | {(n.module or "").split(".")[0] for n in top if isinstance(n, ast.ImportFrom)}
+        assert "torch" not in names, name
+    from raytracing_weekend_amd import torch_probe_sh
+    assert callable(torch_probe_sh.probe_sh_torch)
+
+
+# ---------------------------------------------------------------- sh_ref.directions and sh_ref.basis
+@pytest.mark.parametrize("rng_kind", BOTH)
+def test_directions_are_unit_uniform_and_the_basis_is_orthonormal(rng_kind):
+    """64 keys from 2^32 - 20 on (they wrap), 1024 samples each."""
+    n, spp = 64, 1024
+    r2, z, s2, d = S.parts(n, spp, rng_kind=rng_kind, key_offset=2 ** 32 - 20)
+    assert d.shape == (n, spp, 3) and d.dtype == np.float32
+    assert np.array_equal(z.astype(np.float64), 1.0 - 2.0 * r2.astype(np.float64))  # 1 - 2 r2 is exact
+    assert (s2 >= 0).all()
+    d64 = d.astype(np.float64)
+    length = np.sqrt((d64 * d64).sum(-1))
+    print(f"rng {rng_kind}: max ||d| - 1| = {np.abs(length - 1).max() / 2.0 ** -24:.2f} * 2^-24, min s2 {s2.min():.3e}")
+    assert np.abs(length - 1.0).max() <= 4 * 2.0 ** -24
+    # 4 pi mean(Y_i Y_j) is the identity within six of each entry's own standard errors. An entry without variance (Y_0 Y_0, a
+    # product of two float32 constants) is bounded by the constants' rounding instead: two relative errors of 2^-24, so below 1e-6
+    y = S.basis(d).astype(np.float64).reshape(-1, 9)
+    prod = 4.0 * np.pi * y[:, :, None] * y[:, None, :]
+    gram, se = prod.mean(0), prod.std(0, ddof=1) / np.sqrt(len(y))
+    worst = (np.abs(gram - np.eye(9))[se > 1e-9] / se[se > 1e-9]).max()
+    print(f"rng {rng_kind}: the worst Gram entry lies {worst:.2f} standard errors from the identity")
+    assert (np.abs(gram - np.eye(9)) <= np.maximum(6.0 * se, 1e-6)).all(), gram
+    # bake.sh_basis is the same basis
+    assert np.array_equal(bake.sh_basis(d[:2]).view(np.uint32), S.basis(d[:2]).view(np.uint32))
+
+
+@pytest.mark.parametrize("rng_kind", BOTH)
+def test_directions_depend_on_key_and_sample_index_alone(rng_kind):
+    whole = S.directions(6, 32, rng_kind=rng_kind, key_offset=2 ** 32 - 3)
+    assert np.array_equal(S.directions(6, 16, rng_kind=rng_kind, key_offset=2 ** 32 - 3, sample_offset=16).view(np.uint32), whole[:, 16:].view(np.uint32))
+    for i in range(6):
+        one = S.directions(1, 32, rng_kind=rng_kind, key_offset=(2 ** 32 - 3 + i) & 0xffffffff)
+        assert np.array_equal(one[0].view(np.uint32), whole[i].view(np.uint32)), i
+    assert len(np.unique(whole.reshape(-1, 3).view(np.uint32), axis=0)) == 6 * 32
+    # these are rtw_probe's uniforms: the same (key, sample) gives the cosine lobe's azimuth
+    import probe_ref as P
+    r1, r2 = P.uniforms(7, 3, 0x6314759, rng_kind)
+    d = S.directions(1, 1, rng_kind=rng_kind, key_offset=7, sample_offset=3)[0, 0]
+    assert d[2] == np.float32(1.0) - np.float32(2.0) * r2
+
+
+# ---------------------------------------------------------------- bake
+def test_probe_grid_order_and_endpoints():
+    g = bake.probe_grid((1, 2, 3), (5, 8, 4), 3, 4, 2, tmin=1e-3, tmax=50.0)
+    assert g.shape == (24, 8) and g.dtype == np.float32
+    assert np.array_equal(g[0, :3], [1, 2, 3]) and np.array_equal(g[-1, :3], [5, 8, 4])
+    assert np.array_equal(g[:3, 0], [1, 3, 5]) and (g[:3, 1] == 2).all() and (g[:3, 2] == 3).all()  # x fastest
+    assert np.array_equal(g[0:12:3, 1], [2, 4, 6, 8]) and (g[:12, 2] == 3).all() and (g[12:, 2] == 4).all()  # then y, then z
+    ix, iy, iz = 2, 1, 1
+    assert np.array_equal(g[(iz * 4 + iy) * 3 + ix, :3], [5, 4, 4])
+    assert not g[:, 3:6].any() and (g[:, 6] == np.float32(1e-3)).all() and (g[:, 7] == np.float32(50.0)).all()
+    d = bake.probe_grid((0, 0, 0), (1, 1, 1), 1, 1, 1)
+    assert d.shape == (1, 8) and not d[0, :6].any() and d[0, 6] == np.float32(1e-6) and d[0, 7] == np.float32(1e27)
+    for bad in ((0, 1, 1), (1, -1, 1), (1, 1, 0)):
+        with pytest.raises(ValueError):
+            bake.probe_grid((0, 0, 0), (1, 1, 1), *bad)
+
+
+def test_sh_irradiance_of_a_linear_sky():
+    """L = a + b y has c_0 = 2 sqrt(pi) a, c_y = b * 0.4886025 * 4 pi / 3 and nothing else; its irradiance at the normal +-y is
+    pi (a +- 2 b / 3)."""
+    a, b = np.array([0.75, 0.85, 1.0]), np.array([-0.25, -0.15, 0.0])
+    c = np.zeros((9, 3))
+    c[0] = 2.0 * np.sqrt(np.pi) * a
+    c[1] = b * 0.4886025 * 4.0 * np.pi / 3.0
+    up, down = bake.sh_irradiance(c, (0, 1, 0)), bake.sh_irradiance(c, (0, -1, 0))
+    assert up.shape == (3,) and up.dtype == np.float64
+    assert np.allclose(up, np.pi * (a + 2 * b / 3), rtol=1e-6, atol=0) and np.allclose(down, np.pi * (a - 2 * b / 3), rtol=1e-6, atol=0)
+    # batches broadcast: (n, 9, 4) coefficients with (n, 3) normals, and one normal for all
+    cc = np.zeros((5, 9, 4), np.float32)
+    cc[:, :, :3] = c
+    nn = np.tile(np.array([[0, 1, 0]], np.float32), (5, 1))
+    e = bake.sh_irradiance(cc, nn)
+    assert e.shape == (5, 4) and np.allclose(e[:, :3], up, rtol=1e-6) and not e[:, 3].any()
+    assert np.allclose(bake.sh_irradiance(cc, (0, 1, 0)), e)
+    # band 2: L = z^2 has irradiance pi / 4 + (pi / 4)(3 nz^2 - 1) * (1 / 3)... checked numerically against the integral instead
+    rng = np.random.default_rng(2)
+    w = rng.normal(size=(200000, 3))
+    w /= np.linalg.norm(w, axis=1, keepdims=True)
+    lum = 0.3 + 0.5 * w[:, 0] * w[:, 2] + 0.2 * w[:, 2] ** 2
+    coef = (4 * np.pi * (bake.sh_basis(w.astype(np.float32)).astype(np.float64) * lum[:, None]).mean(0))[:, None]
+    nrm = np.array([0.6, 0.0, 0.8])
+    direct = 4 * np.pi * (lum * np.maximum(w @ nrm, 0.0)).mean()
+    assert abs(bake.sh_irradiance(coef, nrm.astype(np.float32))[0] - direct) <= 0.02 * direct  # (Monte Carlo: 200 000 directions)
+
+
+# ---------------------------------------------------------------- the planning header, under the sanitizers
+def test_plan_header_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "probe_sh_plan_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                           "-Werror", "-o", exe, os.path.join(abi.REPO_DIR, "tests", "native", "probe_sh_plan_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "probe_sh_plan_check ok" in out.stdout, out.stdout + out.stderr[-2000:]

@@ -635,6 +635,64 @@ int rtw_probe_sh(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance
 int rtw_probe_sh_device(rtw_ctx* ctx, const float* points, size_t n, const rtw_radiance_params* params, void* d_sh, void* hip_stream,
                         rtw_stats* stats);
 
+/* Views: batched frames from the caller's own cameras (turntables, stereo pairs, the six faces of a cube map at many positions, a
+ * few thousand small training views), in one call, from the uploaded scene. The scene blob carries one camera and only
+ * rtw_upload_scene changes it; rtw_radiance takes fixed rays, so no jitter inside the pixel and no lens sample. Here the camera
+ * ray is generated on the device, from a record per view.
+ *   Views: `views` holds n_views records. camera is rtw_scene_header.camera, time0 / time1 included; camera_type its
+ *     rtw_camera_type; seed that view's rtw_params.seed; reserved is 0. All views of a call share width, height and the sampling.
+ *   Equivalence: frame v is, bit for bit, the frame rtw_render makes of the uploaded scene with the header's camera and camera_type
+ *     replaced by views[v]'s, under rtw_params {width, height, spp, max_depth, seed = views[v].seed, all rows, rng_kind,
+ *     sample_offset, estimator}. The stream key of pixel (x, y) is width * y + x; the pixel jitter, the lens sample (drawn by the
+ *     TEA+LCG stream for a perspective camera only), the environment and orthographic formulas, the gather-time draw over the view's
+ *     own time0 / time1 and the first ray time are that render's, operation for operation; the first segment uses the estimator's
+ *     start distance and 1e27f. Views that share a seed share their random streams, as frames rendered one after another with one
+ *     seed do: the caller decorrelates views with `seed`.
+ *   Output: n_views * height * width float4; pixel (x, y) of view v at (v * height + y) * width + x, row 0 the bottom row: the sum
+ *     of the samples' radiance in the order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from sample_offset, divided by
+ *     (float)spp, alpha 1.0f. A pixel depends on its view record, its (x, y) and the params alone: not on n_views, its view's
+ *     index, the launch geometry, how the call is cut into chunks or ranges, or tuning knobs.
+ *   rtw_views: host pointers. The records are copied to a device buffer the context keeps and grows; the frames are staged out
+ *     through rtw_radiance's staging slab in chunks of at most RTW_RADIANCE_CHUNK pixels of the flattened (view, y, x) index (a chunk
+ *     may begin and end mid-row and mid-view). It reads the records: a camera_type outside 0..2 or a non-zero view `reserved` is
+ *     RTW_ERR_INVALID_ARG.
+ *   rtw_views_device: device pointers on the context's device, both 16-byte aligned. Ordered on hip_stream exactly as
+ *     rtw_radiance_device is; returns when the frames are written. NULL selects the context's own non-blocking stream, NOT the
+ *     legacy default stream. It does not read the records back: on the device a camera_type that is neither RTW_CAM_ENVIRONMENT nor
+ *     RTW_CAM_ORTHOGRAPHIC is a perspective camera (lens draws included), and `reserved` is ignored. Calls beyond 128 spp keep one
+ *     16-byte sum per pixel and unit in rtw_radiance's scratch slab, capped by RTW_RADIANCE_SLAB_BYTES: a larger call runs as
+ *     consecutive ranges of flattened pixels. It allocates nothing per call once the context's scratch is large enough.
+ *   Groups (n_devices > 1): the call runs on device_ids[0]; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   stats (may be NULL): samples = n_views*width*height*spp; segments and shadow_rays = the sums of those renders' counts (a render
+ *     counts the one-segment samples of the pixels it culls; this call traces them); algorithmic_bytes and seconds as rtw_radiance
+ *     reports them; the per-kernel arrays are 0.
+ *   Errors: RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for NULL params, width, height or spp <= 0, max_depth < 0, a bad
+ *     rng_kind or estimator, sample_offset < 0 or sample_offset + spp > INT32_MAX, params reserved != 0,
+ *     n_views * width * height > 2^31 - 1, with n_views > 0 a NULL views or output, (rtw_views_device) a misaligned views or output,
+ *     and (rtw_views) a bad record as above. A refused call writes nothing and leaves *stats alone. n_views = 0 is RTW_OK and
+ *     launches nothing. The context stays usable after an error. */
+typedef struct rtw_view {
+    rtw_camera camera;     /* as rtw_scene_header.camera, time0 / time1 included */
+    int32_t camera_type;   /* rtw_camera_type */
+    uint32_t seed;         /* this view's rtw_params.seed */
+    uint32_t reserved[2];  /* 0 */
+} rtw_view;                /* 112 B */
+
+typedef struct rtw_view_params {
+    int32_t width, height;  /* of every view of the call */
+    int32_t spp;            /* samples per pixel, > 0 */
+    int32_t max_depth;      /* as rtw_params.max_depth */
+    int32_t rng_kind;       /* rtw_rng_kind */
+    int32_t sample_offset;  /* first sample index; sample_offset + spp <= INT32_MAX */
+    int32_t estimator;      /* rtw_estimator */
+    uint32_t reserved;      /* 0, else RTW_ERR_INVALID_ARG */
+} rtw_view_params;          /* 32 B */
+
+int rtw_views(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_view_params* params, float* rgba_out, rtw_stats* stats);
+int rtw_views_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, void* d_rgba, void* hip_stream,
+                     rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

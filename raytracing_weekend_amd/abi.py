@@ -127,12 +127,23 @@ class ProbeParams(C.Structure):
                 ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("key_offset", C.c_uint32), ("mode", C.c_int32)]
 
 
+class View(C.Structure):
+    """rtw_view (include/rtw.h): one camera of rtw_views / rtw_views_device and the seed of its frame."""
+    _fields_ = [("camera", Camera), ("camera_type", C.c_int32), ("seed", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ViewParams(C.Structure):
+    """rtw_view_params (include/rtw.h): the frame size and the sampling all views of a call share."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32), ("max_depth", C.c_int32), ("rng_kind", C.c_int32),
+                ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("reserved", C.c_uint32)]
+
+
 HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
                "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
                "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
                "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
-               "rtw_probe_sh", "rtw_probe_sh_device"]
+               "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device"]
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -229,6 +240,10 @@ def load_hip():
         lib.rtw_probe_sh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_probe_sh_device.restype = C.c_int
         lib.rtw_probe_sh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_views.restype = C.c_int
+        lib.rtw_views.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_views_device.restype = C.c_int
+        lib.rtw_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -320,6 +335,51 @@ def make_probe_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, s
     if mode not in PROBE_MODES:
         raise ValueError(f"probe: mode {mode!r} is neither 'irradiance' nor 'occlusion'")
     return ProbeParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, PROBE_MODES[mode])
+
+
+def make_view(camera, camera_type=RTW_CAM_PERSPECTIVE, seed=0x6314759):
+    """rtw_view of a Camera (copied) or of anything Camera's 24 floats can be read from (bake.look_at's array): the camera, its
+    rtw_camera_type and the seed of its frame."""
+    if isinstance(camera, Camera):
+        cam = Camera.from_buffer_copy(bytes(camera))
+    else:
+        a = np.ascontiguousarray(camera, dtype=np.float32)
+        if a.shape != (24,):
+            raise ValueError(f"make_view: camera of shape {a.shape}, expected a Camera or 24 floats")
+        cam = Camera.from_buffer_copy(a.tobytes())
+    if isinstance(camera_type, bool) or not isinstance(camera_type, (int, np.integer)) or not 0 <= camera_type <= 2:
+        raise ValueError(f"make_view: camera_type = {camera_type!r}, expected 0, 1 or 2")
+    v = View()
+    v.camera = cam
+    v.camera_type = int(camera_type)
+    v.seed = int(seed) & 0xffffffff
+    return v
+
+
+def scene_view(blob, seed=0x6314759):
+    """The scene blob's own camera and camera type as an rtw_view: its frame is render()'s frame of that blob under `seed`."""
+    h = SceneHeader.from_buffer_copy(blob[:C.sizeof(SceneHeader)])
+    return make_view(h.camera, h.camera_type, seed)
+
+
+def view_array(views):
+    """A contiguous ctypes array of View from a View, a sequence of them or such an array."""
+    if isinstance(views, View):
+        views = [views]
+    if isinstance(views, C.Array) and views._type_ is View:
+        return views
+    views = list(views)
+    if not all(isinstance(v, View) for v in views):
+        raise ValueError("views: expected abi.View records (abi.make_view, abi.scene_view, bake.cube_views, bake.orbit_views)")
+    return (View * len(views))(*views)
+
+
+def make_view_params(width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0):
+    """rtw_view_params; width, height and spp must be positive integers (the library checks the rest)."""
+    for name, v in (("width", width), ("height", height), ("spp", spp)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError(f"views: {name} = {v!r}, expected a positive integer")
+    return ViewParams(int(width), int(height), int(spp), int(max_depth), rng_kind, sample_offset, estimator, 0)
 
 
 def local_rows(params):
@@ -591,6 +651,28 @@ class Renderer:
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
         self._check(self.lib.rtw_probe_sh_device(self.ctx, C.c_void_p(points_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                                  None if stats is None else C.byref(stats)), "rtw_probe_sh_device")
+
+    # ---- batched frames from the caller's own cameras (include/rtw.h rtw_views / rtw_views_device)
+    def views(self, views, width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, stats=None):
+        """rtw_views on View records (make_view, scene_view, bake.cube_views, bake.orbit_views): the (n, height, width, 4) float32
+        frames, row 0 the bottom row, alpha 1. Frame v is render()'s frame of the uploaded scene with views[v]'s camera in its
+        header and views[v].seed as the seed. `stats`: a Stats to fill, or None."""
+        arr = view_array(views)
+        vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
+        if len(arr) * int(width) * int(height) > 0x7fffffff:
+            raise ValueError("views: more than 2^31 - 1 pixels in one call")
+        out = np.empty((len(arr), int(height), int(width), 4), dtype=np.float32)
+        self._check(self.lib.rtw_views(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), out.ctypes.data,
+                                       None if stats is None else C.byref(stats)), "rtw_views")
+        return out
+
+    def views_device(self, n, views_ptr, out_ptr, width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
+                     stream_ptr=0, stats=None):
+        """rtw_views_device on raw device pointers, as radiance_device takes them: n rtw_view records (112 B each) at views_ptr,
+        n * height * width float4 written at out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
+        vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
+        self._check(self.lib.rtw_views_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
+                                              None if stats is None else C.byref(stats)), "rtw_views_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

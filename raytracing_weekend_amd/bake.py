@@ -1,6 +1,9 @@
 """Baking on top of rtw_probe and rtw_probe_sh (include/rtw.h): the probes at the texel centres of an axis-aligned rectangle primitive
 and the baked map - irradiance or ambient occlusion - in the layout of an RTW_TEX_IMAGE of that primitive; the points of an
-irradiance volume, the spherical-harmonic basis of rtw_probe_sh and the irradiance its nine coefficients give for a normal."""
+irradiance volume, the spherical-harmonic basis of rtw_probe_sh and the irradiance its nine coefficients give for a normal.
+Cameras for rtw_views: look_at (the host description's perspective camera), the six faces of a cube map and a turntable."""
+import math
+
 import numpy as np
 
 from . import abi
@@ -105,3 +108,91 @@ def sh_irradiance(coeffs, normals):
     y = sh_basis(normals).astype(np.float64)
     band = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
     return ((y * band)[..., :, None] * c).sum(axis=-2)
+
+
+def _normalize32(v):
+    f = np.float32
+    dd = f(f(f(v[0] * v[0]) + f(v[1] * v[1])) + f(v[2] * v[2]))
+    return (f(1.0) / np.sqrt(dd)) * v
+
+
+def _cross32(a, b):
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], np.float32)
+
+
+def look_at(frm, to, up, vfov, aspect, aperture=0.0, focus_dist=1.0, t0=0.0, t1=0.0):
+    """The 24 float32 of an rtw_camera (origin, u, v, w, lower_left, horizontal, vertical, lens_radius, time0, time1) of a perspective
+    camera at `frm` looking at `to`, by the host description's ioPerspectiveCamera formulas in float32: w = normalize(frm - to),
+    u = normalize(cross(up, w)), v = cross(w, u); vfov is top to bottom in degrees, aspect width over height; the lens radius is
+    aperture / 2 and the frame stands at focus_dist: lower_left = frm - hw f u - hh f v - f w, horizontal = 2 hw f u, vertical =
+    2 hh f v with hh = tan(vfov / 2), hw = aspect hh. abi.make_view takes the array."""
+    f = np.float32
+    frm, to, up = (np.asarray(a, np.float64).astype(np.float32).reshape(3) for a in (frm, to, up))
+    w = _normalize32(frm - to)
+    u = _normalize32(_cross32(up, w))
+    v = _cross32(w, u)
+    theta = f(vfov) * f(np.pi) / f(180.0)
+    hh = np.tan(theta / f(2.0), dtype=np.float32)
+    hw = f(aspect) * hh
+    fd = f(focus_dist)
+    ll = frm - (hw * fd) * u - (hh * fd) * v - fd * w
+    hor = (f(2.0) * hw * fd) * u
+    ver = (f(2.0) * hh * fd) * v
+    return np.concatenate([frm, u, v, w, ll, hor, ver, [f(aperture) / f(2.0), f(t0), f(t1)]]).astype(np.float32)
+
+
+# cube_views' faces, in order: the direction the face looks along and its up vector
+CUBE_FACES = (((1, 0, 0), (0, 1, 0)), ((-1, 0, 0), (0, 1, 0)), ((0, 1, 0), (0, 0, -1)), ((0, -1, 0), (0, 0, 1)),
+              ((0, 0, 1), (0, 1, 0)), ((0, 0, -1), (0, 1, 0)))
+
+
+def cube_views(position, seed=0x6314759):
+    """Six abi.View for Renderer.views: the 90 degree perspective cameras (aspect 1, no lens, focus distance 1) of a cube map at
+    `position`, in the order +x, -x, +y, -y, +z, -z (CUBE_FACES: up is +y for the four side faces, -z for +y and +z for -y). `seed`
+    is one seed for all six faces or a sequence of six."""
+    pos = np.asarray(position, np.float64).reshape(3)
+    seeds = [seed] * 6 if isinstance(seed, (int, np.integer)) else list(seed)
+    if len(seeds) != 6:
+        raise ValueError("cube_views: seed is one integer or six")
+    return [abi.make_view(look_at(pos, pos + np.array(d, np.float64), up, 90.0, 1.0), abi.RTW_CAM_PERSPECTIVE, s)
+            for (d, up), s in zip(CUBE_FACES, seeds)]
+
+
+def orbit_views(blob, n, seed=0x6314759):
+    """n abi.View for Renderer.views: a turntable of the scene blob's camera. View 0 is the blob's camera, copied and not recomputed;
+    view k is that camera (its type, lens and times kept) rotated rigidly by 360 k / n degrees about the camera's v axis through
+    the pivot lower_left + horizontal / 2 + vertical / 2, the centre of its frame: points (origin, lower_left) turn about the
+    pivot, vectors (u, v, w, horizontal, vertical) about the origin; computed in double precision and rounded to float32 once. `seed` is one
+    seed for every view or a sequence of n."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n <= 0:
+        raise ValueError(f"orbit_views: n = {n!r}, expected a positive integer")
+    seeds = [seed] * n if isinstance(seed, (int, np.integer)) else list(seed)
+    if len(seeds) != n:
+        raise ValueError("orbit_views: seed is one integer or n of them")
+    base = abi.scene_view(blob, seeds[0])
+    c = [float(x) for x in np.frombuffer(bytes(base.camera), np.float32)]
+    fields = [c[3 * i:3 * i + 3] for i in range(7)]  # origin, u, v, w, lower_left, horizontal, vertical
+    v, ll, hor, ver = fields[2], fields[4], fields[5], fields[6]
+    pivot = [(ll[i] + hor[i] / 2.0) + ver[i] / 2.0 for i in range(3)]
+    norm = math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    axis = [v[i] / norm for i in range(3)]
+    out = [base]
+    for k in range(1, n):
+        # Rodrigues' rotation in Python floats, every operation written out: the command-line tool's -orbit makes the same views
+        ang = (2.0 * math.pi * float(k)) / float(n)
+        cs, sn = math.cos(ang), math.sin(ang)
+        omc = 1.0 - cs
+
+        def rot(x):
+            cr = [axis[1] * x[2] - axis[2] * x[1], axis[2] * x[0] - axis[0] * x[2], axis[0] * x[1] - axis[1] * x[0]]
+            d = (axis[0] * x[0] + axis[1] * x[1]) + axis[2] * x[2]
+            return [(x[i] * cs + cr[i] * sn) + axis[i] * (d * omc) for i in range(3)]
+        cam = []
+        for f, x in enumerate(fields):
+            if f in (0, 4):  # points turn about the pivot, vectors about the origin
+                r = rot([x[i] - pivot[i] for i in range(3)])
+                cam += [pivot[i] + r[i] for i in range(3)]
+            else:
+                cam += rot(x)
+        out.append(abi.make_view(np.array(cam + c[21:24], np.float64).astype(np.float32), base.camera_type, seeds[k]))
+    return out

@@ -60,6 +60,7 @@
 #include "rtw_radiance_plan.h"
 #include "rtw_probe.h"
 #include "rtw_probe_sh.h"
+#include "rtw_view.h"
 #include "rtw_adaptive.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
@@ -68,6 +69,7 @@
 #include "rtw_radiance.hip"  // (likewise)
 #include "rtw_probe.hip"  // (likewise)
 #include "rtw_probe_sh.hip"  // (likewise)
+#include "rtw_view.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -177,6 +179,8 @@ struct rtw_ctx {
     size_t rad_slab_bytes = 0;
     void* rad_stage = nullptr;
     size_t rad_stage_bytes = 0;
+    void* view_buf = nullptr;  // rtw_views: the call's view records
+    size_t view_bytes = 0;
     unsigned long long* rad_ctl = nullptr;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
@@ -497,6 +501,7 @@ int impl_destroy(rtw_ctx* c) {
     if (c->cast_buf) (void)hipFree(c->cast_buf);
     if (c->rad_slab) (void)hipFree(c->rad_slab);
     if (c->rad_stage) (void)hipFree(c->rad_stage);
+    if (c->view_buf) (void)hipFree(c->view_buf);
     if (c->rad_ctl) (void)hipFree(c->rad_ctl);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1949,13 +1954,18 @@ int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float*
 
 // ---- rtw_radiance / rtw_radiance_device and rtw_probe / rtw_probe_device (rtw.h): whole paths along the caller's rays through
 // k_radiance, or from the caller's probes through k_probe / k_probe_occlusion, or from the caller's points through k_probe_sh
-// (rtw_probe_sh / rtw_probe_sh_device). The families share everything on the host but the kernels and the size of a result:
-// `query` says which one a call serves.
+// (rtw_probe_sh / rtw_probe_sh_device), or from the caller's cameras through k_view (rtw_views / rtw_views_device: the "rays" are
+// the pixels of the flattened (view, y, x) index). The families share everything on the host but the kernels and the size of a
+// result: `query` says which one a call serves.
 typedef void (*RadianceKernel)(const DScene, const RadianceArgs);
 typedef void (*RadianceResolve)(const float4*, float4*, uint32_t, uint32_t, float);
 typedef void (*OcclusionKernel)(const DScene, const OcclusionArgs);
 constexpr int kQueryRadiance = -1;  // (else rtw_probe's mode: RTW_PROBE_IRRADIANCE or RTW_PROBE_OCCLUSION)
 constexpr int kQueryProbeSh = -2;   // rtw_probe_sh: nine float4 per point
+constexpr int kQueryViews = -3;     // rtw_views: d_rays holds the view records, n counts pixels
+typedef void (*ViewKernel)(const DScene, const ViewArgs);
+// what a views call adds to a query: the frame and the flattened pixel that ray 0 of the issue is
+struct ViewFrame { int32_t width, height; uint64_t first; };
 // float4 of one result: the output stride of a query
 constexpr size_t query_stride(int query) { return query == kQueryProbeSh ? 9 : 1; }
 
@@ -1965,6 +1975,12 @@ RadianceKernel radiance_kernel(int rng_kind, int feat, bool probe, bool sh = fal
     if (sh) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe_sh, RTW_RNG_TEA_LCG) : RTW_RK(k_probe_sh, RTW_RNG_PHILOX);
     if (probe) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe, RTW_RNG_TEA_LCG) : RTW_RK(k_probe, RTW_RNG_PHILOX);
     return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_radiance, RTW_RNG_TEA_LCG) : RTW_RK(k_radiance, RTW_RNG_PHILOX);
+#undef RTW_RK
+}
+
+ViewKernel view_kernel(int rng_kind, int feat) {
+#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_view, RTW_RNG_TEA_LCG) : RTW_RK(k_view, RTW_RNG_PHILOX);
 #undef RTW_RK
 }
 
@@ -2038,9 +2054,10 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
 // n rays (or probes) at d_rays (device) -> their means at d_out, issued on stream s of device context d and not waited for: one
 // k_radiance (k_probe) launch per ray range (rtw_radiance_plan.h: all the rays unless the unit-sum slab would pass its cap), ray i on
 // the stream of key_offset + i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s. A result is `stride` float4
-// (query_stride: nine for rtw_probe_sh, whose slab and ranges are the plan's 144-byte variants).
+// (query_stride: nine for rtw_probe_sh, whose slab and ranges are the plan's 144-byte variants). kQueryViews: d_rays holds the view
+// records of the whole call and ray i is flattened pixel vf->first + i (k_view; keys and seeds come from the pixel, not from here).
 int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_rays, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
-                   float4* d_out, hipStream_t s, int query) {
+                   float4* d_out, hipStream_t s, int query, const ViewFrame* vf = nullptr) {
     if (query == RTW_PROBE_OCCLUSION) return occlusion_issue(c, d, tune, d_rays, n, RP, key_offset, d_out, s);
     uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
     const bool sh = query == kQueryProbeSh;
@@ -2063,10 +2080,12 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
     DScene sc = d->sc;
     apply_estimator(sc, RP->estimator);
     const bool probe = query == RTW_PROBE_IRRADIANCE;
+    const bool views = query == kQueryViews;
     const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe, sh);
+    const ViewKernel kv = view_kernel(RP->rng_kind, sc.has_tex);
     const RadianceResolve resolve = sh ? k_probe_sh_resolve : probe ? k_probe_resolve : k_radiance_resolve;
     const size_t lds = d->info.lds_bytes;
-    const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, 0);
+    const size_t per_cu = (size_t)path_wg_per_cu(views ? (const void*)kv : (const void*)k, lds, 0);
     const uint32_t units = radiance_units(RP->spp);
     const uint64_t per = sh ? probe_sh_range_points(n, RP->spp, tune.radiance_slab_bytes) : radiance_range_rays(n, RP->spp, tune.radiance_slab_bytes);
     if (units > 1) {
@@ -2076,7 +2095,7 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
     for (uint64_t r = 0, nr = radiance_n_ranges(n, per); r < nr; r++) {
         const RadianceRange rg = radiance_range(n, per, r);
         RadianceArgs a{};
-        a.rays = (const float4*)d_rays + 2 * rg.first;
+        a.rays = views ? (const float4*)d_rays : (const float4*)d_rays + 2 * rg.first;
         a.out = units > 1 ? (float4*)d->rad_slab : d_out + rg.first * stride;
         a.queue = queue;
         a.stats = d->rad_ctl;
@@ -2088,7 +2107,19 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         a.spp = (uint32_t)RP->spp; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
         a.key0 = radiance_key(key_offset, rg.first);
         HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+        if (views) {
+            ViewArgs va{};
+            va.rays = a.rays; va.out = a.out; va.queue = a.queue; va.stats = a.stats;
+            va.n = a.n; va.units_per_ray = a.units_per_ray; va.n_units = a.n_units; va.job_units = a.job_units; va.n_jobs = a.n_jobs;
+            va.divn_m = a.divn_m; va.divn_s1 = a.divn_s1; va.divn_s2 = a.divn_s2;
+            va.spp = a.spp; va.sample0 = a.sample0; va.max_depth = a.max_depth;
+            va.width = (uint32_t)vf->width; va.height = (uint32_t)vf->height; va.first = (uint32_t)(vf->first + rg.first);
+            magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
+            magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
+            hipLaunchKernelGGL(kv, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, va);
+        } else {
+            hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+        }
         HIP_TRY(c, hipGetLastError());
         if (units > 1) {
             hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count * stride)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first * stride, a.n, units,
@@ -2227,6 +2258,94 @@ int impl_sh_probe(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_
     return query_host(c, "rtw_probe_sh", points, n, RP, sh_out, stats, kQueryProbeSh);
 }
 
+// ---- rtw_views / rtw_views_device (rtw.h): a radiance query whose rays are the pixels of the call's frames
+static_assert(sizeof(rtw_view) == 112 && sizeof(rtw_view_params) == 32, "rtw.h states these sizes");
+
+int views_check(rtw_ctx* c, const char* what, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const void* out, rtw_radiance_params& rp) {
+    if (!c->has_scene) return fail(c, RTW_ERR_NO_SCENE, std::string(what) + " before rtw_upload_scene");
+    if (!VP) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null params");
+    if (VP->width <= 0 || VP->height <= 0) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad width or height");
+    rp = rtw_radiance_params{VP->spp, VP->max_depth, 0u, VP->rng_kind, VP->sample_offset, VP->estimator, 0u, VP->reserved};
+    const int rc = radiance_check(c, what, nullptr, 0, &rp, nullptr);  // the sampling fields; the count and the pointers are checked here
+    if (rc) return rc;
+    if (!view_pixels_ok(n_views, VP->width, VP->height)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": more than 2^31 - 1 pixels");
+    if (n_views > 0 && (!views || !out)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null views or output");
+    return RTW_OK;
+}
+
+int impl_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    int rc = views_check(c, "rtw_views_device", d_views, n_views, VP, d_rgba, rp);
+    if (rc) return rc;
+    if (n_views > 0 && (((uintptr_t)d_views & 15) || ((uintptr_t)d_rgba & 15)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_device: views and the output must be 16-byte aligned");
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    const ViewFrame vf{VP->width, VP->height, 0};
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    if ((rc = radiance_issue(c, d, read_tuning(), (const float*)d_views, n, &rp, 0u, (float4*)d_rgba, s, kQueryViews, &vf)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
+}
+
+int impl_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, float* rgba_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    int rc = views_check(c, "rtw_views", views, n_views, VP, rgba_out, rp);
+    if (rc) return rc;
+    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
+        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views: view " + std::to_string(v) + ": bad camera_type");
+        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views: view " + std::to_string(v) + ": reserved must be 0");
+    }
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const Tuning tune = read_tuning();
+    const size_t chunk = std::min(n, tune.radiance_chunk);
+    if (n_views * sizeof(rtw_view) > d->view_bytes) {
+        if (d->view_buf) (void)hipFree(d->view_buf);
+        d->view_buf = nullptr; d->view_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
+        d->view_bytes = n_views * sizeof(rtw_view);
+    }
+    if (chunk * 16 > d->rad_stage_bytes) {  // rtw_radiance's staging slab, here a chunk's results alone
+        if (d->rad_stage) (void)hipFree(d->rad_stage);
+        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, chunk * 16));
+        d->rad_stage_bytes = chunk * 16;
+    }
+    float4* const st_out = (float4*)d->rad_stage;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
+        const size_t m = std::min(chunk, n - i0);
+        const ViewFrame vf{VP->width, VP->height, (uint64_t)i0};
+        if ((rc = radiance_issue(c, d, tune, (const float*)d->view_buf, m, &rp, 0u, st_out, d->stream, kQueryViews, &vf)) != RTW_OK) return rc;
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
+    }
+    return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -2317,6 +2436,12 @@ int rtw_probe_sh(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_p
 }
 int rtw_probe_sh_device(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, void* d_sh, void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_sh_probe_device(c, points, n, RP, d_sh, hip_stream, stats); });
+}
+int rtw_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, float* rgba_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_views(c, views, n_views, VP, rgba_out, stats); });
+}
+int rtw_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_views_device(c, d_views, n_views, VP, d_rgba, hip_stream, stats); });
 }
 
 }  // extern "C"

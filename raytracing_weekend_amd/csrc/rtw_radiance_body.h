@@ -8,6 +8,10 @@
 // A third value of the macro's argument, 2, makes k_probe_sh's body (rtw_probe_sh.hip): the first direction is uniform over the sphere
 // and every sample adds Y_j(d) * L to nine coefficients. Every statement of that kernel alone stands under a compile-time
 // (int)(PROBE_) == 2, so the two older kernels' generated code does not move.
+// A fourth value, 3, makes k_view's body (rtw_view.hip): the lane's "ray" is a pixel of the flattened (view, y, x) index and the
+// regeneration step is raygen<>'s camera, read from the pixel's view record. The stream key is the pixel's own (width * y + x) and
+// the seed the view's; both are taken from the pixel index again in every iteration and nothing of the camera lives across the
+// segment loop. Every statement of that kernel alone stands under a compile-time (int)(PROBE_) == 3.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +21,7 @@
 #include "rtw_radiance.h"
 #include "rtw_probe.h"
 #include "rtw_probe_sh.h"
+#include "rtw_view.h"
 
 namespace rtwk {
 
@@ -87,6 +92,92 @@ RTW_DEV void probe_sh_basis(const v3 d, float* Y) {
     Y[8] = 0.546274215f * ((x * x) - (y * y));
 }
 
+// k_view (rtw.h rtw_views): pixel `ray` of a launch is pixel a.first + ray of the call's flattened index
+// (view * height + y) * width + x. The stream key of a pixel is width * y + x, its index inside its frame.
+RTW_DEV void view_split(const ViewArgs& a, const uint32_t ray, uint32_t& view, uint32_t& key) {
+    const uint32_t p = a.first + ray;
+    view = fastdiv(p, a.divf_m, a.divf_s1, a.divf_s2);
+    key = p - view * (a.width * a.height);
+}
+RTW_DEV uint32_t view_key(const ViewArgs& a, const uint32_t ray) {
+    uint32_t view, key;
+    view_split(a, ray, view, key);
+    return key;
+}
+RTW_DEV uint32_t view_seed(const ViewArgs& a, const uint32_t ray) {
+    uint32_t view, key;
+    view_split(a, ray, view, key);
+    return ((const uint32_t*)a.rays)[(size_t)view * (kViewFloat4 * 4u) + kViewSeedWord];
+}
+
+// raygen<>'s camera path of sample `sample` of pixel `ray` (rtw_kernels.h), statement for statement, with the camera, its type and
+// its times read from the pixel's view record instead of the scene: the draws (the TEA+LCG stream takes its lens sample for a
+// perspective camera only; a type that is neither environment nor orthographic is a perspective camera), the generator left where
+// raygen<> leaves it, the gather time from the view's own time0 / time1, the first ray time, origin and direction
+template <int KIND>
+RTW_DEV void view_raygen(const DScene& sc, const ViewArgs& a, const uint32_t ray, const uint32_t seed, const uint32_t sample, Rng<KIND>& g, float& gt,
+                         float& ray_time, v3& o, v3& d) {
+    uint32_t view, pixel;
+    view_split(a, ray, view, pixel);
+    const uint32_t y = fastdiv(pixel, a.divw_m, a.divw_s1, a.divw_s2);
+    const uint32_t x = pixel - y * a.width;
+    const float4* const rec = a.rays + (size_t)view * kViewFloat4;  // seven 16-byte loads
+    const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6];
+    const v3 c_origin = V(q0.x, q0.y, q0.z), c_u = V(q0.w, q1.x, q1.y), c_v = V(q1.z, q1.w, q2.x), c_w = V(q2.y, q2.z, q2.w);
+    const v3 c_ll = V(q3.x, q3.y, q3.z), c_h = V(q3.w, q4.x, q4.y), c_vert = V(q4.z, q4.w, q5.x);
+    const float lens_radius = q5.y, time0 = q5.z, time1 = q5.w;
+    const int cam_type = (int)__float_as_uint(q6.x);
+    const bool perspective = cam_type != RTW_CAM_ENVIRONMENT && cam_type != RTW_CAM_ORTHOGRAPHIC;
+    float r0, r1, r2, r3, r4;
+    if (KIND == RTW_RNG_TEA_LCG) {
+        uint32_t s = tea<64>(pixel, sample);
+        r0 = lcg_rnd(s); r1 = lcg_rnd(s);
+        r2 = 0.0f; r3 = 0.0f;
+        if (perspective) { r2 = lcg_rnd(s); r3 = lcg_rnd(s); }
+        g.init(seed, pixel, sample, s, s);
+        r4 = lcg_rnd(s);
+    } else {
+        uint32_t w[4];
+        philox4x32_10(pixel, sample, 0u, 0u, seed, 0u, w);
+        r0 = u24(w[0]); r1 = u24(w[1]); r2 = u24(w[2]); r3 = u24(w[3]);
+        r4 = (float)(((w[0] & 0xffu) << 16) | ((w[1] & 0xffu) << 8) | (w[2] & 0xffu)) * (1.0f / 16777216.0f);
+        g.init(seed, pixel, sample, 0u, sample);
+    }
+    const float s = ((float)x + r0) / (float)a.width;
+    const float t = ((float)y + r1) / (float)a.height;
+    o = c_origin;
+    if (lens_radius != 0.0f) {
+        float sn, cs;
+        sincos2pi(r2, sn, cs);
+        float sq = __builtin_sqrtf(r3);
+        float rx = lens_radius * (sn * sq);
+        float ry = lens_radius * (cs * sq);
+        o = vadd(o, vfma(c_v, ry, vscale(c_u, rx)));
+    }
+    d = vfma(c_h, s, c_ll);
+    d = vfma(c_vert, t, d);
+    if (cam_type == RTW_CAM_ENVIRONMENT) {
+        float sx, cx, sy, cy;
+        sincos2pi(s, sx, cx);
+        sincos2pi(t * 0.5f, sy, cy);
+        const v3 e = V(cx * sy, -cy, sx * sy);
+        o = c_origin;
+        d = normalize3(vfma(c_w, e.z, vfma(c_v, e.y, vscale(c_u, e.x))));
+    } else if (cam_type == RTW_CAM_ORTHOGRAPHIC) {
+        o = vadd(d, c_origin);
+        d = vneg(normalize3(c_w));
+    } else {
+        d = vsub(d, o);
+    }
+    gt = fma_(r4, time1 - time0, time0);  // (r4 = k / 2^24: gather_time_of's value for gk = k)
+    ray_time = (KIND == RTW_RNG_TEA_LCG || sc.has_motion) ? g.ray_time(0u) : 0.0f;
+}
+// the three names for the launches of the older kernels, whose body names them under a condition that is never true there
+RTW_DEV uint32_t view_key(const RadianceArgs&, const uint32_t) { return 0u; }
+RTW_DEV uint32_t view_seed(const RadianceArgs&, const uint32_t) { return 0u; }
+template <int KIND>
+RTW_DEV void view_raygen(const DScene&, const RadianceArgs&, const uint32_t, const uint32_t, const uint32_t, Rng<KIND>&, float&, float&, v3&, v3&) {}
+
 // k_probe_sh's per-lane LDS rows (stride kBlock): the 27 sums of the open block of 16 samples, coefficient-major, then the first
 // direction of the lane's current path. Both are touched once per path (a path is hundreds of instructions) and would otherwise
 // have to live in VGPRs across the segment loop, which is full at 128. The unit sums - touched once per 16 paths - run in the words
@@ -151,31 +242,39 @@ constexpr uint32_t kShSums = 27, kShRows = kShSums + 3;
         } \
         if (__ballot(!need) == 0ull) break; \
         const bool busy = !need; \
-        const uint32_t key = a.key0 + ray, sample = a.sample0 + s_cur; \
+        const uint32_t key = (int)(PROBE_) == 3 ? view_key(a, ray) : a.key0 + ray, sample = a.sample0 + s_cur; \
+        const uint32_t seed = (int)(PROBE_) == 3 ? view_seed(a, ray) : a.seed; \
         Rng<KIND> g; \
-        if (busy && !alive) {  /* regeneration: the next sample of this lane's unit starts on the caller's ray, or at the caller's probe */ \
+        if ((int)(PROBE_) == 3 && busy && !alive) {  /* regeneration: the next sample of this lane's pixel starts at its view's camera */ \
+            view_raygen<KIND>(sc, a, ray, seed, sample, g, gt, ray_time, o, d); \
+            seg_tmin = sc.ray_tmin; seg_tmax = 1.e27f;  /* the estimator's start distance, as a render's camera ray */ \
+            rng_a = g.a; rng_b = g.b; \
+            T = V(1.f, 1.f, 1.f); L = V(0.f, 0.f, 0.f); \
+            nee_prev = 0; depth = 0; alive = true; \
+        } \
+        if ((int)(PROBE_) != 3 && busy && !alive) {  /* regeneration: the next sample of this lane's unit starts on the caller's ray, or at the caller's probe */ \
             const float4 r0 = a.rays[2 * (size_t)ray], r1 = a.rays[2 * (size_t)ray + 1];  /* two 16-byte loads */ \
             o = V(r0.x, r0.y, r0.z); d = V(r0.w, r1.x, r1.y); \
             seg_tmin = r1.z; seg_tmax = r1.w;  /* the caller's interval bounds the first segment only */ \
             if ((int)(PROBE_) == 2) { \
                 /* floats 3..5 are loaded and unused; the direction waits in LDS for the path's end, where the basis is taken */ \
                 float jitter[2]; \
-                radiance_raygen<KIND, true>(sc, a.seed, key, sample, g, gt, ray_time, jitter); \
+                radiance_raygen<KIND, true>(sc, seed, key, sample, g, gt, ray_time, jitter); \
                 d = probe_sh_direction(jitter[0], jitter[1]); \
                 s_sh[kShSums][tid] = d.x; s_sh[kShSums + 1][tid] = d.y; s_sh[kShSums + 2][tid] = d.z; \
             } else if (PROBE_) { \
                 /* a probe keeps nothing between its samples: the basis is rebuilt from the normal that the two loads above bring anyway */ \
                 float jitter[2]; \
-                radiance_raygen<KIND, true>(sc, a.seed, key, sample, g, gt, ray_time, jitter); \
+                radiance_raygen<KIND, true>(sc, seed, key, sample, g, gt, ray_time, jitter); \
                 d = probe_direction(d, jitter[0], jitter[1]); \
             } else { \
-                radiance_raygen<KIND, false>(sc, a.seed, key, sample, g, gt, ray_time, nullptr); \
+                radiance_raygen<KIND, false>(sc, seed, key, sample, g, gt, ray_time, nullptr); \
             } \
             rng_a = g.a; rng_b = g.b; \
             T = V(1.f, 1.f, 1.f); L = V(0.f, 0.f, 0.f); \
             nee_prev = 0; depth = 0; alive = true; \
         } \
-        if (busy) g.init(a.seed, key, sample, rng_a, KIND == RTW_RNG_TEA_LCG ? rng_b : sample); \
+        if (busy) g.init(seed, key, sample, rng_a, KIND == RTW_RNG_TEA_LCG ? rng_b : sample); \
         if (busy) { \
             float th; \
             int prim; \
@@ -241,7 +340,7 @@ constexpr uint32_t kShSums = 27, kShRows = kShSums + 3;
                         if (a.units_per_ray == 1u) {  /* at most 128 spp: the unit sum is the total, the lane writes the mean */ \
                             const v3 sum = vadd(V(0.f, 0.f, 0.f), u); \
                             const float nf = (float)a.spp; \
-                            if (PROBE_) a.out[ray] = make_float4((sum.x / nf) * kProbePi, (sum.y / nf) * kProbePi, (sum.z / nf) * kProbePi, 1.0f); \
+                            if ((int)(PROBE_) == 1) a.out[ray] = make_float4((sum.x / nf) * kProbePi, (sum.y / nf) * kProbePi, (sum.z / nf) * kProbePi, 1.0f); \
                             else a.out[ray] = make_float4(sum.x / nf, sum.y / nf, sum.z / nf, 1.0f); \
                         } else { \
                             a.out[(size_t)(b_done / kSumUnitBlocks) * a.n + ray] = make_float4(u.x, u.y, u.z, 0.f); \

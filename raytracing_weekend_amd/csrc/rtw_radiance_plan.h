@@ -49,6 +49,24 @@ inline uint64_t probe_sh_range_points(uint64_t n, int32_t spp, uint64_t cap_byte
     return std::min<uint64_t>(std::max<uint64_t>(points, 1), std::max<uint64_t>(n, 1));
 }
 
+// rtw_views numbers the pixels of a call (view * height + y) * width + x and runs them as a radiance query's rays: the same units,
+// slab, ranges and jobs over n = n_views * width * height, which has to stay a launch's ray count. The product is taken in 64 bits
+// and by division, so that no n_views, however large, wraps it (width, height > 0).
+inline bool view_pixels_ok(uint64_t n_views, int32_t width, int32_t height) {
+    const uint64_t frame = (uint64_t)(uint32_t)width * (uint64_t)(uint32_t)height;
+    return n_views == 0 || (frame <= kRadianceMaxLaunchUnits && n_views <= kRadianceMaxLaunchUnits / frame);
+}
+inline uint64_t view_pixels(uint64_t n_views, int32_t width, int32_t height) { return n_views * (uint64_t)(uint32_t)width * (uint64_t)(uint32_t)height; }
+// pixel p of the flattened index: its view, row and column, and its stream key width * y + x (what the kernel computes with
+// magic_div's constants for width and width * height)
+struct ViewPixel { uint64_t view; uint32_t y, x, key; };
+inline ViewPixel view_pixel(uint64_t p, int32_t width, int32_t height) {
+    const uint64_t frame = (uint64_t)(uint32_t)width * (uint64_t)(uint32_t)height;
+    const uint64_t view = p / frame;
+    const uint32_t key = (uint32_t)(p - view * frame);
+    return ViewPixel{view, key / (uint32_t)width, key % (uint32_t)width, key};
+}
+
 // range r of the cut of [0, n) into ranges of `per` rays: [first, first + count); count = 0 past the end
 struct RadianceRange { uint64_t first, count; };
 inline uint64_t radiance_n_ranges(uint64_t n, uint64_t per) { return (n + per - 1) / per; }

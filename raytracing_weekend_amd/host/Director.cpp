@@ -3,6 +3,7 @@
 //   Director::createScene   Director.cpp:951-969  -> ioScene::init + marshalScene + rtw_upload_scene
 //   Director::renderFrame   Director.cpp:971-1008 -> rtw_render (optixLaunch + D2H copy; no AI denoiser), or an accumulation
 //                                                    session (rtw_accum_*: what the accum_buffer left commented out at :485-488 was for)
+//   Director::renderOrbit   (no counterpart)      -> rtw_views: n frames of a turntable in one call
 //   Director::printPPM      Director.cpp:1010-1031
 //   Director::destroy       Director.cpp:66-104   -> rtw_destroy
 #include "Director.h"
@@ -10,6 +11,7 @@
 #include <cmath>
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <iterator>
@@ -54,6 +56,12 @@ void Director::createScene(unsigned int sceneNumber) {
 
 void Director::marshalAndUpload() {
     std::vector<uint8_t> blob = rtwhost::marshalScene(m_scene);
+    if (blob.size() >= sizeof(rtw_scene_header)) {
+        rtw_scene_header h;
+        std::memcpy(&h, blob.data(), sizeof h);
+        m_camera = h.camera;
+        m_blobCameraType = h.camera_type;
+    }
     int rc = rtw_upload_scene(m_ctx, blob.data(), blob.size());
     if (rc != RTW_OK) die(m_ctx, "rtw_upload_scene", rc);
 }
@@ -139,6 +147,72 @@ void Director::renderFrame() {
         std::cerr << "INFO: " << m_stats.samples << " samples, " << m_stats.segments << " segments, " << m_stats.shadow_rays
                   << " shadow rays in " << m_stats.seconds << " s on the GPU = " << m_stats.samples / s / 1e6 << " Msamples/s, "
                   << m_stats.algorithmic_bytes / s / 1e9 << " GB/s algorithmic" << std::endl;
+    }
+}
+
+// bake.orbit_views in C++: the same operations in the same order in double precision, rounded to float once, so that the views -
+// and with them the frames - are the ones Python makes
+void Director::orbitViews(const rtw_camera& camera, int cameraType, uint32_t seed, int n, std::vector<rtw_view>& out) {
+    typedef double V3[3];
+    auto view = [&](const rtw_camera& c) {
+        rtw_view v{};
+        v.camera = c;
+        v.camera_type = cameraType;
+        v.seed = seed;
+        return v;
+    };
+    out.assign(1, view(camera));  // view 0: the camera itself, copied
+    const float* fields[7] = {camera.origin, camera.u, camera.v, camera.w, camera.lower_left, camera.horizontal, camera.vertical};
+    V3 c[7], pivot, axis;
+    for (int f = 0; f < 7; f++)
+        for (int i = 0; i < 3; i++) c[f][i] = static_cast<double>(fields[f][i]);
+    for (int i = 0; i < 3; i++) pivot[i] = (c[4][i] + c[5][i] / 2.0) + c[6][i] / 2.0;
+    const double norm = std::sqrt((c[2][0] * c[2][0] + c[2][1] * c[2][1]) + c[2][2] * c[2][2]);
+    for (int i = 0; i < 3; i++) axis[i] = c[2][i] / norm;
+    for (int k = 1; k < n; k++) {
+        const double ang = (2.0 * M_PI * static_cast<double>(k)) / static_cast<double>(n);
+        const double cs = std::cos(ang), sn = std::sin(ang), omc = 1.0 - cs;
+        auto rot = [&](const V3 x, V3 r) {
+            const V3 cr = {axis[1] * x[2] - axis[2] * x[1], axis[2] * x[0] - axis[0] * x[2], axis[0] * x[1] - axis[1] * x[0]};
+            const double d = (axis[0] * x[0] + axis[1] * x[1]) + axis[2] * x[2];
+            for (int i = 0; i < 3; i++) r[i] = (x[i] * cs + cr[i] * sn) + axis[i] * (d * omc);
+        };
+        rtw_camera t = camera;
+        float* dst[7] = {t.origin, t.u, t.v, t.w, t.lower_left, t.horizontal, t.vertical};
+        for (int f = 0; f < 7; f++) {
+            const bool point = f == 0 || f == 4;  // points turn about the pivot, vectors about the origin
+            V3 x, r;
+            for (int i = 0; i < 3; i++) x[i] = point ? c[f][i] - pivot[i] : c[f][i];
+            rot(x, r);
+            for (int i = 0; i < 3; i++) dst[f][i] = static_cast<float>(point ? pivot[i] + r[i] : r[i]);
+        }
+        out.push_back(view(t));
+    }
+}
+
+void Director::renderOrbit(int n, const std::function<void(int)>& onFrame) {
+    std::vector<rtw_view> views;
+    orbitViews(m_camera, m_blobCameraType, m_seed, n, views);
+    rtw_view_params vp{};
+    vp.width = m_Nx;
+    vp.height = m_Ny;
+    vp.spp = m_Ns;
+    vp.max_depth = m_maxRayDepth;
+    vp.rng_kind = m_rngKind;
+    vp.estimator = m_estimator;
+    const size_t frame = static_cast<size_t>(m_Nx) * m_Ny * 4;
+    std::vector<float> frames(frame * views.size());
+    const int rc = rtw_views(m_ctx, views.data(), views.size(), &vp, frames.data(), &m_stats);
+    if (rc != RTW_OK) die(m_ctx, "rtw_views", rc);
+    if (_verbose) {
+        const double s = m_stats.seconds > 0 ? m_stats.seconds : 1e-9;
+        std::cerr << "INFO: orbit: " << views.size() << " views, " << m_stats.samples << " samples, " << m_stats.segments << " segments, "
+                  << m_stats.shadow_rays << " shadow rays in " << m_stats.seconds << " s on the GPU = " << m_stats.samples / s / 1e6 << " Msamples/s"
+                  << std::endl;
+    }
+    for (size_t k = 0; k < views.size(); k++) {
+        m_hostBuffer.assign(frames.begin() + static_cast<std::ptrdiff_t>(k * frame), frames.begin() + static_cast<std::ptrdiff_t>((k + 1) * frame));
+        onFrame(static_cast<int>(k));
     }
 }
 

@@ -25,6 +25,11 @@ public:
 
     void createScene(unsigned int sceneNumber);
     void renderFrame();
+    // a turntable through rtw_views, one call for all n frames: view 0 is the scene's camera, view k that camera turned rigidly by
+    // 360 k / n degrees about its v axis through the centre of its frame (raytracing_weekend_amd.bake.orbit_views, operation for
+    // operation in double precision); every view renders with the seed. onFrame(k) is called with frame k in hostBuffer(), in order.
+    void renderOrbit(int n, const std::function<void(int)>& onFrame);
+    static void orbitViews(const rtw_camera& camera, int cameraType, uint32_t seed, int n, std::vector<rtw_view>& out);
     void printPPM();
     // additions: an 8K frame is ~400 MB as ASCII P3; P6 is 100 MB, PFM keeps the linear floats
     bool writeBinaryPPM(const std::string& path) const;  // P6, same sqrt + 255.99 quantisation as printPPM
@@ -89,6 +94,8 @@ private:
     int m_progStep = 0;
     std::function<void(int)> m_onFrame;
     std::string m_checkpoint, m_resume;
+    rtw_camera m_camera{};  // the uploaded blob's camera and its kind (renderOrbit turns it)
+    int m_blobCameraType = RTW_CAM_PERSPECTIVE;
     rtw_ctx* m_ctx = nullptr;
     rtwhost::ioScene m_scene;
     std::vector<float> m_hostBuffer;

@@ -3,9 +3,11 @@
 // plus what the benchmark configurations need and the reference hard-wires:
 //   -d depth (reference: 20, Director.cpp:42)   -seed N   -rng philox|lcg   -gpu id   -gpus N   -o file.ppm|file.png|file.pfm
 //   -progressive N   -checkpoint file   -resume file   (accumulation sessions: previews, checkpoints, resumed renders)
+//   -orbit N   (a turntable of N views through rtw_views, one file per view)
 // The reference's resolution / sample clamps (main.cpp:21-27) are widened so that 200x200 and
 // 7680x4320 are reachable, and its scene range bug (only scene 4 selectable, main.cpp:69) is not kept.
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <stdexcept>
@@ -75,6 +77,10 @@ int main(int argc, char* argv[]) {
     -checkpoint F  Write the accumulation session's state to F when the render ends (-ns a multiple of 16)
     -resume F      Start from the state in F instead of from zero: -ns is the new total (at least what F holds); scene, size
                    and parameters must be those F was rendered with
+    -orbit N       Render a turntable of N views in one call (rtw_views): view 0 is the scene's camera, view k that camera turned by
+                   360 k / N degrees about its vertical axis through the centre of its frame. Needs -o NAME.ext and writes
+                   NAME_000.ext, NAME_001.ext, ... with the writer of that extension; -seed applies to every view. It does not
+                   combine with -denoise, -aov, -adaptive, -progressive, -checkpoint or -resume
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -149,7 +155,7 @@ int main(int argc, char* argv[]) {
         director.setAdaptive(thr, minSpp, step);
     }
 
-    const std::string& outPath = cl_input.getCmdOption("-o");
+    std::string outPath = cl_input.getCmdOption("-o");
     auto writeOutput = [&]() {
         auto ends = [&](const char* ext) { return outPath.size() > 4 && outPath.compare(outPath.size() - 4, 4, ext) == 0; };
         return ends(".pfm") ? director.writePFM(outPath) : ends(".png") ? director.writePNG(outPath) : director.writeBinaryPPM(outPath);
@@ -175,6 +181,17 @@ int main(int argc, char* argv[]) {
         director.setResume(f);
     }
 
+    int orbit = 0;
+    if (cl_input.cmdOptionExists("-orbit")) {
+        if (!intOption(cl_input, "-orbit", "number of views (-orbit)", orbit) || orbit <= 0) {
+            std::cerr << "ERROR: -orbit needs a number of views (a positive integer)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (outPath.empty()) { std::cerr << "ERROR: -orbit needs -o NAME.ext (it writes NAME_000.ext ...)" << std::endl; return EXIT_FAILURE; }
+        for (const char* flag : {"-denoise", "-aov", "-guided", "-adaptive", "-progressive", "-checkpoint", "-resume"})
+            if (cl_input.cmdOptionExists(flag)) { std::cerr << "ERROR: -orbit does not combine with " << flag << std::endl; return EXIT_FAILURE; }
+    }
+
     auto start = std::chrono::system_clock::now();
     director.init(Nx, Ny, Ns);
     if (Qverbose) {
@@ -183,6 +200,23 @@ int main(int argc, char* argv[]) {
         std::cerr << "INFO: Scene number selected: " << Nscene << std::endl;
     }
     director.createScene(Nscene);
+    if (orbit > 0) {
+        const size_t dot = outPath.find_last_of('.');
+        const std::string stem = dot == std::string::npos ? outPath : outPath.substr(0, dot), ext = dot == std::string::npos ? "" : outPath.substr(dot);
+        const std::string whole = outPath;
+        bool ok = true;
+        director.renderOrbit(orbit, [&](int k) {
+            char idx[16];
+            std::snprintf(idx, sizeof idx, "_%03d", k);
+            outPath = stem + idx + ext;  // (writeOutput picks the writer by the name's extension)
+            if (!writeOutput()) { std::cerr << "ERROR: cannot write " << outPath << std::endl; ok = false; }
+        });
+        outPath = whole;
+        auto stop = std::chrono::system_clock::now();
+        std::cerr << "INFO: Took " << std::chrono::duration<float>(stop - start).count() << " seconds." << std::endl;
+        director.destroy();
+        return ok ? EXIT_SUCCESS : EXIT_FAILURE;
+    }
     director.renderFrame();
     auto stop = std::chrono::system_clock::now();
     std::cerr << "INFO: Took " << std::chrono::duration<float>(stop - start).count() << " seconds." << std::endl;

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """ISA line and scratch-instruction counts of the radiance and probe kernels, from `hipcc -S` with the build's flags (no GPU needed).
 
-usage: scripts/probe_isa.py [unit.hip ...]      default: rtw_radiance.hip rtw_probe.hip rtw_probe_sh.hip of raytracing_weekend_amd/csrc
+usage: scripts/probe_isa.py [unit.hip ...]      default: rtw_radiance.hip rtw_probe.hip rtw_probe_sh.hip rtw_view.hip of raytracing_weekend_amd/csrc
 Prints one line per kernel: ISA lines (instructions: lines that are neither labels, directives nor comments), scratch_ instructions,
 and the VGPR / scratch / static LDS figures of the kernel's .amdhsa block. profiles/probe_rates.txt keeps the output of the parent's
-rtw_radiance.hip beside this tree's, profiles/probe_sh_rates.txt the seven older kernels' beside k_probe_sh's."""
+rtw_radiance.hip beside this tree's, profiles/probe_sh_rates.txt the seven older kernels' beside k_probe_sh's, profiles/view_rates.txt
+the thirteen older instantiations of the shared body in the parent and in this tree, beside k_view's. A unit given by path is compiled
+where it lies, so a parent checkout's units are listed by naming them."""
 import os
 import re
 import subprocess
@@ -38,7 +40,7 @@ def counts(unit):
 
 
 if __name__ == "__main__":
-    units = sys.argv[1:] or [os.path.join(entry.CSRC, u) for u in ("rtw_radiance.hip", "rtw_probe.hip", "rtw_probe_sh.hip")]
+    units = sys.argv[1:] or [os.path.join(entry.CSRC, u) for u in ("rtw_radiance.hip", "rtw_probe.hip", "rtw_probe_sh.hip", "rtw_view.hip")]
     for u in units:
         print(f"# {os.path.basename(u)}")
         for name, n, scratch, vgpr, priv, lds in counts(u):

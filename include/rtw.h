@@ -601,6 +601,45 @@ int rtw_probe(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_param
 int rtw_probe_device(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_params* params, void* d_rgba, void* hip_stream,
                      rtw_stats* stats);
 
+/* Probes sampled to a noise target: rtw_probe with rtw_render_adaptive's stop rule. Every probe takes samples until its own error
+ * estimate falls below a threshold, or up to a cap - a lightmap whose open texels stop after a few dozen samples while its penumbrae
+ * go on to the cap.
+ *   Inputs: the probes, the keys (key_offset + i mod 2^32), the sample indices (sample_offset + s) and the directions are rtw_probe's;
+ *     both modes are supported. params->spp is the cap. `ad` is rtw_render_adaptive's rtw_adaptive; dilate must be 0 (a probe batch
+ *     has no neighbourhood).
+ *   Checkpoints: rtw_render_adaptive's sequence, a function of (min_spp, step_spp, params->spp) alone.
+ *   Result: probe i takes samples [sample_offset, sample_offset + n_i), n_i a checkpoint; a probe that stopped never resumes.
+ *     rgba_out[i] is, bit for bit, rtw_probe's result for that probe with spp = n_i and everything else equal - irradiance:
+ *     (sum / (float)n_i) * 3.14159265f, alpha 1.0f, the sum in the order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from
+ *     sample_offset; occlusion: (float)unoccluded / (float)n_i, alpha 1.0f. spp_out[i] = n_i. spp_out (n int32) and error_out
+ *     (n float) may be NULL; rgba_out (n float4) is required.
+ *   Error estimate: rtw_render_adaptive's statistic, formula and fp64 order. Irradiance: over the probe's radiance block sums S_b
+ *     (the sums before the division and the factor pi). Occlusion: y_b = (float)c_b * 0.0625f, c_b the unoccluded count of block b;
+ *     the rest of the formula is the same. error_out[i] is err at the probe's last checkpoint.
+ *   Stop rule: at checkpoint n_k an active probe stops if n_k is the cap, or if its own err < threshold (strict; a NaN err compares
+ *     false: that probe goes on).
+ *   Independence: the three outputs of probe i depend on its probe, its key and the params alone: not on n, the launch geometry,
+ *     chunks, slab ranges or tuning knobs.
+ *   rtw_probe_adaptive: host pointers, staged through rtw_radiance's slab in chunks of at most RTW_RADIANCE_CHUNK probes; chunk c
+ *     runs with the key of its first probe.
+ *   rtw_probe_adaptive_device: device pointers on the context's device; probes and rgba 16-byte aligned, spp and error 4-byte
+ *     aligned. Ordered on hip_stream exactly as rtw_probe_device is (NULL selects the context's own non-blocking stream, NOT the
+ *     legacy default stream); returns when the results are written. The per-probe state and the lists live in buffers the context
+ *     owns, grows and keeps: nothing is allocated per call once they are large enough. The block sums of a pass live in
+ *     rtw_radiance's scratch slab, capped by RTW_RADIANCE_SLAB_BYTES: a larger pass runs as consecutive ranges of the active list.
+ *     One 4-byte count is read back per checkpoint on the stream.
+ *   stats (may be NULL): samples = sum of n_i. Irradiance: segments and shadow_rays of those samples' paths; occlusion:
+ *     shadow_rays = samples, segments = 0. algorithmic_bytes and seconds as rtw_probe reports them; the per-kernel arrays are 0.
+ *   Groups (n_devices > 1): the query runs on device_ids[0]. An accumulation session on the context is not disturbed.
+ *   Errors: rtw_probe's refusals; also RTW_ERR_INVALID_ARG for a NULL ad, rtw_render_adaptive's refusals for the cap, min_spp,
+ *     step_spp and threshold, dilate != 0, a NULL rgba_out with n > 0, and (rtw_probe_adaptive_device) a misaligned pointer. A
+ *     refused call writes nothing and leaves *stats alone. n = 0 is RTW_OK and launches nothing. The context stays usable after an
+ *     error. */
+int rtw_probe_adaptive(rtw_ctx* ctx, const float* probes, size_t n, const rtw_probe_params* params, const rtw_adaptive* ad,
+                       float* rgba_out, int32_t* spp_out, float* error_out, rtw_stats* stats);
+int rtw_probe_adaptive_device(rtw_ctx* ctx, const float* d_probes, size_t n, const rtw_probe_params* params, const rtw_adaptive* ad,
+                              void* d_rgba, void* d_spp, void* d_error, void* hip_stream, rtw_stats* stats);
+
 /* Spherical-harmonic light probes at free points: the radiance arriving at a point from every direction, projected onto the nine
  * real spherical harmonics of bands 0 to 2 (an irradiance volume's probe; what lights things that move through a baked scene).
  * rtw_probe needs a normal and returns one number per channel; this needs none and returns nine coefficients per channel, which

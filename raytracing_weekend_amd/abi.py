@@ -143,7 +143,8 @@ HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render"
                "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
                "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
                "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
-               "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device"]
+               "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device",
+               "rtw_probe_adaptive", "rtw_probe_adaptive_device"]
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -236,6 +237,12 @@ def load_hip():
         lib.rtw_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_probe_device.restype = C.c_int
         lib.rtw_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_probe_adaptive.restype = C.c_int
+        lib.rtw_probe_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_probe_adaptive_device.restype = C.c_int
+        lib.rtw_probe_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.POINTER(Adaptive), C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.rtw_probe_sh.restype = C.c_int
         lib.rtw_probe_sh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_probe_sh_device.restype = C.c_int
@@ -626,6 +633,35 @@ class Renderer:
         pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
         self._check(self.lib.rtw_probe_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                               None if stats is None else C.byref(stats)), "rtw_probe_device")
+
+    # ---- probes sampled to a noise target (include/rtw.h rtw_probe_adaptive / rtw_probe_adaptive_device)
+    def probe_adaptive(self, probes, cap, max_depth, threshold, min_spp=64, step_spp=0, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0,
+                       estimator=0, key_offset=0, mode="irradiance", stats=None):
+        """rtw_probe_adaptive on (n, 8) float32 probes: every probe takes samples until its error estimate is below `threshold`, at
+        most `cap`. Returns (out, spp, err): the (n, 4) float32 results, the (n,) int32 sample counts n_i and the (n,) float32 errors
+        at each probe's last checkpoint. Row i of out is, bit for bit, row 0 of probe(probes[i:i + 1], spp[i], ..., key_offset + i)."""
+        if not isinstance(probes, np.ndarray) or probes.dtype != np.float32:
+            raise ValueError("probe_adaptive: probes must be a float32 numpy array")
+        if probes.ndim != 2 or probes.shape[1] != 8:
+            raise ValueError(f"probe_adaptive: probes of shape {probes.shape}, expected (n, 8)")
+        pp = make_probe_params(cap, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
+        ad = Adaptive(min_spp, step_spp, threshold, 0)
+        probes = np.ascontiguousarray(probes)
+        n = probes.shape[0]
+        out, spp, err = np.empty((n, 4), dtype=np.float32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        self._check(self.lib.rtw_probe_adaptive(self.ctx, probes.ctypes.data, n, C.byref(pp), C.byref(ad), out.ctypes.data, spp.ctypes.data,
+                                                err.ctypes.data, None if stats is None else C.byref(stats)), "rtw_probe_adaptive")
+        return out, spp, err
+
+    def probe_adaptive_device(self, n, probes_ptr, out_ptr, spp_ptr, err_ptr, cap, max_depth, threshold, min_spp=64, step_spp=0, seed=0x6314759,
+                              rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, mode="irradiance", stream_ptr=0, stats=None):
+        """rtw_probe_adaptive_device on raw device pointers: n probes at probes_ptr, n float4 at out_ptr (both 16-byte aligned), n int32
+        at spp_ptr and n float at err_ptr (4-byte aligned; 0: not wanted), stream_ptr a hipStream_t (0: the context's own stream)."""
+        pp = make_probe_params(cap, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
+        ad = Adaptive(min_spp, step_spp, threshold, 0)
+        self._check(self.lib.rtw_probe_adaptive_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.byref(ad), C.c_void_p(out_ptr),
+                                                       C.c_void_p(spp_ptr), C.c_void_p(err_ptr), C.c_void_p(stream_ptr),
+                                                       None if stats is None else C.byref(stats)), "rtw_probe_adaptive_device")
 
     # ---- spherical-harmonic light probes at free points (include/rtw.h rtw_probe_sh / rtw_probe_sh_device)
     def probe_sh(self, points, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, stats=None):

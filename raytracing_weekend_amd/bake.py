@@ -71,6 +71,14 @@ def bake_rect(renderer, blob, prim, nu, nv, spp, max_depth, side=1, offset=1e-3,
     return renderer.probe(rect_probes(blob, prim, nu, nv, side, offset), spp, max_depth, **kw).reshape(nv, nu, 4)
 
 
+def bake_rect_adaptive(renderer, blob, prim, nu, nv, cap, max_depth, threshold, side=1, offset=1e-3, **kw):
+    """bake_rect sampled to a noise target: Renderer.probe_adaptive on the same probes, every texel up to `cap` samples. Returns the
+    (nv, nu, 4) float32 map, the (nv, nu) int32 samples each texel took and its (nv, nu) float32 error estimate; **kw goes to
+    Renderer.probe_adaptive (min_spp, step_spp, mode, ...). The blob must be the uploaded scene."""
+    out, spp, err = renderer.probe_adaptive(rect_probes(blob, prim, nu, nv, side, offset), cap, max_depth, threshold, **kw)
+    return out.reshape(nv, nu, 4), spp.reshape(nv, nu), err.reshape(nv, nu)
+
+
 def probe_grid(lo, hi, nx, ny, nz, tmin=1e-6, tmax=1e27):
     """(nx * ny * nz, 8) float32 points for Renderer.probe_sh: a regular grid from corner `lo` to corner `hi` (both included; an axis
     with one point sits at lo), x fastest, then y, then z - point (ix, iy, iz) is row (iz * ny + iy) * nx + ix. Floats 3..5 are 0,

@@ -62,6 +62,8 @@
 #include "rtw_probe_sh.h"
 #include "rtw_view.h"
 #include "rtw_adaptive.h"
+#include "rtw_probe_adaptive.h"
+#include "rtw_probe_adaptive_plan.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
@@ -70,6 +72,7 @@
 #include "rtw_probe.hip"  // (likewise)
 #include "rtw_probe_sh.hip"  // (likewise)
 #include "rtw_view.hip"  // (likewise)
+#include "rtw_probe_adaptive.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -182,6 +185,9 @@ struct rtw_ctx {
     void* view_buf = nullptr;  // rtw_views: the call's view records
     size_t view_bytes = 0;
     unsigned long long* rad_ctl = nullptr;
+    // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept
+    void* padapt = nullptr;
+    size_t padapt_probes = 0;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
 
@@ -501,6 +507,7 @@ int impl_destroy(rtw_ctx* c) {
     if (c->cast_buf) (void)hipFree(c->cast_buf);
     if (c->rad_slab) (void)hipFree(c->rad_slab);
     if (c->rad_stage) (void)hipFree(c->rad_stage);
+    if (c->padapt) (void)hipFree(c->padapt);
     if (c->view_buf) (void)hipFree(c->view_buf);
     if (c->rad_ctl) (void)hipFree(c->rad_ctl);
     if (c->d_scene) (void)hipFree(c->d_scene);
@@ -2346,6 +2353,235 @@ int impl_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view
     return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
 }
 
+// ---- rtw_probe_adaptive / rtw_probe_adaptive_device (rtw.h): rtw_probe's samples taken from checkpoint to checkpoint over the list of
+// the probes that are still active (rtw_probe_adaptive.h; the plan is rtw_probe_adaptive_plan.h's). The moments, the decision and the
+// compaction are rtw_render_adaptive's kernels over a frame of n x 1 probes with dilate 0.
+typedef void (*ProbeListKernel)(const DScene, const ProbeListArgs);
+struct ProbeAdaptState {
+    float4 *accum, *upart;
+    double2* mom;
+    uint32_t *n, *total, *list[2], *offsets;
+    float* err;
+    unsigned long long* masks;
+};
+
+// the context's per-probe state for at least n probes: grown after the stream's pending work, kept until rtw_destroy
+int ensure_probe_adapt(rtw_ctx* c, rtw_ctx* d, size_t n, hipStream_t s, ProbeAdaptState& st) {
+    if (n > d->padapt_probes) {
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (d->padapt) (void)hipFree(d->padapt);
+        d->padapt = nullptr; d->padapt_probes = 0;
+        HIP_TRY(c, hipMalloc(&d->padapt, (size_t)probe_adaptive_layout(n).bytes()));
+        d->padapt_probes = n;
+    }
+    const ProbeAdaptiveLayout l = probe_adaptive_layout(n);  // (the layout for n fits in an allocation made for more probes)
+    char* b = (char*)d->padapt;
+    typedef ProbeAdaptiveLayout PL;
+    st.accum = (float4*)(b + l.off[PL::kAccum]); st.upart = (float4*)(b + l.off[PL::kUpart]); st.mom = (double2*)(b + l.off[PL::kMom]);
+    st.n = (uint32_t*)(b + l.off[PL::kN]); st.err = (float*)(b + l.off[PL::kErr]); st.total = (uint32_t*)(b + l.off[PL::kTotal]);
+    st.list[0] = (uint32_t*)(b + l.off[PL::kList0]); st.list[1] = (uint32_t*)(b + l.off[PL::kList1]);
+    st.masks = (unsigned long long*)(b + l.off[PL::kMasks]); st.offsets = (uint32_t*)(b + l.off[PL::kOffsets]);
+    return RTW_OK;
+}
+
+ProbeListKernel probe_list_kernel(int rng_kind, int feat) {
+#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe_list, RTW_RNG_TEA_LCG) : RTW_RK(k_probe_list, RTW_RNG_PHILOX);
+#undef RTW_RK
+}
+
+// n probes at d_probes (device) -> their results at d_out (and d_spp, d_err where not null), on stream s of device context d; probe i
+// on the stream of key_offset + i. One pass, one decision and one count read-back per checkpoint: it returns when the results are
+// written. `samples` receives the sum of the n_i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
+int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_probes, size_t n, const rtw_radiance_params* RP, int mode,
+                         const rtw_adaptive* AD, const std::vector<int>& cps, uint32_t key_offset, float4* d_out, int32_t* d_spp, float* d_err,
+                         hipStream_t s, uint64_t& samples) {
+    const bool occ = mode == RTW_PROBE_OCCLUSION;
+    ProbeAdaptState st{};
+    int rc = ensure_probe_adapt(c, d, n, s, st);
+    if (rc) return rc;
+    DScene sc = d->sc;
+    if (!occ) apply_estimator(sc, RP->estimator);
+    const ProbeListKernel k = occ ? (RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion_list<RTW_RNG_TEA_LCG> : k_probe_occlusion_list<RTW_RNG_PHILOX>)
+                                  : probe_list_kernel(RP->rng_kind, sc.has_tex);
+    const size_t lds = d->info.lds_bytes;
+    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, lds, 0);
+    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    const unsigned all_grid = pixel_grid(d, n);
+    const uint32_t n_waves = (uint32_t)((n + 63) / 64);
+    hipLaunchKernelGGL(k_probe_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.mom, st.n, st.err, st.total, (uint32_t)n);
+    HIP_TRY(c, hipGetLastError());
+    size_t n_active = n;
+    int cur = 0, n_prev = 0;
+    for (size_t kc = 0; kc < cps.size() && n_active > 0; kc++) {
+        const int n_k = cps[kc];
+        const uint32_t nb = probe_adaptive_pass_blocks(n_prev, n_k), blk0 = probe_adaptive_first_block(n_prev);
+        const uint32_t run_blocks = probe_adaptive_run_blocks(n_active, nb, max_grid * kBlock);
+        const uint32_t runs = probe_adaptive_runs(nb, run_blocks);
+        const uint64_t per = probe_adaptive_range_positions(n_active, nb, run_blocks, tune.radiance_slab_bytes);
+        if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
+        for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
+            const RadianceRange rg = radiance_range(n_active, per, r);
+            const uint32_t* const list = st.list[cur] + rg.first;  // (position i of the range is list[1 + i])
+            if (!occ && RP->max_depth == 0) {  // no segment is traced: every block sum is 0
+                HIP_TRY(c, hipMemsetAsync(d->rad_slab, 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
+            } else {
+                ProbeListArgs a{};
+                a.probes = (const float4*)d_probes;
+                a.list = list;
+                a.out = (float4*)d->rad_slab;
+                a.queue = queue;
+                a.stats = d->rad_ctl;
+                a.n = (uint32_t)rg.count; a.n_blocks = nb; a.run_blocks = run_blocks; a.n_units = (uint32_t)(rg.count * runs);
+                const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, max_grid);
+                a.job_units = probe_adaptive_job_units(run_blocks, a.n_units, grid * (kBlock / 64));
+                a.n_jobs = (uint32_t)radiance_n_jobs(a.n_units, a.job_units);
+                magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
+                a.s_from = (uint32_t)n_prev; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
+                a.key0 = key_offset;
+                if (!occ) HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
+                hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+                HIP_TRY(c, hipGetLastError());
+            }
+            if (occ)
+                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, list,
+                                   (uint32_t)rg.count, nb, st.total, st.mom);
+            else
+                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list,
+                                   (uint32_t)rg.count, nb, blk0, st.accum, st.upart, st.mom);
+            HIP_TRY(c, hipGetLastError());
+        }
+        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
+        hipLaunchKernelGGL(k_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
+                           (const uint32_t*)st.n, st.err, st.masks, (uint32_t)n, 1u, (uint32_t)n_k / kSumBlock, kc + 1 == cps.size() ? 1u : 0u,
+                           AD->threshold, 0u);
+        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
+        hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
+                           st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
+        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        n_active = cnt;
+        cur ^= 1;
+        n_prev = n_k;
+    }
+    if (occ)
+        hipLaunchKernelGGL(k_probe_adapt_finish_occlusion, dim3(all_grid), dim3(kBlock), 0, s, (const uint32_t*)st.total, (const uint32_t*)st.n,
+                           (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+    else
+        hipLaunchKernelGGL(k_probe_adapt_finish, dim3(all_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                           (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+    HIP_TRY(c, hipGetLastError());
+    return RTW_OK;
+}
+
+// the checks both variants share; fills the sampling params and the checkpoints
+int probe_adaptive_check(rtw_ctx* c, const char* what, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* AD, const void* out,
+                         rtw_radiance_params& rp, std::vector<int>& cps) {
+    if (c->has_scene && !probe_mode_ok(PP)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad mode");
+    const int rc = radiance_check(c, what, probes, n, probe_sampling(PP, rp), out);
+    if (rc) return rc;
+    if (!AD) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null adaptive settings");
+    if (const char* why = adaptive_checkpoints(AD->min_spp, AD->step_spp, PP->spp, AD->threshold, AD->dilate, cps))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+    if (AD->dilate != 0) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": dilate must be 0 (a probe batch has no neighbourhood)");
+    return RTW_OK;
+}
+
+// rtw_probe's stats for the samples actually taken
+int probe_adaptive_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, uint64_t samples, int mode, hipEvent_t ev[2]) {
+    if (!stats) return RTW_OK;
+    memset(stats, 0, sizeof *stats);
+    stats->samples = samples;
+    if (mode == RTW_PROBE_OCCLUSION) {
+        stats->shadow_rays = samples;
+    } else {
+        unsigned long long hs[8];
+        const int rc = sum_stat_rows(c, d->rad_ctl, hs);
+        if (rc) return rc;
+        stats->segments = hs[0]; stats->shadow_rays = hs[1];
+        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    stats->seconds = (double)ms * 1e-3;
+    return RTW_OK;
+}
+
+int impl_adaptive_probe_device(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* AD, void* d_rgba, void* d_spp,
+                               void* d_error, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    std::vector<int> cps;
+    int rc = probe_adaptive_check(c, "rtw_probe_adaptive_device", probes, n, PP, AD, d_rgba, rp, cps);
+    if (rc) return rc;
+    if (n > 0 && (((uintptr_t)probes & 15) || ((uintptr_t)d_rgba & 15) || ((uintptr_t)d_spp & 3) || ((uintptr_t)d_error & 3)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_probe_adaptive_device: probes and rgba must be 16-byte aligned, spp and error 4-byte aligned");
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    uint64_t samples = 0;
+    if ((rc = probe_adaptive_issue(c, d, read_tuning(), probes, n, &rp, PP->mode, AD, cps, rp.key_offset, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error, s,
+                                   samples)) != RTW_OK)
+        return rc;
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    return probe_adaptive_stats(c, d, stats, samples, PP->mode, ev);
+}
+
+int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* AD, float* rgba_out, int32_t* spp_out,
+                        float* error_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    std::vector<int> cps;
+    int rc = probe_adaptive_check(c, "rtw_probe_adaptive", probes, n, PP, AD, rgba_out, rp, cps);
+    if (rc) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const Tuning tune = read_tuning();
+    const size_t chunk = std::min(n, tune.radiance_chunk);
+    // rtw_radiance's staging slab: a chunk's probes (32 B each), then its results: 16 B of rgba, 4 B of spp, 4 B of err; sections 256-byte aligned
+    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_rgba = al(chunk * 32), o_spp = o_rgba + al(chunk * 16), o_err = o_spp + al(chunk * 4), stage_bytes = o_err + chunk * 4;
+    if (stage_bytes > d->rad_stage_bytes) {
+        if (d->rad_stage) (void)hipFree(d->rad_stage);
+        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
+        d->rad_stage_bytes = stage_bytes;
+    }
+    char* const base = (char*)d->rad_stage;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    uint64_t samples = 0;
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        HIP_TRY(c, hipMemcpyAsync(base, probes + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
+        // chunk c runs with the key of its first probe: the bits do not depend on the chunk size
+        if ((rc = probe_adaptive_issue(c, d, tune, (const float*)base, m, &rp, PP->mode, AD, cps, radiance_key(rp.key_offset, i0), (float4*)(base + o_rgba),
+                                       (int32_t*)(base + o_spp), (float*)(base + o_err), d->stream, samples)) != RTW_OK)
+            return rc;
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base + o_rgba, m * 16, hipMemcpyDeviceToHost, d->stream));
+        if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, d->stream));
+        if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the staging slab is reused by the next chunk
+    }
+    return probe_adaptive_stats(c, d, stats, samples, PP->mode, ev);
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -2436,6 +2672,14 @@ int rtw_probe_sh(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_p
 }
 int rtw_probe_sh_device(rtw_ctx* c, const float* points, size_t n, const rtw_radiance_params* RP, void* d_sh, void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_sh_probe_device(c, points, n, RP, d_sh, hip_stream, stats); });
+}
+int rtw_probe_adaptive(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* ad, float* rgba_out, int32_t* spp_out,
+                       float* error_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_adaptive_probe(c, probes, n, PP, ad, rgba_out, spp_out, error_out, stats); });
+}
+int rtw_probe_adaptive_device(rtw_ctx* c, const float* d_probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* ad, void* d_rgba, void* d_spp,
+                              void* d_error, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_adaptive_probe_device(c, d_probes, n, PP, ad, d_rgba, d_spp, d_error, hip_stream, stats); });
 }
 int rtw_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, float* rgba_out, rtw_stats* stats) {
     return guarded(c, [&] { return impl_views(c, views, n_views, VP, rgba_out, stats); });

@@ -732,6 +732,61 @@ int rtw_views(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_vie
 int rtw_views_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, void* d_rgba, void* hip_stream,
                      rtw_stats* stats);
 
+/* Guides of batched views: rtw_render_guides' buffers for every view of an rtw_views call, in one call, from the uploaded scene.
+ * rtw_render_guides reads the one camera of the scene blob; here the camera ray comes from the view's record, on the device.
+ *   Views and params: rtw_views' records and rtw_view_params. max_depth and estimator are validated as rtw_views validates them and
+ *     unused: a guide ray is one camera segment, and it starts at the scene's own 1e-6 whatever the estimator.
+ *   Equivalence: the guides of view v are, bit for bit, what rtw_render_guides writes for the uploaded scene with the header's
+ *     camera and camera_type replaced by views[v]'s, under rtw_params {width, height, spp, seed = views[v].seed, all rows, rng_kind,
+ *     sample_offset}: the camera rays (pixel jitter, lens draws, all three camera kinds), the gather time over the view's own time0 /
+ *     time1 and the first ray time, participating media skipped, the albedo rules per material, alpha = the fraction of the samples
+ *     that hit, the summation order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS, depth and prim from sample sample_offset alone.
+ *   Output: rtw_guides as it is. Every non-NULL pointer holds n_views * height * width entries in rtw_views' layout: pixel (x, y) of
+ *     view v at (v * height + y) * width + x, row 0 the bottom row; a NULL pointer is a buffer the caller does not want and does not
+ *     change the others. A pixel depends on its view record, its (x, y) and the params alone: not on n_views, its view's index, how
+ *     the call is cut into chunks, the launch geometry or tuning knobs.
+ *   rtw_views_guides: host pointers. The records go to the device buffer rtw_views keeps; only the requested buffers are staged out,
+ *     through rtw_radiance's staging slab, in chunks of at most RTW_RADIANCE_CHUNK pixels of the flattened (view, y, x) index (a chunk
+ *     may begin and end mid-row and mid-view). It reads the records: a camera_type outside 0..2 or a non-zero view `reserved` is
+ *     RTW_ERR_INVALID_ARG.
+ *   rtw_views_guides_device: d_views and the pointers inside *d_out (the struct itself is host memory) are device pointers on the
+ *     context's device: d_views, albedo and normal 16-byte aligned, depth and prim 4-byte aligned. Ordered on hip_stream exactly as
+ *     rtw_views_device is; returns when the buffers are written. NULL selects the context's own non-blocking stream, NOT the legacy
+ *     default stream. It does not read the records back: a camera_type that is neither RTW_CAM_ENVIRONMENT nor RTW_CAM_ORTHOGRAPHIC
+ *     is a perspective camera, and `reserved` is ignored. It allocates nothing per call.
+ *   Groups (n_devices > 1): the call runs on device_ids[0]; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   stats (may be NULL): samples = segments = n_views*width*height*spp (one camera segment per sample); seconds = the device time
+ *     from the call's first event to its last; everything else is 0.
+ *   Errors: rtw_views' (RTW_ERR_NO_SCENE without a scene; RTW_ERR_INVALID_ARG for NULL params, width, height or spp <= 0,
+ *     max_depth < 0, a bad rng_kind or estimator, sample_offset < 0 or sample_offset + spp > INT32_MAX, params reserved != 0,
+ *     n_views * width * height > 2^31 - 1, with n_views > 0 NULL views, (rtw_views_guides) a bad record as above), and: `out` NULL or
+ *     all four of its pointers NULL, (rtw_views_guides_device) a misaligned d_views or buffer. A refused call writes nothing and
+ *     leaves *stats alone. n_views = 0 is RTW_OK and launches nothing. The context stays usable after an error. */
+int rtw_views_guides(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_view_params* params, const rtw_guides* out, rtw_stats* stats);
+int rtw_views_guides_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, const rtw_guides* d_out,
+                            void* hip_stream, rtw_stats* stats);
+
+/* rtw_denoise_guided over batched views: n_views frames of width x height, each filtered on its own, in one call.
+ *   Layout: rgba_in, albedo, normal, rgba_out hold n_views * height * width float4 in rtw_views' layout (albedo and normal as
+ *     rtw_views_guides writes them).
+ *   Equivalence: frame v of rgba_out is, bit for bit, rtw_denoise_guided of frame v alone: the 25 taps and their order, the border
+ *     clamp per frame (a tap never reads another view), the B3 kernel, the three divisors, the colour sigma halving per pass, alpha
+ *     copied.
+ *   rtw_denoise_views: host pointers. rtw_denoise_views_device: device pointers on the context's device, 16-byte aligned; ordered on
+ *     hip_stream as rtw_views_device is (NULL: the context's own non-blocking stream); returns when the frames are written.
+ *   Scratch: the passes alternate between rgba_out and one buffer of the context's (the host entry keeps its device copies beside
+ *     it); the buffer grows on demand and is kept: nothing is allocated per call once it is large enough.
+ *   Groups (n_devices > 1): the call runs on device_ids[0]. Needs no scene. An accumulation session is not disturbed.
+ *   Errors: RTW_ERR_INVALID_ARG for width or height <= 0, iterations outside 1..8, a sigma that is not > 0 (or whose inverse square
+ *     is not finite), width * height > 2^28 (rtw_denoise_guided's limit), n_views * width * height > 2^31 - 1, with n_views > 0 a NULL buffer or an rgba_out that is or overlaps an
+ *     input, (rtw_denoise_views_device) a misaligned buffer. A refused call writes nothing. n_views = 0 is RTW_OK. */
+int rtw_denoise_views(rtw_ctx* ctx, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views,
+                      int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal);
+int rtw_denoise_views_device(rtw_ctx* ctx, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views,
+                             int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal,
+                             void* hip_stream);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

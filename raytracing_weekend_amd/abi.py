@@ -144,7 +144,8 @@ HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render"
                "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
                "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
                "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device",
-               "rtw_probe_adaptive", "rtw_probe_adaptive_device"]
+               "rtw_probe_adaptive", "rtw_probe_adaptive_device",
+               "rtw_views_guides", "rtw_views_guides_device", "rtw_denoise_views", "rtw_denoise_views_device"]
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -251,6 +252,17 @@ def load_hip():
         lib.rtw_views.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_views_device.restype = C.c_int
         lib.rtw_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_views_guides.restype = C.c_int
+        lib.rtw_views_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Guides), C.POINTER(Stats)]
+        lib.rtw_views_guides_device.restype = C.c_int
+        lib.rtw_views_guides_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Guides), C.c_void_p,
+                                                C.POINTER(Stats)]
+        lib.rtw_denoise_views.restype = C.c_int
+        lib.rtw_denoise_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_float, C.c_float, C.c_float]
+        lib.rtw_denoise_views_device.restype = C.c_int
+        lib.rtw_denoise_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -709,6 +721,70 @@ class Renderer:
         vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
         self._check(self.lib.rtw_views_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                               None if stats is None else C.byref(stats)), "rtw_views_device")
+
+    # ---- guides of batched views and their denoiser (include/rtw.h rtw_views_guides / rtw_denoise_views)
+    def views_guides(self, views, width, height, spp=16, which=GUIDES, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stats=None):
+        """rtw_views_guides on View records: the dict render_guides returns with a leading view axis - albedo and normal
+        (n, height, width, 4) float32 (alpha = fraction of the samples that hit), depth (n, height, width) float32, prim
+        (n, height, width) int32 - of the requested names. View v's guides are render_guides' of the uploaded scene with views[v]'s
+        camera in its header and views[v].seed as the seed. `stats`: a Stats to fill, or None."""
+        which = tuple(which)
+        bad = [k for k in which if k not in GUIDES]
+        if bad or not which:
+            raise ValueError(f"views_guides: unknown or no guide names {bad or which}")
+        arr = view_array(views)
+        vp = make_view_params(width, height, spp, 0, rng_kind, sample_offset, 0)
+        if len(arr) * int(width) * int(height) > 0x7fffffff:
+            raise ValueError("views_guides: more than 2^31 - 1 pixels in one call")
+        n, h, w = len(arr), int(height), int(width)
+        shapes = {"albedo": ((n, h, w, 4), np.float32), "normal": ((n, h, w, 4), np.float32), "depth": ((n, h, w), np.float32),
+                  "prim": ((n, h, w), np.int32)}
+        out = {k: np.empty(*shapes[k]) for k in which}
+        g = Guides(**{k: v.ctypes.data for k, v in out.items()})
+        self._check(self.lib.rtw_views_guides(self.ctx, C.cast(arr, C.c_void_p), n, C.byref(vp), C.byref(g),
+                                              None if stats is None else C.byref(stats)), "rtw_views_guides")
+        return out
+
+    def views_guides_device(self, n, views_ptr, out_ptrs, width, height, spp=16, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stream_ptr=0,
+                            stats=None):
+        """rtw_views_guides_device on raw device pointers: n rtw_view records at views_ptr (16-byte aligned), out_ptrs a dict of
+        guide name -> device pointer (albedo, normal: n * height * width float4, 16-byte aligned; depth, prim: as many 4-byte
+        entries), stream_ptr a hipStream_t (0: the context's own stream)."""
+        bad = [k for k in out_ptrs if k not in GUIDES]
+        if bad:
+            raise ValueError(f"views_guides_device: unknown guide names {bad}")
+        vp = make_view_params(width, height, spp, 0, rng_kind, sample_offset, 0)
+        g = Guides(**{k: int(v) for k, v in out_ptrs.items()})
+        self._check(self.lib.rtw_views_guides_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.byref(g), C.c_void_p(stream_ptr),
+                                                     None if stats is None else C.byref(stats)), "rtw_views_guides_device")
+
+    def denoise_views(self, frames, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=DENOISE_SIGMA_ALBEDO,
+                      sigma_normal=DENOISE_SIGMA_NORMAL):
+        """rtw_denoise_views on (n, h, w, 4) float32 frames with (n, h, w, 4) albedo and normal guides (views_guides'); returns the
+        filtered frames: frame v is denoise_guided of frame v alone. Sigmas as denoise_guided's."""
+        src = np.ascontiguousarray(frames, dtype=np.float32)
+        if src.ndim != 4 or src.shape[3] != 4:
+            raise ValueError(f"denoise_views: frames of shape {src.shape}, expected (n, h, w, 4)")
+
+        def guide(g):
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if g.shape != src.shape:
+                raise ValueError(f"denoise_views: guide of shape {g.shape} for frames of shape {src.shape}")
+            return g
+        a, nm = guide(albedo), guide(normal)
+        n, h, w = src.shape[:3]
+        out = np.empty_like(src)
+        self._check(self.lib.rtw_denoise_views(self.ctx, src.ctypes.data, a.ctypes.data, nm.ctypes.data, out.ctypes.data, n, w, h,
+                                               iterations, sigma, sigma_albedo, sigma_normal), "rtw_denoise_views")
+        return out
+
+    def denoise_views_device(self, n, in_ptr, albedo_ptr, normal_ptr, out_ptr, width, height, iterations=5, sigma=0.5,
+                             sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_normal=DENOISE_SIGMA_NORMAL, stream_ptr=0):
+        """rtw_denoise_views_device on raw device pointers (n * height * width float4 each, 16-byte aligned), stream_ptr a
+        hipStream_t (0: the context's own stream)."""
+        self._check(self.lib.rtw_denoise_views_device(self.ctx, C.c_void_p(in_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
+                                                      C.c_void_p(out_ptr), n, width, height, iterations, sigma, sigma_albedo, sigma_normal,
+                                                      C.c_void_p(stream_ptr)), "rtw_denoise_views_device")
 
     def debug_intersect(self, rays, ray_time=None, gather_time=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32)

@@ -23,4 +23,12 @@ __global__ void __launch_bounds__(kBlock) k_atrous_guided(const float4* __restri
                                                           float4* __restrict__ out, int width, int height, int step, float inv_sigma2,
                                                           float inv_sigma_a2, float inv_sigma_n2);
 
+// The same pass over n_views frames of width x height at once (rtw.h rtw_denoise_views): pixel i of the flattened index
+// (view * height + y) * width + x, n = n_views * width * height of them; divf_*: magic_div's constants of width * height, by which
+// the frame is found. A tap is clamped and addressed inside the pixel's own frame.
+__global__ void __launch_bounds__(kBlock) k_atrous_guided_views(const float4* __restrict__ in, const float4* __restrict__ alb,
+                                                                const float4* __restrict__ nrm, float4* __restrict__ out, uint32_t n, int width,
+                                                                int height, uint32_t divf_m, uint32_t divf_s1, uint32_t divf_s2, int step,
+                                                                float inv_sigma2, float inv_sigma_a2, float inv_sigma_n2);
+
 }  // namespace rtwk

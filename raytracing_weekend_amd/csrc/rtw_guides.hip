@@ -5,6 +5,7 @@
 //                    (raygen<>), closest hit through traverse<> with volumes skipped, the closest-hit code's hit record,
 //                    shading normal and texture evaluation
 //   k_atrous_guided  k_atrous with albedo and normal edge-stopping terms
+//   k_atrous_guided_views  k_atrous_guided over the frames of a batch of views, every tap inside its pixel's frame
 #include <hip/hip_runtime.h>
 
 #ifndef RTW_TEMPLATES_ONLY
@@ -118,6 +119,46 @@ __global__ void __launch_bounds__(kBlock) k_atrous_guided(const float4* __restri
                 int xx = x + dx * step;
                 xx = xx < 0 ? 0 : (xx > width - 1 ? width - 1 : xx);
                 const int j = yy * width + xx;
+                const float4 q = in[j], qa = alb[j], qn = nrm[j];
+                const float dr = c.x - q.x, dg = c.y - q.y, db = c.z - q.z;
+                const float d2 = (dr * dr + dg * dg) + db * db;
+                const float ar = ca.x - qa.x, ag = ca.y - qa.y, ab = ca.z - qa.z;
+                const float a2 = (ar * ar + ag * ag) + ab * ab;
+                const float nx = cn.x - qn.x, ny = cn.y - qn.y, nz = cn.z - qn.z;
+                const float n2 = (nx * nx + ny * ny) + nz * nz;
+                float w = (kern[dy + 2] * kern[dx + 2]) / (1.0f + d2 * inv_sigma2);
+                w = w / (1.0f + a2 * inv_sigma_a2);
+                w = w / (1.0f + n2 * inv_sigma_n2);
+                sr = sr + w * q.x; sg = sg + w * q.y; sb = sb + w * q.z; sw = sw + w;
+            }
+        }
+        out[i] = make_float4(sr / sw, sg / sw, sb / sw, c.w);
+    }
+}
+
+// k_atrous_guided over the flattened index of n_views frames: the frame by exact division, the taps clamped and addressed inside
+// it, the operations and their order unchanged (frame v of the result is k_atrous_guided's of frame v alone, bit for bit).
+// n < 2^31 and the grid is at most n / kBlock blocks: i does not wrap.
+__global__ void __launch_bounds__(kBlock) k_atrous_guided_views(const float4* __restrict__ in, const float4* __restrict__ alb,
+                                                                const float4* __restrict__ nrm, float4* __restrict__ out, uint32_t n, int width,
+                                                                int height, uint32_t divf_m, uint32_t divf_s1, uint32_t divf_s2, int step,
+                                                                float inv_sigma2, float inv_sigma_a2, float inv_sigma_n2) {
+    const uint32_t frame = (uint32_t)width * (uint32_t)height;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t view = fastdiv(i, divf_m, divf_s1, divf_s2);
+        const uint32_t base = view * frame;
+        const int p = (int)(i - base);
+        const int y = p / width, x = p - y * width;
+        const float4 c = in[i], ca = alb[i], cn = nrm[i];
+        const float kern[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+        float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+        for (int dy = -2; dy <= 2; dy++) {
+            int yy = y + dy * step;
+            yy = yy < 0 ? 0 : (yy > height - 1 ? height - 1 : yy);
+            for (int dx = -2; dx <= 2; dx++) {
+                int xx = x + dx * step;
+                xx = xx < 0 ? 0 : (xx > width - 1 ? width - 1 : xx);
+                const uint32_t j = base + (uint32_t)(yy * width + xx);
                 const float4 q = in[j], qa = alb[j], qn = nrm[j];
                 const float dr = c.x - q.x, dg = c.y - q.y, db = c.z - q.z;
                 const float d2 = (dr * dr + dg * dg) + db * db;

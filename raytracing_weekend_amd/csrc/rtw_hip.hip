@@ -61,6 +61,7 @@
 #include "rtw_probe.h"
 #include "rtw_probe_sh.h"
 #include "rtw_view.h"
+#include "rtw_view_guides_plan.h"
 #include "rtw_adaptive.h"
 #include "rtw_probe_adaptive.h"
 #include "rtw_probe_adaptive_plan.h"
@@ -184,6 +185,8 @@ struct rtw_ctx {
     size_t rad_stage_bytes = 0;
     void* view_buf = nullptr;  // rtw_views: the call's view records
     size_t view_bytes = 0;
+    void* dn_buf = nullptr;  // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
+    size_t dn_bytes = 0;
     unsigned long long* rad_ctl = nullptr;
     // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept
     void* padapt = nullptr;
@@ -509,6 +512,7 @@ int impl_destroy(rtw_ctx* c) {
     if (c->rad_stage) (void)hipFree(c->rad_stage);
     if (c->padapt) (void)hipFree(c->padapt);
     if (c->view_buf) (void)hipFree(c->view_buf);
+    if (c->dn_buf) (void)hipFree(c->dn_buf);
     if (c->rad_ctl) (void)hipFree(c->rad_ctl);
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2353,6 +2357,214 @@ int impl_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view
     return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
 }
 
+// ---- rtw_views_guides / rtw_views_guides_device (rtw.h): k_guides' pass over the pixels of the call's frames, the camera from the
+// pixel's view record (k_view_guides)
+int views_guides_check(rtw_ctx* c, const char* what, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_guides* G) {
+    rtw_radiance_params rp;
+    static const char some = 0;  // views_check's null test of the output is made here, on the struct
+    const int rc = views_check(c, what, views, n_views, VP, &some, rp);
+    if (rc) return rc;
+    if (!G || (!G->albedo && !G->normal && !G->depth && !G->prim)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": no output buffer");
+    return RTW_OK;
+}
+
+// one k_view_guides launch on stream s of device context d: n flattened pixels from pixel `first` of the call, entry i of g's
+// buffers pixel first + i; the scene as uploaded (the reference's ray tmin whatever VP->estimator says)
+hipError_t views_guides_launch(rtw_ctx* d, const void* d_views, const rtw_view_params* VP, uint64_t first, size_t n, const GuideOut& g, hipStream_t s) {
+    ViewArgs va{};
+    va.rays = (const float4*)d_views;
+    va.n = (uint32_t)n;
+    va.spp = (uint32_t)VP->spp; va.sample0 = (uint32_t)VP->sample_offset;
+    va.width = (uint32_t)VP->width; va.height = (uint32_t)VP->height; va.first = (uint32_t)first;
+    magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
+    magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
+    hipLaunchKernelGGL(k_view_guides, dim3(pixel_grid(d, n)), dim3(kBlock), d->info.lds_bytes, s, d->sc, va, g);
+    return hipGetLastError();
+}
+
+void views_guides_stats(rtw_stats* stats, size_t n, const rtw_view_params* VP, float ms) {
+    stats->samples = stats->segments = (uint64_t)n * (uint64_t)VP->spp;  // one camera segment per sample
+    stats->seconds = (double)ms * 1e-3;
+}
+
+int impl_views_guides_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_guides* G, void* hip_stream,
+                             rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    const int rc = views_guides_check(c, "rtw_views_guides_device", d_views, n_views, VP, G);
+    if (rc) return rc;
+    if (n_views > 0 && (((uintptr_t)d_views & 15) || ((uintptr_t)G->albedo & 15) || ((uintptr_t)G->normal & 15) || ((uintptr_t)G->depth & 3) ||
+                        ((uintptr_t)G->prim & 3)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_guides_device: views, albedo and normal must be 16-byte aligned, depth and prim 4-byte aligned");
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    const GuideOut g{(float4*)G->albedo, (float4*)G->normal, G->depth, G->prim, VP->rng_kind};
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, views_guides_launch(d, d_views, VP, 0, n, g, s));
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        views_guides_stats(stats, n, VP, ms);
+    }
+    return RTW_OK;
+}
+
+int impl_views_guides(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_guides* G, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    const int rc = views_guides_check(c, "rtw_views_guides", views, n_views, VP, G);
+    if (rc) return rc;
+    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
+        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_guides: view " + std::to_string(v) + ": bad camera_type");
+        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_guides: view " + std::to_string(v) + ": reserved must be 0");
+    }
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const size_t chunk = (size_t)view_guides_chunk(n, read_tuning().radiance_chunk);
+    if (n_views * sizeof(rtw_view) > d->view_bytes) {
+        if (d->view_buf) (void)hipFree(d->view_buf);
+        d->view_buf = nullptr; d->view_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
+        d->view_bytes = n_views * sizeof(rtw_view);
+    }
+    void* const dst[4] = {G->albedo, G->normal, G->depth, G->prim};
+    const bool want[4] = {G->albedo != nullptr, G->normal != nullptr, G->depth != nullptr, G->prim != nullptr};
+    const ViewGuideStage stage = view_guides_stage(chunk, want);  // rtw_radiance's staging slab, here a chunk's requested guides alone
+    if (stage.bytes > d->rad_stage_bytes) {
+        if (d->rad_stage) (void)hipFree(d->rad_stage);
+        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, (size_t)stage.bytes));
+        d->rad_stage_bytes = (size_t)stage.bytes;
+    }
+    char* const st = (char*)d->rad_stage;
+    const GuideOut g{want[0] ? (float4*)(st + stage.off[0]) : nullptr, want[1] ? (float4*)(st + stage.off[1]) : nullptr,
+                     want[2] ? (float*)(st + stage.off[2]) : nullptr, want[3] ? (int32_t*)(st + stage.off[3]) : nullptr, VP->rng_kind};
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
+        const size_t m = std::min(chunk, n - i0);
+        HIP_TRY(c, views_guides_launch(d, d->view_buf, VP, (uint64_t)i0, m, g, d->stream));
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        for (int k = 0; k < 4; k++)
+            if (want[k])
+                HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * kGuideEntryBytes[k], st + stage.off[k], m * kGuideEntryBytes[k], hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
+    }
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        views_guides_stats(stats, n, VP, ms);
+    }
+    return RTW_OK;
+}
+
+// ---- rtw_denoise_views / rtw_denoise_views_device (rtw.h): rtw_denoise_guided's passes over all frames at once (k_atrous_guided_views)
+int denoise_views_check(rtw_ctx* c, const char* what, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views,
+                        int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
+    const float inv_a = 1.0f / (sigma_albedo * sigma_albedo), inv_n = 1.0f / (sigma_normal * sigma_normal);
+    if (width <= 0 || height <= 0 || iterations < 1 || iterations > 8 || !(sigma > 0.f) || !(sigma_albedo > 0.f) || !(sigma_normal > 0.f) ||
+        !std::isfinite(inv_a) || !std::isfinite(inv_n) || !denoise_views_frame_ok(width, height))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": bad argument");
+    if (!view_pixels_ok(n_views, width, height)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": more than 2^31 - 1 pixels");
+    if (n_views > 0 && (!rgba_in || !albedo || !normal || !rgba_out || rgba_out == rgba_in || rgba_out == albedo || rgba_out == normal))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": a null buffer, or an output that is an input");
+    // an output that begins inside an input, or an input inside the output, is an alias as well
+    const uintptr_t o0 = (uintptr_t)rgba_out, bytes = (uintptr_t)view_pixels(n_views, width, height) * 16u;
+    for (const float* p : {rgba_in, albedo, normal})
+        if (n_views > 0 && o0 < (uintptr_t)p + bytes && (uintptr_t)p < o0 + bytes)
+            return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": the output overlaps an input");
+    return RTW_OK;
+}
+
+// the context's denoiser scratch, at least `need` bytes: grown after the stream's pending work, which may still read the old one
+int denoise_views_scratch(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
+    if (need <= d->dn_bytes) return RTW_OK;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (d->dn_buf) (void)hipFree(d->dn_buf);
+    d->dn_buf = nullptr; d->dn_bytes = 0;
+    if (hipMalloc(&d->dn_buf, (size_t)need) != hipSuccess) { d->dn_buf = nullptr; return fail(c, RTW_ERR_OOM, "rtw_denoise_views: device allocation failed"); }
+    d->dn_bytes = (size_t)need;
+    return RTW_OK;
+}
+
+// the passes on stream s, not waited for: device buffers of n pixels, `scratch` one more (unused by a single pass)
+hipError_t denoise_views_issue(rtw_ctx* d, const float4* in, const float4* alb, const float4* nrm, float4* out, float4* scratch, size_t n, int32_t width,
+                               int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal, hipStream_t s) {
+    const float inv_a = 1.0f / (sigma_albedo * sigma_albedo), inv_n = 1.0f / (sigma_normal * sigma_normal);
+    uint32_t fm, f1, f2;
+    magic_div((uint32_t)width * (uint32_t)height, fm, f1, f2);
+    const unsigned grid = pixel_grid(d, n);
+    const float4* src = in;
+    float s_i = sigma;
+    for (int it = 0; it < iterations; it++) {
+        float4* const dst = denoise_views_writes_output(iterations, it) ? out : scratch;
+        hipLaunchKernelGGL(k_atrous_guided_views, dim3(grid), dim3(kBlock), 0, s, src, alb, nrm, dst, (uint32_t)n, (int)width, (int)height, fm, f1, f2, 1 << it,
+                           1.0f / (s_i * s_i), inv_a, inv_n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = dst;
+        s_i = s_i * 0.5f;
+    }
+    return hipSuccess;
+}
+
+int impl_denoise_views_device(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
+                              int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal, void* hip_stream) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = denoise_views_check(c, "rtw_denoise_views_device", rgba_in, albedo, normal, rgba_out, n_views, width, height, iterations, sigma, sigma_albedo,
+                                 sigma_normal);
+    if (rc) return rc;
+    if (n_views > 0 && (((uintptr_t)rgba_in & 15) || ((uintptr_t)albedo & 15) || ((uintptr_t)normal & 15) || ((uintptr_t)rgba_out & 15)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise_views_device: the buffers must be 16-byte aligned");
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, width, height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = denoise_views_scratch(c, d, denoise_views_scratch_bytes(n, iterations, false), s)) != RTW_OK) return rc;
+    HIP_TRY(c, denoise_views_issue(d, (const float4*)rgba_in, (const float4*)albedo, (const float4*)normal, (float4*)rgba_out, (float4*)d->dn_buf, n, width,
+                                   height, iterations, sigma, sigma_albedo, sigma_normal, s));
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    return RTW_OK;
+}
+
+int impl_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
+                       int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    int rc = denoise_views_check(c, "rtw_denoise_views", rgba_in, albedo, normal, rgba_out, n_views, width, height, iterations, sigma, sigma_albedo, sigma_normal);
+    if (rc) return rc;
+    if (n_views == 0) return RTW_OK;
+    const size_t n = (size_t)view_pixels(n_views, width, height);
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    if ((rc = denoise_views_scratch(c, d, denoise_views_scratch_bytes(n, iterations, true), d->stream)) != RTW_OK) return rc;
+    const size_t each = (size_t)denoise_views_buffer_bytes(n);
+    char* const b = (char*)d->dn_buf;  // colour, albedo, normal, output, then the ping-pong buffer
+    const float* const src[3] = {rgba_in, albedo, normal};
+    for (int k = 0; k < 3; k++) HIP_TRY(c, hipMemcpyAsync(b + k * each, src[k], n * 16, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(c, denoise_views_issue(d, (const float4*)b, (const float4*)(b + each), (const float4*)(b + 2 * each), (float4*)(b + 3 * each),
+                                   (float4*)(b + 4 * each), n, width, height, iterations, sigma, sigma_albedo, sigma_normal, d->stream));
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, b + 3 * each, n * 16, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(c, hipStreamSynchronize(d->stream));
+    return RTW_OK;
+}
+
 // ---- rtw_probe_adaptive / rtw_probe_adaptive_device (rtw.h): rtw_probe's samples taken from checkpoint to checkpoint over the list of
 // the probes that are still active (rtw_probe_adaptive.h; the plan is rtw_probe_adaptive_plan.h's). The moments, the decision and the
 // compaction are rtw_render_adaptive's kernels over a frame of n x 1 probes with dilate 0.
@@ -2686,6 +2898,23 @@ int rtw_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_
 }
 int rtw_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
     return guarded(c, [&] { return impl_views_device(c, d_views, n_views, VP, d_rgba, hip_stream, stats); });
+}
+int rtw_views_guides(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_guides* out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_views_guides(c, views, n_views, VP, out, stats); });
+}
+int rtw_views_guides_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_guides* d_out, void* hip_stream,
+                            rtw_stats* stats) {
+    return guarded(c, [&] { return impl_views_guides_device(c, d_views, n_views, VP, d_out, hip_stream, stats); });
+}
+int rtw_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
+                      int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {
+    return guarded(c, [&] { return impl_denoise_views(c, rgba_in, albedo, normal, rgba_out, n_views, width, height, iterations, sigma, sigma_albedo, sigma_normal); });
+}
+int rtw_denoise_views_device(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
+                             int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal, void* hip_stream) {
+    return guarded(c, [&] {
+        return impl_denoise_views_device(c, rgba_in, albedo, normal, rgba_out, n_views, width, height, iterations, sigma, sigma_albedo, sigma_normal, hip_stream);
+    });
 }
 
 }  // extern "C"

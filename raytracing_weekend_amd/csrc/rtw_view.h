@@ -5,6 +5,7 @@
 #include <cstddef>
 
 #include "../../include/rtw.h"
+#include "rtw_guides.h"
 #include "rtw_kernels.h"
 #include "rtw_radiance.h"
 
@@ -36,5 +37,10 @@ struct ViewArgs {
 // ray of the lane's pixel from its view record with raygen<>'s statements and draws (rtw_radiance_body.h)
 template <int KIND, int TEX>
 __global__ void __launch_bounds__(kBlock, RTW_MIN_WAVES) k_view(const DScene sc, const ViewArgs a);
+
+// The guides of the same pixels (rtw.h rtw_views_guides): k_guides' loop, one lane per flattened pixel, grid-stride over a.n pixels
+// from pixel a.first; entry i of G's buffers is pixel a.first + i. Of a it reads rays, n, spp, sample0, width, height, first and the
+// two divisors; the camera rays' generator is G.rng_kind. Dynamic LDS: as k_guides (rtw_ctx::lds_bytes, stride kBlock).
+__global__ void __launch_bounds__(kBlock, RTW_MIN_WAVES) k_view_guides(const DScene sc, const ViewArgs a, const GuideOut G);
 
 }  // namespace rtwk

@@ -210,8 +210,40 @@ void Director::renderOrbit(int n, const std::function<void(int)>& onFrame) {
                   << m_stats.shadow_rays << " shadow rays in " << m_stats.seconds << " s on the GPU = " << m_stats.samples / s / 1e6 << " Msamples/s"
                   << std::endl;
     }
+    const bool guidedDenoise = m_guided && m_denoiseIterations > 0;
+    const bool guides = !m_aovPrefix.empty() || guidedDenoise;
+    const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
+    std::vector<float> albedo, normal, depth;
+    if (guides) {  // renderFrame's guide layers, for every view in one call
+        albedo.resize(frame * views.size());
+        normal.resize(frame * views.size());
+        depth.resize(npix * views.size());
+        rtw_view_params g = vp;
+        g.spp = m_guideSpp > 0 ? m_guideSpp : std::min(m_Ns, 16);
+        rtw_guides out{albedo.data(), normal.data(), depth.data(), nullptr};
+        rtw_stats gs{};
+        const int grc = rtw_views_guides(m_ctx, views.data(), views.size(), &g, &out, &gs);
+        if (grc != RTW_OK) die(m_ctx, "rtw_views_guides", grc);
+        if (_verbose) std::cerr << "INFO: guides: " << views.size() << " views, " << g.spp << " spp in " << gs.seconds << " s on the GPU" << std::endl;
+    }
+    if (guidedDenoise) {  // renderFrame's denoiser pass: the display encoding in, linear values back, every view on its own
+        std::vector<float> enc(frames.size()), filtered(frames.size());
+        for (size_t i = 0; i < enc.size(); i++) {
+            float c = frames[i];
+            if ((i & 3) != 3) { c = !(c == c) || c < 0.f ? 0.f : (c > 1.f ? 1.f : c); c = std::sqrt(c); }
+            enc[i] = c;
+        }
+        const int drc = rtw_denoise_views(m_ctx, enc.data(), albedo.data(), normal.data(), filtered.data(), views.size(), m_Nx, m_Ny, m_denoiseIterations,
+                                          m_denoiseSigma, kDenoiseSigmaAlbedo, kDenoiseSigmaNormal);
+        if (drc != RTW_OK) die(m_ctx, "rtw_denoise_views", drc);
+        for (size_t i = 0; i < enc.size(); i++) frames[i] = (i & 3) != 3 ? filtered[i] * filtered[i] : filtered[i];
+    }
     for (size_t k = 0; k < views.size(); k++) {
-        m_hostBuffer.assign(frames.begin() + static_cast<std::ptrdiff_t>(k * frame), frames.begin() + static_cast<std::ptrdiff_t>((k + 1) * frame));
+        auto slice = [k](const std::vector<float>& all, size_t each, std::vector<float>& one) {
+            one.assign(all.begin() + static_cast<std::ptrdiff_t>(k * each), all.begin() + static_cast<std::ptrdiff_t>((k + 1) * each));
+        };
+        slice(frames, frame, m_hostBuffer);
+        if (guides) { slice(albedo, frame, m_albedo); slice(normal, frame, m_normal); slice(depth, npix, m_depth); }
         onFrame(static_cast<int>(k));
     }
 }

@@ -28,6 +28,9 @@ public:
     // a turntable through rtw_views, one call for all n frames: view 0 is the scene's camera, view k that camera turned rigidly by
     // 360 k / n degrees about its v axis through the centre of its frame (raytracing_weekend_amd.bake.orbit_views, operation for
     // operation in double precision); every view renders with the seed. onFrame(k) is called with frame k in hostBuffer(), in order.
+    // With an -aov prefix or a guided denoiser the views' guides come from one rtw_views_guides call (frame k's are what writeGuides
+    // writes inside onFrame(k)), and a guided denoiser filters all frames in one rtw_denoise_views call, with renderFrame's display
+    // encoding and sigmas.
     void renderOrbit(int n, const std::function<void(int)>& onFrame);
     static void orbitViews(const rtw_camera& camera, int cameraType, uint32_t seed, int n, std::vector<rtw_view>& out);
     void printPPM();

@@ -79,8 +79,10 @@ int main(int argc, char* argv[]) {
                    and parameters must be those F was rendered with
     -orbit N       Render a turntable of N views in one call (rtw_views): view 0 is the scene's camera, view k that camera turned by
                    360 k / N degrees about its vertical axis through the centre of its frame. Needs -o NAME.ext and writes
-                   NAME_000.ext, NAME_001.ext, ... with the writer of that extension; -seed applies to every view. It does not
-                   combine with -denoise, -aov, -adaptive, -progressive, -checkpoint or -resume
+                   NAME_000.ext, NAME_001.ext, ... with the writer of that extension; -seed applies to every view. With
+                   -aov PREFIX also PREFIX_000_albedo.pfm, PREFIX_000_normal.pfm, PREFIX_000_depth.pfm, ... (rtw_views_guides);
+                   with -denoise N -guided every view is filtered on its own (rtw_denoise_views). It does not combine with
+                   -denoise without -guided, -adaptive, -progressive, -checkpoint or -resume
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -188,8 +190,14 @@ int main(int argc, char* argv[]) {
             return EXIT_FAILURE;
         }
         if (outPath.empty()) { std::cerr << "ERROR: -orbit needs -o NAME.ext (it writes NAME_000.ext ...)" << std::endl; return EXIT_FAILURE; }
-        for (const char* flag : {"-denoise", "-aov", "-guided", "-adaptive", "-progressive", "-checkpoint", "-resume"})
+        for (const char* flag : {"-adaptive", "-progressive", "-checkpoint", "-resume"})
             if (cl_input.cmdOptionExists(flag)) { std::cerr << "ERROR: -orbit does not combine with " << flag << std::endl; return EXIT_FAILURE; }
+        // the views' denoiser is the guided one (rtw_denoise_views)
+        if (cl_input.cmdOptionExists("-denoise") && !cl_input.cmdOptionExists("-guided")) {
+            std::cerr << "ERROR: -orbit does not combine with -denoise without -guided" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (cl_input.cmdOptionExists("-aov") && aovPrefix.empty()) { std::cerr << "ERROR: -aov needs a prefix" << std::endl; return EXIT_FAILURE; }
     }
 
     auto start = std::chrono::system_clock::now();
@@ -210,6 +218,10 @@ int main(int argc, char* argv[]) {
             std::snprintf(idx, sizeof idx, "_%03d", k);
             outPath = stem + idx + ext;  // (writeOutput picks the writer by the name's extension)
             if (!writeOutput()) { std::cerr << "ERROR: cannot write " << outPath << std::endl; ok = false; }
+            if (!aovPrefix.empty() && !director.writeGuides(aovPrefix + idx)) {
+                std::cerr << "ERROR: cannot write the guide files " << aovPrefix << idx << "_*.pfm" << std::endl;
+                ok = false;
+            }
         });
         outPath = whole;
         auto stop = std::chrono::system_clock::now();

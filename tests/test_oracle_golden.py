@@ -1,7 +1,6 @@
 """CPU suite: the oracle against the committed golden fixtures, closed-form intersections and the
 size-independent properties the path offers (tile independence, sample-range additivity)."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
@@ -188,12 +187,15 @@ def test_rect_bounds_are_inclusive_and_tmin_applies():
     assert t[0] == 4.0 and t[1] == 2.0
 
 
-def test_schlick_and_power_heuristic_constants():
-    # dielectricMaterial.cu:20-26 with eta 1.5: r0 = ((1-1.5)/(1+1.5))^2 = 0.04 ; raydata.cuh:167-171
-    r0 = ((1 - 1.5) / (1 + 1.5)) ** 2
-    assert math.isclose(r0, 0.04)
-    a, b = 0.7, 0.2
-    assert math.isclose(a * a / (a * a + b * b), 0.49 / 0.53)
+def test_schlick_reflection_share_of_the_oracle():
+    """dielectricMaterial.cu:20-26: the share of samples the oracle reflects at glass of eta 1.5, read through the sky
+    (tests/shading_ref.py), against r0 + (1 - r0) (1 - cos)^5 with r0 = ((1 - 1.5) / (1 + 1.5))^2 = 0.04 - at one incidence with
+    16384 samples, and pooled over the incidences of either face (binomial limit at alpha = 1e-4)."""
+    import shading_ref as S
+    assert np.isclose(S.dielectric(np.array([[0.0, -1.0, 0.0]]), (0.0, 1.0, 0.0), 1.5)["p"][0], 0.04)
+    for name in ("direction-glass_share", "direction-glass_above", "direction-glass_below"):
+        for rng in S.RNGS:
+            print(S.check(name, S.oracle_samples(name, rng, S.REF, S.SEEDS[0]), S.REF))
 
 
 # ---------------------------------------------------------------- texture callables (SURVEY 8f rank 1)

@@ -1,0 +1,126 @@
+"""The CPU oracle's materials, media and textures against tests/shading_ref.py, a float64 reading of the reference's programs that
+shares nothing with the oracle: single scatter events observed through the sky (max_depth = 2), free flights observed through an
+emitter behind the medium (max_depth = 1), textures observed on an emitter (max_depth = 1). Thresholds come from shading_ref alone:
+4 x its own fp32-against-float64 constants for deterministic values, Kolmogorov and binomial limits at alpha = 1e-4 for the laws."""
+import numpy as np
+import pytest
+
+import shading_ref as S
+from raytracing_weekend_amd import abi
+
+REF, CORR = S.REF, S.CORR
+
+
+def runs(names, draws=2):
+    """(case, generator, estimator, seed, key base) of every case of the list, for the estimators the case is defined for and the
+    first `draws` of the generator's independent samples (shading_ref.DRAWS: a second seed for Philox, other keys for TEA+LCG)."""
+    out = []
+    for name in names:
+        for est in S.case(name).estimators:
+            out += [pytest.param(name, rng, est, seed, base, id=f"{name}-rng{rng}-est{est}-seed{seed:x}-key{base}")
+                    for rng in S.RNGS for seed, base in S.DRAWS[rng][:draws]]
+    return out
+
+
+def family(prefix):
+    return [n for n in S.CASES if n.startswith(prefix + "-")]
+
+
+STATISTICAL = family("direction") + family("lambert") + family("fuzz") + family("slab") + family("media")
+# a case without draws gives the same samples whatever the seed and the keys: both generators, once
+DRAW_FREE = family("emitter") + family("texture") + family("texture32")
+
+
+@pytest.mark.parametrize("name,rng,est,seed,base", runs(STATISTICAL) + runs(DRAW_FREE, 1))
+def test_oracle_matches_float64_reference(name, rng, est, seed, base):
+    print(S.check(name, S.oracle_samples(name, rng, est, seed, base), est))
+
+
+# ---------------------------------------------------------------- the constants and the quadratures
+def test_measured_constants_hold():
+    got = S.measure_constants()
+    recorded = {"MIRROR": S.MEASURED_CONSTANT_MIRROR, "REFRACT": S.MEASURED_CONSTANT_REFRACT, "IMAGE": S.MEASURED_CONSTANT_IMAGE}
+    recorded.update({"NOISE " + k: v for k, v in S.MEASURED_CONSTANT_NOISE.items()})
+    print(got)
+    got.update({"NOISE " + k: v for k, v in got.pop("NOISE").items()})
+    assert set(got) == set(recorded)
+    for k, v in got.items():
+        assert 0.0 < v <= recorded[k] * 1.0005 and v >= recorded[k] * 0.9, f"MEASURED_CONSTANT_{k}: measured {v:.4f}, recorded {recorded[k]}"
+
+
+def test_quadratures_are_accurate_to_1e_6():
+    for what, err in S.quadrature_errors().items():
+        print(f"{what}: {err:.2e}")
+        assert err < 1e-6, what
+
+
+# ---------------------------------------------------------------- negative controls: the checkers reject wrong expectations
+def rejected(name, est, rng=abi.RTW_RNG_PHILOX, samples=None, **wrong):
+    samples = S.oracle_samples(name, rng, est, S.SEEDS[0]) if samples is None else samples
+    S.check(name, samples, est)  # the right expectation passes on these very samples
+    with pytest.raises(AssertionError) as e:
+        S.check(name, samples, est, **wrong)
+    print(f"{name} with {wrong}: rejected, {e.value}")
+
+
+@pytest.mark.parametrize("name", ["lambert-normal_up", "lambert-tangent_x", "lambert-tangent_z"])
+def test_control_the_other_lobe_is_rejected(name):
+    rejected(name, REF, lobe="cosine")
+    rejected(name, CORR, lobe="reference")
+
+
+def test_control_schlick_with_exponent_4_is_rejected():
+    rejected("direction-glass_above", REF, schlick_exponent=4)
+    rejected("direction-glass_above", CORR, schlick_exponent=4)
+
+
+def test_control_eta_inverted_on_the_back_face_is_rejected():
+    rejected("direction-glass_below", REF, invert_back_eta=True)
+    rejected("direction-glass_below", CORR, invert_back_eta=True)
+
+
+# density x 1.05 moves a share p = exp(-x) by 0.05 x p: at x about 1 that is 0.018 against a standard deviation of 0.0038 at 16384
+# samples, an expected z of 4.9 - too close to 3.89 - so this control runs on four times the samples (expected z 9.8)
+CONTROL_N = 4 * S.N_STAT
+
+
+def more_samples(name, est, n):
+    import oracle
+    import radiance_ref as R
+    c = S.case(name)
+    img, _ = oracle.render(R.ray_blob(c.blob, c.o[0], c.ll[0]), abi.make_params(S.SIDE, n // S.SIDE, 1, c.depth, estimator=est))
+    return img[..., :3].reshape(1, n, 3)
+
+
+@pytest.mark.parametrize("name", ["media-box_normal", "media-sphere_off_centre"])
+def test_control_density_5_percent_off_is_rejected(name):
+    for est in (REF, CORR):
+        rejected(name, est, samples=more_samples(name, est, CONTROL_N), density_factor=1.05)
+
+
+@pytest.mark.parametrize("name", ["media-box_normal", "media-sphere_off_centre", "media-box_xformed"])
+def test_control_the_other_medium_extent_is_rejected(name):
+    rejected(name, REF, bounded=True)
+    rejected(name, CORR, bounded=False)
+
+
+def test_control_checker_with_10_times_y_is_rejected():
+    rejected("texture-checker_constants", REF, checker_py="10*y")
+    rejected("texture-checker_noise_image", REF, checker_py="10*y")
+
+
+def test_control_image_with_row_0_at_v_1_is_rejected():
+    rejected("texture-image", REF, row0_at_v1=True)
+
+
+def test_texture_subsets_keep_every_class_of_point():
+    """The 32-point subsets that rtw_render is given hold every strip, the image's interior, texel-centre, edge and corner points,
+    and both children of either checker."""
+    for name in S.TEXTURE_SUBSETS:
+        c, full = S.case("texture32-" + name), S.case("texture-" + name)
+        val, ok, _, kind = c.expect()
+        assert c.m == 32 and ok.all()
+        assert set(c.strips) == set(full.strips) and set(c.classes) == set(full.classes)
+    assert set(S.case("texture32-image").classes) == {0, 1, 2, 3, 4}
+    assert len(np.unique(S.case("texture32-checker_constants").expect()[0], axis=0)) == 2
+    assert set(S.case("texture32-checker_noise_image").expect()[3]) == {abi.TEX_NOISE, abi.TEX_IMAGE}

@@ -732,6 +732,46 @@ int rtw_views(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_vie
 int rtw_views_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, void* d_rgba, void* hip_stream,
                      rtw_stats* stats);
 
+/* Views sampled to a noise target: rtw_views with rtw_render_adaptive's stop rule. Every pixel of every view takes samples until its
+ * error estimate falls below a threshold, or up to a cap - cube-map faces, turntables and training views whose open pixels stop
+ * after a few dozen samples while penumbrae and glass go on to the cap - without one rtw_upload_scene + rtw_render_adaptive per camera.
+ *   Inputs: the views and the params are rtw_views' own; params->spp is the cap. `ad` is rtw_render_adaptive's rtw_adaptive; dilate
+ *     may be 0 or 1. The checkpoints are rtw_render_adaptive's sequence, a function of (min_spp, step_spp, params->spp) alone.
+ *   Equivalence: the three outputs of view v are, bit for bit, the rgba_out, spp_out and error_out that rtw_render_adaptive writes
+ *     for the uploaded scene with the header's camera and camera_type replaced by views[v]'s, under rtw_params {width, height,
+ *     spp = cap, max_depth, seed = views[v].seed, all rows, rng_kind, sample_offset, estimator} and the same rtw_adaptive. So pixel
+ *     (x, y) of view v stops at a checkpoint n; its colour is rtw_views' colour of that pixel with spp = n; its err is the
+ *     batch-means statistic over its own RTW_SUM_BLOCK-sample block sums (rtw_render_adaptive's formula, fp64 in block order).
+ *   Dilation: with dilate = 1 the 3x3 neighbourhood is clamped to the pixel's own view: a tap never reads another view. An active
+ *     neighbour is one that is active at this checkpoint, as in rtw_render_adaptive.
+ *   Layout: rgba_out holds n_views * height * width float4 in rtw_views' layout (pixel (x, y) of view v at
+ *     (v * height + y) * width + x); spp_out (int32) and error_out (float) use the same layout and may be NULL; rgba_out is required.
+ *   Independence: a pixel's three outputs depend on its view record, its (x, y), the params and `ad` alone: not on n_views, its
+ *     view's index, how the call is cut into batches or slab ranges, the launch geometry or tuning knobs.
+ *   rtw_views_adaptive: host pointers. The records go to the device buffer rtw_views keeps. Because of the dilation the call is cut
+ *     into batches of whole views, max(1, RTW_RADIANCE_CHUNK / (width * height)) views each, whose three results are staged out
+ *     through rtw_radiance's staging slab. It reads the records: a camera_type outside 0..2 or a non-zero view `reserved` is
+ *     RTW_ERR_INVALID_ARG.
+ *   rtw_views_adaptive_device: device pointers on the context's device; views and rgba 16-byte aligned, spp and error 4-byte
+ *     aligned. Ordered on hip_stream exactly as rtw_views_device is (NULL selects the context's own non-blocking stream, NOT the
+ *     legacy default stream); returns when the results are written. It does not read the records back (rtw_views_device's rule for
+ *     camera_type and `reserved`). The per-pixel state and the lists live in the buffer rtw_probe_adaptive keeps, which the context
+ *     owns, grows and keeps: nothing is allocated per call once it is large enough. The block sums of a pass live in rtw_radiance's
+ *     scratch slab, capped by RTW_RADIANCE_SLAB_BYTES: a larger pass runs as consecutive ranges of the active list. One 4-byte
+ *     count is read back per checkpoint on the stream.
+ *   stats (may be NULL): samples = sum of n_p; segments and shadow_rays those of the sampled paths: summed over the views they
+ *     equal the per-view rtw_render_adaptive counts, the pixels a render culls included. algorithmic_bytes and seconds as rtw_views
+ *     reports them; the per-kernel arrays are 0.
+ *   Groups (n_devices > 1): the call runs on device_ids[0]. An accumulation session on the context is not disturbed.
+ *   Errors: rtw_views' refusals; rtw_render_adaptive's refusals for the cap, min_spp, step_spp, threshold and a dilate that is not
+ *     0 or 1; RTW_ERR_INVALID_ARG for a NULL ad, a NULL rgba_out with n_views > 0, and (rtw_views_adaptive_device) a misaligned
+ *     pointer. A refused call writes nothing and leaves *stats alone. n_views = 0 is RTW_OK and launches nothing. The context stays
+ *     usable after an error. */
+int rtw_views_adaptive(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_view_params* params, const rtw_adaptive* ad,
+                       float* rgba_out, int32_t* spp_out, float* error_out, rtw_stats* stats);
+int rtw_views_adaptive_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, const rtw_adaptive* ad,
+                              void* d_rgba, void* d_spp, void* d_error, void* hip_stream, rtw_stats* stats);
+
 /* Guides of batched views: rtw_render_guides' buffers for every view of an rtw_views call, in one call, from the uploaded scene.
  * rtw_render_guides reads the one camera of the scene blob; here the camera ray comes from the view's record, on the device.
  *   Views and params: rtw_views' records and rtw_view_params. max_depth and estimator are validated as rtw_views validates them and

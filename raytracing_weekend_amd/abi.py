@@ -145,7 +145,8 @@ HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render"
                "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
                "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device",
                "rtw_probe_adaptive", "rtw_probe_adaptive_device",
-               "rtw_views_guides", "rtw_views_guides_device", "rtw_denoise_views", "rtw_denoise_views_device"]
+               "rtw_views_guides", "rtw_views_guides_device", "rtw_denoise_views", "rtw_denoise_views_device",
+               "rtw_views_adaptive", "rtw_views_adaptive_device"]
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -252,6 +253,12 @@ def load_hip():
         lib.rtw_views.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.POINTER(Stats)]
         lib.rtw_views_device.restype = C.c_int
         lib.rtw_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_views_adaptive.restype = C.c_int
+        lib.rtw_views_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(Stats)]
+        lib.rtw_views_adaptive_device.restype = C.c_int
+        lib.rtw_views_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Adaptive), C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.rtw_views_guides.restype = C.c_int
         lib.rtw_views_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Guides), C.POINTER(Stats)]
         lib.rtw_views_guides_device.restype = C.c_int
@@ -721,6 +728,36 @@ class Renderer:
         vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
         self._check(self.lib.rtw_views_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
                                               None if stats is None else C.byref(stats)), "rtw_views_device")
+
+    # ---- batched views sampled to a noise target (include/rtw.h rtw_views_adaptive / rtw_views_adaptive_device)
+    def views_adaptive(self, views, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0, dilate=1, rng_kind=RTW_RNG_PHILOX,
+                       sample_offset=0, estimator=0, stats=None):
+        """rtw_views_adaptive on View records: every pixel of every view takes samples until its error estimate is below `threshold`,
+        at most `cap`. Returns (frames, spp, err): the (n, height, width, 4) float32 frames, the (n, height, width) int32 sample counts
+        and the (n, height, width) float32 errors at each pixel's last checkpoint. View v's three arrays are, bit for bit,
+        render_adaptive's of the uploaded scene with views[v]'s camera in its header and views[v].seed as the seed; with dilate = 1
+        the 3x3 neighbourhood stays inside the pixel's own view. `stats`: a Stats to fill, or None."""
+        arr = view_array(views)
+        vp = make_view_params(width, height, cap, max_depth, rng_kind, sample_offset, estimator)
+        if len(arr) * int(width) * int(height) > 0x7fffffff:
+            raise ValueError("views_adaptive: more than 2^31 - 1 pixels in one call")
+        ad = Adaptive(min_spp, step_spp, threshold, dilate)
+        shape = (len(arr), int(height), int(width))
+        out, spp, err = np.empty(shape + (4,), dtype=np.float32), np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float32)
+        self._check(self.lib.rtw_views_adaptive(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), C.byref(ad), out.ctypes.data,
+                                                spp.ctypes.data, err.ctypes.data, None if stats is None else C.byref(stats)), "rtw_views_adaptive")
+        return out, spp, err
+
+    def views_adaptive_device(self, n, views_ptr, out_ptr, spp_ptr, err_ptr, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0,
+                              dilate=1, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, stream_ptr=0, stats=None):
+        """rtw_views_adaptive_device on raw device pointers: n rtw_view records at views_ptr, n * height * width float4 at out_ptr (both
+        16-byte aligned), as many int32 at spp_ptr and float at err_ptr (4-byte aligned; 0: not wanted), stream_ptr a hipStream_t
+        (0: the context's own stream)."""
+        vp = make_view_params(width, height, cap, max_depth, rng_kind, sample_offset, estimator)
+        ad = Adaptive(min_spp, step_spp, threshold, dilate)
+        self._check(self.lib.rtw_views_adaptive_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.byref(ad), C.c_void_p(out_ptr),
+                                                       C.c_void_p(spp_ptr), C.c_void_p(err_ptr), C.c_void_p(stream_ptr),
+                                                       None if stats is None else C.byref(stats)), "rtw_views_adaptive_device")
 
     # ---- guides of batched views and their denoiser (include/rtw.h rtw_views_guides / rtw_denoise_views)
     def views_guides(self, views, width, height, spp=16, which=GUIDES, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stats=None):

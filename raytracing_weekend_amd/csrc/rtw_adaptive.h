@@ -8,26 +8,9 @@
 // layout k_path / k_first read with LIST = 1), in ascending pixel order. Checkpoints fall on block boundaries but not on unit boundaries, so a pass leaves the
 // unit open (upart) and only k_adapt_finish closes it - the order in which k_resolve_blocks / k_resolve + k_finish close it.
 #pragma once
+#include "rtw_adaptive_stat.h"
 
 namespace rtwk {
-
-// the batch-means statistic of one block sum: luminance of the block's mean (rtw.h, in this order, no contraction)
-RTW_DEV float adapt_y(const float4 S) { return ((0.2126f * S.x + 0.7152f * S.y) + 0.0722f * S.z) * 0.0625f; }
-RTW_DEV void adapt_moments(double2& m, const float4 S) {
-    const double y = (double)adapt_y(S);
-    m.x = m.x + y;
-    m.y = m.y + y * y;
-}
-// standard error of sqrt(Y) from the moments of B blocks (rtw.h); NaN stays NaN (and so never compares below a threshold)
-RTW_DEV float adapt_err(const double2 m, const uint32_t B) {
-    const double b = (double)B;
-    const double mean = m.x / b;
-    double v = (m.y - m.x * mean) / (b - 1.0);
-    v = v < 0.0 ? 0.0 : v;
-    const double se = __builtin_sqrt(v / b);
-    const double mm = mean < 1e-3 ? 1e-3 : mean;
-    return (float)(se / (2.0 * __builtin_sqrt(mm)));
-}
 
 // the start of an adaptive render: every pixel active (identity list), sums and moments zero
 __global__ void __launch_bounds__(kBlock) k_adapt_init(uint32_t* __restrict__ list, float4* __restrict__ accum, float4* __restrict__ upart,

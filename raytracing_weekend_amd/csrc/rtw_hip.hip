@@ -65,6 +65,8 @@
 #include "rtw_adaptive.h"
 #include "rtw_probe_adaptive.h"
 #include "rtw_probe_adaptive_plan.h"
+#include "rtw_view_adaptive.h"
+#include "rtw_view_adaptive_plan.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
@@ -74,6 +76,7 @@
 #include "rtw_probe_sh.hip"  // (likewise)
 #include "rtw_view.hip"  // (likewise)
 #include "rtw_probe_adaptive.hip"  // (likewise)
+#include "rtw_view_adaptive.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -188,7 +191,8 @@ struct rtw_ctx {
     void* dn_buf = nullptr;  // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
     size_t dn_bytes = 0;
     unsigned long long* rad_ctl = nullptr;
-    // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept
+    // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept;
+    // rtw_views_adaptive's per-pixel state as well (the same layout over the pixels of a call or batch: a call initialises what it uses)
     void* padapt = nullptr;
     size_t padapt_probes = 0;
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
@@ -2794,6 +2798,202 @@ int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_pro
     return probe_adaptive_stats(c, d, stats, samples, PP->mode, ev);
 }
 
+// ---- rtw_views_adaptive / rtw_views_adaptive_device (rtw.h): rtw_views' samples taken from checkpoint to checkpoint over the list of
+// the pixels that are still active (rtw_view_adaptive.h). The loop, the plan of a pass and the per-pixel state are
+// rtw_probe_adaptive's with n = the pixels of the views at hand (the state lives in the same context-owned allocation); the decision
+// is k_view_adapt_decide's, dilated inside each view.
+typedef void (*ViewListKernel)(const DScene, const ViewListArgs);
+ViewListKernel view_list_kernel(int rng_kind, int feat) {
+#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
+    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_view_list, RTW_RNG_TEA_LCG) : RTW_RK(k_view_list, RTW_RNG_PHILOX);
+#undef RTW_RK
+}
+
+// n_views views at d_views (device) -> their frames at d_out (and d_spp, d_err where not null), on stream s of device context d: pixel
+// i of the outputs is flattened pixel i of these views. One pass, one decision and one count read-back per checkpoint: it returns
+// when the results are written. `samples` receives the sum of the n_p. The counters add up in d->rad_ctl's rows, which the caller
+// zeroed on s.
+int view_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP,
+                        const rtw_radiance_params* RP, const rtw_adaptive* AD, const std::vector<int>& cps, float4* d_out, int32_t* d_spp, float* d_err,
+                        hipStream_t s, uint64_t& samples) {
+    const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
+    ProbeAdaptState st{};
+    int rc = ensure_probe_adapt(c, d, n, s, st);
+    if (rc) return rc;
+    DScene sc = d->sc;
+    apply_estimator(sc, RP->estimator);
+    const ViewListKernel k = view_list_kernel(RP->rng_kind, sc.has_tex);
+    const size_t lds = d->info.lds_bytes;
+    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, lds, 0);
+    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    const unsigned all_grid = pixel_grid(d, n);
+    const uint32_t n_waves = (uint32_t)((n + 63) / 64);
+    ViewArgs va{};  // what view_split / view_raygen read: pixel i of the list is pixel i of these views
+    va.rays = (const float4*)d_views;
+    va.width = (uint32_t)VP->width; va.height = (uint32_t)VP->height; va.first = 0u;
+    magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
+    magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
+    ViewDecideArgs da{};
+    da.width = va.width; da.height = va.height; da.npix = (uint32_t)n;
+    da.divw_m = va.divw_m; da.divw_s1 = va.divw_s1; da.divw_s2 = va.divw_s2;
+    da.divf_m = va.divf_m; da.divf_s1 = va.divf_s1; da.divf_s2 = va.divf_s2;
+    da.dilate = (uint32_t)AD->dilate; da.threshold = AD->threshold;
+    hipLaunchKernelGGL(k_probe_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.mom, st.n, st.err, st.total, (uint32_t)n);
+    HIP_TRY(c, hipGetLastError());
+    size_t n_active = n;
+    int cur = 0, n_prev = 0;
+    for (size_t kc = 0; kc < cps.size() && n_active > 0; kc++) {
+        const int n_k = cps[kc];
+        const uint32_t nb = probe_adaptive_pass_blocks(n_prev, n_k), blk0 = probe_adaptive_first_block(n_prev);
+        const uint32_t run_blocks = probe_adaptive_run_blocks(n_active, nb, max_grid * kBlock);
+        const uint32_t runs = probe_adaptive_runs(nb, run_blocks);
+        const uint64_t per = probe_adaptive_range_positions(n_active, nb, run_blocks, tune.radiance_slab_bytes);
+        if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
+        for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
+            const RadianceRange rg = radiance_range(n_active, per, r);
+            const uint32_t* const list = st.list[cur] + rg.first;  // (position i of the range is list[1 + i])
+            if (RP->max_depth == 0) {  // no segment is traced: every block sum is 0
+                HIP_TRY(c, hipMemsetAsync(d->rad_slab, 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
+            } else {
+                ViewListArgs a{};
+                a.v = va;
+                a.list = list;
+                a.out = (float4*)d->rad_slab;
+                a.queue = queue;
+                a.stats = d->rad_ctl;
+                a.n = (uint32_t)rg.count; a.n_blocks = nb; a.run_blocks = run_blocks; a.n_units = (uint32_t)(rg.count * runs);
+                const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, max_grid);
+                a.job_units = probe_adaptive_job_units(run_blocks, a.n_units, grid * (kBlock / 64));
+                a.n_jobs = (uint32_t)radiance_n_jobs(a.n_units, a.job_units);
+                magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
+                a.s_from = (uint32_t)n_prev; a.sample0 = (uint32_t)RP->sample_offset; a.max_depth = (uint32_t)RP->max_depth;
+                HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
+                hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+                HIP_TRY(c, hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, (uint32_t)rg.count, nb,
+                               blk0, st.accum, st.upart, st.mom);
+            HIP_TRY(c, hipGetLastError());
+        }
+        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
+        da.B = (uint32_t)n_k / kSumBlock; da.at_cap = kc + 1 == cps.size() ? 1u : 0u;
+        hipLaunchKernelGGL(k_view_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
+                           (const uint32_t*)st.n, st.err, st.masks, da);
+        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
+        hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
+                           st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
+        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        n_active = cnt;
+        cur ^= 1;
+        n_prev = n_k;
+    }
+    hipLaunchKernelGGL(k_view_adapt_finish, dim3(all_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                       (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+    HIP_TRY(c, hipGetLastError());
+    return RTW_OK;
+}
+
+// the checks both variants share: rtw_views' and rtw_render_adaptive's; fills the sampling params and the checkpoints
+int views_adaptive_check(rtw_ctx* c, const char* what, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* AD,
+                         const void* out, rtw_radiance_params& rp, std::vector<int>& cps) {
+    const int rc = views_check(c, what, views, n_views, VP, out, rp);
+    if (rc) return rc;
+    if (!AD) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null adaptive settings");
+    if (const char* why = adaptive_checkpoints(AD->min_spp, AD->step_spp, VP->spp, AD->threshold, AD->dilate, cps))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+    return RTW_OK;
+}
+
+int impl_adaptive_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* AD, void* d_rgba,
+                               void* d_spp, void* d_error, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    std::vector<int> cps;
+    int rc = views_adaptive_check(c, "rtw_views_adaptive_device", d_views, n_views, VP, AD, d_rgba, rp, cps);
+    if (rc) return rc;
+    if (n_views > 0 && (((uintptr_t)d_views & 15) || ((uintptr_t)d_rgba & 15) || ((uintptr_t)d_spp & 3) || ((uintptr_t)d_error & 3)))
+        return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive_device: views and rgba must be 16-byte aligned, spp and error 4-byte aligned");
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n_views == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], s));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    uint64_t samples = 0;
+    if ((rc = view_adaptive_issue(c, d, read_tuning(), d_views, n_views, VP, &rp, AD, cps, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error, s, samples)) !=
+        RTW_OK)
+        return rc;
+    HIP_TRY(c, hipEventRecord(ev[1], s));
+    HIP_TRY(c, hipEventSynchronize(ev[1]));
+    return probe_adaptive_stats(c, d, stats, samples, RTW_PROBE_IRRADIANCE, ev);
+}
+
+int impl_adaptive_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* AD, float* rgba_out,
+                        int32_t* spp_out, float* error_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    std::vector<int> cps;
+    int rc = views_adaptive_check(c, "rtw_views_adaptive", views, n_views, VP, AD, rgba_out, rp, cps);
+    if (rc) return rc;
+    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
+        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive: view " + std::to_string(v) + ": bad camera_type");
+        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
+            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive: view " + std::to_string(v) + ": reserved must be 0");
+    }
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_views == 0) return RTW_OK;
+    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    const Tuning tune = read_tuning();
+    // batches of whole views (the dilated rule reads a pixel's neighbours inside its view); a batch's pixels start at view v0's first
+    const size_t frame = (size_t)view_pixels(1, VP->width, VP->height);
+    const size_t per = (size_t)std::min<uint64_t>(view_adaptive_batch_views(VP->width, VP->height, tune.radiance_chunk), n_views), chunk = per * frame;
+    if (n_views * sizeof(rtw_view) > d->view_bytes) {
+        if (d->view_buf) (void)hipFree(d->view_buf);
+        d->view_buf = nullptr; d->view_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
+        d->view_bytes = n_views * sizeof(rtw_view);
+    }
+    // rtw_radiance's staging slab, here a batch's results: 16 B of rgba, 4 B of spp, 4 B of err; sections 256-byte aligned
+    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_spp = al(chunk * 16), o_err = o_spp + al(chunk * 4), stage_bytes = o_err + chunk * 4;
+    if (stage_bytes > d->rad_stage_bytes) {
+        if (d->rad_stage) (void)hipFree(d->rad_stage);
+        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
+        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
+        d->rad_stage_bytes = stage_bytes;
+    }
+    char* const base = (char*)d->rad_stage;
+    hipEvent_t ev[2];
+    HIP_TRY(c, cast_events(d, ev));
+    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
+    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    uint64_t samples = 0;
+    for (uint64_t b = 0, nb = view_adaptive_n_batches(n_views, per); b < nb; b++) {
+        const RadianceRange vb = view_adaptive_batch(n_views, per, b);
+        const size_t i0 = (size_t)vb.first * frame, m = (size_t)vb.count * frame;
+        if ((rc = view_adaptive_issue(c, d, tune, (const rtw_view*)d->view_buf + vb.first, (size_t)vb.count, VP, &rp, AD, cps, (float4*)base,
+                                      (int32_t*)(base + o_spp), (float*)(base + o_err), d->stream, samples)) != RTW_OK)
+            return rc;
+        if (b + 1 == nb) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base, m * 16, hipMemcpyDeviceToHost, d->stream));
+        if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, d->stream));
+        if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the staging slab is reused by the next batch
+    }
+    return probe_adaptive_stats(c, d, stats, samples, RTW_PROBE_IRRADIANCE, ev);
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -2905,6 +3105,14 @@ int rtw_views_guides(rtw_ctx* c, const rtw_view* views, size_t n_views, const rt
 int rtw_views_guides_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_guides* d_out, void* hip_stream,
                             rtw_stats* stats) {
     return guarded(c, [&] { return impl_views_guides_device(c, d_views, n_views, VP, d_out, hip_stream, stats); });
+}
+int rtw_views_adaptive(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* ad, float* rgba_out, int32_t* spp_out,
+                       float* error_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_adaptive_views(c, views, n_views, VP, ad, rgba_out, spp_out, error_out, stats); });
+}
+int rtw_views_adaptive_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* ad, void* d_rgba, void* d_spp,
+                              void* d_error, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_adaptive_views_device(c, d_views, n_views, VP, ad, d_rgba, d_spp, d_error, hip_stream, stats); });
 }
 int rtw_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
                       int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal) {

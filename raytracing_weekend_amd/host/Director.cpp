@@ -3,7 +3,7 @@
 //   Director::createScene   Director.cpp:951-969  -> ioScene::init + marshalScene + rtw_upload_scene
 //   Director::renderFrame   Director.cpp:971-1008 -> rtw_render (optixLaunch + D2H copy; no AI denoiser), or an accumulation
 //                                                    session (rtw_accum_*: what the accum_buffer left commented out at :485-488 was for)
-//   Director::renderOrbit   (no counterpart)      -> rtw_views: n frames of a turntable in one call
+//   Director::renderOrbit   (no counterpart)      -> rtw_views: n frames of a turntable in one call (rtw_views_adaptive with -adaptive)
 //   Director::printPPM      Director.cpp:1010-1031
 //   Director::destroy       Director.cpp:66-104   -> rtw_destroy
 #include "Director.h"
@@ -202,8 +202,24 @@ void Director::renderOrbit(int n, const std::function<void(int)>& onFrame) {
     vp.estimator = m_estimator;
     const size_t frame = static_cast<size_t>(m_Nx) * m_Ny * 4;
     std::vector<float> frames(frame * views.size());
-    const int rc = rtw_views(m_ctx, views.data(), views.size(), &vp, frames.data(), &m_stats);
-    if (rc != RTW_OK) die(m_ctx, "rtw_views", rc);
+    const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
+    std::vector<int32_t> spp;
+    std::vector<float> err;
+    if (m_adaptive) {  // renderFrame's adaptive settings (dilate 1), every view stopping on its own pixels
+        spp.resize(npix * views.size());
+        err.resize(npix * views.size());
+        const rtw_adaptive ad{m_adMinSpp, m_adStepSpp, m_adThreshold, 1};
+        const int rc = rtw_views_adaptive(m_ctx, views.data(), views.size(), &vp, &ad, frames.data(), spp.data(), err.data(), &m_stats);
+        if (rc != RTW_OK) die(m_ctx, "rtw_views_adaptive", rc);
+        if (_verbose) {
+            const double uniform = static_cast<double>(npix) * static_cast<double>(views.size()) * m_Ns;
+            std::cerr << "INFO: adaptive: spp mean " << static_cast<double>(m_stats.samples) / (static_cast<double>(npix) * views.size()) << ", "
+                      << 100.0 * (1.0 - static_cast<double>(m_stats.samples) / uniform) << " % of uniform " << m_Ns << " spp saved" << std::endl;
+        }
+    } else {
+        const int rc = rtw_views(m_ctx, views.data(), views.size(), &vp, frames.data(), &m_stats);
+        if (rc != RTW_OK) die(m_ctx, "rtw_views", rc);
+    }
     if (_verbose) {
         const double s = m_stats.seconds > 0 ? m_stats.seconds : 1e-9;
         std::cerr << "INFO: orbit: " << views.size() << " views, " << m_stats.samples << " samples, " << m_stats.segments << " segments, "
@@ -212,7 +228,6 @@ void Director::renderOrbit(int n, const std::function<void(int)>& onFrame) {
     }
     const bool guidedDenoise = m_guided && m_denoiseIterations > 0;
     const bool guides = !m_aovPrefix.empty() || guidedDenoise;
-    const size_t npix = static_cast<size_t>(m_Nx) * m_Ny;
     std::vector<float> albedo, normal, depth;
     if (guides) {  // renderFrame's guide layers, for every view in one call
         albedo.resize(frame * views.size());
@@ -244,6 +259,10 @@ void Director::renderOrbit(int n, const std::function<void(int)>& onFrame) {
         };
         slice(frames, frame, m_hostBuffer);
         if (guides) { slice(albedo, frame, m_albedo); slice(normal, frame, m_normal); slice(depth, npix, m_depth); }
+        if (m_adaptive) {  // what writeGuides puts beside the guides: the view's sample counts and errors
+            m_sppMap.assign(spp.begin() + static_cast<std::ptrdiff_t>(k * npix), spp.begin() + static_cast<std::ptrdiff_t>((k + 1) * npix));
+            slice(err, npix, m_errMap);
+        }
         onFrame(static_cast<int>(k));
     }
 }

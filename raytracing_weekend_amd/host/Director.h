@@ -30,7 +30,8 @@ public:
     // operation in double precision); every view renders with the seed. onFrame(k) is called with frame k in hostBuffer(), in order.
     // With an -aov prefix or a guided denoiser the views' guides come from one rtw_views_guides call (frame k's are what writeGuides
     // writes inside onFrame(k)), and a guided denoiser filters all frames in one rtw_denoise_views call, with renderFrame's display
-    // encoding and sigmas.
+    // encoding and sigmas. After setAdaptive the frames come from one rtw_views_adaptive call (renderFrame's settings, dilate 1), and
+    // frame k's sample counts and errors are what writeGuides writes beside its guides.
     void renderOrbit(int n, const std::function<void(int)>& onFrame);
     static void orbitViews(const rtw_camera& camera, int cameraType, uint32_t seed, int n, std::vector<rtw_view>& out);
     void printPPM();

@@ -3,7 +3,7 @@
 // plus what the benchmark configurations need and the reference hard-wires:
 //   -d depth (reference: 20, Director.cpp:42)   -seed N   -rng philox|lcg   -gpu id   -gpus N   -o file.ppm|file.png|file.pfm
 //   -progressive N   -checkpoint file   -resume file   (accumulation sessions: previews, checkpoints, resumed renders)
-//   -orbit N   (a turntable of N views through rtw_views, one file per view)
+//   -orbit N   (a turntable of N views through rtw_views, or rtw_views_adaptive with -adaptive, one file per view)
 // The reference's resolution / sample clamps (main.cpp:21-27) are widened so that 200x200 and
 // 7680x4320 are reachable, and its scene range bug (only scene 4 selectable, main.cpp:69) is not kept.
 #include <chrono>
@@ -81,8 +81,10 @@ int main(int argc, char* argv[]) {
                    360 k / N degrees about its vertical axis through the centre of its frame. Needs -o NAME.ext and writes
                    NAME_000.ext, NAME_001.ext, ... with the writer of that extension; -seed applies to every view. With
                    -aov PREFIX also PREFIX_000_albedo.pfm, PREFIX_000_normal.pfm, PREFIX_000_depth.pfm, ... (rtw_views_guides);
-                   with -denoise N -guided every view is filtered on its own (rtw_denoise_views). It does not combine with
-                   -denoise without -guided, -adaptive, -progressive, -checkpoint or -resume
+                   with -denoise N -guided every view is filtered on its own (rtw_denoise_views). With -adaptive T [-min_spp M]
+                   [-step N] every view is sampled to the noise target (rtw_views_adaptive) and -aov PREFIX also writes
+                   PREFIX_000_spp.pfm and PREFIX_000_error.pfm, ... It does not combine with -denoise without -guided,
+                   -progressive, -checkpoint or -resume
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -190,7 +192,7 @@ int main(int argc, char* argv[]) {
             return EXIT_FAILURE;
         }
         if (outPath.empty()) { std::cerr << "ERROR: -orbit needs -o NAME.ext (it writes NAME_000.ext ...)" << std::endl; return EXIT_FAILURE; }
-        for (const char* flag : {"-adaptive", "-progressive", "-checkpoint", "-resume"})
+        for (const char* flag : {"-progressive", "-checkpoint", "-resume"})
             if (cl_input.cmdOptionExists(flag)) { std::cerr << "ERROR: -orbit does not combine with " << flag << std::endl; return EXIT_FAILURE; }
         // the views' denoiser is the guided one (rtw_denoise_views)
         if (cl_input.cmdOptionExists("-denoise") && !cl_input.cmdOptionExists("-guided")) {

@@ -1,4 +1,5 @@
-"""rtw_views_device on torch tensors: cameras in, frames out, everything stays on the device (include/rtw.h rtw_views_device)."""
+"""rtw_views_device on torch tensors: cameras in, frames out, everything stays on the device (include/rtw.h rtw_views_device); the
+views' guides and denoiser, and the views sampled to a noise target (rtw_views_adaptive_device), likewise."""
 import ctypes as C
 
 import numpy as np
@@ -85,6 +86,30 @@ def views_guides_torch(renderer, views, width, height, spp=16, which=abi.GUIDES,
             renderer.views_guides_device(n, views.data_ptr(), {k: v.data_ptr() for k, v in out.items()}, width, height, spp, rng_kind=rng_kind,
                                          sample_offset=sample_offset, stream_ptr=stream.cuda_stream, stats=stats)
     return out
+
+
+def views_adaptive_torch(renderer, views, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0, dilate=1,
+                         rng_kind=abi.RTW_RNG_PHILOX, sample_offset=0, estimator=0, stats=None):
+    """rtw_views_adaptive_device on an (n, 28) float32 CUDA tensor of rtw_view records (views_tensor): (frames, spp, err), the
+    (n, height, width, 4) float32 frames, the (n, height, width) int32 sample counts and the (n, height, width) float32 errors, on
+    the records' device, allocated here, written on torch's current stream; the call returns when they are written. Every pixel
+    takes samples until its error estimate is below `threshold`, at most `cap`. The default stream is waited for as in views_torch."""
+    import torch
+
+    _check_views("views_adaptive_torch", renderer, views, width, height, cap)
+    n, h, w = views.shape[0], int(height), int(width)
+    with torch.cuda.device(views.device):
+        out = torch.empty((n, h, w, 4), dtype=torch.float32, device=views.device)
+        spp = torch.empty((n, h, w), dtype=torch.int32, device=views.device)
+        err = torch.empty((n, h, w), dtype=torch.float32, device=views.device)
+        stream = torch.cuda.current_stream()
+        if n and stream.cuda_stream == 0:
+            stream.synchronize()
+        if n:
+            renderer.views_adaptive_device(n, views.data_ptr(), out.data_ptr(), spp.data_ptr(), err.data_ptr(), width, height, cap, max_depth,
+                                           threshold, min_spp=min_spp, step_spp=step_spp, dilate=dilate, rng_kind=rng_kind,
+                                           sample_offset=sample_offset, estimator=estimator, stream_ptr=stream.cuda_stream, stats=stats)
+    return out, spp, err
 
 
 def denoise_views_torch(renderer, frames, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=abi.DENOISE_SIGMA_ALBEDO,

@@ -1,0 +1,234 @@
+"""CPU suite of the adaptive views (include/rtw.h rtw_views_adaptive / rtw_views_adaptive_device): the additive ABI, the planning
+header under the sanitizers, the referee view_adaptive_ref.reference on hand-made block sums, and a rehearsal of the GPU test's inputs
+on the oracle alone, which shows that those inputs cannot pass vacuously.
+
+The rehearsal's threshold is the median (quantile 0.5) of the positive finite errors at 32 spp over the three views of scene0. With
+it the oracle gives, per view (a lens camera, an environment camera, an orthographic camera), these histograms {n_p: pixels} of
+24 x 16 = 384 pixels (cap 256, min 32, depth 8, Philox); the test prints and asserts on what it computes, not on this record:
+    threshold 0.0201385
+    dilate 0: (a) {32: 155, 48: 38, 80: 44, 128: 35, 192: 7, 256: 105}   (b) {32: 248, 48: 18, 80: 26, 128: 21, 192: 5, 256: 66}
+              (c) {32: 235, 48: 26, 80: 17, 128: 8, 192: 1, 256: 97}
+    dilate 1: (a) {128: 1, 256: 383}   (b) {32: 39, 48: 11, 80: 9, 128: 17, 192: 5, 256: 303}
+              (c) {32: 23, 48: 4, 80: 13, 128: 8, 192: 7, 256: 329}
+One pixel of the 1 152 has a checkpoint error within 1e-6 (relative) of the threshold (the median is taken from those errors). The
+median meets all three conditions, so no other quantile was tried; view (a) under dilation is the thin one: all but one of its
+pixels have a neighbour that goes on to the cap."""
+import ast
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import adaptive_ref as A
+import oracle
+import radiance_ref as R
+import view_adaptive_ref as VA
+import view_ref as V
+from raytracing_weekend_amd import abi
+
+W, H, CAP, MIN_SPP, DEPTH = 24, 16, 256, 32, 8  # the GPU test's frames
+QUANTILE = 0.5
+
+
+# ---------------------------------------------------------------- ABI
+def header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(abi.REPO_DIR, "include", "rtw.h")).read(), flags=re.S)
+
+
+def test_header_declares_both_entry_points_and_stays_at_version_5():
+    text = " ".join(header().split())
+    assert ("int rtw_views_adaptive(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_view_params* params, const rtw_adaptive* ad, "
+            "float* rgba_out, int32_t* spp_out, float* error_out, rtw_stats* stats);") in text
+    assert ("int rtw_views_adaptive_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* params, "
+            "const rtw_adaptive* ad, void* d_rgba, void* d_spp, void* d_error, void* hip_stream, rtw_stats* stats);") in text
+    assert "#define RTW_ABI_VERSION 5" in text
+    assert abi.RTW_ABI_VERSION == 5 and C.sizeof(abi.Adaptive) == 16 and C.sizeof(abi.ViewParams) == 32 and C.sizeof(abi.View) == 112
+    assert C.sizeof(abi.Stats) == 184 and C.sizeof(abi.Params) == 48
+
+
+def test_symbols_are_listed_and_exported():
+    assert "rtw_views_adaptive" in abi.HIP_SYMBOLS and "rtw_views_adaptive_device" in abi.HIP_SYMBOLS
+    lib = abi.load_hip()
+    assert hasattr(lib, "rtw_views_adaptive") and hasattr(lib, "rtw_views_adaptive_device") and lib.rtw_abi_version() == 5
+
+
+def test_both_definitions_run_inside_guarded_and_the_unit_is_built():
+    hip = open(os.path.join(abi.PKG_DIR, "csrc", "rtw_hip.hip")).read()
+    for name in ("rtw_views_adaptive", "rtw_views_adaptive_device"):
+        body = re.search(r"\nint " + name + r"\(rtw_ctx\* c,[^{]*\{(.*?)\n\}", hip, flags=re.S).group(1)
+        assert body.strip().startswith("return guarded(c, [&] {"), name
+    assert '#include "rtw_view_adaptive.hip"' in hip.split("#ifndef RTW_SPLIT_BUILD")[1].split("#endif")[0]  # the single-file variant build
+    entry = open(os.path.join(abi.REPO_DIR, "__graft_entry__.py")).read()
+    assert '("rtw_view_adaptive.hip", "rtw_view_adaptive.o", [])' in entry
+    assert '"rtw_view_adaptive.hip"' not in entry.split("UNIT_FLAGS = ")[1].split("\n")[0]  # the common flags
+    # the kernels live in their own unit and take the camera path from the shared header, as k_view does
+    unit = open(os.path.join(abi.PKG_DIR, "csrc", "rtw_view_adaptive.hip")).read()
+    assert '#include "rtw_radiance_body.h"' in unit and "view_raygen<KIND>(" in unit and "view_key(" in unit and "view_seed(" in unit
+
+
+def test_null_context_is_an_error_not_a_crash():
+    lib = abi.load_hip()
+    views = abi.view_array([abi.scene_view(R.scene("scene0"))] * 2)
+    out, spp, err = np.zeros((2, 4, 4, 4), np.float32), np.zeros((2, 4, 4), np.int32), np.zeros((2, 4, 4), np.float32)
+    ad = abi.Adaptive(32, 0, 0.02, 1)
+    vp = abi.make_view_params(4, 4, 64, 4)
+    for n in (0, 2):
+        assert lib.rtw_views_adaptive(None, C.cast(views, C.c_void_p), n, C.byref(vp), C.byref(ad), out.ctypes.data, spp.ctypes.data, err.ctypes.data,
+                                      None) < 0
+        assert lib.rtw_views_adaptive_device(None, C.cast(views, C.c_void_p), n, C.byref(vp), C.byref(ad), out.ctypes.data, spp.ctypes.data,
+                                             err.ctypes.data, None, None) < 0
+    assert lib.rtw_views_adaptive(None, None, 0, None, None, None, None, None, None) < 0
+    assert lib.rtw_views_adaptive_device(None, None, 0, None, None, None, None, None, None, None) < 0
+    assert not out.any() and not spp.any() and not err.any()
+
+
+def test_torch_is_imported_inside_the_function_only():
+    tree = ast.parse(open(os.path.join(abi.PKG_DIR, "torch_views.py")).read())
+    top = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+    names = {a.name.split(".")[0] for n in top if isinstance(n, ast.Import) for a in n.names} | {(n.module or "").split(".")[0] for n in top if isinstance(n, ast.ImportFrom)}
+    assert "torch" not in names
+    from raytracing_weekend_amd import torch_views
+    assert callable(torch_views.views_adaptive_torch)
+
+
+class NoLibrary:
+    """A Renderer that must refuse before it reaches the library."""
+    ctx = None
+
+    class lib:
+        @staticmethod
+        def rtw_views_adaptive(*a):
+            raise AssertionError("the library was called")
+
+
+def test_python_side_argument_validation():
+    call = abi.Renderer.views_adaptive
+    good = [abi.scene_view(R.scene("scene0"))]
+    for views in ([1, 2], [None], np.zeros((1, 28), np.float32)):
+        with pytest.raises(ValueError):
+            call(NoLibrary, views, 8, 8, 64, 4, 0.02)
+    for cap in (0, -16, 1.5, None, True):
+        with pytest.raises(ValueError):
+            call(NoLibrary, good, 8, 8, cap, 4, 0.02)
+    for w, h in ((0, 8), (8, -1), (2.0, 8)):
+        with pytest.raises(ValueError):
+            call(NoLibrary, good, w, h, 64, 4, 0.02)
+    with pytest.raises(ValueError):
+        call(NoLibrary, good * 3, 1 << 15, 1 << 15, 64, 4, 0.02)  # 3 * 2^30 pixels
+
+
+# ---------------------------------------------------------------- the planning header, under the sanitizers
+def test_plan_header_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "view_adaptive_plan_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                           "-Werror", "-o", exe, os.path.join(abi.REPO_DIR, "tests", "native", "view_adaptive_plan_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "view_adaptive_plan_check ok" in out.stdout, out.stdout + out.stderr[-2000:]
+
+
+# ---------------------------------------------------------------- the referee on hand-made block sums
+def noisy(k):
+    """k block sums that alternate between 1 and 31 in every channel: err stays near 0.47 / sqrt(blocks)"""
+    return np.array([1, 31] * (k // 2), np.float32)[:, None]
+
+
+def test_referee_a_nan_block_and_an_all_zero_view():
+    """Checkpoints of (32, 0, 128): 32, 48, 80, 128. View 0 is all zero; view 1 has one pixel with a NaN in its first block."""
+    assert A.checkpoints(32, 0, 128) == [32, 48, 80, 128]
+    S = np.zeros((8, 2, 3, 4, 3), np.float32)
+    S[:, 1] = 16.0
+    S[0, 1, 1, 2] = np.nan
+    for dilate in (0, 1):
+        img, n, err = VA.reference(S, 0.1, 32, 0, 128, dilate)
+        assert img.shape == (2, 3, 4, 4) and n.shape == (2, 3, 4) and n.dtype == np.int32 and err.dtype == np.float32
+        # the zero view: err 0, every pixel stops at min_spp, black with alpha 1
+        assert (n[0] == 32).all() and not err[0].any() and not img[0, ..., :3].any() and (img[0, ..., 3] == 1.0).all()
+        # the NaN pixel: err NaN at every checkpoint, so it goes to the cap; NaN < T is false, so dilated it holds its 3x3 neighbours
+        # (all of this 3 x 4 view but column 0) with it, and undilated nobody else
+        assert n[1, 1, 2] == 128 and np.isnan(err[1, 1, 2]) and np.isnan(img[1, 1, 2, :3]).all()
+        others = np.ones((3, 4), bool)
+        others[1, 2] = False
+        if dilate:
+            assert (n[1][:, 1:][others[:, 1:]] == 128).all() and (n[1][:, 0] == 32).all()
+        else:
+            assert (n[1][others] == 32).all()
+        assert not err[1][others].any() and (img[1][others][:, :3] == 1.0).all()
+    # threshold 0: nothing stops early, the zero view included; +inf: everything but the NaN pixel (and, dilated, its neighbours) at min_spp
+    for dilate in (0, 1):
+        assert (VA.reference(S, 0.0, 32, 0, 128, dilate)[1] == 128).all()
+        ninf = VA.reference(S, np.inf, 32, 0, 128, dilate)[1]
+        assert (ninf[0] == 32).all() and ninf[1, 1, 2] == 128 and (ninf[1][:, 0] == 32).all()
+
+
+def test_referee_a_noisy_row_never_holds_the_view_before_it():
+    """Two views that are adjacent in the flattened layout: the last (top) row of view 0 is quiet and the first (bottom) row of view 1
+    is noisy. A neighbourhood over the flattened rows would tie view 0's last row to view 1's first; the clamp per view does not."""
+    nv, h, w = 2, 4, 5
+    S = np.full((8, nv, h, w, 3), 16.0, np.float32)  # quiet: y_b = 1, err 0
+    S[:, 1, 0] = noisy(8)[:, None, :]                # view 1, row 0: err 0.47, 0.38, 0.26, 0.18 at the four checkpoints
+    e = VA.checkpoint_errors(S, 32, 0, 128)
+    assert all(float(e[nk][1, 0].min()) > 0.15 for nk in e) and not any(e[nk][0].any() for nk in e)
+    for dilate in (0, 1):
+        _, n, err = VA.reference(S, 0.15, 32, 0, 128, dilate)
+        assert (n[0] == 32).all() and not err[0].any(), (dilate, n[0])  # view 0's quiet pixels stop, its last row included
+        assert (n[1, 0] == 128).all()
+        # inside view 1 the rule does dilate: row 1 waits for row 0, rows 2 and 3 do not
+        assert (n[1, 1] == (128 if dilate else 32)).all() and (n[1, 2:] == 32).all()
+    # the same two frames as ONE frame of 8 rows (what a neighbourhood over the flattened index would be) do tie them: that is the
+    # difference the per-view clamp makes
+    _, n_flat, _ = A.adaptive(S.reshape(8, nv * h, w, 3), 0.15, 32, 0, 128, 1)
+    assert (n_flat[h - 1] == 128).all() and (n_flat[: h - 1] == 32).all()
+    # dilate 0, or one view: adaptive_ref.adaptive itself
+    for dilate in (0, 1):
+        img, n, err = VA.reference(S[:, 1:2], 0.15, 32, 0, 128, dilate)
+        ri, rn, re_ = A.adaptive(S[:, 1], 0.15, 32, 0, 128, dilate)
+        assert np.array_equal(img[0], ri) and np.array_equal(n[0], rn) and np.array_equal(err[0], re_)
+    assert VA.histogram(VA.reference(S, 0.15, 32, 0, 128, 1)[1]) == {32: 30, 128: 10}
+    tie = np.zeros((2, 3, 3), bool)
+    tie[0, 2, 2] = True
+    assert VA.spread(tie)[0].sum() == 4 and not VA.spread(tie)[1].any()
+
+
+# ---------------------------------------------------------------- rehearsal of the GPU test's inputs, on the oracle alone
+@functools.lru_cache(maxsize=None)
+def oracle_blocks():
+    """S[b, v, y, x, 3]: the block sums of scene0's three cameras from the oracle at 16 spp (mean x 16 is exact)."""
+    blob, views = R.scene("scene0"), V.cameras("scene0")
+    S = np.empty((CAP // 16, len(views), H, W, 3), np.float32)
+    for v, view in enumerate(views):
+        vb = V.view_blob(blob, view)
+        for b in range(CAP // 16):
+            p = abi.make_params(W, H, 16, DEPTH, seed=view.seed, rng_kind=abi.RTW_RNG_PHILOX, sample_offset=16 * b)
+            img, _ = oracle.render(vb, p, threads=4)
+            S[b, v] = img[..., :3] * np.float32(16)
+    return S
+
+
+def rehearsal_threshold(S, q=QUANTILE):
+    e = VA.checkpoint_errors(S, MIN_SPP, 0, CAP)[MIN_SPP]
+    e = e[np.isfinite(e) & (e > 0)]
+    return float(np.float32(np.quantile(e.astype(np.float64), q)))
+
+
+def test_rehearsal_the_gpu_tests_inputs_cannot_pass_vacuously():
+    """Statistical, not a bit check: the oracle's samples are the GPU's up to the last bits of a few of them."""
+    assert A.checkpoints(MIN_SPP, 0, CAP) == [32, 48, 80, 128, 192, 256]
+    S = oracle_blocks()
+    T = rehearsal_threshold(S)
+    print("threshold (quantile %.2f of the positive finite errors at %d spp): %.6g" % (QUANTILE, MIN_SPP, T))
+    n = {}
+    for dilate in (0, 1):
+        _, n[dilate], _ = VA.reference(S, T, MIN_SPP, 0, CAP, dilate)
+        for v in range(S.shape[1]):
+            hist = VA.histogram(n[dilate][v])
+            print("dilate %d view %d:" % (dilate, v), hist)
+            assert len(hist) >= 2, (dilate, v, hist)  # every view has at least two distinct n_p
+    assert np.count_nonzero(n[0] != n[1]) >= 1  # dilation changes at least one pixel
+    assert (n[1] >= n[0]).all()  # (and only ever upwards)
+    ties = VA.near_ties(S, T, MIN_SPP, 0, CAP)
+    print("pixels within 1e-6 of the threshold at a checkpoint:", int(ties.sum()), "of", ties.size)
+    assert ties.mean() <= 0.02

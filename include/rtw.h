@@ -216,7 +216,24 @@ typedef struct rtw_scene_header {
  * Your Life", mixture_pdf): at a diffuse vertex the scattered direction is drawn from the light list or
  * from the cosine lobe with probability 1/2 each, the throughput carries albedo * p_cos / (p_cos / 2 + p_light / 2) with
  * p_light the true solid-angle density of the light list (the reference's rect_*_value stubs return constants), no
- * shadow probe is traced and every emitter hit counts - one-sample multiple importance sampling, balance heuristic. */
+ * shadow probe is traced and every emitter hit counts - one-sample multiple importance sampling, balance heuristic.
+ * What the three corrected estimators share beside the integrand:
+ *   Listed emitters. A light definition describes a primitive when that primitive is an untransformed rectangle
+ *     (xform 0) with a diffuse-light material, vec_u and vec_v are exactly its edges (a1 - a0 along its first in-plane
+ *     axis, b1 - b0 along its second, in x, y, z order), position is exactly its (a0, b0) corner in those two axes, and
+ *     |position[axis] - k| <= 0.01 * max(a1 - a0, b1 - b0). The first such primitive in scene order is taken. The
+ *     definition is then sampled on the primitive's plane (position[axis] = k; Cornell: 554 -> 554.9) and
+ *     the primitive is a listed emitter: under RTW_EST_CORRECTED its hit is dropped after a vertex that took a light
+ *     sample and counts in full at the camera and after a specular vertex. Emitters that no definition describes
+ *     always count. RTW_EST_REFERENCE reads the definitions as they are and knows no listed emitters.
+ *   The shadow probe runs along the unit direction over (5e-5, r - 5e-5) under RTW_EST_REFERENCE (closehit.cu:100) and
+ *     over (1e-3, r - 1e-3) under RTW_EST_CORRECTED, like every ray the corrected estimators start: whatever lies
+ *     within 1e-3 of either end does not shadow. It is traced where the light sample's pdf and the BSDF's are positive
+ *     and the BSDF value is not zero (closehit.cu:89-95: none at a black surface). It is a traversal like any other:
+ *     a medium on its way draws a free flight from the path's generator and blocks it with probability 1 - T.
+ *   p_light of RTW_EST_MIXTURE counts a light from either side: the light branch aims at the drawn point whichever
+ *     way the definition's normal looks, so the density of a direction is the sum over the parallelograms it crosses of
+ *     r^2 / (n_lights * area * |cos|). */
 typedef enum rtw_estimator {
     RTW_EST_REFERENCE = 0,
     RTW_EST_CORRECTED = 1,

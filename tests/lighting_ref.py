@@ -1,0 +1,802 @@
+"""A float64 numpy reference for direct lighting - which light is drawn, where on it, what the sample weighs, when an emitter hit
+counts: a second reading of include/rtw.h (rtw_estimator, rtw_light, rtw_pdf), DESIGN.md / SURVEY.md (Q1, Q3, Q4, Q12) and of the
+reference's shaders/closehit.cu, pdf/*.cu, material/lambertianMaterial.cu and material/diffuseLight.cu. The laws were written
+without looking at oracle/rtw_oracle.c or the kernels, with one exception that this text does not disclaim: which primitive a light
+definition describes (moved_lights) is the project's own rule, which no reference program has. It was taken from the scene
+preparation (csrc/rtw_scene.h, match_lights), is now stated in include/rtw.h under rtw_estimator, and moved_lights restates that
+statement: a misreading of it would be shared, so own_emitter-d1 checks its effect (the plane sampled) and not the rule. The
+corrected estimators' probe interval, their rule for a black vertex and the mixture's two-sided light density are likewise the
+project's choices, stated in rtw.h; each has a case here that tells the stated choice from the other one. Shared
+by test_lighting_cpu.py (the oracle against this file) and test_gpu_lighting.py (the kernels against this file, then against the
+oracle). The third of three such references: geometry_ref.py (closest hits), shading_ref.py (scatter events, media, textures).
+
+How an event is observed
+  The ray       d = (0.5, -1, 0.25), origin -d, meets a Lambertian rectangle in the plane y = 0 at the origin: t = 1, the hit point
+                is exact, the shading normal is +y. Constant albedo (0.5, 0.25, 1). No sky. One sample per key (shading_ref.Case).
+  Channels      light i emits in channel i only, so a sample's non-zero channel names the light that was drawn; where only light
+                samples contribute at most one channel is non-zero. nonwhite_pair, the point lights and mirror_to_light emit in
+                every channel instead: they catch a swapped channel, which the coding cannot.
+  Depth         max_depth = 1 shows the light sample alone (RTW_EST_REFERENCE, RTW_EST_CORRECTED); max_depth = 2 shows the emitter
+                hits of RTW_EST_CORRECTED_NO_NEE and RTW_EST_MIXTURE, and RTW_EST_CORRECTED's rule for a hit after a light sample.
+                The second segment meets an emitter (the path ends, diffuseLight.cu:66), nothing, or a black surface.
+
+The laws (k is the sample per unit albedo * Le; n_l = number of lights; w the unit direction to the sampled point; r its distance)
+  corrected, depth 1    a light uniformly (closehit.cu:80), a point uniformly on its parallelogram position + a vec_u + b vec_v - the
+                definition moved onto the emitting rectangle it describes where there is one (moved_lights) -,
+                k = n_l / pi * ndl * cos_l * area / r^2 with ndl = w . n and cos_l = -w . light.normal; 0 where ndl <= 0 or
+                cos_l <= 1e-6 (rectPdf.cu:14, :138) - there no probe is traced - or where the probe finds anything in
+                (1e-3, r - 1e-3): the corrected estimators start every ray 1e-3 out and end the probe as far from the light
+                (rtw.h; probe_eps). probe_far_end and probe_near_end put a thin rectangle 4.9e-4 from either end. The mean over everything is albedo * Le * F, F the point-to-polygon form
+                factor (Lambert's contour formula on the polygon clipped to the receiver's hemisphere, form_factor) less the
+                form factor of every occluder's central projection onto the light (visible_form_factor).
+  reference, depth 1    every light is sampled on the header's rtw_pdf.rect (closehit.cu:82-84 hands Parameter.pdf.pdfrect to the
+                generator whichever light was drawn: SURVEY Q12 "and every light but the first"), pdf = r^2 / (area_i cos_i) from
+                the drawn light's own area and normal (rectPdf.cu:137-141), emission * n_l, and the sample is
+                albedo / pi * emission * weight * ndl / pdf with weight = pdf^2 / (pdf^2 + b^2), b = max(0, ndl / pi) (closehit.cu:111-113,
+                lambertianMaterial.cu:74-81; Q3). The probe is traced where pdf > 0 and b > 0, over (5e-5, r - 5e-5)
+                (closehit.cu:97-101).
+  no light sampling     depth 2: a sample is exactly albedo * Le of the emitter the cosine-distributed direction meets from its
+                emitting side, else 0: the hit count per channel is binomial with p = the visible form factor.
+  mixture       depth 2: the direction comes from the light list (a light uniformly, a point uniformly) or from the cosine lobe with
+                probability 1/2 each; the sample is albedo * Le * p_cos / (p_cos / 2 + p_light / 2) on an emitter hit, p_cos = ndl /
+                pi, p_light = sum over the lights the direction crosses, from either side (rtw.h; mixture_behind), of r_i^2 /
+                (n_l area_i |cos_i|). No probe. The weight never exceeds 2 and is 2 on an emitter that no light definition
+                describes. A parallelogram's rim belongs to it; the margin an implementation gives the rim is below what a
+                sample can show and is not modelled.
+  corrected, depth 2    the light sample of depth 1, plus albedo * Le of an emitter hit where that emitter is not a listed one (a
+                primitive that a light definition describes): a listed emitter's hit is dropped after a light sample and counts in
+                full after a specular vertex (mirror_to_light), an unlisted emitter's hit always counts.
+  point lights  vec_u = vec_v = 0, area = 1: one deterministic value, point_value(); the fp32 bound is K_FACTOR *
+                MEASURED_CONSTANT_LIGHT * 2^-24 relative, the constant measured as shading_ref.py measures its own: this file at
+                float32 against itself at float64 over the tests' twelve positions (`python tests/lighting_ref.py`).
+  through a medium      the probe is a traversal like any other: a medium's intersection program draws a free flight from the
+                path's generator (geometry/volumeBox.cu:57-105) and reports a hit inside the interval, so a probe through a medium
+                is blocked with probability 1 - T, T = shading_ref.transmittance over the probe's interval. A point light makes T
+                one number.
+
+What is asserted on a sample array (LightCase.check)
+  mean          per channel by z-test against the law's own mean and variance (midpoint grid of GRID^2 points per light; the grid
+                against itself at half resolution and against the closed form: quadrature_errors()).
+  range         every non-zero sample inside [min, max] of the law over the light (midpoints and a lattice of cell corners, the
+                domain's edges among them), widened by RANGE_SLACK = K_FACTOR * MEASURED_CONSTANT_LIGHT * 2^-24, the fp32 bound of
+                a sample, + MEASURED_GRID_RANGE, the largest change of an extreme between the grid and the grid at half resolution
+                (quadrature_errors(); re-measured by the CPU test).
+  shares        the non-zero count per channel by the binomial rule; shadow_rays (where given) by the binomial rule against the
+                share of samples the law sends a probe for, exactly 0 where the law sends none. At depth 2 the count is the first
+                vertex's: the second is an emitter, where the path ends, or a black surface, where the BSDF value is zero and no
+                probe is traced (closehit.cu:95; occluded-d2 has such vertices).
+  shape         Kolmogorov of the non-zero samples against the law's CDF (the grid's values, weighted, as 16385 quantiles).
+  exact         channels the law leaves dark are exactly 0; emitter hits are exactly albedo * Le.
+Nothing is left out of any case (the printed share is 0): the conditions above are part of the laws, not exclusions.
+Statistical limits are shading_ref's KS_LIMIT and Z_LIMIT; n = 16384 keys in every case, the deterministic ones too (a draw that
+leaked into some lanes' samples would show), 65536 where a channel's hit probability is below 0.05.
+"""
+import functools
+import os
+import sys
+
+import numpy as np
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import geometry_ref as G
+import radiance_ref as R
+import shading_ref as S
+from raytracing_weekend_amd import abi
+
+REF, CORR, NO_NEE, MIX = abi.RTW_EST_REFERENCE, abi.RTW_EST_CORRECTED, abi.RTW_EST_CORRECTED_NO_NEE, abi.RTW_EST_MIXTURE
+U, K_FACTOR, KS_LIMIT, Z_LIMIT = S.U, S.K_FACTOR, S.KS_LIMIT, S.Z_LIMIT
+N_STAT, N_RARE = S.N_STAT, 4 * S.N_STAT
+GRID = 2048
+QUANTILES = 16385
+COS_EPS = 1e-6                                        # DENOMINATOR_EPSILON, rectPdf.cu:14
+PROBE_EPS = float(np.float32(500) * np.float32(1e-7))  # closehit.cu:100: the reference estimator's probe
+CORRECTED_EPS = float(np.float32(1e-3))                 # include/rtw.h: the corrected estimators' rays and probes
+RAY_D = (0.5, -1.0, 0.25)
+NORMAL = np.array([0.0, 1.0, 0.0])
+ALBEDO = (0.5, 0.25, 1.0)
+# `python tests/lighting_ref.py`: point_value at float32 against itself at float64 over POINT_LIGHTS, both estimators, relative, in 2^-24
+MEASURED_CONSTANT_LIGHT = 4.0104  # the reference estimator at (1, 2, -0.5); the corrected one's largest is 1.8088
+# quadrature_errors(): the largest relative change of a law's extremes between the grid and the grid at half resolution (the
+# extremes' error falls with the square of the cell, so the change is three times what is left)
+MEASURED_GRID_RANGE = 3.58e-7
+RANGE_SLACK = K_FACTOR * MEASURED_CONSTANT_LIGHT * U + MEASURED_GRID_RANGE  # relative: the fp32 bound of a sample plus the grid's
+LATTICE_NUDGE = 2.0 ** -30
+
+
+def _dot(a, b):
+    return (a * b).sum(-1)
+
+
+# ---------------------------------------------------------------- scene description (the law reads these, the blob is built from them)
+class Light:
+    def __init__(self, position, u, v, normal, emission, area=None):
+        self.position, self.u, self.v = (np.asarray(a, np.float64) for a in (position, u, v))
+        self.normal, self.emission = np.asarray(normal, np.float64), np.asarray(emission, np.float64)
+        self.area = float(np.linalg.norm(np.cross(self.u, self.v))) if area is None else float(area)
+
+    def abi(self):
+        lt = abi.Light()
+        for k in range(3):
+            lt.position[k], lt.vec_u[k], lt.vec_v[k] = self.position[k], self.u[k], self.v[k]
+            lt.normal[k], lt.emission[k] = self.normal[k], self.emission[k]
+        lt.area = self.area
+        return lt
+
+    def moved(self, axis, k):
+        position = self.position.copy()
+        position[axis] = k
+        return Light(position, self.u, self.v, self.normal, self.emission, self.area)
+
+    def polygon(self):
+        p = self.position
+        return np.array([p, p + self.u, p + self.u + self.v, p + self.v])
+
+    def is_point(self):
+        return not self.u.any() and not self.v.any()
+
+
+class Rect:
+    """An axis-aligned rectangle primitive: plane `axis` = k, the extents (a0, a1, b0, b1) along the two other axes in x, y, z order.
+    kind: "lambert", "light" (diffuse light of radiance `color`, emitting on the side of its shading normal: +axis, -axis when flip)
+    or "metal" (fuzz 0)."""
+
+    def __init__(self, axis, ext, k, kind, color, flip=0):
+        self.axis, self.ext, self.k, self.kind, self.color, self.flip = axis, tuple(float(e) for e in ext), float(k), kind, np.asarray(color, np.float64), flip
+        self.aa, self.ab = (1 if axis == 0 else 0), (1 if axis == 2 else 2)
+
+    def normal(self):
+        n = np.zeros(3)
+        n[self.axis] = -1.0 if self.flip else 1.0
+        return n
+
+    def point(self, a, b):
+        p = np.empty(np.shape(a) + (3,))
+        p[..., self.axis], p[..., self.aa], p[..., self.ab] = self.k, a, b
+        return p
+
+    def polygon(self):
+        a0, a1, b0, b1 = self.ext
+        return self.point(np.array([a0, a1, a1, a0]), np.array([b0, b0, b1, b1]))
+
+    def area(self):
+        return (self.ext[1] - self.ext[0]) * (self.ext[3] - self.ext[2])
+
+
+def moved_lights(lights, rects):
+    """DESIGN.md, Lights and their primitives: a light definition describes an untransformed emitting rectangle when vec_u and vec_v
+    are the rectangle's edges along its first and second in-plane axis, its position is the rectangle's (a0, b0) corner and its
+    plane lies within 1 % of the longer edge of the rectangle's. The corrected estimators sample the definition on the rectangle's
+    plane, and that rectangle is a listed emitter. Returns (lights as sampled, listed flag per rectangle)."""
+    out, listed = list(lights), [False] * len(rects)
+    for i, lt in enumerate(lights):
+        for j, rc in enumerate(rects):
+            if rc.kind != "light":
+                continue
+            ea, eb = rc.ext[1] - rc.ext[0], rc.ext[3] - rc.ext[2]
+            u, v = np.zeros(3), np.zeros(3)
+            u[rc.aa], v[rc.ab] = ea, eb
+            if (np.array_equal(lt.u, u) and np.array_equal(lt.v, v) and lt.position[rc.aa] == rc.ext[0] and lt.position[rc.ab] == rc.ext[2]
+                    and abs(lt.position[rc.axis] - rc.k) <= 0.01 * max(ea, eb)):
+                out[i], listed[j] = lt.moved(rc.axis, rc.k), True
+                break
+    return out, listed
+
+
+# ---------------------------------------------------------------- geometry of the laws
+def clip_to_hemisphere(poly, n):
+    out = []
+    for i in range(len(poly)):
+        a, b = poly[i], poly[(i + 1) % len(poly)]
+        da, db = a @ n, b @ n
+        if da >= 0:
+            out.append(a)
+        if (da >= 0) != (db >= 0):
+            out.append(a + (b - a) * (da / (da - db)))
+    return np.array(out)
+
+
+def form_factor(poly, n=NORMAL, clip=True):
+    """Lambert's contour formula: the form factor of a planar polygon (vertices relative to the receiver point) seen from a receiver
+    of unit normal n, (1 / 2 pi) |sum over the edges of the angle the edge subtends times n . the edge's unit normal|, on the polygon
+    clipped to the receiver's hemisphere."""
+    p = clip_to_hemisphere(np.asarray(poly, np.float64), n) if clip else np.asarray(poly, np.float64)
+    if len(p) < 3:
+        return 0.0
+    s = 0.0
+    for i in range(len(p)):
+        a, b = p[i], p[(i + 1) % len(p)]
+        c = np.cross(a, b)
+        cn = np.linalg.norm(c)
+        if cn == 0:
+            continue
+        s += np.arccos(np.clip(a @ b / np.linalg.norm(a) / np.linalg.norm(b), -1.0, 1.0)) * (c / cn) @ n
+    return abs(s) / (2.0 * np.pi)
+
+
+def probe_eps(estimator):
+    """What the shadow probe leaves out at either end (include/rtw.h rtw_estimator): 5e-5 under the reference estimator
+    (closehit.cu:100), 1e-3 under the corrected ones, whose rays all start that far out."""
+    return PROBE_EPS if estimator == REF else CORRECTED_EPS
+
+
+def blocked(points, rects, eps):
+    """True where the probe from the receiver point (the origin) to `points` (..., 3) finds a rectangle inside (eps, r - eps)
+    along the unit direction (closehit.cu:97-101: any hit, whichever side, whatever the material)."""
+    r = np.sqrt(_dot(points, points))
+    out = np.zeros(points.shape[:-1], bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = points / r[..., None]
+        for rc in rects:
+            t = rc.k / w[..., rc.axis]
+            a, b = t * w[..., rc.aa], t * w[..., rc.ab]
+            out |= (t > eps) & (t < r - eps) & (a >= rc.ext[0]) & (a <= rc.ext[1]) & (b >= rc.ext[2]) & (b <= rc.ext[3])
+    return out
+
+
+def shadows_on(plane_axis, plane_k, polygon, rects):
+    """The central projections, from the origin onto the plane axis = plane_k, of the rectangles parallel to it that lie between:
+    each must fall inside `polygon` (an axis-aligned rectangle of that plane), so that the visible form factor is a difference."""
+    lo, hi = polygon.min(0), polygon.max(0)
+    out = []
+    for rc in rects:
+        if rc.axis != plane_axis or not 0.0 < rc.k / plane_k < 1.0:
+            continue
+        sh = rc.polygon() * (plane_k / rc.k)
+        if (sh.max(0) < lo).any() or (sh.min(0) > hi).any():
+            continue  # the projection misses the polygon altogether
+        assert (sh.min(0) >= lo - 1e-12).all() and (sh.max(0) <= hi + 1e-12).all(), "an occluder's shadow must lie inside what it shadows"
+        out.append(sh)
+    return out
+
+
+def visible_form_factor(axis, k, polygon, rects):
+    return form_factor(polygon) - sum(form_factor(sh) for sh in shadows_on(axis, k, polygon, rects))
+
+
+def _grid(n):
+    g = (np.arange(n) + 0.5) / n
+    return np.meshgrid(g, g, indexing="ij")
+
+
+class Table:
+    """What a law keeps of the values it takes over a grid: the probability that a sample is non-zero, the mean and the second
+    moment of a sample (zeros included), the range of the non-zero values and their CDF as weighted quantiles."""
+
+    def __init__(self, values, weights, total):
+        """values (m,) >= 0 with probabilities `weights` (m,); `total` = the probability mass of the whole grid (the rest is 0)."""
+        values, weights = np.ravel(values), np.ravel(weights)
+        pos = values > 0
+        v, w = values[pos], weights[pos]
+        self.share = float(w.sum() / total)
+        self.m1, self.m2 = float((v * w).sum() / total), float((v * v * w).sum() / total)
+        if len(v):
+            order = np.argsort(v, kind="stable")
+            v, cw = v[order], np.cumsum(w[order])
+            cw /= cw[-1]
+            self.lo, self.hi = float(v[0]), float(v[-1])
+            idx = np.minimum(np.searchsorted(cw, np.linspace(0.0, 1.0, QUANTILES)), len(v) - 1)
+            self.x, self.q = v[idx], np.linspace(0.0, 1.0, QUANTILES)
+        else:
+            self.lo = self.hi = 0.0
+            self.x, self.q = np.zeros(2), np.array([0.0, 1.0])
+
+    def cdf(self, x):
+        return np.interp(np.asarray(x, np.float64), self.x, self.q, left=0.0, right=1.0)
+
+    def widen(self, lo, hi):
+        self.lo, self.hi = min(self.lo, lo), max(self.hi, hi)
+
+
+# ---------------------------------------------------------------- the light sample (depth 1)
+def light_kernel(lt, pts, n_l, estimator, ft=np.float64, n_lights_factor=True, area_factor=1.0, clip_horizon=True, heuristic=True):
+    """(k, probe): the light sample per unit albedo * Le at the sampled points pts (..., 3), relative to the receiver point, for a
+    drawn light lt, and where a probe is traced. The keyword arguments are the wrong models of the negative controls."""
+    pts = np.asarray(pts, ft)
+    r2 = _dot(pts, pts)
+    r = np.sqrt(r2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = pts / r[..., None]
+        ndl = _dot(w, NORMAL.astype(ft))
+        cos_l = -_dot(w, lt.normal.astype(ft))
+        probe = (cos_l > ft(COS_EPS)) & (r > ft(COS_EPS)) & ((ndl > 0) if clip_horizon else (ndl != 0))
+        nl = ft(n_l if n_lights_factor else 1.0)
+        area = ft(np.float32(lt.area)) * ft(area_factor)
+        if estimator == REF:
+            pdf = r2 / (area * cos_l)
+            b = np.abs(ndl) / ft(np.pi)
+            weight = (pdf * pdf) / (pdf * pdf + b * b) if heuristic else ft(1.0)
+            k = nl / ft(np.pi) * weight * np.abs(ndl) / pdf
+        else:
+            k = nl / ft(np.pi) * np.abs(ndl) * cos_l * area / r2
+    return np.where(probe, k, ft(0.0)), probe
+
+
+def point_value(position, normal, emission, estimator, ft=np.float64):
+    """The one value a point light of area 1 gives at the receiver, (3,)."""
+    lt = Light(position, (0, 0, 0), (0, 0, 0), normal, emission, area=1.0)
+    k, _ = light_kernel(lt, np.asarray(position, ft), 1, estimator, ft)
+    return np.asarray(ALBEDO, ft) * np.asarray(emission, ft) * k
+
+
+class SampleLaw:
+    """The law of the depth-1 light sample of one scene and estimator: per light a Table of k (zeros: not eligible, or blocked) and
+    the share of samples a probe is traced for."""
+
+    def __init__(self, lights, rects, pdf_rect, estimator, grid=GRID, own_rectangle=False, eps=None, **model):
+        self.n_l = len(lights)
+        eps = probe_eps(estimator) if eps is None else eps
+        self.tables, self.probe_share = [], 0.0
+        for lt in lights:
+            if estimator == REF and not own_rectangle:
+                axis, ext, k = pdf_rect
+                span = Rect(axis, ext, k, "lambert", (0, 0, 0))
+                degenerate = ext[0] == ext[1] and ext[2] == ext[3]
+            else:
+                degenerate = lt.is_point()
+            a, b = _grid(1 if degenerate else grid)
+            if estimator == REF and not own_rectangle:
+                pts = span.point(ext[0] + a * (ext[1] - ext[0]), ext[2] + b * (ext[3] - ext[2]))
+            else:
+                pts = lt.position + a[..., None] * lt.u + b[..., None] * lt.v
+            k, probe = light_kernel(lt, pts, self.n_l, estimator, **model)
+            k = np.where(blocked(pts, rects, eps), 0.0, k)
+            cell = 1.0 / k.size
+            tb = Table(k, np.full(k.shape, cell / self.n_l), 1.0)  # the light is drawn with probability 1 / n_l
+            if not degenerate:
+                # the range over the closed domain: the lattice of cell corners (edges and corners of the domain among them)
+                # beside the midpoints; where the law's zero set crosses the domain the values come down to 0
+                a, b = np.meshgrid(np.linspace(0.0, 1.0, grid // 2 + 1), np.linspace(0.0, 1.0, grid // 2 + 1), indexing="ij")
+                if estimator == REF and not own_rectangle:
+                    nodes = span.point(ext[0] + a * (ext[1] - ext[0]), ext[2] + b * (ext[3] - ext[2]))
+                else:
+                    nodes = lt.position + a[..., None] * lt.u + b[..., None] * lt.v
+                kn, pn = light_kernel(lt, nodes, self.n_l, estimator, **model)
+                tb.widen(0.0 if not (probe.all() and pn.all()) else float(kn.min()), float(kn.max()))
+            self.tables.append(tb)
+            self.probe_share += float(probe.mean()) / self.n_l
+
+
+# ---------------------------------------------------------------- emitter hits (depth 2)
+class HitLaw:
+    """Per emitting rectangle, the law of the depth-2 emitter hit per unit albedo * Le: `visible` = its visible form factor (closed
+    form), and for the mixture estimator a Table of the weight p_cos / (p_cos / 2 + p_light / 2) under the mixture's own density."""
+
+    def __init__(self, lights, rects, mixture, grid=GRID, one_over_n_lights=True, two_sided=True):
+        sampled, self.listed = moved_lights(lights, rects)
+        self.emitters = [j for j, rc in enumerate(rects) if rc.kind == "light" and rc.normal()[rc.axis] * rc.k < 0]  # faces the origin
+        self.visible = {j: visible_form_factor(rects[j].axis, rects[j].k, rects[j].polygon(), [r for r in rects if r.kind != "light"]) for j in self.emitters}
+        self.tables = {}
+        if not mixture:
+            return
+        n_l = len(sampled)
+
+        def weigh(pts, others):
+            """(weight, p_mix, w, r2) at points of an emitter: 0 where the ray from the origin meets something else first."""
+            r2 = _dot(pts, pts)
+            w = pts / np.sqrt(r2)[..., None]
+            p_cos = np.maximum(_dot(w, NORMAL), 0.0) / np.pi
+            p_light = np.zeros_like(p_cos)
+            for lt in sampled:  # the lights the direction crosses: the plane inside the parallelogram, from either side (rtw.h)
+                ng = np.cross(lt.u, lt.v)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    t = (lt.position @ ng) / _dot(w, ng)
+                    rel = t[..., None] * w - lt.position
+                    m = np.array([[lt.u @ lt.u, lt.u @ lt.v], [lt.u @ lt.v, lt.v @ lt.v]])
+                    sol = np.linalg.solve(m, np.stack([_dot(rel, lt.u), _dot(rel, lt.v)], 0).reshape(2, -1)).reshape((2,) + t.shape)
+                    cos_l = -_dot(w, lt.normal)
+                    cos_l = np.abs(cos_l) if two_sided else cos_l
+                    meets = (t > 0) & (sol >= -1e-12).all(0) & (sol <= 1 + 1e-12).all(0) & (cos_l > COS_EPS)  # the rim belongs to the light
+                    p_light += np.where(meets, t * t / (lt.area * cos_l) / (n_l if one_over_n_lights else 1.0), 0.0)
+            p_mix = 0.5 * p_cos + 0.5 * p_light
+            with np.errstate(divide="ignore", invalid="ignore"):
+                weight = np.where(p_cos > 0, p_cos / p_mix, 0.0)
+            return np.where(blocked(pts, others, CORRECTED_EPS), 0.0, weight), p_mix, w, r2
+        for j in self.emitters:
+            rc = rects[j]
+            others = [r for k_, r in enumerate(rects) if k_ != j]
+            a, b = _grid(grid)
+            weight, p_mix, w, r2 = weigh(rc.point(rc.ext[0] + a * (rc.ext[1] - rc.ext[0]), rc.ext[2] + b * (rc.ext[3] - rc.ext[2])), others)
+            solid = np.abs(w[..., rc.axis]) / r2 * rc.area() / weight.size  # the cell's solid angle
+            tb = Table(weight, p_mix * solid, 1.0)
+            # the range over the closed rectangle: the lattice of cell corners beside the midpoints. The weight jumps where the
+            # direction enters a light's parallelogram, so each lattice point is taken from all four sides (+- LATTICE_NUDGE).
+            lat = np.linspace(0.0, 1.0, grid // 8 + 1)
+            for da in (-LATTICE_NUDGE, LATTICE_NUDGE):
+                for db in (-LATTICE_NUDGE, LATTICE_NUDGE):
+                    a, b = np.meshgrid(np.clip(lat + da, 0.0, 1.0), np.clip(lat + db, 0.0, 1.0), indexing="ij")
+                    wn = weigh(rc.point(rc.ext[0] + a * (rc.ext[1] - rc.ext[0]), rc.ext[2] + b * (rc.ext[3] - rc.ext[2])), others)[0]
+                    if (wn > 0).any():
+                        tb.widen(float(wn[wn > 0].min()), float(wn.max()))
+            self.tables[j] = tb
+
+
+def _share_z(k, n, p):
+    """The binomial z of k of n at probability p; a certain outcome (p = 0 or 1) must be met exactly."""
+    if 0.0 < p < 1.0:
+        return S.binomial_z(k, n, p)
+    return 0.0 if k == round(n * p) else float("inf")
+
+
+# ---------------------------------------------------------------- cases
+def _constant(rgb):
+    return S._constant(rgb)
+
+
+class LightCase(S.Case):
+    """One scene at one depth. lights: Light definitions; rects: the Rect primitives, the receiver first; pdf_rect: (axis, (a0, a1,
+    b0, b1), k) of the header's rtw_pdf; media: shading_ref.media_scene's tuples."""
+
+    def __init__(self, lights, rects, pdf_rect, depth, estimators, n=N_STAT, media=(), d=RAY_D):
+        self.lights, self.rects, self.pdf_rect, self.depth, self.estimators, self.media = list(lights), list(rects), pdf_rect, depth, estimators, media
+        hdr = S._header(0)
+        hdr.pdf.gen, hdr.pdf.p0_gen, hdr.pdf.p1_gen = abi.RTW_PDF_MIXTURE, abi.RTW_PDF_COSINE, abi.RTW_PDF_RECT_X + pdf_rect[0]
+        for i, e in enumerate(tuple(pdf_rect[1]) + (pdf_rect[2],)):
+            hdr.pdf.rect[i] = e
+        prims, mats, texs = [], [], []
+        for rc in self.rects:
+            mat = {"lambert": abi.MAT_LAMBERTIAN, "light": abi.MAT_DIFFUSE_LIGHT, "metal": abi.MAT_METAL}[rc.kind]
+            prims.append(S._prim(S.RECT_OF_AXIS[rc.axis], rc.ext + (rc.k,), material=len(mats), flip=rc.flip))
+            mats.append(abi.Material(type=mat, texture=len(texs), fuzz_or_eta=0.0, bsdf_eval=S.BSDF_EVAL.get(mat, -1)))
+            texs.append(_constant(rc.color))
+        for kind, geo, density in media:
+            prims.append(S._prim(abi.PRIM_VOLUME_BOX if kind == "box" else abi.PRIM_VOLUME_SPHERE, tuple(geo) + (density,), material=len(mats)))
+            mats.append(abi.Material(type=abi.MAT_ISOTROPIC, texture=len(texs), fuzz_or_eta=0.0, bsdf_eval=-1))
+            texs.append(_constant((1.0, 1.0, 1.0)))
+        blob = abi.assemble_scene({"header": hdr, "prims": prims, "xforms": [G.identity_xform()], "lights": [lt.abi() for lt in self.lights],
+                                   "materials": mats, "textures": texs, "texdata": b""})
+        d = np.asarray(d, np.float64)
+        super().__init__(blob, -d, d, n)
+        self.albedo = self.rects[0].color
+        self._laws = {}
+
+    # -- the laws, computed once per model
+    def sample_law(self, estimator, **model):
+        key = (estimator,) + tuple(sorted(model.items()))
+        if key not in self._laws:
+            model = dict(model)
+            # the reference estimator reads the definitions as they are; the corrected ones move them (unmoved: a wrong model)
+            lights = self.lights if estimator == REF or model.pop("unmoved", False) else moved_lights(self.lights, self.rects)[0]
+            self._laws[key] = SampleLaw(lights, self.rects, self.pdf_rect, estimator, **model)
+        return self._laws[key]
+
+    def hit_law(self, mixture, **model):
+        key = ("hit", mixture) + tuple(sorted(model.items()))
+        if key not in self._laws:
+            self._laws[key] = HitLaw(self.lights, self.rects, mixture, **model)
+        return self._laws[key]
+
+    def transmittance(self):
+        """Of the probe to light 0, a point light, through the media (corrected estimators: bounded media)."""
+        if not self.media:
+            return 1.0
+        p = self.lights[0].position
+        return S.transmittance(self.blob, np.zeros(3), p / np.linalg.norm(p), CORRECTED_EPS, True)
+
+    # -- the assertions
+    def _owned(self, emission):
+        """{channel: index} for the channels in which exactly one of the rows of `emission` is non-zero."""
+        lit = (np.asarray(emission) != 0) & (self.albedo != 0)
+        return {c: int(np.nonzero(lit[:, c])[0][0]) for c in range(3) if lit[:, c].sum() == 1}
+
+    def check(self, samples, estimator, shadow_rays=None, count_listed_hits=False, **model):
+        s = np.asarray(samples, np.float64).reshape(-1, 3)
+        n, figs, bad = len(s), [], []
+        want_mean, want_m2 = np.zeros(3), np.zeros(3)
+        light_terms = estimator in (REF, CORR)
+        le = np.array([lt.emission for lt in self.lights]).reshape(-1, 3)
+
+        def hold(ok, text):
+            if not ok:
+                bad.append(text)
+
+        def z_of(mean, m1, m2):
+            var = max(m2 - m1 * m1, 0.0)
+            return (mean - m1) / np.sqrt(var / n) if var > 0 else (0.0 if mean == m1 else np.inf)
+        t_medium = self.transmittance()
+        if light_terms and self.lights:
+            law = self.sample_law(estimator, **model)
+            for i, tb in enumerate(law.tables):
+                scale = self.albedo * le[i]
+                want_mean += scale * tb.m1 * t_medium
+                want_m2 += scale * scale * tb.m2 * t_medium
+            for c, i in self._owned(le).items():
+                tb, scale = law.tables[i], self.albedo[c] * le[i, c]
+                x = s[:, c][s[:, c] != 0] / scale
+                share = tb.share * t_medium
+                if share == 0:
+                    continue  # the mean's exact zero below covers it
+                z = _share_z(len(x), n, share)
+                lo, hi = tb.lo * (1 - RANGE_SLACK), tb.hi * (1 + RANGE_SLACK)
+                inside = bool(len(x) == 0 or (x.min() >= lo and x.max() <= hi))
+                ks = S.ks_sqrt_n(x, tb.cdf) if tb.hi > tb.lo * (1 + 1e-9) and len(x) else 0.0
+                figs.append(f"light {i} in channel {c}: non-zero {len(x)} of {n} (law {share:.4f}, z = {z:+.2f}), range [{x.min() if len(x) else 0:.6g}, "
+                            f"{x.max() if len(x) else 0:.6g}] in law's [{tb.lo:.6g}, {tb.hi:.6g}]: {inside}, KS sqrt(n) = {ks:.2f}")
+                hold(abs(z) <= Z_LIMIT and inside and ks <= KS_LIMIT, figs[-1])
+            if shadow_rays is not None:
+                # at depth 2 too: the second vertex is an emitter (the path ends there) or a black surface (no probe: rtw.h)
+                p = law.probe_share
+                z = _share_z(shadow_rays, n, p)
+                figs.append(f"shadow rays {shadow_rays} of {n} (law {p:.4f}, z = {z:+.2f})")
+                hold(abs(z) <= Z_LIMIT, figs[-1])
+            coded = [c for c, i in self._owned(le).items()]
+            if self.depth == 1 and len(coded) == len(self.lights) > 1:
+                hold(((s != 0).sum(1) <= 1).all(), "more than one channel is non-zero in a sample that holds one light sample")
+        elif shadow_rays is not None:
+            figs.append(f"shadow rays {shadow_rays} (law: none)")
+            hold(shadow_rays == 0, figs[-1])
+        if self.depth >= 2 and self.rects[0].kind == "lambert":
+            hits = self.hit_law(estimator == MIX, **(model if estimator == MIX else {}))
+            em = np.array([self.rects[j].color for j in hits.emitters]).reshape(-1, 3)
+            owned = self._owned(em)
+            for e, j in enumerate(hits.emitters):
+                scale, f = self.albedo * em[e], hits.visible[j]
+                if estimator == MIX:
+                    tb = hits.tables[j]
+                    want_mean += scale * tb.m1
+                    want_m2 += scale * scale * tb.m2
+                elif estimator == NO_NEE or not hits.listed[j] or count_listed_hits:
+                    # a hit's second moment beside the light sample's, taken as independent of it (the cross term matters only to the
+                    # wrong model, which adds a listed emitter's hit to its light sample in the same channel)
+                    want_m2 += scale * scale * f + 2.0 * want_mean * scale * f
+                    want_mean += scale * f
+                for c in [c for c, k in owned.items() if k == e]:
+                    x = s[:, c][s[:, c] != 0]
+                    if estimator == MIX:
+                        tb = hits.tables[j]
+                        z = _share_z(len(x), n, tb.share)
+                        lo, hi = scale[c] * tb.lo * (1 - RANGE_SLACK), scale[c] * min(tb.hi * (1 + RANGE_SLACK), 2.0 * (1 + RANGE_SLACK))
+                        inside = bool(len(x) == 0 or (x.min() >= lo and x.max() <= hi))
+                        ks = S.ks_sqrt_n(x / scale[c], tb.cdf) if tb.hi > tb.lo * (1 + 1e-4) and len(x) else 0.0
+                        figs.append(f"emitter {j} in channel {c}: non-zero {len(x)} of {n} (law {tb.share:.4f}, z = {z:+.2f}), weights [{x.min() / scale[c] if len(x) else 0:.6g}, "
+                                    f"{x.max() / scale[c] if len(x) else 0:.6g}] in law's [{tb.lo:.6g}, {tb.hi:.6g}]: {inside}, KS sqrt(n) = {ks:.2f}")
+                        hold(abs(z) <= Z_LIMIT and inside and ks <= KS_LIMIT, figs[-1])
+                    elif estimator == NO_NEE or not hits.listed[j]:
+                        z = S.binomial_z(len(x), n, f)
+                        exact = bool((x == np.float32(scale[c])).all())
+                        figs.append(f"emitter {j} in channel {c}: {len(x)} hits of {n} (form factor {f:.5f}, z = {z:+.2f}), every hit exactly albedo * Le: {exact}")
+                        hold(abs(z) <= Z_LIMIT and exact, figs[-1])
+        mean = s.mean(0)
+        for c in range(3):
+            if want_mean[c] == 0:
+                figs.append(f"channel {c}: law 0, largest sample {np.abs(s[:, c]).max():.3g}")
+                hold(not s[:, c].any(), figs[-1])
+            else:
+                z = z_of(mean[c], want_mean[c], want_m2[c])
+                figs.append(f"channel {c}: mean {mean[c]:.6f}, law {want_mean[c]:.6f}, z = {z:+.2f}")
+                hold(abs(z) <= Z_LIMIT, figs[-1])
+        fig = f"left out 0 of {n} samples; " + "; ".join(figs)
+        assert not bad, "FAILED: " + " | ".join(bad) + " || all figures: " + fig
+        return fig
+
+
+class ExactCase(LightCase):
+    """Every sample is one value, held to `value(estimator)` (3,) float64 within `units` * 2^-24 relative (0: equality), or is 0
+    with the probability 1 - T of a medium on the probe's way."""
+
+    def __init__(self, *a, value=None, units=0.0, **kw):
+        super().__init__(*a, **kw)
+        self.value, self.units = value, units
+
+    def check(self, samples, estimator, shadow_rays=None, value_factor=1.0, **model):
+        s = np.asarray(samples, np.float64).reshape(-1, 3)
+        n, want, t = len(s), np.asarray(self.value(estimator), np.float64) * value_factor, self.transmittance()
+        dark = ~s.any(1)
+        lit = s[~dark]
+        err = float((np.abs(lit / np.where(want != 0, want, 1.0) - 1.0)[:, want != 0]).max() / U) if len(lit) and want.any() else 0.0
+        zero_ok = bool(not lit[:, want == 0].any()) if len(lit) else True
+        fig = f"left out 0 of {n} samples; {len(lit)} lit, {len(np.unique(lit, axis=0))} distinct, off the float64 value by {err:.2f} x 2^-24 relative (bound {self.units:.2f})"
+        ok = zero_ok and err <= self.units
+        if not want.any():
+            ok = ok and dark.all()
+        elif t == 1.0:
+            ok = ok and not dark.any()
+        else:
+            z = S.binomial_z(int(dark.sum()), n, 1.0 - t)
+            fig += f"; blocked {int(dark.sum())} of {n} (1 - T = {1 - t:.4f}, z = {z:+.2f})"
+            ok = ok and 0.05 < t < 0.95 and abs(z) <= Z_LIMIT
+        if shadow_rays is not None:
+            probes = n if (want.any() and estimator in (REF, CORR) and self.rects[0].kind == "lambert") else 0
+            fig += f"; shadow rays {shadow_rays} (law {probes})"
+            ok = ok and shadow_rays == probes
+        assert ok, "FAILED: " + fig
+        return fig
+
+
+RECEIVER = Rect(1, (-1000.0, 1000.0, -1000.0, 1000.0), 0.0, "lambert", ALBEDO)
+# three lights without primitives: a y-rectangle above facing down, an x-rectangle at the side facing -x, a skewed parallelogram
+# that straddles the receiver's horizon (its corner heights are -0.5, 1.5, 2 and 0)
+L_ABOVE = Light((-1.0, 2.0, -0.5), (2.0, 0.0, 0.0), (0.0, 0.0, 1.5), (0.0, -1.0, 0.0), (4.0, 0.0, 0.0))
+L_SIDE = Light((3.0, 0.5, -1.0), (0.0, 2.5, 0.0), (0.0, 0.0, 2.0), (-1.0, 0.0, 0.0), (0.0, 6.0, 0.0))
+_SKEW_U, _SKEW_V = np.array([0.25, 2.0, 0.5]), np.array([1.5, 0.5, 0.0])
+_SKEW_N = np.cross(_SKEW_U, _SKEW_V)
+_SKEW_POS = np.array([-2.0, -0.5, 2.5])
+_SKEW_N = _SKEW_N / np.linalg.norm(_SKEW_N) * (-1.0 if (_SKEW_POS + 0.5 * _SKEW_U + 0.5 * _SKEW_V) @ _SKEW_N > 0 else 1.0)  # towards the receiver
+L_SKEW = Light(_SKEW_POS, _SKEW_U, _SKEW_V, _SKEW_N.astype(np.float32), (0.0, 0.0, 3.0))
+FOREIGN_PDF = (1, (-0.75, 1.25, -0.25, 0.75), 1.75)   # another plane and extent than any light's
+# emitting primitives: the two that L_ABOVE and L_SIDE describe, flagged to face the receiver, and one no definition describes
+E_ABOVE = Rect(1, (-1.0, 1.0, -0.5, 1.0), 2.0, "light", (4.0, 0.0, 0.0), flip=1)
+E_SIDE = Rect(0, (0.5, 3.0, -1.0, 1.0), 3.0, "light", (0.0, 6.0, 0.0), flip=1)
+E_UNLISTED = Rect(2, (-2.0, 2.0, 0.5, 2.0), -4.0, "light", (0.0, 0.0, 3.0))
+# its projection onto y = 2 is x in [-0.5, 0.25], z in [-0.125, 0.625]: inside E_ABOVE, on cell borders of the 2048^2 grid
+OCCLUDER = Rect(1, (-0.25, 0.125, -0.0625, 0.3125), 1.0, "lambert", (0.0, 0.0, 0.0))
+# Cornell's proportions: the emitting rectangle 0.9 above its definition's plane, the pdf rectangle on the definition's
+E_OWN = Rect(1, (-40.0, 90.0, -30.0, 75.0), 200.9, "light", (15.0, 0.0, 0.0), flip=1)
+L_OWN = Light((-40.0, 200.0, -30.0), (130.0, 0.0, 0.0), (0.0, 0.0, 105.0), (0.0, -1.0, 0.0), (15.0, 0.0, 0.0))
+OWN_PDF = (1, (-40.0, 90.0, -30.0, 75.0), 200.0)
+E_WHITE = Rect(1, (-1.0, 1.0, -0.5, 1.0), 2.0, "light", (4.0, 4.0, 4.0), flip=1)
+L_WHITE = Light((-1.0, 2.0, -0.5), (2.0, 0.0, 0.0), (0.0, 0.0, 1.5), (0.0, -1.0, 0.0), (4.0, 4.0, 4.0))
+ABOVE_PDF = (1, (-1.0, 1.0, -0.5, 1.0), 2.0)
+L_BEHIND = Light((-1.0, 2.0, -0.5), (2.0, 0.0, 0.0), (0.0, 0.0, 1.5), (0.0, 1.0, 0.0), (4.0, 0.0, 0.0))  # faces up: the receiver is behind it
+# a light seen from behind that no primitive carries, in front of E_ABOVE: its projection onto y = 2 is OCCLUDER's. The mixture's
+# light branch aims through it, so E_ABOVE's weight falls where a direction crosses it (rtw.h: p_light counts either side)
+L_BACK = Light((-0.25, 1.0, -0.0625), (0.5, 0.0, 0.0), (0.0, 0.0, 0.375), (0.0, 1.0, 0.0), (0.0, 6.0, 0.0))
+# thin black rectangles 2^-11 = 4.9e-4 from an end of the probe - between the reference estimator's 5e-5 and the corrected ones'
+# 1e-3 -, each on the way to the half x > 0 (x < 0) of the light above: they shadow half the reference estimator's samples and none
+# of the corrected estimator's. The near one is met by no camera ray: NEAR_D passes y = 2^-11 at x = -2^-10.
+THIN = 2.0 ** -11
+THIN_FAR = Rect(1, (-2.0, 0.0, -2.0, 2.0), 2.0 - THIN, "lambert", (0.0, 0.0, 0.0))
+THIN_NEAR = Rect(1, (0.0, 2.0 * THIN, -2.0 * THIN, 2.0 * THIN), THIN, "lambert", (0.0, 0.0, 0.0))
+NEAR_D = (2.0, -1.0, 0.25)
+MIRROR_D = (0.25, -1.0, 0.125)  # reflected at the origin it meets E_MIRROR at (0.5, 2, 0.25)
+E_MIRROR = Rect(1, (-1.0, 1.0, -0.5, 1.0), 2.0, "light", (4.0, 6.0, 3.0), flip=1)
+L_MIRROR = Light((-1.0, 2.0, -0.5), (2.0, 0.0, 0.0), (0.0, 0.0, 1.5), (0.0, -1.0, 0.0), (4.0, 6.0, 3.0))
+POINT_EMISSION = (4.0, 2.0, 1.0)
+# (position, normal): the three normal axes, grazing cos_l (1/64), grazing ndl (1/64), distances from 2^-3 to 2^10
+POINT_LIGHTS = (((1.0, 2.0, -0.5), (0.0, -1.0, 0.0)), ((0.0, 0.125, 0.0), (0.0, -1.0, 0.0)), ((3.0, 0.5, -1.0), (-1.0, 0.0, 0.0)),
+                ((-3.0, 0.5, 1.0), (1.0, 0.0, 0.0)), ((0.5, 1.0, 4.0), (0.0, 0.0, -1.0)), ((0.5, 1.0, -4.0), (0.0, 0.0, 1.0)),
+                ((0.125, 8.0, 0.0), (-1.0, 0.0, 0.0)), ((0.0, 8.0, -0.125), (0.0, 0.0, 1.0)), ((8.0, 0.125, 0.0), (-1.0, 0.0, 0.0)),
+                ((0.0, 0.125, 8.0), (0.0, 0.0, -1.0)), ((0.0, 1024.0, 0.0), (0.0, -1.0, 0.0)), ((384.0, 512.0, -640.0), (0.0, -1.0, 0.0)))
+MEDIUM = ("box", (1.5, 0.5, -1.0, 2.5, 2.5, 1.0), 0.8)  # the probe towards (4, 3, 0) crosses 1.25 of it: T = e^-1
+MEDIUM_LIGHT = ((4.0, 3.0, 0.0), (-1.0, 0.0, 0.0))
+
+
+def _point_case(position, normal, media=()):
+    axis = int(np.argmax(np.abs(normal)))
+    aa, ab = (1 if axis == 0 else 0), (1 if axis == 2 else 2)
+    pdf = (axis, (position[aa], position[aa], position[ab], position[ab]), position[axis])
+    lt = Light(position, (0, 0, 0), (0, 0, 0), normal, POINT_EMISSION, area=1.0)
+    return ExactCase([lt], [RECEIVER], pdf, 1, (CORR,) if media else (REF, CORR), media=media,
+                     value=lambda est: point_value(position, normal, POINT_EMISSION, est), units=K_FACTOR * MEASURED_CONSTANT_LIGHT)
+
+
+def _mirror_case():
+    mirror = Rect(1, RECEIVER.ext, 0.0, "metal", (1.0, 1.0, 1.0))
+    return ExactCase([L_MIRROR], [mirror, E_MIRROR], ABOVE_PDF, 2, (REF, CORR, NO_NEE, MIX), d=MIRROR_D, value=lambda est: np.array(E_MIRROR.color))
+
+
+D2 = (CORR, NO_NEE, MIX)
+CASES = {
+    "three_lights-d1": lambda: LightCase([L_ABOVE, L_SIDE, L_SKEW], [RECEIVER], FOREIGN_PDF, 1, (REF, CORR)),
+    "two_emitters_one_unlisted-d1": lambda: LightCase([L_ABOVE, L_SIDE], [RECEIVER, E_ABOVE, E_SIDE, E_UNLISTED], FOREIGN_PDF, 1, (CORR,)),
+    "two_emitters_one_unlisted-d2": lambda: LightCase([L_ABOVE, L_SIDE], [RECEIVER, E_ABOVE, E_SIDE, E_UNLISTED], FOREIGN_PDF, 2, D2, n=N_RARE),
+    "occluded-d1": lambda: LightCase([L_ABOVE, L_SIDE], [RECEIVER, E_ABOVE, E_SIDE, E_UNLISTED, OCCLUDER], FOREIGN_PDF, 1, (CORR,)),
+    "occluded-d2": lambda: LightCase([L_ABOVE, L_SIDE], [RECEIVER, E_ABOVE, E_SIDE, E_UNLISTED, OCCLUDER], FOREIGN_PDF, 2, D2, n=N_RARE),
+    "behind-d1": lambda: LightCase([L_BEHIND], [RECEIVER], ABOVE_PDF, 1, (REF, CORR)),
+    "own_emitter-d1": lambda: LightCase([L_OWN], [RECEIVER, E_OWN], OWN_PDF, 1, (REF, CORR)),
+    "own_emitter-d2": lambda: LightCase([L_OWN], [RECEIVER, E_OWN], OWN_PDF, 2, D2),
+    "nonwhite_pair-d1": lambda: LightCase([L_WHITE], [RECEIVER, E_WHITE], ABOVE_PDF, 1, (REF, CORR)),
+    "nonwhite_pair-d2": lambda: LightCase([L_WHITE], [RECEIVER, E_WHITE], ABOVE_PDF, 2, D2),
+    "mirror_to_light-d2": _mirror_case,
+    "probe_far_end-d1": lambda: LightCase([L_ABOVE], [RECEIVER, E_ABOVE, THIN_FAR], ABOVE_PDF, 1, (REF, CORR)),
+    "probe_near_end-d1": lambda: LightCase([L_ABOVE], [RECEIVER, E_ABOVE, THIN_NEAR], ABOVE_PDF, 1, (REF, CORR), d=NEAR_D),
+    "mixture_behind-d2": lambda: LightCase([L_ABOVE, L_BACK], [RECEIVER, E_ABOVE], FOREIGN_PDF, 2, D2),
+    "through_medium-d1": lambda: _point_case(*MEDIUM_LIGHT, media=(MEDIUM,)),
+}
+CASES.update({f"point{i:02d}-d1": (lambda p=p, nrm=nrm: _point_case(p, nrm)) for i, (p, nrm) in enumerate(POINT_LIGHTS)})
+RNGS, DRAWS, SEEDS = S.RNGS, S.DRAWS, S.SEEDS
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    return CASES[name]()
+
+
+def drawn(name):
+    """Whether the case's samples depend on the draws (a deterministic case runs once per generator)."""
+    c = case(name)
+    return not isinstance(c, ExactCase) or bool(c.media)
+
+
+def check(name, samples, estimator, **kw):
+    """The assertions of case `name` on its samples (any shape (..., 3)); returns the figures for the caller to print."""
+    return f"{name}, estimator {estimator}: " + case(name).check(samples, estimator, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_samples(name, rng_kind, estimator, seed, key_base=0):
+    """((1, keys_per_ray, 3) float32 samples, shadow rays): the oracle's answer for case `name`, computed once and left unchanged."""
+    import oracle
+    c = case(name)
+    img, st = oracle.render(R.ray_blob(c.blob, c.o[0], c.ll[0]), S.render_params(c, 0, rng_kind, estimator, seed, key_base), threads=4)
+    out = img[..., :3].reshape(1, c.keys_per_ray, 3).copy()
+    out.setflags(write=False)
+    return out, int(st.shadow_rays)
+
+
+def irradiance_law(name):
+    """{channel: (Le, visible form factor)} of the emitters of case `name` at the receiver point: an irradiance probe of one
+    sample at depth 1 is pi * Le of the emitter its cosine-distributed direction meets, so the irradiance is pi * sum Le_c F_c."""
+    c = case(name)
+    hits = c.hit_law(False)
+    return {int(np.nonzero(c.rects[j].color)[0][0]): (float(c.rects[j].color.max()), hits.visible[j]) for j in hits.emitters}
+
+
+def check_irradiance(name, samples, pi32=np.float32(3.14159265)):
+    """The assertions on (n, 3) float32 irradiance probes of one sample and one segment each at the receiver point of case `name`:
+    every probe is exactly 0 or float32(pi) * Le in the emitter's channel, the hit count per channel is binomial with p = the
+    visible form factor, the mean is pi * Le * F by z-test."""
+    law, n, figs, ok = irradiance_law(name), len(samples), [], True
+    for ch in range(3):
+        x = np.asarray(samples)[:, ch]
+        if ch not in law:
+            ok = ok and not x.any()
+            figs.append(f"channel {ch}: law 0, largest probe {np.abs(x).max():.3g}")
+            continue
+        le, f = law[ch]
+        hits = int((x != 0).sum())
+        z = S.binomial_z(hits, n, f)
+        exact = bool(np.isin(x, (np.float32(0), np.float32(le) * pi32)).all())
+        mean, want = float(x.astype(np.float64).mean()), np.pi * le * f
+        mean_z = (mean - want) / (np.pi * le * np.sqrt(f * (1.0 - f) / n))
+        figs.append(f"channel {ch}: {hits} hits of {n} (form factor {f:.5f}, z = {z:+.2f}), irradiance {mean:.5f} (law {want:.5f}, z = {mean_z:+.2f}), "
+                    f"every hit exactly pi * Le: {exact}")
+        ok = ok and exact and abs(z) <= Z_LIMIT and abs(mean_z) <= Z_LIMIT
+    fig = f"{name}: " + "; ".join(figs)
+    assert ok, "FAILED: " + fig
+    return fig
+
+
+# ---------------------------------------------------------------- the measurements behind the constant and the grids
+def measure_constant(verbose=False):
+    """point_value at float32 against itself at float64 over the tests' point lights, relative, in units of 2^-24."""
+    worst = 0.0
+    for (p, nrm) in POINT_LIGHTS + (MEDIUM_LIGHT,):
+        for est in (REF, CORR):
+            v64, v32 = point_value(p, nrm, POINT_EMISSION, est), point_value(p, nrm, POINT_EMISSION, est, np.float32)
+            e = float(np.abs(v32.astype(np.float64) / v64 - 1.0).max() / U)
+            if verbose:
+                print(f"point light at {p}, normal {nrm}, estimator {est}: {e:.4f}")
+            worst = max(worst, e)
+    return worst
+
+
+def _extremes(a, b):
+    """The relative change of a Table's extremes between two grids."""
+    return max(abs(a.hi / b.hi - 1), abs(a.lo / b.lo - 1) if a.lo > 0 and b.lo > 0 else 0.0)
+
+
+def quadrature_errors():
+    """What the grids are worth, relative: each light's and emitter's mean against the closed form and against the grid at half
+    resolution (the second moment and the non-zero share too)."""
+    out = {}
+    for name in ("three_lights-d1", "occluded-d1", "own_emitter-d1"):
+        c = case(name)
+        for est in c.estimators:
+            fine, half = c.sample_law(est), c.sample_law(est, grid=GRID // 2)
+            lights = c.lights if est == REF else moved_lights(c.lights, c.rects)[0]
+            for i, (a, b) in enumerate(zip(fine.tables, half.tables)):
+                out[f"{name}, estimator {est}, light {i}: grid - grid at half resolution (mean, second moment, share)"] = max(
+                    abs(a.m1 / b.m1 - 1), abs(a.m2 / b.m2 - 1), abs(a.share / b.share - 1))
+                out[f"{name}, estimator {est}, light {i}: extremes"] = _extremes(a, b)
+                if est == CORR:
+                    axis = int(np.argmax(np.abs(np.cross(lights[i].u, lights[i].v))))
+                    rect_like = np.count_nonzero(lights[i].u) == 1 and np.count_nonzero(lights[i].v) == 1
+                    dull = [rc for rc in c.rects if rc.kind != "light"]
+                    f = visible_form_factor(axis, lights[i].position[axis], lights[i].polygon(), dull) if rect_like else form_factor(lights[i].polygon())
+                    out[f"{name}, estimator {est}, light {i}: grid mean - Lambert's formula"] = abs(a.m1 / f - 1)
+    for name in ("occluded-d2", "own_emitter-d2", "mixture_behind-d2"):
+        c = case(name)
+        fine, half = c.hit_law(True), c.hit_law(True, grid=GRID // 2)
+        for j in fine.emitters:
+            out[f"{name}, mixture, emitter {j}: grid mean - Lambert's formula"] = abs(fine.tables[j].m1 / fine.visible[j] - 1)
+            out[f"{name}, mixture, emitter {j}: grid - grid at half resolution (second moment, share)"] = max(
+                abs(fine.tables[j].m2 / half.tables[j].m2 - 1), abs(fine.tables[j].share / half.tables[j].share - 1))
+            out[f"{name}, mixture, emitter {j}: extremes"] = _extremes(fine.tables[j], half.tables[j])
+    return out
+
+
+if __name__ == "__main__":
+    print(f"MEASURED_CONSTANT_LIGHT = {measure_constant(verbose=True):.4f}")
+    for k_, v_ in quadrature_errors().items():
+        print(f"{k_}: {v_:.2e}")

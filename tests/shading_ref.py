@@ -2,6 +2,8 @@
 the reference's material, medium, texture and miss programs (material/*.cu, lib/sampling.cuh, lib/onb.cuh, geometry/volumeBox.cu,
 volumeSphere.cu, texture/*.cu, miss/miss.cu, raygen/raygen.cu), written without looking at oracle/rtw_oracle.c or the kernels. Shared
 by test_shading_cpu.py (the oracle against this file) and test_gpu_shading.py (the kernels against this file, then against the oracle).
+Its neighbours: geometry_ref.py (the closest hit itself, shading normals, texture coordinates) and lighting_ref.py (direct lighting:
+the light sample, its probe and the emitter hits under all four estimators), which reuses this file's cases, draws and limits.
 
 How a single event is observed
   Sky decoder   max_depth = 2, sky_light = 1, no lights, white constant albedo. The second segment misses everything and the sample's

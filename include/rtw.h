@@ -103,6 +103,16 @@ typedef enum rtw_pdf_gen {
     RTW_PDF_RECT_Z = 5
 } rtw_pdf_gen;
 
+/* Camera draws (pixel = the stream key width * y + x, sample = the absolute sample index):
+ *   RTW_RNG_TEA_LCG takes no seed. In order: jitter x, jitter y, the two lens draws (perspective camera only, see
+ *     rtw_camera_type), the gather-time draw. The first ray time is the same LCG output as the gather-time draw: raygen.cu:100
+ *     copies the seed into the payload before raygen.cu:103 draws the gather time, and rayColor starts from the copy.
+ *   RTW_RNG_PHILOX: a word w gives the 24-bit uniform (w >> 8) / 2^24. Words 0-3 of block (pixel, sample, 0, 0) are jitter x,
+ *     jitter y and the two lens draws, for every camera kind. The gather-time draw is the fifth uniform of that block,
+ *     ((w0 & 0xff) << 16 | (w1 & 0xff) << 8 | (w2 & 0xff)) / 2^24: the low bytes the four uniforms leave unused. The camera
+ *     ray's time is word 0 of block (pixel, sample, 0, 2), the first draw of stream 2; later segments go on in that stream.
+ *   The gather time is time0 + draw * (time1 - time0) of the camera in use. A ray time is the raw uniform in [0, 1), as
+ *   raygen.cu:48 hands rnd(seed) to optixTraverse: it does not span time0 / time1. */
 typedef enum rtw_rng_kind {
     RTW_RNG_PHILOX = 0,  /* Philox4x32-10, key=(seed,0), counter=(pixel, sample, block, stream)        */
     RTW_RNG_TEA_LCG = 1  /* the reference's own: tea<64>(pixel, sample) + 24-bit LCG rnd() + xorshift
@@ -173,7 +183,9 @@ typedef struct rtw_pdf {
  *   RTW_CAM_ORTHOGRAPHIC  origin = lower_left + s*horizontal + t*vertical + camera origin (as camera.cuh:52 states it: the origin
  *                         enters twice when lower_left is built the way ioOrthographicCamera builds it); direction = -normalize(w)
  * Only the perspective camera draws a lens sample (two draws, consumed even at lens radius 0: camera.cu:11-19); the other
- * two take no seed in the reference and draw nothing (visible in the TEA+LCG stream; Philox raygen draws are positional). */
+ * two take no seed in the reference and draw nothing (visible in the TEA+LCG stream; Philox raygen draws are positional).
+ * time0 / time1 are the shutter of every kind: the reference's environment and orthographic constructors take t0, t1 and drop
+ * them (scene/ioCamera.h:126-128, 149-151; neither is ever built there), the host description's pass them on. */
 typedef enum rtw_camera_type { RTW_CAM_PERSPECTIVE = 0, RTW_CAM_ENVIRONMENT = 1, RTW_CAM_ORTHOGRAPHIC = 2 } rtw_camera_type;
 
 typedef struct rtw_camera {
@@ -524,7 +536,8 @@ int rtw_cast_device(rtw_ctx* ctx, const float* rays, const float* ray_time, cons
  *     k = key_offset + i (mod 2^32; a render's key is width*y + x) and sample index sample_offset + s. Philox: block (k, sample, 0, 0),
  *     whose words 0-3 (jitter, lens) are drawn and unused and whose low bytes give the gather-time draw, then stream 1 from draw 0 and
  *     ray times from stream 2. TEA+LCG: tea<64>(k, sample), four LCG draws discarded, the path's two generator words, then the
- *     gather-time draw. Gather time and ray times span the uploaded scene's camera.time0 / time1.
+ *     gather-time draw. The gather time spans the uploaded scene's camera.time0 / time1; ray times are the raw uniforms in [0, 1)
+ *     (rtw_rng_kind above).
  *     Hence: a scene whose header carries ray i as a perspective camera with horizontal = vertical = 0 and lens_radius = 0 (origin = o,
  *     lower_left with lower_left - o = d in float32), rendered by rtw_render at a pixel with stream key k, gives ray i's result, bit for bit.
  *   Output: rgba_out[i] = the sum of the samples' radiance in the summation order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from

@@ -23,6 +23,13 @@
 //   accumulation sessions (rtw_accum_*): the same launches over a range of samples, resolved into a state the session owns
 //     (rtw_accum.h) that keeps the summation unit open between adds; splitting and the saved form: rtw_accum_state.h
 //
+//   the query family (rtw_cast, rtw_radiance, rtw_probe, rtw_probe_sh, rtw_views, rtw_views_guides, rtw_denoise_views, rtw_probe_adaptive,
+//     rtw_views_adaptive, each with a _device variant): the caller's rays, probes, points or cameras through kernels of their own
+//     translation units. On the host they share one scaffold: grow_buffer for every buffer a context grows on demand, QueryCall
+//     (query_open / query_close: device context, stream, the two timing events, the control words), query_chunks for the host
+//     variants' upload / issue / copy-back loop through one staging slab (laid out by rtw_stage_plan.h), query_stats for the tail,
+//     and adaptive_issue, the checkpoint loop of the two adaptive families
+//
 // render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
 // (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU), through the
 // schedules they share with the adaptive renderer and the sessions (issue_path_pass, run_batches).
@@ -58,6 +65,7 @@
 #include "rtw_cast.h"
 #include "rtw_radiance.h"
 #include "rtw_radiance_plan.h"
+#include "rtw_stage_plan.h"
 #include "rtw_probe.h"
 #include "rtw_probe_sh.h"
 #include "rtw_view.h"
@@ -177,20 +185,18 @@ struct rtw_ctx {
         double2* mom = nullptr;
         float* err = nullptr;
     } acc;
-    // rtw_cast's staging (the host variant): one allocation of cast_rays rays' inputs and outputs, grown on demand, kept until rtw_destroy
-    void* cast_buf = nullptr;
-    size_t cast_rays = 0;
-    // rtw_radiance's scratch, grown on demand and kept until rtw_destroy: the unit sums [unit][ray] of calls beyond 128 spp, the host
-    // variant's staging (rad_stage_bytes: a chunk's rays and their results) and the control words (kStatRows rows of 8 counters, then the queue word)
-    void* rad_slab = nullptr;
+    // The query family's scratch (rtw_cast ... rtw_views_adaptive), each grown on demand (grow_buffer) and kept until rtw_destroy.
+    // The host variants' staging slab: one chunk's inputs and results, laid out per call by rtw_stage_plan.h. Every call that uses it
+    // returns synchronised, so one slab serves them all.
+    void* stage_slab = nullptr;
+    size_t stage_bytes = 0;
+    void* rad_slab = nullptr;  // the unit sums [unit][ray] of calls beyond 128 spp; the block sums of an adaptive pass
     size_t rad_slab_bytes = 0;
-    void* rad_stage = nullptr;
-    size_t rad_stage_bytes = 0;
-    void* view_buf = nullptr;  // rtw_views: the call's view records
+    void* view_buf = nullptr;  // the view records of a host call
     size_t view_bytes = 0;
     void* dn_buf = nullptr;  // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
     size_t dn_bytes = 0;
-    unsigned long long* rad_ctl = nullptr;
+    unsigned long long* rad_ctl = nullptr;  // the control words: kStatRows rows of 8 counters, then the queue word (query_open)
     // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept;
     // rtw_views_adaptive's per-pixel state as well (the same layout over the pixels of a call or batch: a call initialises what it uses)
     void* padapt = nullptr;
@@ -511,9 +517,8 @@ int impl_destroy(rtw_ctx* c) {
     if (c->stage) (void)hipFree(c->stage);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_out) (void)hipFree(c->d_out);
-    if (c->cast_buf) (void)hipFree(c->cast_buf);
+    if (c->stage_slab) (void)hipFree(c->stage_slab);
     if (c->rad_slab) (void)hipFree(c->rad_slab);
-    if (c->rad_stage) (void)hipFree(c->rad_stage);
     if (c->padapt) (void)hipFree(c->padapt);
     if (c->view_buf) (void)hipFree(c->view_buf);
     if (c->dn_buf) (void)hipFree(c->dn_buf);
@@ -1871,8 +1876,30 @@ int cast_check(rtw_ctx* c, const char* what, const float* rays, size_t n, int32_
     return RTW_OK;
 }
 
-// two timing events of the context's pool (no event is created once a context has timed anything)
-hipError_t cast_events(rtw_ctx* d, hipEvent_t ev[2]) {
+// ---- the host scaffold of the query family (everything from here to rtw_views_adaptive): the buffers a context grows on demand, the
+// scope of one call (device context, stream, the two timing events, the control words, the staging slab), the chunk loop of the host
+// variants, the view records and the stats tail. What is specific to an entry point is its checks, what it stages and what it issues.
+
+// A device buffer that a context grows on demand and keeps until rtw_destroy: at least `need` of the capacity's unit (bytes; probes
+// for padapt), `bytes` large when it has to be made anew. drain: the stream whose pending work may still read the old buffer and is
+// waited for before that is freed, or null where every use has been waited for. A failed allocation leaves the pointer null and the
+// capacity 0.
+hipError_t grow_buffer(void*& buf, size_t& cap, size_t need, size_t bytes, const hipStream_t* drain) {
+    if (need <= cap) return hipSuccess;
+    if (drain) {
+        const hipError_t e = hipStreamSynchronize(*drain);
+        if (e != hipSuccess) return e;
+    }
+    if (buf) (void)hipFree(buf);
+    buf = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(&buf, bytes);
+    if (e != hipSuccess) { buf = nullptr; return e; }
+    cap = need;
+    return hipSuccess;
+}
+
+// the context's two timing events, out of its pool (no event is created once a context has timed anything)
+hipError_t timing_events(rtw_ctx* d, hipEvent_t ev[2]) {
     while (d->ev_pool.size() < 2) {
         hipEvent_t n = nullptr;
         const hipError_t e = hipEventCreate(&n);
@@ -1883,88 +1910,164 @@ hipError_t cast_events(rtw_ctx* d, hipEvent_t ev[2]) {
     return hipSuccess;
 }
 
-void cast_stats(rtw_stats* stats, size_t n, int32_t mode, float ms) {
+// One call of the family, from the last refusal to the return.
+struct QueryCall {
+    rtw_ctx* d = nullptr;     // the device context it runs on (a group's first device)
+    hipStream_t s = nullptr;  // the caller's stream, or the context's
+    hipEvent_t ev[2] = {};    // ev[0] before the first thing the call puts on s, ev[1] after the last launch
+    char* stage = nullptr;    // the context's staging slab (host variants)
+    bool ended = false;       // ev[1] is recorded and waited for (query_chunks does that)
+};
+
+// Opens a call on `hip_stream` (null: the context's own). stage_bytes: what the call needs of the staging slab (rtw_stage_plan.h), 0 for
+// none; it is grown before anything is timed, and never while something reads it: every call that uses it returns synchronised.
+// ctl: the call counts in d->rad_ctl (kStatRows rows of 8 counters, then the queue word), whose rows are zeroed on the stream.
+// timed = false leaves ev[0] alone: the call only waits for ev[1].
+int query_open(rtw_ctx* c, QueryCall& q, void* hip_stream, size_t stage_bytes, bool ctl, bool timed = true) {
+    rtw_ctx* const d = q.d = c->kids.empty() ? c : c->kids[0];
+    HIP_TRY(c, hipSetDevice(d->device));
+    q.s = hip_stream ? (hipStream_t)hip_stream : d->stream;
+    HIP_TRY(c, grow_buffer(d->stage_slab, d->stage_bytes, stage_bytes, stage_bytes, nullptr));
+    q.stage = (char*)d->stage_slab;
+    HIP_TRY(c, timing_events(d, q.ev));
+    if (ctl && !d->rad_ctl) HIP_TRY(c, hipMalloc((void**)&d->rad_ctl, (kStatRows * 8 + 2) * sizeof(unsigned long long)));
+    if (timed) HIP_TRY(c, hipEventRecord(q.ev[0], q.s));
+    if (ctl) HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), q.s));
+    return RTW_OK;
+}
+
+// Closes it: records ev[1] and waits for it, unless the chunk loop has done so; `seconds` (where not null) receives the device time
+// between the two events.
+int query_close(rtw_ctx* c, QueryCall& q, double* seconds) {
+    if (!q.ended) {
+        HIP_TRY(c, hipEventRecord(q.ev[1], q.s));
+        HIP_TRY(c, hipEventSynchronize(q.ev[1]));
+        q.ended = true;
+    }
+    if (seconds) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, q.ev[0], q.ev[1]));
+        *seconds = (double)ms * 1e-3;
+    }
+    return RTW_OK;
+}
+
+// The host variants' loop over chunks of at most `chunk` of the call's n items, all through the one staging slab: upload(i0, m),
+// issue(i0, m), ev[1] after the last chunk's issue, download(i0, m), and a wait, because the next chunk reuses the slab (and the
+// caller's memory is his again when the call returns). Each callable returns an RTW code.
+template <class Upload, class Issue, class Download>
+int query_chunks(rtw_ctx* c, QueryCall& q, size_t n, size_t chunk, Upload upload, Issue issue, Download download) {
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        int rc;
+        if ((rc = upload(i0, m)) != RTW_OK || (rc = issue(i0, m)) != RTW_OK) return rc;
+        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(q.ev[1], q.s));
+        if ((rc = download(i0, m)) != RTW_OK) return rc;
+        HIP_TRY(c, hipStreamSynchronize(q.s));
+    }
+    q.ended = true;
+    return RTW_OK;
+}
+int no_upload(size_t, size_t) { return RTW_OK; }  // (the views: their records are uploaded once, before the loop)
+
+// The view records of a host entry, which the host can read: `what` names the entry point.
+int view_records_check(rtw_ctx* c, const char* what, const rtw_view* views, size_t n_views) {
+    for (size_t v = 0; v < n_views; v++) {
+        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
+            return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": view " + std::to_string(v) + ": bad camera_type");
+        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
+            return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": view " + std::to_string(v) + ": reserved must be 0");
+    }
+    return RTW_OK;
+}
+// ... and their copy to the context's record buffer, on the call's stream (after ev[0]: the upload is part of the call's time)
+int view_records_upload(rtw_ctx* c, QueryCall& q, const rtw_view* views, size_t n_views) {
+    const size_t bytes = n_views * sizeof(rtw_view);
+    HIP_TRY(c, grow_buffer(q.d->view_buf, q.d->view_bytes, bytes, bytes, nullptr));
+    HIP_TRY(c, hipMemcpyAsync(q.d->view_buf, views, bytes, hipMemcpyHostToDevice, q.s));
+    return RTW_OK;
+}
+
+// The stats tail of the calls that trace paths or occlusion rays: closes the call, then the samples taken, the counters of the rows
+// (occlusion: every sample is one occlusion ray, nothing else is traced) and the device time.
+int query_stats(rtw_ctx* c, QueryCall& q, rtw_stats* stats, uint64_t samples, bool occlusion) {
+    double seconds = 0.0;
+    int rc = query_close(c, q, stats ? &seconds : nullptr);
+    if (rc != RTW_OK || !stats) return rc;
+    memset(stats, 0, sizeof *stats);
+    stats->samples = samples;
+    if (occlusion) {
+        stats->shadow_rays = samples;
+    } else {
+        unsigned long long hs[8];
+        if ((rc = sum_stat_rows(c, q.d->rad_ctl, hs)) != RTW_OK) return rc;
+        stats->segments = hs[0]; stats->shadow_rays = hs[1];
+        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
+    }
+    stats->seconds = seconds;
+    return RTW_OK;
+}
+
+void cast_stats(rtw_stats* stats, size_t n, int32_t mode) {
     memset(stats, 0, sizeof *stats);
     (mode == RTW_CAST_ANY ? stats->shadow_rays : stats->segments) = (uint64_t)n;
-    stats->seconds = (double)ms * 1e-3;
 }
 
 int impl_cast_device(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
                      void* hip_stream, rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
-    const int rc = cast_check(c, "rtw_cast_device", rays, n, mode, out);
+    int rc = cast_check(c, "rtw_cast_device", rays, n, mode, out);
     if (rc) return rc;
     if (n > 0 && (((uintptr_t)rays & 15) || ((uintptr_t)out->normal & 15) || ((uintptr_t)out->uv & 7)))
         return fail(c, RTW_ERR_INVALID_ARG, "rtw_cast_device: rays and normal must be 16-byte aligned, uv 8-byte aligned");
-    if (stats) cast_stats(stats, n, mode, 0.f);  // (after every refusal: a refused call leaves *stats alone)
+    if (stats) cast_stats(stats, n, mode);  // (after every refusal: a refused call leaves *stats alone)
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, false)) != RTW_OK) return rc;
     const CastArgs a{(const float4*)rays, ray_time, gather_time, (uint64_t)n, out->t, out->prim, out->material, (float4*)out->normal, (float2*)out->uv};
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, cast_launch(d, mode, a, s));
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        stats->seconds = (double)ms * 1e-3;
-    }
-    return RTW_OK;
+    HIP_TRY(c, cast_launch(q.d, mode, a, q.s));
+    return query_close(c, q, stats ? &stats->seconds : nullptr);
 }
 
 int impl_cast(rtw_ctx* c, const float* rays, const float* ray_time, const float* gather_time, size_t n, int32_t mode, const rtw_hits* out,
               rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
-    const int rc = cast_check(c, "rtw_cast", rays, n, mode, out);
+    int rc = cast_check(c, "rtw_cast", rays, n, mode, out);
     if (rc) return rc;
-    if (stats) cast_stats(stats, n, mode, 0.f);
+    if (stats) cast_stats(stats, n, mode);
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const size_t chunk = std::min(n, read_tuning().cast_chunk);
-    // the staging slab: per ray 32 B of ray, two times, and the five outputs (4 + 4 + 4 + 16 + 8 B), every section 256-byte aligned
-    const size_t width[8] = {32, 4, 4, 4, 4, 4, 16, 8};
-    if (chunk > d->cast_rays) {
-        if (d->cast_buf) (void)hipFree(d->cast_buf);
-        d->cast_buf = nullptr; d->cast_rays = 0;
-        size_t bytes = 0;
-        for (size_t w : width) bytes += (chunk * w + 255) & ~(size_t)255;
-        HIP_TRY(c, hipMalloc(&d->cast_buf, bytes));
-        d->cast_rays = chunk;
-    }
-    char* sec[8];
-    {
-        size_t off = 0;
-        for (int k = 0; k < 8; k++) { sec[k] = (char*)d->cast_buf + off; off += (d->cast_rays * width[k] + 255) & ~(size_t)255; }
-    }
+    // staged per ray: 32 B of ray, the two times the caller gave, and those of the five outputs he wants (4 + 4 + 4 + 16 + 8 B)
+    const uint64_t width[8] = {32, 4, 4, 4, 4, 4, 16, 8};
     void* const dst[5] = {out->t, out->prim, out->material, out->normal, out->uv};
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {
-        const size_t m = std::min(chunk, n - i0);
-        HIP_TRY(c, hipMemcpyAsync(sec[0], rays + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
-        if (ray_time) HIP_TRY(c, hipMemcpyAsync(sec[1], ray_time + i0, m * 4, hipMemcpyHostToDevice, d->stream));
-        if (gather_time) HIP_TRY(c, hipMemcpyAsync(sec[2], gather_time + i0, m * 4, hipMemcpyHostToDevice, d->stream));
-        CastArgs a{(const float4*)sec[0], ray_time ? (const float*)sec[1] : nullptr, gather_time ? (const float*)sec[2] : nullptr, (uint64_t)m,
-                   dst[0] ? (float*)sec[3] : nullptr, dst[1] ? (int32_t*)sec[4] : nullptr, dst[2] ? (int32_t*)sec[5] : nullptr,
-                   dst[3] ? (float4*)sec[6] : nullptr, dst[4] ? (float2*)sec[7] : nullptr};
-        HIP_TRY(c, cast_launch(d, mode, a, d->stream));
-        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        for (int k = 0; k < 5; k++)
-            if (dst[k]) HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * width[3 + k], sec[3 + k], m * width[3 + k], hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
-    }
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        stats->seconds = (double)ms * 1e-3;
-    }
-    return RTW_OK;
+    const bool want[8] = {true, ray_time != nullptr, gather_time != nullptr, dst[0] != nullptr, dst[1] != nullptr, dst[2] != nullptr, dst[3] != nullptr,
+                          dst[4] != nullptr};
+    const StagePlan st = stage_plan(chunk, 8, width, want);
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)st.bytes, false)) != RTW_OK) return rc;
+    char* sec[8];
+    for (int k = 0; k < 8; k++) sec[k] = want[k] ? q.stage + st.off[k] : nullptr;
+    rc = query_chunks(
+        c, q, n, chunk,
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(sec[0], rays + 8 * i0, m * 32, hipMemcpyHostToDevice, q.s));
+            if (ray_time) HIP_TRY(c, hipMemcpyAsync(sec[1], ray_time + i0, m * 4, hipMemcpyHostToDevice, q.s));
+            if (gather_time) HIP_TRY(c, hipMemcpyAsync(sec[2], gather_time + i0, m * 4, hipMemcpyHostToDevice, q.s));
+            return RTW_OK;
+        },
+        [&](size_t, size_t m) -> int {
+            const CastArgs a{(const float4*)sec[0], (const float*)sec[1], (const float*)sec[2], (uint64_t)m, (float*)sec[3],
+                             (int32_t*)sec[4],      (int32_t*)sec[5],     (float4*)sec[6],      (float2*)sec[7]};
+            HIP_TRY(c, cast_launch(q.d, mode, a, q.s));
+            return RTW_OK;
+        },
+        [&](size_t i0, size_t m) -> int {
+            for (int k = 0; k < 5; k++)
+                if (dst[k]) HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * width[3 + k], sec[3 + k], m * width[3 + k], hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_close(c, q, stats ? &stats->seconds : nullptr);
 }
 
 // ---- rtw_radiance / rtw_radiance_device and rtw_probe / rtw_probe_device (rtw.h): whole paths along the caller's rays through
@@ -1984,19 +2087,19 @@ struct ViewFrame { int32_t width, height; uint64_t first; };
 // float4 of one result: the output stride of a query
 constexpr size_t query_stride(int query) { return query == kQueryProbeSh ? 9 : 1; }
 
-// launch()'s rule: generator x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator)
-RadianceKernel radiance_kernel(int rng_kind, int feat, bool probe, bool sh = false) {
-#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
-    if (sh) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe_sh, RTW_RNG_TEA_LCG) : RTW_RK(k_probe_sh, RTW_RNG_PHILOX);
-    if (probe) return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe, RTW_RNG_TEA_LCG) : RTW_RK(k_probe, RTW_RNG_PHILOX);
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_radiance, RTW_RNG_TEA_LCG) : RTW_RK(k_radiance, RTW_RNG_PHILOX);
-#undef RTW_RK
-}
+// launch()'s rule for the family's shading kernels: the instantiation K_<generator, feature level> (0 hot, 1 cold features, 2 cold
+// features + the mixture estimator) for a call's rng_kind and the scene's level
+#define RTW_PICK_F(K_, R_, FEAT_) ((FEAT_) == 2 ? K_<R_, 2> : (FEAT_) == 1 ? K_<R_, 1> : K_<R_, 0>)
+#define RTW_PICK(K_, RNG_, FEAT_) ((RNG_) == RTW_RNG_TEA_LCG ? RTW_PICK_F(K_, RTW_RNG_TEA_LCG, FEAT_) : RTW_PICK_F(K_, RTW_RNG_PHILOX, FEAT_))
 
-ViewKernel view_kernel(int rng_kind, int feat) {
-#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_view, RTW_RNG_TEA_LCG) : RTW_RK(k_view, RTW_RNG_PHILOX);
-#undef RTW_RK
+// width, height, first and the exact divisions of a frame as view_split / view_raygen read them: what every ViewArgs of the family has
+ViewArgs view_frame_args(const void* d_views, int32_t width, int32_t height, uint64_t first) {
+    ViewArgs va{};
+    va.rays = (const float4*)d_views;
+    va.width = (uint32_t)width; va.height = (uint32_t)height; va.first = (uint32_t)first;
+    magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
+    magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
+    return va;
 }
 
 // the checks the variants share (c: the context the caller holds; a group's has_scene covers its devices)
@@ -2014,19 +2117,9 @@ int radiance_check(rtw_ctx* c, const char* what, const float* rays, size_t n, co
     return RTW_OK;
 }
 
-int radiance_ctl(rtw_ctx* c, rtw_ctx* d) {
-    if (!d->rad_ctl) HIP_TRY(c, hipMalloc((void**)&d->rad_ctl, (kStatRows * 8 + 2) * sizeof(unsigned long long)));
-    return RTW_OK;
-}
-
 // the context's unit slab, at least `need` bytes: grown after the stream's pending work, which may still read the old one
 int radiance_slab(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
-    if (need <= d->rad_slab_bytes) return RTW_OK;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (d->rad_slab) (void)hipFree(d->rad_slab);
-    d->rad_slab = nullptr; d->rad_slab_bytes = 0;
-    HIP_TRY(c, hipMalloc(&d->rad_slab, (size_t)need));
-    d->rad_slab_bytes = (size_t)need;
+    HIP_TRY(c, grow_buffer(d->rad_slab, d->rad_slab_bytes, (size_t)need, (size_t)need, &s));
     return RTW_OK;
 }
 
@@ -2096,8 +2189,10 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
     apply_estimator(sc, RP->estimator);
     const bool probe = query == RTW_PROBE_IRRADIANCE;
     const bool views = query == kQueryViews;
-    const RadianceKernel k = radiance_kernel(RP->rng_kind, sc.has_tex, probe, sh);
-    const ViewKernel kv = view_kernel(RP->rng_kind, sc.has_tex);
+    const RadianceKernel k = sh      ? RTW_PICK(k_probe_sh, RP->rng_kind, sc.has_tex)
+                             : probe ? RTW_PICK(k_probe, RP->rng_kind, sc.has_tex)
+                                     : RTW_PICK(k_radiance, RP->rng_kind, sc.has_tex);
+    const ViewKernel kv = RTW_PICK(k_view, RP->rng_kind, sc.has_tex);
     const RadianceResolve resolve = sh ? k_probe_sh_resolve : probe ? k_probe_resolve : k_radiance_resolve;
     const size_t lds = d->info.lds_bytes;
     const size_t per_cu = (size_t)path_wg_per_cu(views ? (const void*)kv : (const void*)k, lds, 0);
@@ -2123,14 +2218,11 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         a.key0 = radiance_key(key_offset, rg.first);
         HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
         if (views) {
-            ViewArgs va{};
-            va.rays = a.rays; va.out = a.out; va.queue = a.queue; va.stats = a.stats;
+            ViewArgs va = view_frame_args(a.rays, vf->width, vf->height, vf->first + rg.first);
+            va.out = a.out; va.queue = a.queue; va.stats = a.stats;
             va.n = a.n; va.units_per_ray = a.units_per_ray; va.n_units = a.n_units; va.job_units = a.job_units; va.n_jobs = a.n_jobs;
             va.divn_m = a.divn_m; va.divn_s1 = a.divn_s1; va.divn_s2 = a.divn_s2;
             va.spp = a.spp; va.sample0 = a.sample0; va.max_depth = a.max_depth;
-            va.width = (uint32_t)vf->width; va.height = (uint32_t)vf->height; va.first = (uint32_t)(vf->first + rg.first);
-            magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
-            magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
             hipLaunchKernelGGL(kv, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, va);
         } else {
             hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
@@ -2145,26 +2237,6 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
     return RTW_OK;
 }
 
-// after the call's last event: the counters of the rows and the device time
-int radiance_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, size_t n, const rtw_radiance_params* RP, hipEvent_t ev[2], int query) {
-    if (!stats) return RTW_OK;
-    memset(stats, 0, sizeof *stats);
-    stats->samples = (uint64_t)n * (uint64_t)RP->spp;
-    if (query == RTW_PROBE_OCCLUSION) {  // every sample is one occlusion ray, nothing else is traced
-        stats->shadow_rays = stats->samples;
-    } else {
-        unsigned long long hs[8];
-        const int rc = sum_stat_rows(c, d->rad_ctl, hs);
-        if (rc) return rc;
-        stats->segments = hs[0]; stats->shadow_rays = hs[1];
-        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    stats->seconds = (double)ms * 1e-3;
-    return RTW_OK;
-}
-
 // the device variant of either family: `what` names the entry point in messages
 int query_device(rtw_ctx* c, const char* what, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream,
                  rtw_stats* stats, int query) {
@@ -2174,18 +2246,10 @@ int query_device(rtw_ctx* c, const char* what, const float* rays, size_t n, cons
         return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": rays and the output must be 16-byte aligned");
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
-    if ((rc = radiance_issue(c, d, read_tuning(), rays, n, RP, RP->key_offset, (float4*)d_rgba, s, query)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return radiance_stats(c, d, stats, n, RP, ev, query);
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, true)) != RTW_OK) return rc;
+    if ((rc = radiance_issue(c, q.d, read_tuning(), rays, n, RP, RP->key_offset, (float4*)d_rgba, q.s, query)) != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * (uint64_t)RP->spp, query == RTW_PROBE_OCCLUSION);
 }
 
 // the host variant of either family
@@ -2194,36 +2258,31 @@ int query_host(rtw_ctx* c, const char* what, const float* rays, size_t n, const 
     if (rc) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const Tuning tune = read_tuning();
     const size_t chunk = std::min(n, tune.radiance_chunk);
-    // the staging slab: per ray 32 B of ray and 16 B of result per float4 of the query's stride, both sections 256-byte aligned
+    // staged per ray: 32 B of ray and 16 B of result per float4 of the query's stride
     const size_t stride = query_stride(query);
-    const size_t rays_bytes = (chunk * 32 + 255) & ~(size_t)255, stage_bytes = rays_bytes + chunk * 16 * stride;
-    if (stage_bytes > d->rad_stage_bytes) {
-        if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
-        d->rad_stage_bytes = stage_bytes;
-    }
-    float* const st_rays = (float*)d->rad_stage;
-    float4* const st_out = (float4*)((char*)d->rad_stage + rays_bytes);
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {
-        const size_t m = std::min(chunk, n - i0);
-        HIP_TRY(c, hipMemcpyAsync(st_rays, rays + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
+    const uint64_t width[2] = {32, 16 * stride};
+    const bool want[2] = {true, true};
+    const StagePlan st = stage_plan(chunk, 2, width, want);
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)st.bytes, true)) != RTW_OK) return rc;
+    float* const st_rays = (float*)(q.stage + st.off[0]);
+    float4* const st_out = (float4*)(q.stage + st.off[1]);
+    rc = query_chunks(
+        c, q, n, chunk,
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(st_rays, rays + 8 * i0, m * 32, hipMemcpyHostToDevice, q.s));
+            return RTW_OK;
+        },
         // chunk c runs with the key of its first ray: the bits do not depend on the chunk size
-        if ((rc = radiance_issue(c, d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, d->stream, query)) != RTW_OK) return rc;
-        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * stride * i0, st_out, m * 16 * stride, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
-    }
-    return radiance_stats(c, d, stats, n, RP, ev, query);
+        [&](size_t i0, size_t m) { return radiance_issue(c, q.d, tune, st_rays, m, RP, radiance_key(RP->key_offset, i0), st_out, q.s, query); },
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * stride * i0, st_out, m * 16 * stride, hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * (uint64_t)RP->spp, query == RTW_PROBE_OCCLUSION);
 }
 
 int impl_radiance_device(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params* RP, void* d_rgba, void* hip_stream, rtw_stats* stats) {
@@ -2298,67 +2357,41 @@ int impl_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n_views == 0) return RTW_OK;
     const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, true)) != RTW_OK) return rc;
     const ViewFrame vf{VP->width, VP->height, 0};
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
-    if ((rc = radiance_issue(c, d, read_tuning(), (const float*)d_views, n, &rp, 0u, (float4*)d_rgba, s, kQueryViews, &vf)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
+    if ((rc = radiance_issue(c, q.d, read_tuning(), (const float*)d_views, n, &rp, 0u, (float4*)d_rgba, q.s, kQueryViews, &vf)) != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * (uint64_t)rp.spp, false);
 }
 
 int impl_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, float* rgba_out, rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
     rtw_radiance_params rp;
     int rc = views_check(c, "rtw_views", views, n_views, VP, rgba_out, rp);
-    if (rc) return rc;
-    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
-        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views: view " + std::to_string(v) + ": bad camera_type");
-        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views: view " + std::to_string(v) + ": reserved must be 0");
-    }
+    if (rc || (rc = view_records_check(c, "rtw_views", views, n_views))) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_views == 0) return RTW_OK;
     const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const Tuning tune = read_tuning();
     const size_t chunk = std::min(n, tune.radiance_chunk);
-    if (n_views * sizeof(rtw_view) > d->view_bytes) {
-        if (d->view_buf) (void)hipFree(d->view_buf);
-        d->view_buf = nullptr; d->view_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
-        d->view_bytes = n_views * sizeof(rtw_view);
-    }
-    if (chunk * 16 > d->rad_stage_bytes) {  // rtw_radiance's staging slab, here a chunk's results alone
-        if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, chunk * 16));
-        d->rad_stage_bytes = chunk * 16;
-    }
-    float4* const st_out = (float4*)d->rad_stage;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
-        const size_t m = std::min(chunk, n - i0);
-        const ViewFrame vf{VP->width, VP->height, (uint64_t)i0};
-        if ((rc = radiance_issue(c, d, tune, (const float*)d->view_buf, m, &rp, 0u, st_out, d->stream, kQueryViews, &vf)) != RTW_OK) return rc;
-        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
-    }
-    return radiance_stats(c, d, stats, n, &rp, ev, kQueryViews);
+    const uint64_t width[1] = {16};  // staged: a chunk's results alone
+    const bool want[1] = {true};
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)stage_plan(chunk, 1, width, want).bytes, true)) != RTW_OK) return rc;
+    if ((rc = view_records_upload(c, q, views, n_views)) != RTW_OK) return rc;
+    float4* const st_out = (float4*)q.stage;
+    rc = query_chunks(
+        c, q, n, chunk, no_upload,
+        [&](size_t i0, size_t m) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
+            const ViewFrame vf{VP->width, VP->height, (uint64_t)i0};
+            return radiance_issue(c, q.d, tune, (const float*)q.d->view_buf, m, &rp, 0u, st_out, q.s, kQueryViews, &vf);
+        },
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * (uint64_t)rp.spp, false);
 }
 
 // ---- rtw_views_guides / rtw_views_guides_device (rtw.h): k_guides' pass over the pixels of the call's frames, the camera from the
@@ -2375,26 +2408,24 @@ int views_guides_check(rtw_ctx* c, const char* what, const rtw_view* views, size
 // one k_view_guides launch on stream s of device context d: n flattened pixels from pixel `first` of the call, entry i of g's
 // buffers pixel first + i; the scene as uploaded (the reference's ray tmin whatever VP->estimator says)
 hipError_t views_guides_launch(rtw_ctx* d, const void* d_views, const rtw_view_params* VP, uint64_t first, size_t n, const GuideOut& g, hipStream_t s) {
-    ViewArgs va{};
-    va.rays = (const float4*)d_views;
+    ViewArgs va = view_frame_args(d_views, VP->width, VP->height, first);
     va.n = (uint32_t)n;
     va.spp = (uint32_t)VP->spp; va.sample0 = (uint32_t)VP->sample_offset;
-    va.width = (uint32_t)VP->width; va.height = (uint32_t)VP->height; va.first = (uint32_t)first;
-    magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
-    magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
     hipLaunchKernelGGL(k_view_guides, dim3(pixel_grid(d, n)), dim3(kBlock), d->info.lds_bytes, s, d->sc, va, g);
     return hipGetLastError();
 }
 
-void views_guides_stats(rtw_stats* stats, size_t n, const rtw_view_params* VP, float ms) {
-    stats->samples = stats->segments = (uint64_t)n * (uint64_t)VP->spp;  // one camera segment per sample
-    stats->seconds = (double)ms * 1e-3;
+// closes the call; its stats where they are wanted
+int views_guides_close(rtw_ctx* c, QueryCall& q, rtw_stats* stats, size_t n, const rtw_view_params* VP) {
+    const int rc = query_close(c, q, stats ? &stats->seconds : nullptr);
+    if (rc == RTW_OK && stats) stats->samples = stats->segments = (uint64_t)n * (uint64_t)VP->spp;  // one camera segment per sample
+    return rc;
 }
 
 int impl_views_guides_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, const rtw_guides* G, void* hip_stream,
                              rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
-    const int rc = views_guides_check(c, "rtw_views_guides_device", d_views, n_views, VP, G);
+    int rc = views_guides_check(c, "rtw_views_guides_device", d_views, n_views, VP, G);
     if (rc) return rc;
     if (n_views > 0 && (((uintptr_t)d_views & 15) || ((uintptr_t)G->albedo & 15) || ((uintptr_t)G->normal & 15) || ((uintptr_t)G->depth & 3) ||
                         ((uintptr_t)G->prim & 3)))
@@ -2402,77 +2433,44 @@ int impl_views_guides_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n_views == 0) return RTW_OK;
     const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, false)) != RTW_OK) return rc;
     const GuideOut g{(float4*)G->albedo, (float4*)G->normal, G->depth, G->prim, VP->rng_kind};
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, views_guides_launch(d, d_views, VP, 0, n, g, s));
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        views_guides_stats(stats, n, VP, ms);
-    }
-    return RTW_OK;
+    HIP_TRY(c, views_guides_launch(q.d, d_views, VP, 0, n, g, q.s));
+    return views_guides_close(c, q, stats, n, VP);
 }
 
 int impl_views_guides(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_guides* G, rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
-    const int rc = views_guides_check(c, "rtw_views_guides", views, n_views, VP, G);
-    if (rc) return rc;
-    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
-        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_guides: view " + std::to_string(v) + ": bad camera_type");
-        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_guides: view " + std::to_string(v) + ": reserved must be 0");
-    }
+    int rc = views_guides_check(c, "rtw_views_guides", views, n_views, VP, G);
+    if (rc || (rc = view_records_check(c, "rtw_views_guides", views, n_views))) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_views == 0) return RTW_OK;
     const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const size_t chunk = (size_t)view_guides_chunk(n, read_tuning().radiance_chunk);
-    if (n_views * sizeof(rtw_view) > d->view_bytes) {
-        if (d->view_buf) (void)hipFree(d->view_buf);
-        d->view_buf = nullptr; d->view_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
-        d->view_bytes = n_views * sizeof(rtw_view);
-    }
     void* const dst[4] = {G->albedo, G->normal, G->depth, G->prim};
     const bool want[4] = {G->albedo != nullptr, G->normal != nullptr, G->depth != nullptr, G->prim != nullptr};
-    const ViewGuideStage stage = view_guides_stage(chunk, want);  // rtw_radiance's staging slab, here a chunk's requested guides alone
-    if (stage.bytes > d->rad_stage_bytes) {
-        if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, (size_t)stage.bytes));
-        d->rad_stage_bytes = (size_t)stage.bytes;
-    }
-    char* const st = (char*)d->rad_stage;
+    const ViewGuideStage stage = view_guides_stage(chunk, want);  // staged: a chunk's requested guides alone
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)stage.bytes, false)) != RTW_OK) return rc;
+    if ((rc = view_records_upload(c, q, views, n_views)) != RTW_OK) return rc;
+    char* const st = q.stage;
     const GuideOut g{want[0] ? (float4*)(st + stage.off[0]) : nullptr, want[1] ? (float4*)(st + stage.off[1]) : nullptr,
                      want[2] ? (float*)(st + stage.off[2]) : nullptr, want[3] ? (int32_t*)(st + stage.off[3]) : nullptr, VP->rng_kind};
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
-        const size_t m = std::min(chunk, n - i0);
-        HIP_TRY(c, views_guides_launch(d, d->view_buf, VP, (uint64_t)i0, m, g, d->stream));
-        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        for (int k = 0; k < 4; k++)
-            if (want[k])
-                HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * kGuideEntryBytes[k], st + stage.off[k], m * kGuideEntryBytes[k], hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the slab is reused by the next chunk
-    }
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        views_guides_stats(stats, n, VP, ms);
-    }
-    return RTW_OK;
+    rc = query_chunks(
+        c, q, n, chunk, no_upload,
+        [&](size_t i0, size_t m) -> int {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
+            HIP_TRY(c, views_guides_launch(q.d, q.d->view_buf, VP, (uint64_t)i0, m, g, q.s));
+            return RTW_OK;
+        },
+        [&](size_t i0, size_t m) -> int {
+            for (int k = 0; k < 4; k++)
+                if (want[k])
+                    HIP_TRY(c, hipMemcpyAsync((char*)dst[k] + i0 * kGuideEntryBytes[k], st + stage.off[k], m * kGuideEntryBytes[k], hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return views_guides_close(c, q, stats, n, VP);
 }
 
 // ---- rtw_denoise_views / rtw_denoise_views_device (rtw.h): rtw_denoise_guided's passes over all frames at once (k_atrous_guided_views)
@@ -2497,10 +2495,8 @@ int denoise_views_check(rtw_ctx* c, const char* what, const float* rgba_in, cons
 int denoise_views_scratch(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
     if (need <= d->dn_bytes) return RTW_OK;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (d->dn_buf) (void)hipFree(d->dn_buf);
-    d->dn_buf = nullptr; d->dn_bytes = 0;
-    if (hipMalloc(&d->dn_buf, (size_t)need) != hipSuccess) { d->dn_buf = nullptr; return fail(c, RTW_ERR_OOM, "rtw_denoise_views: device allocation failed"); }
-    d->dn_bytes = (size_t)need;
+    if (grow_buffer(d->dn_buf, d->dn_bytes, (size_t)need, (size_t)need, nullptr) != hipSuccess)
+        return fail(c, RTW_ERR_OOM, "rtw_denoise_views: device allocation failed");
     return RTW_OK;
 }
 
@@ -2535,17 +2531,12 @@ int impl_denoise_views_device(rtw_ctx* c, const float* rgba_in, const float* alb
         return fail(c, RTW_ERR_INVALID_ARG, "rtw_denoise_views_device: the buffers must be 16-byte aligned");
     if (n_views == 0) return RTW_OK;
     const size_t n = (size_t)view_pixels(n_views, width, height);
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = denoise_views_scratch(c, d, denoise_views_scratch_bytes(n, iterations, false), s)) != RTW_OK) return rc;
-    HIP_TRY(c, denoise_views_issue(d, (const float4*)rgba_in, (const float4*)albedo, (const float4*)normal, (float4*)rgba_out, (float4*)d->dn_buf, n, width,
-                                   height, iterations, sigma, sigma_albedo, sigma_normal, s));
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return RTW_OK;
+    QueryCall q;  // (untimed: ev[1] is the completion wait alone)
+    if ((rc = query_open(c, q, hip_stream, 0, false, false)) != RTW_OK) return rc;
+    if ((rc = denoise_views_scratch(c, q.d, denoise_views_scratch_bytes(n, iterations, false), q.s)) != RTW_OK) return rc;
+    HIP_TRY(c, denoise_views_issue(q.d, (const float4*)rgba_in, (const float4*)albedo, (const float4*)normal, (float4*)rgba_out, (float4*)q.d->dn_buf, n,
+                                   width, height, iterations, sigma, sigma_albedo, sigma_normal, q.s));
+    return query_close(c, q, nullptr);
 }
 
 int impl_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, const float* normal, float* rgba_out, size_t n_views, int32_t width,
@@ -2583,14 +2574,8 @@ struct ProbeAdaptState {
 
 // the context's per-probe state for at least n probes: grown after the stream's pending work, kept until rtw_destroy
 int ensure_probe_adapt(rtw_ctx* c, rtw_ctx* d, size_t n, hipStream_t s, ProbeAdaptState& st) {
-    if (n > d->padapt_probes) {
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (d->padapt) (void)hipFree(d->padapt);
-        d->padapt = nullptr; d->padapt_probes = 0;
-        HIP_TRY(c, hipMalloc(&d->padapt, (size_t)probe_adaptive_layout(n).bytes()));
-        d->padapt_probes = n;
-    }
     const ProbeAdaptiveLayout l = probe_adaptive_layout(n);  // (the layout for n fits in an allocation made for more probes)
+    HIP_TRY(c, grow_buffer(d->padapt, d->padapt_probes, n, (size_t)l.bytes(), &s));
     char* b = (char*)d->padapt;
     typedef ProbeAdaptiveLayout PL;
     st.accum = (float4*)(b + l.off[PL::kAccum]); st.upart = (float4*)(b + l.off[PL::kUpart]); st.mom = (double2*)(b + l.off[PL::kMom]);
@@ -2600,28 +2585,33 @@ int ensure_probe_adapt(rtw_ctx* c, rtw_ctx* d, size_t n, hipStream_t s, ProbeAda
     return RTW_OK;
 }
 
-ProbeListKernel probe_list_kernel(int rng_kind, int feat) {
-#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_probe_list, RTW_RNG_TEA_LCG) : RTW_RK(k_probe_list, RTW_RNG_PHILOX);
-#undef RTW_RK
-}
+// One range of one pass as the list kernels take it: the members that ProbeListArgs and ViewListArgs have under these names
+struct ListPass {
+    const uint32_t* list;  // (position i of the range is list[1 + i])
+    float4* out;
+    uint32_t* queue;
+    unsigned long long* stats;
+    uint32_t n, n_blocks, run_blocks, n_units, job_units, n_jobs, divn_m, divn_s1, divn_s2, s_from;
+    unsigned grid;
+};
 
-// n probes at d_probes (device) -> their results at d_out (and d_spp, d_err where not null), on stream s of device context d; probe i
-// on the stream of key_offset + i. One pass, one decision and one count read-back per checkpoint: it returns when the results are
-// written. `samples` receives the sum of the n_i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
-int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_probes, size_t n, const rtw_radiance_params* RP, int mode,
-                         const rtw_adaptive* AD, const std::vector<int>& cps, uint32_t key_offset, float4* d_out, int32_t* d_spp, float* d_err,
-                         hipStream_t s, uint64_t& samples) {
-    const bool occ = mode == RTW_PROBE_OCCLUSION;
+// The checkpoint loop of rtw_probe_adaptive and rtw_views_adaptive over n entries (probes, or the pixels of the views at hand), on
+// stream s of device context d: per checkpoint one pass over the list of the active entries (rtw_probe_adaptive_plan.h: runs, ranges
+// that fit the slab cap), the family's decision, the compaction and one count read-back; it returns when `finish` has been issued.
+// `samples` receives the sum of the entries' sample counts. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
+// What a family hands in: `kernel`, its sampling kernel (for the occupancy); zero_depth, no segment is traced and every block sum is
+// 0; use_queue, the kernel takes its jobs from the queue word; and the four launches that differ, each given the state:
+//   sample(p)                          the sampling kernel over range p, block sums to p.out
+//   resolve(st, list, count, nb, blk0) the block sums of a range into the listed entries' sums and moments
+//   decide(st, grid, B, at_cap)        the stop rule after B blocks: masks and err
+//   finish(st, grid)                   the results
+template <class Sample, class Resolve, class Decide, class Finish>
+int adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, size_t n, const void* kernel, bool zero_depth, bool use_queue, const std::vector<int>& cps,
+                   hipStream_t s, uint64_t& samples, Sample sample, Resolve resolve, Decide decide, Finish finish) {
     ProbeAdaptState st{};
     int rc = ensure_probe_adapt(c, d, n, s, st);
     if (rc) return rc;
-    DScene sc = d->sc;
-    if (!occ) apply_estimator(sc, RP->estimator);
-    const ProbeListKernel k = occ ? (RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion_list<RTW_RNG_TEA_LCG> : k_probe_occlusion_list<RTW_RNG_PHILOX>)
-                                  : probe_list_kernel(RP->rng_kind, sc.has_tex);
-    const size_t lds = d->info.lds_bytes;
-    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, lds, 0);
+    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu(kernel, d->info.lds_bytes, 0);
     uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
     const unsigned all_grid = pixel_grid(d, n);
     const uint32_t n_waves = (uint32_t)((n + 63) / 64);
@@ -2638,39 +2628,30 @@ int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float
         if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
         for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
             const RadianceRange rg = radiance_range(n_active, per, r);
-            const uint32_t* const list = st.list[cur] + rg.first;  // (position i of the range is list[1 + i])
-            if (!occ && RP->max_depth == 0) {  // no segment is traced: every block sum is 0
+            const uint32_t* const list = st.list[cur] + rg.first;
+            if (zero_depth) {
                 HIP_TRY(c, hipMemsetAsync(d->rad_slab, 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
             } else {
-                ProbeListArgs a{};
-                a.probes = (const float4*)d_probes;
-                a.list = list;
-                a.out = (float4*)d->rad_slab;
-                a.queue = queue;
-                a.stats = d->rad_ctl;
-                a.n = (uint32_t)rg.count; a.n_blocks = nb; a.run_blocks = run_blocks; a.n_units = (uint32_t)(rg.count * runs);
-                const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, max_grid);
-                a.job_units = probe_adaptive_job_units(run_blocks, a.n_units, grid * (kBlock / 64));
-                a.n_jobs = (uint32_t)radiance_n_jobs(a.n_units, a.job_units);
-                magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
-                a.s_from = (uint32_t)n_prev; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
-                a.key0 = key_offset;
-                if (!occ) HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
-                hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+                ListPass p{};
+                p.list = list;
+                p.out = (float4*)d->rad_slab;
+                p.queue = queue;
+                p.stats = d->rad_ctl;
+                p.n = (uint32_t)rg.count; p.n_blocks = nb; p.run_blocks = run_blocks; p.n_units = (uint32_t)(rg.count * runs);
+                p.grid = (unsigned)std::min<size_t>(((size_t)p.n_units + kBlock - 1) / kBlock, max_grid);
+                p.job_units = probe_adaptive_job_units(run_blocks, p.n_units, (size_t)p.grid * (kBlock / 64));
+                p.n_jobs = (uint32_t)radiance_n_jobs(p.n_units, p.job_units);
+                magic_div(p.n, p.divn_m, p.divn_s1, p.divn_s2);
+                p.s_from = (uint32_t)n_prev;
+                if (use_queue) HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
+                sample(p);
                 HIP_TRY(c, hipGetLastError());
             }
-            if (occ)
-                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, list,
-                                   (uint32_t)rg.count, nb, st.total, st.mom);
-            else
-                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list,
-                                   (uint32_t)rg.count, nb, blk0, st.accum, st.upart, st.mom);
+            resolve(st, list, (uint32_t)rg.count, nb, blk0);
             HIP_TRY(c, hipGetLastError());
         }
         samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
-        hipLaunchKernelGGL(k_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
-                           (const uint32_t*)st.n, st.err, st.masks, (uint32_t)n, 1u, (uint32_t)n_k / kSumBlock, kc + 1 == cps.size() ? 1u : 0u,
-                           AD->threshold, 0u);
+        decide(st, std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8), (uint32_t)n_k / kSumBlock, kc + 1 == cps.size() ? 1u : 0u);
         hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
         hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
                            st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
@@ -2682,14 +2663,52 @@ int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float
         cur ^= 1;
         n_prev = n_k;
     }
-    if (occ)
-        hipLaunchKernelGGL(k_probe_adapt_finish_occlusion, dim3(all_grid), dim3(kBlock), 0, s, (const uint32_t*)st.total, (const uint32_t*)st.n,
-                           (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
-    else
-        hipLaunchKernelGGL(k_probe_adapt_finish, dim3(all_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
-                           (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+    finish(st, all_grid);
     HIP_TRY(c, hipGetLastError());
     return RTW_OK;
+}
+
+// n probes at d_probes (device) -> their results at d_out (and d_spp, d_err where not null); probe i on the stream of key_offset + i
+int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_probes, size_t n, const rtw_radiance_params* RP, int mode,
+                         const rtw_adaptive* AD, const std::vector<int>& cps, uint32_t key_offset, float4* d_out, int32_t* d_spp, float* d_err,
+                         hipStream_t s, uint64_t& samples) {
+    const bool occ = mode == RTW_PROBE_OCCLUSION;
+    DScene sc = d->sc;
+    if (!occ) apply_estimator(sc, RP->estimator);
+    const ProbeListKernel k = occ ? (RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion_list<RTW_RNG_TEA_LCG> : k_probe_occlusion_list<RTW_RNG_PHILOX>)
+                                  : RTW_PICK(k_probe_list, RP->rng_kind, sc.has_tex);
+    return adaptive_issue(
+        c, d, tune, n, (const void*)k, !occ && RP->max_depth == 0, !occ, cps, s, samples,
+        [&](const ListPass& p) {
+            ProbeListArgs a{};
+            a.probes = (const float4*)d_probes;
+            a.list = p.list; a.out = p.out; a.queue = p.queue; a.stats = p.stats;
+            a.n = p.n; a.n_blocks = p.n_blocks; a.run_blocks = p.run_blocks; a.n_units = p.n_units; a.job_units = p.job_units; a.n_jobs = p.n_jobs;
+            a.divn_m = p.divn_m; a.divn_s1 = p.divn_s1; a.divn_s2 = p.divn_s2;
+            a.s_from = p.s_from; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
+            a.key0 = key_offset;
+            hipLaunchKernelGGL(k, dim3(p.grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+        },
+        [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
+            if (occ)
+                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, list, count, nb,
+                                   st.total, st.mom);
+            else
+                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, count, nb, blk0,
+                                   st.accum, st.upart, st.mom);
+        },
+        [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // rtw_render_adaptive's rule over a frame of n x 1, dilate 0
+            hipLaunchKernelGGL(k_adapt_decide, dim3(grid), dim3(kBlock), 0, s, (const double2*)st.mom, (const uint32_t*)st.n, st.err, st.masks, (uint32_t)n, 1u,
+                               B, at_cap, AD->threshold, 0u);
+        },
+        [&](const ProbeAdaptState& st, unsigned grid) {
+            if (occ)
+                hipLaunchKernelGGL(k_probe_adapt_finish_occlusion, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)st.total, (const uint32_t*)st.n,
+                                   (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+            else
+                hipLaunchKernelGGL(k_probe_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart,
+                                   (const uint32_t*)st.n, (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+        });
 }
 
 // the checks both variants share; fills the sampling params and the checkpoints
@@ -2705,26 +2724,6 @@ int probe_adaptive_check(rtw_ctx* c, const char* what, const float* probes, size
     return RTW_OK;
 }
 
-// rtw_probe's stats for the samples actually taken
-int probe_adaptive_stats(rtw_ctx* c, rtw_ctx* d, rtw_stats* stats, uint64_t samples, int mode, hipEvent_t ev[2]) {
-    if (!stats) return RTW_OK;
-    memset(stats, 0, sizeof *stats);
-    stats->samples = samples;
-    if (mode == RTW_PROBE_OCCLUSION) {
-        stats->shadow_rays = samples;
-    } else {
-        unsigned long long hs[8];
-        const int rc = sum_stat_rows(c, d->rad_ctl, hs);
-        if (rc) return rc;
-        stats->segments = hs[0]; stats->shadow_rays = hs[1];
-        stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    stats->seconds = (double)ms * 1e-3;
-    return RTW_OK;
-}
-
 int impl_adaptive_probe_device(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* AD, void* d_rgba, void* d_spp,
                                void* d_error, void* hip_stream, rtw_stats* stats) {
     if (!c) return RTW_ERR_INVALID_ARG;
@@ -2736,21 +2735,13 @@ int impl_adaptive_probe_device(rtw_ctx* c, const float* probes, size_t n, const 
         return fail(c, RTW_ERR_INVALID_ARG, "rtw_probe_adaptive_device: probes and rgba must be 16-byte aligned, spp and error 4-byte aligned");
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, true)) != RTW_OK) return rc;
     uint64_t samples = 0;
-    if ((rc = probe_adaptive_issue(c, d, read_tuning(), probes, n, &rp, PP->mode, AD, cps, rp.key_offset, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error, s,
-                                   samples)) != RTW_OK)
+    if ((rc = probe_adaptive_issue(c, q.d, read_tuning(), probes, n, &rp, PP->mode, AD, cps, rp.key_offset, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error,
+                                   q.s, samples)) != RTW_OK)
         return rc;
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return probe_adaptive_stats(c, d, stats, samples, PP->mode, ev);
+    return query_stats(c, q, stats, samples, PP->mode == RTW_PROBE_OCCLUSION);
 }
 
 int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_probe_params* PP, const rtw_adaptive* AD, float* rgba_out, int32_t* spp_out,
@@ -2762,40 +2753,35 @@ int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_pro
     if (rc) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const Tuning tune = read_tuning();
     const size_t chunk = std::min(n, tune.radiance_chunk);
-    // rtw_radiance's staging slab: a chunk's probes (32 B each), then its results: 16 B of rgba, 4 B of spp, 4 B of err; sections 256-byte aligned
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_rgba = al(chunk * 32), o_spp = o_rgba + al(chunk * 16), o_err = o_spp + al(chunk * 4), stage_bytes = o_err + chunk * 4;
-    if (stage_bytes > d->rad_stage_bytes) {
-        if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
-        d->rad_stage_bytes = stage_bytes;
-    }
-    char* const base = (char*)d->rad_stage;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    // staged per probe: 32 B of probe, then its results: 16 B of rgba, 4 B of spp, 4 B of err
+    const uint64_t width[4] = {32, 16, 4, 4};
+    const bool want[4] = {true, true, true, true};
+    const StagePlan st = stage_plan(chunk, 4, width, want);
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)st.bytes, true)) != RTW_OK) return rc;
+    char* const base = q.stage;
+    const size_t o_rgba = (size_t)st.off[1], o_spp = (size_t)st.off[2], o_err = (size_t)st.off[3];
     uint64_t samples = 0;
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {
-        const size_t m = std::min(chunk, n - i0);
-        HIP_TRY(c, hipMemcpyAsync(base, probes + 8 * i0, m * 32, hipMemcpyHostToDevice, d->stream));
-        // chunk c runs with the key of its first probe: the bits do not depend on the chunk size
-        if ((rc = probe_adaptive_issue(c, d, tune, (const float*)base, m, &rp, PP->mode, AD, cps, radiance_key(rp.key_offset, i0), (float4*)(base + o_rgba),
-                                       (int32_t*)(base + o_spp), (float*)(base + o_err), d->stream, samples)) != RTW_OK)
-            return rc;
-        if (i0 + m >= n) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base + o_rgba, m * 16, hipMemcpyDeviceToHost, d->stream));
-        if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, d->stream));
-        if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the staging slab is reused by the next chunk
-    }
-    return probe_adaptive_stats(c, d, stats, samples, PP->mode, ev);
+    rc = query_chunks(
+        c, q, n, chunk,
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(base, probes + 8 * i0, m * 32, hipMemcpyHostToDevice, q.s));
+            return RTW_OK;
+        },
+        [&](size_t i0, size_t m) {  // chunk c runs with the key of its first probe: the bits do not depend on the chunk size
+            return probe_adaptive_issue(c, q.d, tune, (const float*)base, m, &rp, PP->mode, AD, cps, radiance_key(rp.key_offset, i0), (float4*)(base + o_rgba),
+                                        (int32_t*)(base + o_spp), (float*)(base + o_err), q.s, samples);
+        },
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base + o_rgba, m * 16, hipMemcpyDeviceToHost, q.s));
+            if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, q.s));
+            if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_stats(c, q, stats, samples, PP->mode == RTW_PROBE_OCCLUSION);
 }
 
 // ---- rtw_views_adaptive / rtw_views_adaptive_device (rtw.h): rtw_views' samples taken from checkpoint to checkpoint over the list of
@@ -2803,97 +2789,45 @@ int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_pro
 // rtw_probe_adaptive's with n = the pixels of the views at hand (the state lives in the same context-owned allocation); the decision
 // is k_view_adapt_decide's, dilated inside each view.
 typedef void (*ViewListKernel)(const DScene, const ViewListArgs);
-ViewListKernel view_list_kernel(int rng_kind, int feat) {
-#define RTW_RK(K_, R_) (feat == 2 ? K_<R_, 2> : feat == 1 ? K_<R_, 1> : K_<R_, 0>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_RK(k_view_list, RTW_RNG_TEA_LCG) : RTW_RK(k_view_list, RTW_RNG_PHILOX);
-#undef RTW_RK
-}
 
-// n_views views at d_views (device) -> their frames at d_out (and d_spp, d_err where not null), on stream s of device context d: pixel
-// i of the outputs is flattened pixel i of these views. One pass, one decision and one count read-back per checkpoint: it returns
-// when the results are written. `samples` receives the sum of the n_p. The counters add up in d->rad_ctl's rows, which the caller
-// zeroed on s.
+// n_views views at d_views (device) -> their frames at d_out (and d_spp, d_err where not null): pixel i of the outputs is flattened
+// pixel i of these views
 int view_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP,
                         const rtw_radiance_params* RP, const rtw_adaptive* AD, const std::vector<int>& cps, float4* d_out, int32_t* d_spp, float* d_err,
                         hipStream_t s, uint64_t& samples) {
     const size_t n = (size_t)view_pixels(n_views, VP->width, VP->height);
-    ProbeAdaptState st{};
-    int rc = ensure_probe_adapt(c, d, n, s, st);
-    if (rc) return rc;
     DScene sc = d->sc;
     apply_estimator(sc, RP->estimator);
-    const ViewListKernel k = view_list_kernel(RP->rng_kind, sc.has_tex);
-    const size_t lds = d->info.lds_bytes;
-    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, lds, 0);
-    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
-    const unsigned all_grid = pixel_grid(d, n);
-    const uint32_t n_waves = (uint32_t)((n + 63) / 64);
-    ViewArgs va{};  // what view_split / view_raygen read: pixel i of the list is pixel i of these views
-    va.rays = (const float4*)d_views;
-    va.width = (uint32_t)VP->width; va.height = (uint32_t)VP->height; va.first = 0u;
-    magic_div(va.width, va.divw_m, va.divw_s1, va.divw_s2);
-    magic_div(va.width * va.height, va.divf_m, va.divf_s1, va.divf_s2);
+    const ViewListKernel k = RTW_PICK(k_view_list, RP->rng_kind, sc.has_tex);
+    const ViewArgs va = view_frame_args(d_views, VP->width, VP->height, 0);  // pixel i of the list is pixel i of these views
     ViewDecideArgs da{};
     da.width = va.width; da.height = va.height; da.npix = (uint32_t)n;
     da.divw_m = va.divw_m; da.divw_s1 = va.divw_s1; da.divw_s2 = va.divw_s2;
     da.divf_m = va.divf_m; da.divf_s1 = va.divf_s1; da.divf_s2 = va.divf_s2;
     da.dilate = (uint32_t)AD->dilate; da.threshold = AD->threshold;
-    hipLaunchKernelGGL(k_probe_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.mom, st.n, st.err, st.total, (uint32_t)n);
-    HIP_TRY(c, hipGetLastError());
-    size_t n_active = n;
-    int cur = 0, n_prev = 0;
-    for (size_t kc = 0; kc < cps.size() && n_active > 0; kc++) {
-        const int n_k = cps[kc];
-        const uint32_t nb = probe_adaptive_pass_blocks(n_prev, n_k), blk0 = probe_adaptive_first_block(n_prev);
-        const uint32_t run_blocks = probe_adaptive_run_blocks(n_active, nb, max_grid * kBlock);
-        const uint32_t runs = probe_adaptive_runs(nb, run_blocks);
-        const uint64_t per = probe_adaptive_range_positions(n_active, nb, run_blocks, tune.radiance_slab_bytes);
-        if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
-        for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
-            const RadianceRange rg = radiance_range(n_active, per, r);
-            const uint32_t* const list = st.list[cur] + rg.first;  // (position i of the range is list[1 + i])
-            if (RP->max_depth == 0) {  // no segment is traced: every block sum is 0
-                HIP_TRY(c, hipMemsetAsync(d->rad_slab, 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
-            } else {
-                ViewListArgs a{};
-                a.v = va;
-                a.list = list;
-                a.out = (float4*)d->rad_slab;
-                a.queue = queue;
-                a.stats = d->rad_ctl;
-                a.n = (uint32_t)rg.count; a.n_blocks = nb; a.run_blocks = run_blocks; a.n_units = (uint32_t)(rg.count * runs);
-                const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, max_grid);
-                a.job_units = probe_adaptive_job_units(run_blocks, a.n_units, grid * (kBlock / 64));
-                a.n_jobs = (uint32_t)radiance_n_jobs(a.n_units, a.job_units);
-                magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
-                a.s_from = (uint32_t)n_prev; a.sample0 = (uint32_t)RP->sample_offset; a.max_depth = (uint32_t)RP->max_depth;
-                HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
-                hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
-                HIP_TRY(c, hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, (uint32_t)rg.count, nb,
-                               blk0, st.accum, st.upart, st.mom);
-            HIP_TRY(c, hipGetLastError());
-        }
-        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
-        da.B = (uint32_t)n_k / kSumBlock; da.at_cap = kc + 1 == cps.size() ? 1u : 0u;
-        hipLaunchKernelGGL(k_view_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
-                           (const uint32_t*)st.n, st.err, st.masks, da);
-        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
-        hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
-                           st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
-        HIP_TRY(c, hipGetLastError());
-        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
-        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        n_active = cnt;
-        cur ^= 1;
-        n_prev = n_k;
-    }
-    hipLaunchKernelGGL(k_view_adapt_finish, dim3(all_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
-                       (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
-    HIP_TRY(c, hipGetLastError());
-    return RTW_OK;
+    return adaptive_issue(
+        c, d, tune, n, (const void*)k, RP->max_depth == 0, true, cps, s, samples,
+        [&](const ListPass& p) {
+            ViewListArgs a{};
+            a.v = va;
+            a.list = p.list; a.out = p.out; a.queue = p.queue; a.stats = p.stats;
+            a.n = p.n; a.n_blocks = p.n_blocks; a.run_blocks = p.run_blocks; a.n_units = p.n_units; a.job_units = p.job_units; a.n_jobs = p.n_jobs;
+            a.divn_m = p.divn_m; a.divn_s1 = p.divn_s1; a.divn_s2 = p.divn_s2;
+            a.s_from = p.s_from; a.sample0 = (uint32_t)RP->sample_offset; a.max_depth = (uint32_t)RP->max_depth;
+            hipLaunchKernelGGL(k, dim3(p.grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+        },
+        [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
+            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, count, nb, blk0, st.accum,
+                               st.upart, st.mom);
+        },
+        [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // the rule dilated inside each view
+            da.B = B; da.at_cap = at_cap;
+            hipLaunchKernelGGL(k_view_adapt_decide, dim3(grid), dim3(kBlock), 0, s, (const double2*)st.mom, (const uint32_t*)st.n, st.err, st.masks, da);
+        },
+        [&](const ProbeAdaptState& st, unsigned grid) {
+            hipLaunchKernelGGL(k_view_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                               (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+        });
 }
 
 // the checks both variants share: rtw_views' and rtw_render_adaptive's; fills the sampling params and the checkpoints
@@ -2918,21 +2852,13 @@ int impl_adaptive_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_vie
         return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive_device: views and rgba must be 16-byte aligned, spp and error 4-byte aligned");
     if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
     if (n_views == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
-    const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], s));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), s));
+    QueryCall q;
+    if ((rc = query_open(c, q, hip_stream, 0, true)) != RTW_OK) return rc;
     uint64_t samples = 0;
-    if ((rc = view_adaptive_issue(c, d, read_tuning(), d_views, n_views, VP, &rp, AD, cps, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error, s, samples)) !=
-        RTW_OK)
+    if ((rc = view_adaptive_issue(c, q.d, read_tuning(), d_views, n_views, VP, &rp, AD, cps, (float4*)d_rgba, (int32_t*)d_spp, (float*)d_error, q.s,
+                                  samples)) != RTW_OK)
         return rc;
-    HIP_TRY(c, hipEventRecord(ev[1], s));
-    HIP_TRY(c, hipEventSynchronize(ev[1]));
-    return probe_adaptive_stats(c, d, stats, samples, RTW_PROBE_IRRADIANCE, ev);
+    return query_stats(c, q, stats, samples, false);
 }
 
 int impl_adaptive_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, const rtw_adaptive* AD, float* rgba_out,
@@ -2941,57 +2867,38 @@ int impl_adaptive_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const
     rtw_radiance_params rp;
     std::vector<int> cps;
     int rc = views_adaptive_check(c, "rtw_views_adaptive", views, n_views, VP, AD, rgba_out, rp, cps);
-    if (rc) return rc;
-    for (size_t v = 0; v < n_views; v++) {  // the host can read the records
-        if (views[v].camera_type < RTW_CAM_PERSPECTIVE || views[v].camera_type > RTW_CAM_ORTHOGRAPHIC)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive: view " + std::to_string(v) + ": bad camera_type");
-        if (views[v].reserved[0] != 0u || views[v].reserved[1] != 0u)
-            return fail(c, RTW_ERR_INVALID_ARG, "rtw_views_adaptive: view " + std::to_string(v) + ": reserved must be 0");
-    }
+    if (rc || (rc = view_records_check(c, "rtw_views_adaptive", views, n_views))) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_views == 0) return RTW_OK;
-    rtw_ctx* d = c->kids.empty() ? c : c->kids[0];
-    HIP_TRY(c, hipSetDevice(d->device));
     const Tuning tune = read_tuning();
-    // batches of whole views (the dilated rule reads a pixel's neighbours inside its view); a batch's pixels start at view v0's first
-    const size_t frame = (size_t)view_pixels(1, VP->width, VP->height);
-    const size_t per = (size_t)std::min<uint64_t>(view_adaptive_batch_views(VP->width, VP->height, tune.radiance_chunk), n_views), chunk = per * frame;
-    if (n_views * sizeof(rtw_view) > d->view_bytes) {
-        if (d->view_buf) (void)hipFree(d->view_buf);
-        d->view_buf = nullptr; d->view_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->view_buf, n_views * sizeof(rtw_view)));
-        d->view_bytes = n_views * sizeof(rtw_view);
-    }
-    // rtw_radiance's staging slab, here a batch's results: 16 B of rgba, 4 B of spp, 4 B of err; sections 256-byte aligned
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_spp = al(chunk * 16), o_err = o_spp + al(chunk * 4), stage_bytes = o_err + chunk * 4;
-    if (stage_bytes > d->rad_stage_bytes) {
-        if (d->rad_stage) (void)hipFree(d->rad_stage);
-        d->rad_stage = nullptr; d->rad_stage_bytes = 0;
-        HIP_TRY(c, hipMalloc(&d->rad_stage, stage_bytes));
-        d->rad_stage_bytes = stage_bytes;
-    }
-    char* const base = (char*)d->rad_stage;
-    hipEvent_t ev[2];
-    HIP_TRY(c, cast_events(d, ev));
-    if ((rc = radiance_ctl(c, d)) != RTW_OK) return rc;
-    HIP_TRY(c, hipEventRecord(ev[0], d->stream));
-    HIP_TRY(c, hipMemcpyAsync(d->view_buf, views, n_views * sizeof(rtw_view), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), d->stream));
+    // batches of whole views (the dilated rule reads a pixel's neighbours inside its view): chunks of per * frame pixels are
+    // view_adaptive_batch's views [i0 / frame, (i0 + m) / frame) (rtw_view_adaptive_plan.h view_adaptive_chunk)
+    const size_t frame = (size_t)view_pixels(1, VP->width, VP->height), n = n_views * frame;
+    const size_t per = (size_t)std::min<uint64_t>(view_adaptive_batch_views(VP->width, VP->height, tune.radiance_chunk), n_views);
+    const size_t chunk = (size_t)view_adaptive_chunk(per, VP->width, VP->height);
+    const uint64_t width[3] = {16, 4, 4};  // staged: a batch's results, 16 B of rgba, 4 B of spp, 4 B of err per pixel
+    const bool want[3] = {true, true, true};
+    const StagePlan st = stage_plan(chunk, 3, width, want);
+    QueryCall q;
+    if ((rc = query_open(c, q, nullptr, (size_t)st.bytes, true)) != RTW_OK) return rc;
+    if ((rc = view_records_upload(c, q, views, n_views)) != RTW_OK) return rc;
+    char* const base = q.stage;
+    const size_t o_spp = (size_t)st.off[1], o_err = (size_t)st.off[2];
     uint64_t samples = 0;
-    for (uint64_t b = 0, nb = view_adaptive_n_batches(n_views, per); b < nb; b++) {
-        const RadianceRange vb = view_adaptive_batch(n_views, per, b);
-        const size_t i0 = (size_t)vb.first * frame, m = (size_t)vb.count * frame;
-        if ((rc = view_adaptive_issue(c, d, tune, (const rtw_view*)d->view_buf + vb.first, (size_t)vb.count, VP, &rp, AD, cps, (float4*)base,
-                                      (int32_t*)(base + o_spp), (float*)(base + o_err), d->stream, samples)) != RTW_OK)
-            return rc;
-        if (b + 1 == nb) HIP_TRY(c, hipEventRecord(ev[1], d->stream));
-        HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base, m * 16, hipMemcpyDeviceToHost, d->stream));
-        if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, d->stream));
-        if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(c, hipStreamSynchronize(d->stream));  // the staging slab is reused by the next batch
-    }
-    return probe_adaptive_stats(c, d, stats, samples, RTW_PROBE_IRRADIANCE, ev);
+    rc = query_chunks(
+        c, q, n, chunk, no_upload,
+        [&](size_t i0, size_t m) {  // a batch's pixels start at its first view's first
+            return view_adaptive_issue(c, q.d, tune, (const rtw_view*)q.d->view_buf + i0 / frame, m / frame, VP, &rp, AD, cps, (float4*)base,
+                                       (int32_t*)(base + o_spp), (float*)(base + o_err), q.s, samples);
+        },
+        [&](size_t i0, size_t m) -> int {
+            HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, base, m * 16, hipMemcpyDeviceToHost, q.s));
+            if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out + i0, base + o_spp, m * 4, hipMemcpyDeviceToHost, q.s));
+            if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out + i0, base + o_err, m * 4, hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_stats(c, q, stats, samples, false);
 }
 
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {

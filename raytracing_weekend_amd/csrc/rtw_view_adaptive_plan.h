@@ -24,6 +24,10 @@ inline uint64_t view_adaptive_batch_views(int32_t width, int32_t height, uint64_
 // batch b of the cut of n_views views: views [first, first + count); count = 0 past the end (radiance_range over views)
 inline uint64_t view_adaptive_n_batches(uint64_t n_views, uint64_t per) { return radiance_n_ranges(n_views, per); }
 inline RadianceRange view_adaptive_batch(uint64_t n_views, uint64_t per, uint64_t b) { return radiance_range(n_views, per, b); }
+// The host entry walks the call's flattened pixels in uniform chunks of this many: `per` whole views. Chunk b then is pixels
+// [b * chunk, min((b + 1) * chunk, n_views * frame)), which are exactly the views of view_adaptive_batch(n_views, per, b): both ends
+// are multiples of the frame.
+inline uint64_t view_adaptive_chunk(uint64_t per, int32_t width, int32_t height) { return per * (uint64_t)(uint32_t)width * (uint64_t)(uint32_t)height; }
 
 // The pixel that tap (dx, dy), each in -1..1, of flattened pixel p reads under dilate = 1: p's own view, the row and the column
 // clamped to the frame (k_view_adapt_decide: view * width * height + yy * width + xx). It never leaves the view's frame.

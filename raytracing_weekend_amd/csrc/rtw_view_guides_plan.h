@@ -10,22 +10,20 @@
 
 #include "../../include/rtw.h"
 #include "rtw_radiance_plan.h"
+#include "rtw_stage_plan.h"
 
 namespace rtwk {
 
 // bytes of one entry of rtw_guides' buffers, in the struct's order: albedo, normal (float4), depth (float), prim (int32)
 constexpr uint64_t kGuideEntryBytes[4] = {16, 16, 4, 4};
 
-// The staging of one chunk of the host entry, inside rtw_radiance's staging slab: the requested buffers one after another, each
-// 256-byte aligned; a buffer nobody asked for takes nothing. off[k] is valid where want[k].
+// The staging of one chunk of the host entry, inside the query family's staging slab (rtw_stage_plan.h stage_plan over the four entry
+// sizes): the requested buffers one after another, each 256-byte aligned; a buffer nobody asked for takes nothing. off[k] is valid
+// where want[k].
 struct ViewGuideStage { uint64_t off[4]; uint64_t bytes; };
 inline ViewGuideStage view_guides_stage(uint64_t chunk, const bool want[4]) {
-    ViewGuideStage s{};
-    for (int k = 0; k < 4; k++) {
-        s.off[k] = s.bytes;
-        if (want[k]) s.bytes += (chunk * kGuideEntryBytes[k] + 255ull) & ~255ull;
-    }
-    return s;
+    const StagePlan p = stage_plan(chunk, 4, kGuideEntryBytes, want);
+    return ViewGuideStage{{p.off[0], p.off[1], p.off[2], p.off[3]}, p.bytes};
 }
 // pixels of one chunk: all of them, or as many as RTW_RADIANCE_CHUNK says (at least 1)
 inline uint64_t view_guides_chunk(uint64_t n, uint64_t knob) { return std::min<uint64_t>(std::max<uint64_t>(n, 1), std::max<uint64_t>(knob, 1)); }

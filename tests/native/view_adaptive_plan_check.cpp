@@ -1,7 +1,8 @@
 // CPU check of rtw_views_adaptive's planning (raytracing_weekend_amd/csrc/rtw_view_adaptive_plan.h), compiled with
 // g++ -fsanitize=address,undefined and run by tests/test_views_adaptive_cpu.py: the tap of the dilated stop rule stays inside the
 // pixel's own view and is the clamped pixel of that view (exhaustively on small shapes, and near 2^31 - 1 pixels), the batches of the
-// host entry are whole views that tile the call for chunk values of 1, a frame exactly and beyond, and a pass over the pixels of a
+// host entry are whole views that tile the call for chunk values of 1, a frame exactly and beyond (and are what the entry's loop
+// over uniform chunks of view_adaptive_chunk pixels visits), and a pass over the pixels of a
 // batch is a pass rtw_probe_adaptive's plan can number. Prints "view_adaptive_plan_check ok" and returns 0, or says what failed.
 #include <cstdio>
 #include <vector>
@@ -56,6 +57,11 @@ static void batches(uint64_t n_views, int w, int h, uint64_t chunk) {
         const RadianceRange g = view_adaptive_batch(n_views, eff, b);
         CHECK(g.first == next && g.count >= 1 && g.count <= eff);
         CHECK(view_pixels_ok(g.count, w, h));
+        {   // the host entry's loop: uniform chunks of view_adaptive_chunk pixels over the call's n pixels are these views
+            const uint64_t n = n_views * frame, chunk = view_adaptive_chunk(eff, w, h), i0 = b * chunk, m = std::min<uint64_t>(chunk, n - i0);
+            CHECK(chunk == eff * frame && i0 < n && (i0 + chunk >= n) == (b + 1 == nb));
+            CHECK(i0 % frame == 0 && m % frame == 0 && i0 / frame == g.first && m / frame == g.count);
+        }
         next = g.first + g.count;
         if (nb > 64 && b == 31) {  // (a long cut: the first batches, then the tail)
             b = nb - 33;

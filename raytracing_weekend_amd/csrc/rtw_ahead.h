@@ -17,6 +17,12 @@
 #ifndef RTW_PATH_GATE_BOUNDS
 #define RTW_PATH_GATE_BOUNDS 1  // 1: the scene-bounds test of camera rays runs only in iterations where it decides whether the wave walks
 #endif
+// The one-light instantiation (DESIGN.md 4.1 "One listed light is a compile-time fact"): 1: k_path<..., NEE1 = 1> compiles shade_a's light
+// sample for exactly one listed rectangle light read from the LDS page; 0: that instantiation is the generic code (the instruction stream
+// the kernel had without it)
+#ifndef RTW_PATH_NEE1
+#define RTW_PATH_NEE1 1
+#endif
 
 namespace rtwk {
 

@@ -100,6 +100,8 @@ namespace rtwk {
 RTW_EXT(k_path)
 extern template __global__ void k_path<RTW_RNG_PHILOX, 1, 1>(const KArgs);
 extern template __global__ void k_path<RTW_RNG_TEA_LCG, 1, 1>(const KArgs);
+extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>(const KArgs);
+extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1>(const KArgs);
 RTW_EXT(k_first)
 RTW_EXT(k_shade)
 RTW_EXT(k_bounce)
@@ -340,7 +342,17 @@ Kernel trace_bvh_kernel(int block, int mode) {
 
 // k_path's instantiation: RNG kind x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator); media scenes
 // take the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5). list: the LIST = 1 twin (rtw_render_adaptive)
-Kernel path_kernel(int rng_kind, int feat, int n_vol, bool list = false) {
+// The hot instantiation with Philox has a one-light twin (rtw_kernels.h k_path NEE1), for scenes whose light sample is always the same
+// case of shade_a: exactly one listed light, the reference estimator (feature level 0 has no other), a rectangle generator.
+bool path_nee1(int rng_kind, const DScene& sc) {
+    int gen = sc.pdf.gen;
+    if (gen == RTW_PDF_MIXTURE || gen == RTW_PDF_MIXTURE_BIAS) gen = sc.pdf.p1_gen;
+    return rng_kind == RTW_RNG_PHILOX && sc.has_tex == 0 && sc.estimator == RTW_EST_REFERENCE && sc.n_lights == 1 &&
+           (gen == RTW_PDF_RECT_X || gen == RTW_PDF_RECT_Y || gen == RTW_PDF_RECT_Z);
+}
+Kernel path_kernel(int rng_kind, const DScene& sc, bool list = false) {
+    const int feat = sc.has_tex, n_vol = sc.n_vol;
+    if (path_nee1(rng_kind, sc)) return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>;
 #define RTW_PK(R_, L_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1, L_> : feat == 2 ? k_path<R_, 2, 0, L_> : feat == 1 ? k_path<R_, 1, 0, L_> : k_path<R_, 0, 0, L_>)
     if (list) return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 1) : RTW_PK(RTW_RNG_PHILOX, 1);
     return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 0) : RTW_PK(RTW_RNG_PHILOX, 0);
@@ -360,7 +372,7 @@ void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipSt
     const int feat = a.sc.has_tex;  // 0 hot, 1 cold features, 2 cold features + the mixture estimator (rtw_kernels.h shade_a)
     if (list) {
         if (which == RTW_K_FIRST) hipLaunchKernelGGL(first_list_kernel(rng_kind, feat), dim3(grid), dim3(kBlock), lds, s, a);
-        else hipLaunchKernelGGL(path_kernel(rng_kind, feat, a.sc.n_vol, true), dim3(grid), dim3(kBlock), lds, s, a);
+        else hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, true), dim3(grid), dim3(kBlock), lds, s, a);
         return;
     }
 #define RTW_LAUNCH_SHADING_R(K_, LDS_, R_)                                                                        \
@@ -381,7 +393,7 @@ void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipSt
         else if (a.sc.n_generic == 0) hipLaunchKernelGGL((k_trace<true>), dim3(grid), dim3(kBlock), lds, s, a);
         else hipLaunchKernelGGL((k_trace<false>), dim3(grid), dim3(kBlock), lds, s, a);
         break;
-    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, feat, a.sc.n_vol), dim3(grid), dim3(kBlock), lds, s, a); break;
+    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, a.sc), dim3(grid), dim3(kBlock), lds, s, a); break;
     default: RTW_LAUNCH_SHADING(k_bounce, lds); break;
 #undef RTW_LAUNCH_SHADING
 #undef RTW_LAUNCH_SHADING_R
@@ -940,7 +952,7 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)P->spp;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc), 0, tune.path_grid_mult);
     const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, cull.live_groups);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     if ((rc = grow_order(c, plan.n_groups)) != RTW_OK) return rc;
@@ -1272,7 +1284,7 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
     // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
     Tuning t = tune;
     if (t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol, true), 0, t.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, true), 0, t.path_grid_mult);
     const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     int rc = grow_blocksum(c, plan.need_slots * n_list);
@@ -1453,7 +1465,7 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)(n_to - n_from);
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc.has_tex, base.sc.n_vol), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc), 0, tune.path_grid_mult);
     const size_t n_groups = (npix + 63) / 64;
     if ((rc = grow_order(c, n_groups)) != RTW_OK) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));

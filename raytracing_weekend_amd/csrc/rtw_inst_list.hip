@@ -17,6 +17,7 @@ namespace rtwk {
     template __global__ void k_path<R_, 2, 0, 1>(const KArgs); template __global__ void k_path<R_, 1, 1, 1>(const KArgs);
 #if !defined(RTW_INST_KIND) || RTW_INST_KIND == 0
 RTW_INST(RTW_RNG_PHILOX)
+template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1>(const KArgs);  // the one-light instantiation (NEE1)
 #endif
 #if !defined(RTW_INST_KIND) || RTW_INST_KIND == 1
 RTW_INST(RTW_RNG_TEA_LCG)

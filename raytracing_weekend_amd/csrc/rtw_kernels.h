@@ -281,7 +281,11 @@ RTW_DEV float light_list_pdf(const rtw_light* __restrict__ lights, const int nl,
 // TEX: 0 = the hot instantiation; 1 = the one for scenes with non-constant textures or media and for the corrected
 // estimators (the cold features); 2 = 1 + the mixture estimator (its light-list pdf loop costs the others registers:
 // inlined into instantiation 1 it put 20 bytes of scratch into k_shade and k_path and 4-7 % onto scenes 2, 3 and 4)
-template <int KIND, int TEX>
+// NEE1 (k_path's one-light instantiation, TEX == 0 only): the host vouches for exactly one listed light, the reference estimator, a
+// rectangle generator (RTW_PDF_RECT_X / Y / Z, a mixture's child p1 included) and the LDS page pc. The light sample then is the pc
+// reads, draws 2 and 3 of the block in registers and one rectangle axis; the cases below that such a scene never takes - the index
+// draw and the record loads of several lights, the reads without the page, other generators - are not compiled.
+template <int KIND, int TEX, bool NEE1 = false>
 RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 dir, const float gather_time, const float t, const int prim,
                     v3& so, v3& sd, v3& att, v3& radiance, Nee& nee, const uint32_t* noise_lds, uint32_t& nee_prev, const u32x4* hr_lds = nullptr,
                     const PathConsts* pc = nullptr) {
@@ -430,7 +434,8 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
     RTW_MARK2("sa_nee");
     RTW_SUB(7);
     // next-event estimation, closehit.cu:70-94: sample the light; the visibility probe comes later
-    const int nl = sc.n_lights;
+    static_assert(!NEE1 || TEX == 0, "the one-light instantiation has no cold features");
+    const int nl = NEE1 ? 1 : sc.n_lights;
     if (est == RTW_EST_CORRECTED && ev == EV_HIT && !specular && nl > 0) {
         // each listed light over its own parallelogram (moved onto the emitting rectangle at upload), area-measure
         // estimator, no heuristic weight
@@ -501,7 +506,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
             lnrm = V(lt->normal[0], lt->normal[1], lt->normal[2]);
             lemi = V(lt->emission[0], lt->emission[1], lt->emission[2]);
             larea = lt->area;
-        } else if (pc != nullptr) {
+        } else if (NEE1 || pc != nullptr) {
             lnrm = ld3(pc->lnrm); lemi = ld3(pc->lemi); larea = pc->larea;
         } else {
             const RTW_CONST rtw_light* lt = as_const(sc.lights);
@@ -511,7 +516,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         }
         int gen;  // mixturePdf.cu:25-38: always child p1 (Q4)
         float rc0, rc1, rc2, rc3, rc4;
-        if (pc != nullptr) {
+        if (NEE1 || pc != nullptr) {
             gen = __builtin_amdgcn_readfirstlane(pc->gen);
             rc0 = pc->rect[0]; rc1 = pc->rect[1]; rc2 = pc->rect[2]; rc3 = pc->rect[3]; rc4 = pc->rect[4];
         } else {
@@ -521,7 +526,7 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         }
         float lpdf = 0.0f, ldist = 0.0f;
         v3 ldir = V(0.f, 0.f, 0.f), lem = V(0.f, 0.f, 0.f);
-        if (gen == RTW_PDF_RECT_X || gen == RTW_PDF_RECT_Y || gen == RTW_PDF_RECT_Z) {
+        if (NEE1 || gen == RTW_PDF_RECT_X || gen == RTW_PDF_RECT_Y || gen == RTW_PDF_RECT_Z) {
             // rectPdf.cu:124-193
             float ra, rb;
             if (KIND == RTW_RNG_PHILOX && nl == 1) {
@@ -542,7 +547,9 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
                 ldir = vscale(ldir, rcp_(ldist));
                 float costa = dot3(vneg(ldir), lnrm);
                 if (costa > 1.0e-6f) {
-                    lem = vscale(lemi, (float)nl);
+                    // one light: the scale is x * 1.0f, which returns every x unchanged (a NaN keeps its payload or not: the emission
+                    // of an uploaded scene is finite), so NEE1 does not multiply
+                    lem = NEE1 ? lemi : vscale(lemi, (float)nl);
                     lpdf = (ldist * ldist) / (larea * costa);
                 }
             }
@@ -1371,7 +1378,9 @@ RTW_DEV constexpr int rtw_phase_id(const char* n) { return n[0] == 'r' && n[2] =
 // (A.order, see KArgs), to the listed shard-local pixel, jobs are taken in plain position order (no k_classify), and block b of list
 // position i goes to slot [b][i] (stride n_list). The host runs these passes with block sums (unit_sums = 0), so the LDS unit sums
 // are free and s_usum[0] holds each lane's list position. Everything after the refill is the same code.
-template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0>
+// NEE1 = 1 (hot instantiation, Philox): the scene lists exactly one light, a rectangle, under the reference estimator - facts of
+// rtw_upload_scene that the host's path_kernel() checks (rtw_hip.hip path_nee1) - and shade_a compiles that light sample alone.
+template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0, int NEE1 = 0>
 __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVES) : RTW_PATH_WAVES) k_path(const KArgs A) {
     RTW_NOISE_SHARED
     __shared__ u32x4 s_hitrec[kPathMaxPrims * 6];
@@ -1556,7 +1565,7 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
         if (busy) {
             v3 so, sd, att, radiance;
             Nee nee;
-            const int ev = shade_a<KIND, TEX>(A.sc, g, o, d, gt, th, prim, so, sd, att, radiance, nee, noise_lds, nee_prev, s_hitrec, &s_pc);
+            const int ev = shade_a<KIND, TEX, NEE1 && RTW_PATH_NEE1>(A.sc, g, o, d, gt, th, prim, so, sd, att, radiance, nee, noise_lds, nee_prev, s_hitrec, &s_pc);
             n_seg++;
 #ifdef RTW_SUBPHASE_TIMERS
             rtw_sub_stamp(0);  // 0: everything outside the closest-hit program

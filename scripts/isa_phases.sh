@@ -1,20 +1,21 @@
 #!/bin/bash
-# usage: scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0> per phase (between the
-# phase-fence comments). Compiles rtw_inst_path.hip the way __graft_entry__.build() does (HIP_FLAGS + that unit's UNIT_FLAGS) and
-# prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
+# usage: [NEE1=0|1] scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0,NEE1> per phase
+# (between the phase-fence comments; NEE1 = 1, the default, is the one-light instantiation the headline scene runs). Compiles
+# rtw_inst_path.hip the way __graft_entry__.build() does (HIP_FLAGS + that unit's UNIT_FLAGS) and prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
 # divisions (v_div_fixup_f32, fallbacks of the short forms included), sqrt = its roots (v_sqrt_f32), rcp_short / rsq_short = the
 # short forms of rtw_math.h (a v_rcp_f32 without a v_div_fixup_f32; v_rsq_f32). Exits 1 when the kernel is not found.
 R=$(cd "$(dirname "$0")/.." && pwd)
+K=_ZN4rtwk6k_pathILi0ELi0ELi0ELi0ELi${NEE1:-1}EEEvNS_5KArgsE
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 FLAGS=$(cd "$R" && python3 -c "
 import __graft_entry__ as g
 print(' '.join([f for f in g.HIP_FLAGS if f != '-shared'] + ['-DRTW_SPLIT_BUILD'] + g.UNIT_FLAGS['rtw_inst_path.hip']))") || exit 1
 ${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS "$@" -S --cuda-device-only -o "$T/rtw.s" "$R/raytracing_weekend_amd/csrc/rtw_inst_path.hip" || exit 1
-awk '/^_ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE:/{f=1} f{print} /s_endpgm/{if(f){exit}}' "$T/rtw.s" > "$T/kpath.s"
-if [ ! -s "$T/kpath.s" ]; then echo "isa_phases: no k_pathILi0ELi0ELi0ELi0EEE in the assembly" >&2; exit 1; fi
-awk '/\.amdhsa_kernel _ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE/{f=1} f&&/amdhsa_next_free_vgpr|amdhsa_private_segment_fixed_size/{print} /\.end_amdhsa_kernel/{f=0}' "$T/rtw.s"
-awk '/^_ZN4rtwk6k_pathILi0ELi0ELi0ELi0EEEvNS_5KArgsE:/{f=1} f&&/^; codeLenInByte/{print; exit}' "$T/rtw.s"
+awk '/^'$K':/{f=1} f{print} /s_endpgm/{if(f){exit}}' "$T/rtw.s" > "$T/kpath.s"
+if [ ! -s "$T/kpath.s" ]; then echo "isa_phases: no $K in the assembly" >&2; exit 1; fi
+awk '/\.amdhsa_kernel '$K'/{f=1} f&&/amdhsa_next_free_vgpr|amdhsa_private_segment_fixed_size/{print} /\.end_amdhsa_kernel/{f=0}' "$T/rtw.s"
+awk '/^'$K':/{f=1} f&&/^; codeLenInByte/{print; exit}' "$T/rtw.s"
 python3 - "$T/kpath.s" <<'PY'
 import re,collections,sys
 cur="pre"; cnt=collections.OrderedDict()
@@ -34,6 +35,10 @@ for l in open(sys.argv[1]):
     elif op.startswith(('global_','scratch_','buffer_','flat_')): c['vmem']+=1
     if op.startswith('v_mov'): c['v_mov']+=1
     if op.startswith(('v_readlane','v_writelane')): c['lane']+=1
+    if op.startswith('v_readlane'): c['readlane']+=1
+    if op.startswith('v_readfirstlane'): c['readfirstlane']+=1
+    if op.startswith('scratch_'): c['scratch']+=1
+    if op.startswith('v_mad_u64_u32'): c['mad_u64']+=1
     if op.startswith('v_cndmask'): c['cndmask']+=1
     if op.startswith('v_cmp'): c['cmp']+=1
     if op.startswith('v_div_fixup_f32'): c['div']+=1

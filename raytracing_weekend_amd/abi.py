@@ -138,15 +138,52 @@ class ViewParams(C.Structure):
                 ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("reserved", C.c_uint32)]
 
 
-HIP_SYMBOLS = ["rtw_abi_version", "rtw_create", "rtw_upload_scene", "rtw_render", "rtw_render_device",
-               "rtw_destroy", "rtw_last_error", "rtw_debug_intersect", "rtw_denoise", "rtw_render_guides", "rtw_denoise_guided",
-               "rtw_render_adaptive", "rtw_debug_math", "rtw_accum_begin", "rtw_accum_add", "rtw_accum_read", "rtw_accum_read_device",
-               "rtw_accum_status", "rtw_accum_save", "rtw_accum_restore", "rtw_accum_end", "rtw_cast", "rtw_cast_device",
-               "rtw_radiance", "rtw_radiance_device", "rtw_probe", "rtw_probe_device",
-               "rtw_probe_sh", "rtw_probe_sh_device", "rtw_views", "rtw_views_device",
-               "rtw_probe_adaptive", "rtw_probe_adaptive_device",
-               "rtw_views_guides", "rtw_views_guides_device", "rtw_denoise_views", "rtw_denoise_views_device",
-               "rtw_views_adaptive", "rtw_views_adaptive_device"]
+_PTR, _STATS = C.c_void_p, C.POINTER(Stats)
+_DENOISE = [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float]  # two sizes, iterations, the three sigmas
+
+
+def _query(params, *outputs):
+    """The argtypes of a query call and of its _device variant (the stream before the stats): context, batch, n, the parameter
+    structs, the outputs, stats."""
+    head = [_PTR, _PTR, C.c_size_t] + [C.POINTER(p) for p in params] + list(outputs)
+    return head + [_STATS], head + [_PTR, _STATS]
+
+
+# include/rtw.h's entry points: name -> argtypes. All return int but rtw_last_error, a C string.
+HIP_SIGNATURES = {
+    "rtw_abi_version": [],
+    "rtw_create": [C.POINTER(_PTR), C.c_int, C.POINTER(C.c_int)],
+    "rtw_upload_scene": [_PTR, _PTR, C.c_size_t],
+    "rtw_render": [_PTR, C.POINTER(Params), _PTR, _STATS],
+    "rtw_render_device": [_PTR, C.POINTER(Params), _PTR, _PTR, _STATS],
+    "rtw_destroy": [_PTR],
+    "rtw_last_error": [_PTR],
+    "rtw_debug_intersect": [_PTR, _PTR, _PTR, _PTR, C.c_int, _PTR, _PTR],
+    "rtw_denoise": [_PTR, _PTR, _PTR, C.c_int32, C.c_int32, C.c_int32, C.c_float],
+    "rtw_render_guides": [_PTR, C.POINTER(Params), C.POINTER(Guides), _STATS],
+    "rtw_denoise_guided": [_PTR, _PTR, _PTR, _PTR, _PTR] + _DENOISE,
+    "rtw_render_adaptive": [_PTR, C.POINTER(Params), C.POINTER(Adaptive), _PTR, _PTR, _PTR, _STATS],
+    "rtw_debug_math": [_PTR, C.c_int, C.POINTER(C.c_uint64)],
+    "rtw_accum_begin": [_PTR, C.POINTER(Params), C.c_uint32],
+    "rtw_accum_add": [_PTR, C.c_int32, _STATS],
+    "rtw_accum_read": [_PTR, _PTR, _PTR],
+    "rtw_accum_read_device": [_PTR, _PTR, _PTR],
+    "rtw_accum_status": [_PTR, C.POINTER(AccumInfo)],
+    "rtw_accum_save": [_PTR, _PTR, C.c_size_t],
+    "rtw_accum_restore": [_PTR, _PTR, C.c_size_t],
+    "rtw_accum_end": [_PTR],
+    "rtw_cast": [_PTR, _PTR, _PTR, _PTR, C.c_size_t, C.c_int32, C.POINTER(Hits), _STATS],
+    "rtw_cast_device": [_PTR, _PTR, _PTR, _PTR, C.c_size_t, C.c_int32, C.POINTER(Hits), _PTR, _STATS],
+    "rtw_denoise_views": [_PTR, _PTR, _PTR, _PTR, _PTR, C.c_size_t] + _DENOISE,
+    "rtw_denoise_views_device": [_PTR, _PTR, _PTR, _PTR, _PTR, C.c_size_t] + _DENOISE + [_PTR],
+}
+for _name, _sig in (("rtw_radiance", _query([RadianceParams], _PTR)), ("rtw_probe", _query([ProbeParams], _PTR)),
+                    ("rtw_probe_sh", _query([RadianceParams], _PTR)), ("rtw_views", _query([ViewParams], _PTR)),
+                    ("rtw_probe_adaptive", _query([ProbeParams, Adaptive], _PTR, _PTR, _PTR)),
+                    ("rtw_views_guides", _query([ViewParams, Guides])),
+                    ("rtw_views_adaptive", _query([ViewParams, Adaptive], _PTR, _PTR, _PTR))):
+    HIP_SIGNATURES[_name], HIP_SIGNATURES[_name + "_device"] = _sig
+HIP_SYMBOLS = list(HIP_SIGNATURES)
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
 CAST_MODES = {"closest": 0, "any": 1}  # RTW_CAST_CLOSEST, RTW_CAST_ANY
 # rtw_hits' outputs: name -> (numpy dtype, trailing shape)
@@ -154,6 +191,8 @@ CAST_OUTPUTS = {"t": (np.float32, ()), "prim": (np.int32, ()), "material": (np.i
 RTW_ACCUM_ERROR = 1  # rtw_accum_begin's flag: keep the moments, so that accum_read can return the error map
 MATH_OPS = {"rcp": 0, "sqrt": 1, "rcp_sqrt": 2, "rcp_one_step": 3, "rcp_two_steps": 4, "sqrt_residual_only": 5, "sqrt_coupled": 6}  # rtw_debug_math's op
 GUIDES = ("albedo", "normal", "depth", "prim")
+# a guide buffer: name -> (trailing shape, dtype name) after the leading (rows, w) or (n, h, w)
+GUIDE_LAYOUT = {"albedo": ((4,), "float32"), "normal": ((4,), "float32"), "depth": ((), "float32"), "prim": ((), "int32")}
 # Default edge-stopping sigmas of Renderer.denoise_guided (see there)
 DENOISE_SIGMA_ALBEDO = 0.4
 DENOISE_SIGMA_NORMAL = 0.5
@@ -182,94 +221,9 @@ def load_hip():
             raise RuntimeError(f"{HIP_LIB} is missing: the HIP extension must be built "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`); no CPU fallback exists")
         lib = C.CDLL(HIP_LIB)
-        lib.rtw_abi_version.restype = C.c_int
-        lib.rtw_create.restype = C.c_int
-        lib.rtw_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]
-        lib.rtw_upload_scene.restype = C.c_int
-        lib.rtw_upload_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.rtw_render.restype = C.c_int
-        lib.rtw_render.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_render_device.restype = C.c_int
-        lib.rtw_render_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_destroy.restype = C.c_int
-        lib.rtw_destroy.argtypes = [C.c_void_p]
-        lib.rtw_last_error.restype = C.c_char_p
-        lib.rtw_last_error.argtypes = [C.c_void_p]
-        lib.rtw_denoise.restype = C.c_int
-        lib.rtw_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]
-        lib.rtw_render_adaptive.restype = C.c_int
-        lib.rtw_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.POINTER(Stats)]
-        lib.rtw_render_guides.restype = C.c_int
-        lib.rtw_render_guides.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Guides), C.POINTER(Stats)]
-        lib.rtw_denoise_guided.restype = C.c_int
-        lib.rtw_denoise_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_float, C.c_float, C.c_float]
-        lib.rtw_debug_intersect.restype = C.c_int
-        lib.rtw_debug_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib.rtw_debug_math.restype = C.c_int
-        lib.rtw_debug_math.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
-        lib.rtw_accum_begin.restype = C.c_int
-        lib.rtw_accum_begin.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32]
-        lib.rtw_accum_add.restype = C.c_int
-        lib.rtw_accum_add.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Stats)]
-        lib.rtw_accum_read.restype = C.c_int
-        lib.rtw_accum_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.rtw_accum_read_device.restype = C.c_int
-        lib.rtw_accum_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.rtw_accum_status.restype = C.c_int
-        lib.rtw_accum_status.argtypes = [C.c_void_p, C.POINTER(AccumInfo)]
-        lib.rtw_accum_save.restype = C.c_int
-        lib.rtw_accum_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.rtw_accum_restore.restype = C.c_int
-        lib.rtw_accum_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.rtw_accum_end.restype = C.c_int
-        lib.rtw_accum_end.argtypes = [C.c_void_p]
-        lib.rtw_cast.restype = C.c_int
-        lib.rtw_cast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Hits), C.POINTER(Stats)]
-        lib.rtw_cast_device.restype = C.c_int
-        lib.rtw_cast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(Hits), C.c_void_p,
-                                        C.POINTER(Stats)]
-        lib.rtw_radiance.restype = C.c_int
-        lib.rtw_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_radiance_device.restype = C.c_int
-        lib.rtw_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p,
-                                            C.POINTER(Stats)]
-        lib.rtw_probe.restype = C.c_int
-        lib.rtw_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_probe_device.restype = C.c_int
-        lib.rtw_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_probe_adaptive.restype = C.c_int
-        lib.rtw_probe_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_probe_adaptive_device.restype = C.c_int
-        lib.rtw_probe_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeParams), C.POINTER(Adaptive), C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_probe_sh.restype = C.c_int
-        lib.rtw_probe_sh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_probe_sh_device.restype = C.c_int
-        lib.rtw_probe_sh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_views.restype = C.c_int
-        lib.rtw_views.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_views_device.restype = C.c_int
-        lib.rtw_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_views_adaptive.restype = C.c_int
-        lib.rtw_views_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_views_adaptive_device.restype = C.c_int
-        lib.rtw_views_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Adaptive), C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        lib.rtw_views_guides.restype = C.c_int
-        lib.rtw_views_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Guides), C.POINTER(Stats)]
-        lib.rtw_views_guides_device.restype = C.c_int
-        lib.rtw_views_guides_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ViewParams), C.POINTER(Guides), C.c_void_p,
-                                                C.POINTER(Stats)]
-        lib.rtw_denoise_views.restype = C.c_int
-        lib.rtw_denoise_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
-                                          C.c_int32, C.c_float, C.c_float, C.c_float]
-        lib.rtw_denoise_views_device.restype = C.c_int
-        lib.rtw_denoise_views_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
-                                                 C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        for name, argtypes in HIP_SIGNATURES.items():
+            f = getattr(lib, name)
+            f.restype, f.argtypes = (C.c_char_p if name == "rtw_last_error" else C.c_int), argtypes
         if lib.rtw_abi_version() != RTW_ABI_VERSION:
             raise RuntimeError("librtw_hip.so ABI version mismatch")
         _hip = lib
@@ -332,6 +286,60 @@ def assemble_scene(parts):
     return bytes(buf)
 
 
+def _positive(prefix, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+        raise ValueError(f"{prefix}: {name} = {v!r}, expected a positive integer")
+
+
+def _batch(prefix, name, a):
+    """The (n, 8) float32 batch of a query, contiguous. Anything that is not a float32 ndarray already is refused, not converted."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+        raise ValueError(f"{prefix}: {name} must be a float32 numpy array")
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"{prefix}: {name} of shape {a.shape}, expected (n, 8)")
+    return np.ascontiguousarray(a)
+
+
+def _check_pixels(prefix, n, width, height):
+    if n * int(width) * int(height) > 0x7fffffff:
+        raise ValueError(f"{prefix}: more than 2^31 - 1 pixels in one call")
+
+
+def _view_batch(prefix, views, width, height, spp, max_depth, rng_kind, sample_offset, estimator):
+    """(the View array, the rtw_view_params) of a host call on views, refused when it has too many pixels."""
+    arr = view_array(views)
+    vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
+    _check_pixels(prefix, len(arr), width, height)
+    return arr, vp
+
+
+def _guide_names(prefix, which):
+    which = tuple(which)
+    bad = [k for k in which if k not in GUIDES]
+    if bad or not which:
+        raise ValueError(f"{prefix}: unknown or no guide names {bad or which}")
+    return which
+
+
+def _guide_buffers(which, lead):
+    """({name: array of shape lead + the guide's own}, the Guides that points at them)"""
+    out = {k: np.empty(lead + GUIDE_LAYOUT[k][0], GUIDE_LAYOUT[k][1]) for k in which}
+    return out, Guides(**{k: v.ctypes.data for k, v in out.items()})
+
+
+def _adaptive_outputs(lead):
+    """(values, sample counts, errors) of an adaptive call over `lead` pixels or probes"""
+    return np.empty(lead + (4,), dtype=np.float32), np.empty(lead, dtype=np.int32), np.empty(lead, dtype=np.float32)
+
+
+def _ref(stats):
+    return None if stats is None else C.byref(stats)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def make_params(width, height, spp, max_depth, seed=0x6314759, row0=0, row1=None, rng_kind=RTW_RNG_PHILOX,
                 sample_offset=0, samples_per_pass=0, row_stride=0, estimator=0):
     p = Params()
@@ -349,15 +357,13 @@ def make_params(width, height, spp, max_depth, seed=0x6314759, row0=0, row1=None
 
 def make_radiance_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0):
     """rtw_radiance_params; spp must be a positive integer (the library checks the rest)."""
-    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp <= 0:
-        raise ValueError(f"radiance: spp = {spp!r}, expected a positive integer")
+    _positive("radiance", "spp", spp)
     return RadianceParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, 0)
 
 
 def make_probe_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, mode="irradiance"):
     """rtw_probe_params; spp must be a positive integer and mode "irradiance" or "occlusion" (the library checks the rest)."""
-    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp <= 0:
-        raise ValueError(f"probe: spp = {spp!r}, expected a positive integer")
+    _positive("probe", "spp", spp)
     if mode not in PROBE_MODES:
         raise ValueError(f"probe: mode {mode!r} is neither 'irradiance' nor 'occlusion'")
     return ProbeParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, PROBE_MODES[mode])
@@ -403,8 +409,7 @@ def view_array(views):
 def make_view_params(width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0):
     """rtw_view_params; width, height and spp must be positive integers (the library checks the rest)."""
     for name, v in (("width", width), ("height", height), ("spp", spp)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
-            raise ValueError(f"views: {name} = {v!r}, expected a positive integer")
+        _positive("views", name, v)
     return ViewParams(int(width), int(height), int(spp), int(max_depth), rng_kind, sample_offset, estimator, 0)
 
 
@@ -461,17 +466,8 @@ class Renderer:
         """rtw_render_guides: first-hit guide buffers of the rows `params` renders, as a dict of the requested names:
         albedo and normal (rows, w, 4) float32 (alpha = fraction of the samples that hit), depth (rows, w) float32,
         prim (rows, w) int32. `stats`: a Stats to fill, or None."""
-        which = tuple(which)
-        bad = [k for k in which if k not in GUIDES]
-        if bad or not which:
-            raise ValueError(f"render_guides: unknown or no guide names {bad or which}")
-        rows = local_rows(params)
-        shapes = {"albedo": ((rows, params.width, 4), np.float32), "normal": ((rows, params.width, 4), np.float32),
-                  "depth": ((rows, params.width), np.float32), "prim": ((rows, params.width), np.int32)}
-        out = {k: np.empty(*shapes[k]) for k in which}
-        g = Guides(**{k: v.ctypes.data for k, v in out.items()})
-        self._check(self.lib.rtw_render_guides(self.ctx, C.byref(params), C.byref(g), None if stats is None else C.byref(stats)),
-                    "rtw_render_guides")
+        out, g = _guide_buffers(_guide_names("render_guides", which), (local_rows(params), params.width))
+        self._check(self.lib.rtw_render_guides(self.ctx, C.byref(params), C.byref(g), _ref(stats)), "rtw_render_guides")
         return out
 
     def denoise_guided(self, img, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=DENOISE_SIGMA_ALBEDO,
@@ -501,10 +497,7 @@ class Renderer:
         """rtw_render_adaptive: params.spp is the cap. Returns (img, spp, err, stats): the (rows, w, 4) float32 image, the
         (rows, w) int32 sample count of every pixel, the (rows, w) float32 error estimate at its last checkpoint and the Stats.
         Pixel p of img is, bit for bit, pixel p of render(params with spp = spp[p])."""
-        rows = local_rows(params)
-        img = np.empty((rows, params.width, 4), dtype=np.float32)
-        spp = np.empty((rows, params.width), dtype=np.int32)
-        err = np.empty((rows, params.width), dtype=np.float32)
+        img, spp, err = _adaptive_outputs((local_rows(params), params.width))
         ad = Adaptive(min_spp, step_spp, threshold, dilate)
         st = Stats()
         self._check(self.lib.rtw_render_adaptive(self.ctx, C.byref(params), C.byref(ad), img.ctypes.data, spp.ctypes.data,
@@ -590,9 +583,7 @@ class Renderer:
         rt, gt = times(ray_time), times(gather_time)
         out = {k: np.empty((n,) + CAST_OUTPUTS[k][1], CAST_OUTPUTS[k][0]) for k in names}
         h = Hits(**{k: v.ctypes.data for k, v in out.items()})
-        self._check(self.lib.rtw_cast(self.ctx, rays.ctypes.data, None if rt is None else rt.ctypes.data,
-                                      None if gt is None else gt.ctypes.data, n, CAST_MODES[mode], C.byref(h),
-                                      None if stats is None else C.byref(stats)), "rtw_cast")
+        self._check(self.lib.rtw_cast(self.ctx, rays.ctypes.data, _ptr(rt), _ptr(gt), n, CAST_MODES[mode], C.byref(h), _ref(stats)), "rtw_cast")
         return out
 
     def cast_device(self, n, rays_ptr, out_ptrs, ray_time_ptr=0, gather_time_ptr=0, mode="closest", stream_ptr=0, stats=None):
@@ -600,23 +591,17 @@ class Renderer:
         dict name -> device pointer of the outputs wanted, stream_ptr a hipStream_t (0: the context's own stream)."""
         h = Hits(**{k: C.c_void_p(v) for k, v in out_ptrs.items()})
         self._check(self.lib.rtw_cast_device(self.ctx, C.c_void_p(rays_ptr), C.c_void_p(ray_time_ptr), C.c_void_p(gather_time_ptr), n,
-                                             CAST_MODES[mode], C.byref(h), C.c_void_p(stream_ptr),
-                                             None if stats is None else C.byref(stats)), "rtw_cast_device")
+                                             CAST_MODES[mode], C.byref(h), C.c_void_p(stream_ptr), _ref(stats)), "rtw_cast_device")
 
     # ---- path-traced radiance along the caller's own rays (include/rtw.h rtw_radiance / rtw_radiance_device)
     def radiance(self, rays, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, stats=None):
         """rtw_radiance on (n, 8) float32 rays (origin, direction, tmin, tmax: tmin and tmax bound the first segment): the (n, 4)
         float32 mean radiance of spp paths along every ray, alpha 1. Ray i draws from the stream of key_offset + i, samples
         sample_offset ... sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
-        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32:
-            raise ValueError("radiance: rays must be a float32 numpy array")
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError(f"radiance: rays of shape {rays.shape}, expected (n, 8)")
+        rays = _batch("radiance", "rays", rays)
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
-        rays = np.ascontiguousarray(rays)
         out = np.empty((rays.shape[0], 4), dtype=np.float32)
-        self._check(self.lib.rtw_radiance(self.ctx, rays.ctypes.data, rays.shape[0], C.byref(rp), out.ctypes.data,
-                                          None if stats is None else C.byref(stats)), "rtw_radiance")
+        self._check(self.lib.rtw_radiance(self.ctx, rays.ctypes.data, rays.shape[0], C.byref(rp), out.ctypes.data, _ref(stats)), "rtw_radiance")
         return out
 
     def radiance_device(self, n, rays_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
@@ -625,7 +610,7 @@ class Renderer:
         (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
         self._check(self.lib.rtw_radiance_device(self.ctx, C.c_void_p(rays_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
-                                                 None if stats is None else C.byref(stats)), "rtw_radiance_device")
+                                                 _ref(stats)), "rtw_radiance_device")
 
     # ---- irradiance and ambient occlusion at surface points (include/rtw.h rtw_probe / rtw_probe_device)
     def probe(self, probes, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
@@ -634,15 +619,10 @@ class Renderer:
         1 - mode "irradiance": the irradiance (cosine-weighted paths, mean radiance times pi); mode "occlusion": the fraction of the
         same directions that reach tmax unoccluded, in all three channels. Probe i draws from the stream of key_offset + i, samples
         sample_offset ... sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
-        if not isinstance(probes, np.ndarray) or probes.dtype != np.float32:
-            raise ValueError("probe: probes must be a float32 numpy array")
-        if probes.ndim != 2 or probes.shape[1] != 8:
-            raise ValueError(f"probe: probes of shape {probes.shape}, expected (n, 8)")
+        probes = _batch("probe", "probes", probes)
         pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
-        probes = np.ascontiguousarray(probes)
         out = np.empty((probes.shape[0], 4), dtype=np.float32)
-        self._check(self.lib.rtw_probe(self.ctx, probes.ctypes.data, probes.shape[0], C.byref(pp), out.ctypes.data,
-                                       None if stats is None else C.byref(stats)), "rtw_probe")
+        self._check(self.lib.rtw_probe(self.ctx, probes.ctypes.data, probes.shape[0], C.byref(pp), out.ctypes.data, _ref(stats)), "rtw_probe")
         return out
 
     def probe_device(self, n, probes_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
@@ -651,7 +631,7 @@ class Renderer:
         out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
         pp = make_probe_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
         self._check(self.lib.rtw_probe_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
-                                              None if stats is None else C.byref(stats)), "rtw_probe_device")
+                                              _ref(stats)), "rtw_probe_device")
 
     # ---- probes sampled to a noise target (include/rtw.h rtw_probe_adaptive / rtw_probe_adaptive_device)
     def probe_adaptive(self, probes, cap, max_depth, threshold, min_spp=64, step_spp=0, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0,
@@ -659,17 +639,13 @@ class Renderer:
         """rtw_probe_adaptive on (n, 8) float32 probes: every probe takes samples until its error estimate is below `threshold`, at
         most `cap`. Returns (out, spp, err): the (n, 4) float32 results, the (n,) int32 sample counts n_i and the (n,) float32 errors
         at each probe's last checkpoint. Row i of out is, bit for bit, row 0 of probe(probes[i:i + 1], spp[i], ..., key_offset + i)."""
-        if not isinstance(probes, np.ndarray) or probes.dtype != np.float32:
-            raise ValueError("probe_adaptive: probes must be a float32 numpy array")
-        if probes.ndim != 2 or probes.shape[1] != 8:
-            raise ValueError(f"probe_adaptive: probes of shape {probes.shape}, expected (n, 8)")
+        probes = _batch("probe_adaptive", "probes", probes)
         pp = make_probe_params(cap, max_depth, seed, rng_kind, sample_offset, estimator, key_offset, mode)
         ad = Adaptive(min_spp, step_spp, threshold, 0)
-        probes = np.ascontiguousarray(probes)
         n = probes.shape[0]
-        out, spp, err = np.empty((n, 4), dtype=np.float32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        out, spp, err = _adaptive_outputs((n,))
         self._check(self.lib.rtw_probe_adaptive(self.ctx, probes.ctypes.data, n, C.byref(pp), C.byref(ad), out.ctypes.data, spp.ctypes.data,
-                                                err.ctypes.data, None if stats is None else C.byref(stats)), "rtw_probe_adaptive")
+                                                err.ctypes.data, _ref(stats)), "rtw_probe_adaptive")
         return out, spp, err
 
     def probe_adaptive_device(self, n, probes_ptr, out_ptr, spp_ptr, err_ptr, cap, max_depth, threshold, min_spp=64, step_spp=0, seed=0x6314759,
@@ -680,7 +656,7 @@ class Renderer:
         ad = Adaptive(min_spp, step_spp, threshold, 0)
         self._check(self.lib.rtw_probe_adaptive_device(self.ctx, C.c_void_p(probes_ptr), n, C.byref(pp), C.byref(ad), C.c_void_p(out_ptr),
                                                        C.c_void_p(spp_ptr), C.c_void_p(err_ptr), C.c_void_p(stream_ptr),
-                                                       None if stats is None else C.byref(stats)), "rtw_probe_adaptive_device")
+                                                       _ref(stats)), "rtw_probe_adaptive_device")
 
     # ---- spherical-harmonic light probes at free points (include/rtw.h rtw_probe_sh / rtw_probe_sh_device)
     def probe_sh(self, points, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0, stats=None):
@@ -688,15 +664,10 @@ class Renderer:
         radiance arriving at every point on the nine real spherical harmonics of bands 0 to 2, spp samples per point, w = 0
         (bake.sh_irradiance evaluates them for a normal). Point i draws from the stream of key_offset + i, samples sample_offset ...
         sample_offset + spp - 1. `stats`: a Stats to fill, or None."""
-        if not isinstance(points, np.ndarray) or points.dtype != np.float32:
-            raise ValueError("probe_sh: points must be a float32 numpy array")
-        if points.ndim != 2 or points.shape[1] != 8:
-            raise ValueError(f"probe_sh: points of shape {points.shape}, expected (n, 8)")
+        points = _batch("probe_sh", "points", points)
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
-        points = np.ascontiguousarray(points)
         out = np.empty((points.shape[0], 9, 4), dtype=np.float32)
-        self._check(self.lib.rtw_probe_sh(self.ctx, points.ctypes.data, points.shape[0], C.byref(rp), out.ctypes.data,
-                                          None if stats is None else C.byref(stats)), "rtw_probe_sh")
+        self._check(self.lib.rtw_probe_sh(self.ctx, points.ctypes.data, points.shape[0], C.byref(rp), out.ctypes.data, _ref(stats)), "rtw_probe_sh")
         return out
 
     def probe_sh_device(self, n, points_ptr, out_ptr, spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
@@ -705,20 +676,16 @@ class Renderer:
         written at out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
         rp = make_radiance_params(spp, max_depth, seed, rng_kind, sample_offset, estimator, key_offset)
         self._check(self.lib.rtw_probe_sh_device(self.ctx, C.c_void_p(points_ptr), n, C.byref(rp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
-                                                 None if stats is None else C.byref(stats)), "rtw_probe_sh_device")
+                                                 _ref(stats)), "rtw_probe_sh_device")
 
     # ---- batched frames from the caller's own cameras (include/rtw.h rtw_views / rtw_views_device)
     def views(self, views, width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, stats=None):
         """rtw_views on View records (make_view, scene_view, bake.cube_views, bake.orbit_views): the (n, height, width, 4) float32
         frames, row 0 the bottom row, alpha 1. Frame v is render()'s frame of the uploaded scene with views[v]'s camera in its
         header and views[v].seed as the seed. `stats`: a Stats to fill, or None."""
-        arr = view_array(views)
-        vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
-        if len(arr) * int(width) * int(height) > 0x7fffffff:
-            raise ValueError("views: more than 2^31 - 1 pixels in one call")
+        arr, vp = _view_batch("views", views, width, height, spp, max_depth, rng_kind, sample_offset, estimator)
         out = np.empty((len(arr), int(height), int(width), 4), dtype=np.float32)
-        self._check(self.lib.rtw_views(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), out.ctypes.data,
-                                       None if stats is None else C.byref(stats)), "rtw_views")
+        self._check(self.lib.rtw_views(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), out.ctypes.data, _ref(stats)), "rtw_views")
         return out
 
     def views_device(self, n, views_ptr, out_ptr, width, height, spp, max_depth, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0,
@@ -727,7 +694,7 @@ class Renderer:
         n * height * width float4 written at out_ptr (both 16-byte aligned), stream_ptr a hipStream_t (0: the context's own stream)."""
         vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
         self._check(self.lib.rtw_views_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.c_void_p(out_ptr), C.c_void_p(stream_ptr),
-                                              None if stats is None else C.byref(stats)), "rtw_views_device")
+                                              _ref(stats)), "rtw_views_device")
 
     # ---- batched views sampled to a noise target (include/rtw.h rtw_views_adaptive / rtw_views_adaptive_device)
     def views_adaptive(self, views, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0, dilate=1, rng_kind=RTW_RNG_PHILOX,
@@ -737,15 +704,11 @@ class Renderer:
         and the (n, height, width) float32 errors at each pixel's last checkpoint. View v's three arrays are, bit for bit,
         render_adaptive's of the uploaded scene with views[v]'s camera in its header and views[v].seed as the seed; with dilate = 1
         the 3x3 neighbourhood stays inside the pixel's own view. `stats`: a Stats to fill, or None."""
-        arr = view_array(views)
-        vp = make_view_params(width, height, cap, max_depth, rng_kind, sample_offset, estimator)
-        if len(arr) * int(width) * int(height) > 0x7fffffff:
-            raise ValueError("views_adaptive: more than 2^31 - 1 pixels in one call")
+        arr, vp = _view_batch("views_adaptive", views, width, height, cap, max_depth, rng_kind, sample_offset, estimator)
         ad = Adaptive(min_spp, step_spp, threshold, dilate)
-        shape = (len(arr), int(height), int(width))
-        out, spp, err = np.empty(shape + (4,), dtype=np.float32), np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float32)
+        out, spp, err = _adaptive_outputs((len(arr), int(height), int(width)))
         self._check(self.lib.rtw_views_adaptive(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), C.byref(ad), out.ctypes.data,
-                                                spp.ctypes.data, err.ctypes.data, None if stats is None else C.byref(stats)), "rtw_views_adaptive")
+                                                spp.ctypes.data, err.ctypes.data, _ref(stats)), "rtw_views_adaptive")
         return out, spp, err
 
     def views_adaptive_device(self, n, views_ptr, out_ptr, spp_ptr, err_ptr, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0,
@@ -757,7 +720,7 @@ class Renderer:
         ad = Adaptive(min_spp, step_spp, threshold, dilate)
         self._check(self.lib.rtw_views_adaptive_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.byref(ad), C.c_void_p(out_ptr),
                                                        C.c_void_p(spp_ptr), C.c_void_p(err_ptr), C.c_void_p(stream_ptr),
-                                                       None if stats is None else C.byref(stats)), "rtw_views_adaptive_device")
+                                                       _ref(stats)), "rtw_views_adaptive_device")
 
     # ---- guides of batched views and their denoiser (include/rtw.h rtw_views_guides / rtw_denoise_views)
     def views_guides(self, views, width, height, spp=16, which=GUIDES, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stats=None):
@@ -765,21 +728,10 @@ class Renderer:
         (n, height, width, 4) float32 (alpha = fraction of the samples that hit), depth (n, height, width) float32, prim
         (n, height, width) int32 - of the requested names. View v's guides are render_guides' of the uploaded scene with views[v]'s
         camera in its header and views[v].seed as the seed. `stats`: a Stats to fill, or None."""
-        which = tuple(which)
-        bad = [k for k in which if k not in GUIDES]
-        if bad or not which:
-            raise ValueError(f"views_guides: unknown or no guide names {bad or which}")
-        arr = view_array(views)
-        vp = make_view_params(width, height, spp, 0, rng_kind, sample_offset, 0)
-        if len(arr) * int(width) * int(height) > 0x7fffffff:
-            raise ValueError("views_guides: more than 2^31 - 1 pixels in one call")
-        n, h, w = len(arr), int(height), int(width)
-        shapes = {"albedo": ((n, h, w, 4), np.float32), "normal": ((n, h, w, 4), np.float32), "depth": ((n, h, w), np.float32),
-                  "prim": ((n, h, w), np.int32)}
-        out = {k: np.empty(*shapes[k]) for k in which}
-        g = Guides(**{k: v.ctypes.data for k, v in out.items()})
-        self._check(self.lib.rtw_views_guides(self.ctx, C.cast(arr, C.c_void_p), n, C.byref(vp), C.byref(g),
-                                              None if stats is None else C.byref(stats)), "rtw_views_guides")
+        which = _guide_names("views_guides", which)
+        arr, vp = _view_batch("views_guides", views, width, height, spp, 0, rng_kind, sample_offset, 0)  # no paths: no depth, no estimator
+        out, g = _guide_buffers(which, (len(arr), int(height), int(width)))
+        self._check(self.lib.rtw_views_guides(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), C.byref(g), _ref(stats)), "rtw_views_guides")
         return out
 
     def views_guides_device(self, n, views_ptr, out_ptrs, width, height, spp=16, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stream_ptr=0,
@@ -793,7 +745,7 @@ class Renderer:
         vp = make_view_params(width, height, spp, 0, rng_kind, sample_offset, 0)
         g = Guides(**{k: int(v) for k, v in out_ptrs.items()})
         self._check(self.lib.rtw_views_guides_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.byref(g), C.c_void_p(stream_ptr),
-                                                     None if stats is None else C.byref(stats)), "rtw_views_guides_device")
+                                                     _ref(stats)), "rtw_views_guides_device")
 
     def denoise_views(self, frames, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=DENOISE_SIGMA_ALBEDO,
                       sigma_normal=DENOISE_SIGMA_NORMAL):
@@ -830,10 +782,8 @@ class Renderer:
         gt = None if gather_time is None else np.ascontiguousarray(gather_time, dtype=np.float32)
         t = np.empty(n, dtype=np.float32)
         prim = np.empty(n, dtype=np.int32)
-        self._check(self.lib.rtw_debug_intersect(self.ctx, rays.ctypes.data,
-                                                 None if rt is None else rt.ctypes.data,
-                                                 None if gt is None else gt.ctypes.data,
-                                                 n, t.ctypes.data, prim.ctypes.data), "rtw_debug_intersect")
+        self._check(self.lib.rtw_debug_intersect(self.ctx, rays.ctypes.data, _ptr(rt), _ptr(gt), n, t.ctypes.data, prim.ctypes.data),
+                    "rtw_debug_intersect")
         return t, prim
 
     def debug_math(self, op):

@@ -1,8 +1,5 @@
 """rtw_cast_device on torch tensors: rays in, hits out, everything stays on the device (include/rtw.h rtw_cast_device)."""
-from . import abi
-
-_TORCH_DTYPES = {"t": "float32", "prim": "int32", "material": "int32", "normal": "float32", "uv": "float32"}
-
+from . import _torch_call as T, abi
 
 def cast_torch(renderer, rays, ray_time=None, gather_time=None, mode="closest", want=("t", "prim", "material", "normal", "uv"), stats=None):
     """Closest-hit (mode "closest") or occlusion (mode "any") queries of an abi.Renderer on an (n, 8) float32 CUDA tensor of rays
@@ -17,8 +14,7 @@ def cast_torch(renderer, rays, ray_time=None, gather_time=None, mode="closest", 
     if rays.dim() != 2 or rays.shape[1] != 8:
         raise ValueError(f"cast_torch: rays of shape {tuple(rays.shape)}, expected (n, 8)")
     n = rays.shape[0]
-    if not rays.is_cuda or rays.device.index != renderer.devices[0]:
-        raise ValueError(f"cast_torch: rays on {rays.device}, the renderer answers on cuda:{renderer.devices[0]}")
+    T.check_device("cast_torch", "rays", rays, renderer)
     for name, a in (("rays", rays), ("ray_time", ray_time), ("gather_time", gather_time)):
         if a is None:
             continue
@@ -26,13 +22,8 @@ def cast_torch(renderer, rays, ray_time=None, gather_time=None, mode="closest", 
             raise ValueError(f"cast_torch: {name} must be a contiguous float32 CUDA tensor on the rays' device")
         if name != "rays" and tuple(a.shape) != (n,):
             raise ValueError(f"cast_torch: {name} of shape {tuple(a.shape)} for {n} rays")
-    with torch.cuda.device(rays.device):
-        out = {k: torch.empty((n,) + abi.CAST_OUTPUTS[k][1], dtype=getattr(torch, _TORCH_DTYPES[k]), device=rays.device) for k in names}
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.cast_device(n, rays.data_ptr(), {k: v.data_ptr() for k, v in out.items()},
-                                 0 if ray_time is None else ray_time.data_ptr(), 0 if gather_time is None else gather_time.data_ptr(),
-                                 mode=mode, stream_ptr=stream.cuda_stream, stats=stats)
-    return out
+    return T.run(rays, n, lambda: {k: T.empty(rays, (n,) + abi.CAST_OUTPUTS[k][1], abi.CAST_OUTPUTS[k][0].__name__) for k in names},
+                 lambda out, stream: renderer.cast_device(n, rays.data_ptr(), {k: v.data_ptr() for k, v in out.items()},
+                                                          0 if ray_time is None else ray_time.data_ptr(),
+                                                          0 if gather_time is None else gather_time.data_ptr(),
+                                                          mode=mode, stream_ptr=stream, stats=stats))

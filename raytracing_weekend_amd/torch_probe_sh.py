@@ -1,6 +1,6 @@
 """rtw_probe_sh_device on torch tensors: points in, spherical-harmonic coefficients out, everything stays on the device
 (include/rtw.h rtw_probe_sh_device)."""
-from . import abi
+from . import _torch_call as T, abi
 
 
 def probe_sh_torch(renderer, points, spp, max_depth, seed=0x6314759, rng_kind=abi.RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
@@ -11,23 +11,9 @@ def probe_sh_torch(renderer, points, spp, max_depth, seed=0x6314759, rng_kind=ab
     contiguous and live on the renderer's device. No host copy is made. torch's default stream has the null handle, which
     rtw_probe_sh_device reads as "the context's own stream" - a stream that does not wait for the default stream's pending work - so
     under the default stream that work is waited for here, before the call."""
-    import torch
-
-    if points.dim() != 2 or points.shape[1] != 8:
-        raise ValueError(f"probe_sh_torch: points of shape {tuple(points.shape)}, expected (n, 8)")
-    n = points.shape[0]
-    if not points.is_cuda or points.device.index != renderer.devices[0]:
-        raise ValueError(f"probe_sh_torch: points on {points.device}, the renderer answers on cuda:{renderer.devices[0]}")
-    if points.dtype != torch.float32 or not points.is_contiguous():
-        raise ValueError("probe_sh_torch: points must be a contiguous float32 CUDA tensor")
+    n = T.check_tensor("probe_sh_torch", "points", points, (8,), renderer)
     abi.make_radiance_params(spp, max_depth)  # (spp is checked even when there is nothing to trace)
-    with torch.cuda.device(points.device):
-        out = torch.empty((n, 9, 4), dtype=torch.float32, device=points.device)
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.probe_sh_device(n, points.data_ptr(), out.data_ptr(), spp, max_depth, seed=seed, rng_kind=rng_kind,
-                                     sample_offset=sample_offset, estimator=estimator, key_offset=key_offset,
-                                     stream_ptr=stream.cuda_stream, stats=stats)
-    return out
+    return T.run(points, n, lambda: T.empty(points, (n, 9, 4)),
+                 lambda out, stream: renderer.probe_sh_device(n, points.data_ptr(), out.data_ptr(), spp, max_depth, seed=seed, rng_kind=rng_kind,
+                                                              sample_offset=sample_offset, estimator=estimator, key_offset=key_offset,
+                                                              stream_ptr=stream, stats=stats))

@@ -1,5 +1,5 @@
 """rtw_radiance_device on torch tensors: rays in, mean radiance out, everything stays on the device (include/rtw.h rtw_radiance_device)."""
-from . import abi
+from . import _torch_call as T, abi
 
 
 def radiance_torch(renderer, rays, spp, max_depth, seed=0x6314759, rng_kind=abi.RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
@@ -9,23 +9,9 @@ def radiance_torch(renderer, rays, spp, max_depth, seed=0x6314759, rng_kind=abi.
     stream; the call returns when it is written. The tensor must be contiguous and live on the renderer's device. No host copy is
     made. torch's default stream has the null handle, which rtw_radiance_device reads as "the context's own stream" - a stream that
     does not wait for the default stream's pending work - so under the default stream that work is waited for here, before the call."""
-    import torch
-
-    if rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError(f"radiance_torch: rays of shape {tuple(rays.shape)}, expected (n, 8)")
-    n = rays.shape[0]
-    if not rays.is_cuda or rays.device.index != renderer.devices[0]:
-        raise ValueError(f"radiance_torch: rays on {rays.device}, the renderer answers on cuda:{renderer.devices[0]}")
-    if rays.dtype != torch.float32 or not rays.is_contiguous():
-        raise ValueError("radiance_torch: rays must be a contiguous float32 CUDA tensor")
+    n = T.check_tensor("radiance_torch", "rays", rays, (8,), renderer)
     abi.make_radiance_params(spp, max_depth)  # (spp is checked even when there is nothing to trace)
-    with torch.cuda.device(rays.device):
-        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.radiance_device(n, rays.data_ptr(), out.data_ptr(), spp, max_depth, seed=seed, rng_kind=rng_kind,
-                                     sample_offset=sample_offset, estimator=estimator, key_offset=key_offset,
-                                     stream_ptr=stream.cuda_stream, stats=stats)
-    return out
+    return T.run(rays, n, lambda: T.empty(rays, (n, 4)),
+                 lambda out, stream: renderer.radiance_device(n, rays.data_ptr(), out.data_ptr(), spp, max_depth, seed=seed, rng_kind=rng_kind,
+                                                              sample_offset=sample_offset, estimator=estimator, key_offset=key_offset,
+                                                              stream_ptr=stream, stats=stats))

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi
+from . import _torch_call as T, abi
 
 
 def views_tensor(views, device):
@@ -24,41 +24,18 @@ def views_torch(renderer, views, width, height, spp, max_depth, rng_kind=abi.RTW
     orthographic is a perspective camera. torch's default stream has the null handle, which rtw_views_device reads as "the
     context's own stream" - a stream that does not wait for the default stream's pending work - so under the default stream that
     work is waited for here, before the call."""
-    import torch
+    lead = _check_views("views_torch", renderer, views, width, height, spp, max_depth)
+    return T.run(views, lead[0], lambda: T.empty(views, lead + (4,)),
+                 lambda out, stream: renderer.views_device(lead[0], views.data_ptr(), out.data_ptr(), width, height, spp, max_depth, rng_kind=rng_kind,
+                                                           sample_offset=sample_offset, estimator=estimator, stream_ptr=stream, stats=stats))
 
-    if views.dim() != 2 or views.shape[1] != C.sizeof(abi.View) // 4:
-        raise ValueError(f"views_torch: views of shape {tuple(views.shape)}, expected (n, {C.sizeof(abi.View) // 4})")
-    n = views.shape[0]
-    if not views.is_cuda or views.device.index != renderer.devices[0]:
-        raise ValueError(f"views_torch: views on {views.device}, the renderer answers on cuda:{renderer.devices[0]}")
-    if views.dtype != torch.float32 or not views.is_contiguous():
-        raise ValueError("views_torch: views must be a contiguous float32 CUDA tensor")
+
+def _check_views(what, renderer, views, width, height, spp, max_depth=0):
+    """The checks of a tensor of view records and of the sizes; the (n, height, width) its outputs lead with."""
+    n = T.check_tensor(what, "views", views, (C.sizeof(abi.View) // 4,), renderer)
     abi.make_view_params(width, height, spp, max_depth)  # (the sizes are checked even when there is nothing to render)
-    if n * int(width) * int(height) > 0x7fffffff:
-        raise ValueError("views_torch: more than 2^31 - 1 pixels in one call")
-    with torch.cuda.device(views.device):
-        out = torch.empty((n, int(height), int(width), 4), dtype=torch.float32, device=views.device)
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.views_device(n, views.data_ptr(), out.data_ptr(), width, height, spp, max_depth, rng_kind=rng_kind,
-                                  sample_offset=sample_offset, estimator=estimator, stream_ptr=stream.cuda_stream, stats=stats)
-    return out
-
-
-def _check_views(what, renderer, views, width, height, spp):
-    import torch
-
-    if views.dim() != 2 or views.shape[1] != C.sizeof(abi.View) // 4:
-        raise ValueError(f"{what}: views of shape {tuple(views.shape)}, expected (n, {C.sizeof(abi.View) // 4})")
-    if not views.is_cuda or views.device.index != renderer.devices[0]:
-        raise ValueError(f"{what}: views on {views.device}, the renderer answers on cuda:{renderer.devices[0]}")
-    if views.dtype != torch.float32 or not views.is_contiguous():
-        raise ValueError(f"{what}: views must be a contiguous float32 CUDA tensor")
-    abi.make_view_params(width, height, spp, 0)  # (the sizes are checked even when there is nothing to render)
-    if views.shape[0] * int(width) * int(height) > 0x7fffffff:
-        raise ValueError(f"{what}: more than 2^31 - 1 pixels in one call")
+    abi._check_pixels(what, n, width, height)
+    return n, int(height), int(width)
 
 
 def views_guides_torch(renderer, views, width, height, spp=16, which=abi.GUIDES, rng_kind=abi.RTW_RNG_PHILOX, sample_offset=0, stats=None):
@@ -67,25 +44,12 @@ def views_guides_torch(renderer, views, width, height, spp=16, which=abi.GUIDES,
     (n, height, width) int32 - on the records' device, allocated here, written on torch's current stream; the call returns when
     they are written. Under torch's default stream (the null handle, which the library reads as "the context's own stream") the
     stream's pending work is waited for here, before the call."""
-    import torch
-
-    which = tuple(which)
-    bad = [k for k in which if k not in abi.GUIDES]
-    if bad or not which:
-        raise ValueError(f"views_guides_torch: unknown or no guide names {bad or which}")
-    _check_views("views_guides_torch", renderer, views, width, height, spp)
-    n, h, w = views.shape[0], int(height), int(width)
-    shapes = {"albedo": ((n, h, w, 4), torch.float32), "normal": ((n, h, w, 4), torch.float32), "depth": ((n, h, w), torch.float32),
-              "prim": ((n, h, w), torch.int32)}
-    with torch.cuda.device(views.device):
-        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=views.device) for k in which}
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.views_guides_device(n, views.data_ptr(), {k: v.data_ptr() for k, v in out.items()}, width, height, spp, rng_kind=rng_kind,
-                                         sample_offset=sample_offset, stream_ptr=stream.cuda_stream, stats=stats)
-    return out
+    which = abi._guide_names("views_guides_torch", which)
+    lead = _check_views("views_guides_torch", renderer, views, width, height, spp)
+    return T.run(views, lead[0], lambda: {k: T.empty(views, lead + abi.GUIDE_LAYOUT[k][0], abi.GUIDE_LAYOUT[k][1]) for k in which},
+                 lambda out, stream: renderer.views_guides_device(lead[0], views.data_ptr(), {k: v.data_ptr() for k, v in out.items()}, width, height,
+                                                                  spp, rng_kind=rng_kind, sample_offset=sample_offset, stream_ptr=stream,
+                                                                  stats=stats))
 
 
 def views_adaptive_torch(renderer, views, width, height, cap, max_depth, threshold, min_spp=64, step_spp=0, dilate=1,
@@ -94,22 +58,12 @@ def views_adaptive_torch(renderer, views, width, height, cap, max_depth, thresho
     (n, height, width, 4) float32 frames, the (n, height, width) int32 sample counts and the (n, height, width) float32 errors, on
     the records' device, allocated here, written on torch's current stream; the call returns when they are written. Every pixel
     takes samples until its error estimate is below `threshold`, at most `cap`. The default stream is waited for as in views_torch."""
-    import torch
-
-    _check_views("views_adaptive_torch", renderer, views, width, height, cap)
-    n, h, w = views.shape[0], int(height), int(width)
-    with torch.cuda.device(views.device):
-        out = torch.empty((n, h, w, 4), dtype=torch.float32, device=views.device)
-        spp = torch.empty((n, h, w), dtype=torch.int32, device=views.device)
-        err = torch.empty((n, h, w), dtype=torch.float32, device=views.device)
-        stream = torch.cuda.current_stream()
-        if n and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n:
-            renderer.views_adaptive_device(n, views.data_ptr(), out.data_ptr(), spp.data_ptr(), err.data_ptr(), width, height, cap, max_depth,
-                                           threshold, min_spp=min_spp, step_spp=step_spp, dilate=dilate, rng_kind=rng_kind,
-                                           sample_offset=sample_offset, estimator=estimator, stream_ptr=stream.cuda_stream, stats=stats)
-    return out, spp, err
+    lead = _check_views("views_adaptive_torch", renderer, views, width, height, cap)
+    return T.run(views, lead[0], lambda: T.empty_adaptive(views, lead),
+                 lambda out, stream: renderer.views_adaptive_device(lead[0], views.data_ptr(), *(t.data_ptr() for t in out), width, height, cap,
+                                                                    max_depth, threshold, min_spp=min_spp, step_spp=step_spp, dilate=dilate,
+                                                                    rng_kind=rng_kind, sample_offset=sample_offset, estimator=estimator,
+                                                                    stream_ptr=stream, stats=stats))
 
 
 def denoise_views_torch(renderer, frames, albedo, normal, iterations=5, sigma=0.5, sigma_albedo=abi.DENOISE_SIGMA_ALBEDO,
@@ -117,24 +71,13 @@ def denoise_views_torch(renderer, frames, albedo, normal, iterations=5, sigma=0.
     """rtw_denoise_views_device on (n, height, width, 4) float32 CUDA tensors (frames, and the albedo and normal of
     views_guides_torch): the filtered frames, allocated here, written on torch's current stream; the call returns when they are
     written. Frame v is denoise_guided of frame v alone. The default stream is waited for as in views_torch."""
-    import torch
-
     if frames.dim() != 4 or frames.shape[3] != 4:
         raise ValueError(f"denoise_views_torch: frames of shape {tuple(frames.shape)}, expected (n, height, width, 4)")
     for name, t in (("frames", frames), ("albedo", albedo), ("normal", normal)):
         if tuple(t.shape) != tuple(frames.shape):
             raise ValueError(f"denoise_views_torch: {name} of shape {tuple(t.shape)} for frames of shape {tuple(frames.shape)}")
-        if not t.is_cuda or t.device.index != renderer.devices[0]:
-            raise ValueError(f"denoise_views_torch: {name} on {t.device}, the renderer answers on cuda:{renderer.devices[0]}")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"denoise_views_torch: {name} must be a contiguous float32 CUDA tensor")
+        T.check_tensor("denoise_views_torch", name, t, None, renderer)
     n, h, w = (int(v) for v in frames.shape[:3])
-    with torch.cuda.device(frames.device):
-        out = torch.empty_like(frames)
-        stream = torch.cuda.current_stream()
-        if n and h and w and stream.cuda_stream == 0:
-            stream.synchronize()
-        if n and h and w:
-            renderer.denoise_views_device(n, frames.data_ptr(), albedo.data_ptr(), normal.data_ptr(), out.data_ptr(), w, h, iterations, sigma,
-                                          sigma_albedo, sigma_normal, stream_ptr=stream.cuda_stream)
-    return out
+    return T.run(frames, n and h and w, lambda: T.empty(frames, frames.shape),
+                 lambda out, stream: renderer.denoise_views_device(n, frames.data_ptr(), albedo.data_ptr(), normal.data_ptr(), out.data_ptr(), w, h,
+                                                                   iterations, sigma, sigma_albedo, sigma_normal, stream_ptr=stream))

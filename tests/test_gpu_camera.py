@@ -11,33 +11,17 @@ import pytest
 
 import camera_ref as L
 import view_ref as V
+import gpu_common
+from gpu_common import UPLOADS_LDS as UPLOADS, gpu, same_bits  # noqa: F401
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}, "no_lds": {"RTW_LDS_KB": "0"}}  # both knobs are read at upload
 WALL_CASES = [n for n in L.CASES if n.startswith("wall")]
 
 
 def upload(gpu, monkeypatch, blob, how="as_uploaded", path=None):
-    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_PATH"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    if path is not None:
-        monkeypatch.setenv("RTW_PATH", path)
-    gpu.upload_scene(blob)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
+    gpu_common.upload(gpu, monkeypatch, blob, how, knobs=gpu_common.UPLOAD_KNOBS + ("RTW_PATH",), env=None if path is None else {"RTW_PATH": path})
 
 
 def all_runs(draws=(0, 1)):

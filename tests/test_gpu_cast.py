@@ -10,41 +10,19 @@ import torch  # (before the HIP library is loaded, as in a run of the whole suit
 
 import cast_ref as R
 import geometry_ref as G
+import gpu_common
 import oracle
+from gpu_common import UPLOADS_LDS as UPLOADS, check_stream_order, gpu, left_alone, same_dict as same  # noqa: F401
+from gpu_common import sentinel_stats, to_numpy, words as bits
 from raytracing_weekend_amd import abi
 from raytracing_weekend_amd.torch_cast import cast_torch
 
 pytestmark = pytest.mark.gpu
 
 ALL = ("t", "prim", "material", "normal", "uv")
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}, "no_lds": {"RTW_LDS_KB": "0"}}  # both knobs are read at upload
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_CAST_CHUNK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    """Two result dicts (or arrays) carry the same bits."""
-    if isinstance(a, dict):
-        return a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(bits(a), bits(b))
+upload = functools.partial(gpu_common.upload, knobs=("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_CAST_CHUNK"))
 
 
 @functools.lru_cache(maxsize=None)
@@ -430,10 +408,6 @@ def test_no_rays_is_ok_and_writes_nothing(gpu, monkeypatch):
 
 
 # ---------------------------------------------------------------- 6. the device path through torch
-def to_numpy(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
 def test_cast_torch_equals_cast_and_is_ordered_on_the_current_stream(gpu, monkeypatch):
     blob, rays, rt, gt, _, _, _ = case("random16_motion")
     upload(gpu, monkeypatch, blob)
@@ -447,32 +421,7 @@ def test_cast_torch_equals_cast_and_is_ordered_on_the_current_stream(gpu, monkey
     # a subset: the others are not allocated, the requested ones unchanged
     sub = cast_torch(gpu, d_rays, d_rt, d_gt, want=("prim", "uv"))
     assert list(sub) == ["prim", "uv"] and same(to_numpy(sub), {k: want["closest"][k] for k in ("prim", "uv")})
-    # a side stream: the rays are written on it immediately before the call, behind work that keeps the stream busy; results that
-    # are right can only have been computed after that write
-    side = torch.cuda.Stream(device="cuda:0")
-    stale = torch.zeros_like(d_rays)
-    busy = torch.empty(1 << 26, device="cuda:0")
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_rays, non_blocking=True)
-        got = cast_torch(gpu, stale, d_rt, d_gt)
-    assert same(to_numpy(got), want["closest"])
-    torch.cuda.synchronize()
-    # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-    stale.zero_()
-    torch.cuda.synchronize()
-    for _ in range(8):
-        busy.normal_()
-    stale.copy_(d_rays, non_blocking=True)
-    assert same(to_numpy(cast_torch(gpu, stale, d_rt, d_gt)), want["closest"])
-    with pytest.raises(ValueError):
-        cast_torch(gpu, torch.from_numpy(rays))                      # a host tensor
-    with pytest.raises(ValueError):
-        cast_torch(gpu, d_rays.double())
-    with pytest.raises(ValueError):
-        cast_torch(gpu, d_rays[:, :7])
+    check_stream_order(lambda t: cast_torch(gpu, t, d_rt, d_gt), d_rays, lambda got: same(to_numpy(got), want["closest"]))
 
 
 # ---------------------------------------------------------------- 7. one batch whose byte offsets pass 2^32 and 2^34
@@ -547,9 +496,9 @@ def test_every_refusal_leaves_the_context_usable(gpu, monkeypatch):
         (D_, 1000, 0, abi.Hits(uv=dp["uv"] + 4)),
     ]
     for r_, n, mode, h in dev_refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_cast_device(gpu.ctx, r_, None, None, n, mode, None if h is None else C.byref(h), None, C.byref(st)) == -1, (n, mode)
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert left_alone(st)  # a refused call leaves *stats alone
         still_fine()
     assert lib.rtw_cast_device(gpu.ctx, D_, None, None, 1000, 0, C.byref(abi.Hits(uv=dp["uv"] + 8, t=dp["t"] + 4)), None, None) == 0  # aligned enough
     assert same(out, sentinels(1000))  # no refused call wrote anything

@@ -10,31 +10,14 @@ import pytest
 import geometry_ref as G
 import guides_ref
 import oracle
+import gpu_common
+from gpu_common import UPLOADS_LDS as UPLOADS, gpu, same_bits  # noqa: F401
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}, "no_lds": {"RTW_LDS_KB": "0"}}  # both knobs are read at upload
-
-
-def upload(gpu, monkeypatch, blob, how):
-    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+upload = functools.partial(gpu_common.upload, knobs=gpu_common.UPLOAD_KNOBS)
 
 
 # ---------------------------------------------------------------- (a) closest hits against the float64 reference

@@ -5,54 +5,29 @@ offsets, independence of the batch, chunks and slab ranges, keys that wrap, anal
 sessions, rtw_render afterwards, and the lightmap baker."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch  # (before the HIP library is loaded, as in a run of the whole suite)
 
 import geometry_ref as G
+import gpu_common
 import probe_ref as P
 import radiance_ref as R
+from gpu_common import (BOTH, GOLDEN_PAIR, KNOBS, UPLOADS, check_golden_render, check_stream_order,  # noqa: F401
+                        golden, gpu, left_alone, same, sentinel_stats, upload)
 from raytracing_weekend_amd import abi, bake
 from raytracing_weekend_amd.torch_probe import probe_torch
 
 pytestmark = pytest.mark.gpu
+first_difference = functools.partial(gpu_common.first_difference, what="probes")
 
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
 SCENES = ("scene0", "scene1", "scene3", "random_volumes_motion")
 # occlusion distances of the scenes' sizes: a good part of the probes is then neither open nor closed
 TMAX = {"scene0": 150.0, "scene1": 3.0, "scene3": 150.0, "random_volumes_motion": 70.0}
 N, SPP, DEPTH, KEY = R.N, R.SPP, R.DEPTH, R.KEY  # 96 probes (one and a half waves), 48 spp (three blocks), depth 8, key offset 5
 PI = np.float32(np.pi)
 assert PI == np.float32(3.14159265)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def first_difference(got, want):
-    bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(1))[0]
-    return f"{len(bad)} probes differ, first {bad[0]}: {got[bad[0]]} != {want[bad[0]]}" if len(bad) else ""
 
 
 _probes = {}
@@ -326,8 +301,6 @@ def test_probe_torch_equals_probe_and_is_ordered_on_the_current_stream(gpu, monk
     probes = probes_of(gpu, name).copy()
     probes[:, 7] = TMAX[name]
     d_probes = torch.from_numpy(probes).cuda()
-    side = torch.cuda.Stream(device="cuda:0")
-    busy = torch.empty(1 << 26, device="cuda:0")
     for mode in ("irradiance", "occlusion"):
         kw = dict(key_offset=KEY, mode=mode)
         s0, st = abi.Stats(), abi.Stats()
@@ -335,27 +308,8 @@ def test_probe_torch_equals_probe_and_is_ordered_on_the_current_stream(gpu, monk
         got = probe_torch(gpu, d_probes, SPP, DEPTH, stats=st, **kw)
         assert got.is_cuda and tuple(got.shape) == (N, 4) and same(got.cpu().numpy(), want) and want[:, :3].sum() > 0
         assert (st.segments, st.shadow_rays, st.samples) == (s0.segments, s0.shadow_rays, N * SPP) and st.seconds > 0.0
-        # a side stream: the probes are written on it immediately before the call, behind work that keeps the stream busy
-        stale = torch.zeros_like(d_probes)
-        torch.cuda.synchronize()
-        with torch.cuda.stream(side):
-            for _ in range(8):
-                busy.normal_()
-            stale.copy_(d_probes, non_blocking=True)
-            got = probe_torch(gpu, stale, SPP, DEPTH, **kw)
-        assert same(got.cpu().numpy(), want)
-        torch.cuda.synchronize()
-        # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-        stale.zero_()
-        torch.cuda.synchronize()
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_probes, non_blocking=True)
-        assert same(probe_torch(gpu, stale, SPP, DEPTH, **kw).cpu().numpy(), want)
+        check_stream_order(lambda t: probe_torch(gpu, t, SPP, DEPTH, **kw), d_probes, lambda got: same(got.cpu().numpy(), want))
         assert tuple(probe_torch(gpu, torch.zeros((0, 8), device="cuda:0"), 4, 4, mode=mode).shape) == (0, 4)
-    for bad in (torch.from_numpy(probes), d_probes.double(), d_probes[:, :7], d_probes[:, ::1].t().contiguous().t()):
-        with pytest.raises(ValueError):
-            probe_torch(gpu, bad, SPP, DEPTH)
     for spp, mode in ((0, "irradiance"), (4, "ao")):
         with pytest.raises(ValueError):
             probe_torch(gpu, d_probes, spp, DEPTH, mode=mode)
@@ -393,16 +347,16 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
                   pp(mode=1, spp=0), pp(mode=1, estimator=4), pp(mode=1, max_depth=-1)]
     refusals = [(R_, n, p, O_) for p in bad_params] + [(R_, 1 << 31, pp(), O_), (None, n, pp(), O_), (R_, n, pp(), None), (R_, n, pp(mode=1), None)]
     for r_, m, p, o_ in refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_probe(gpu.ctx, r_, m, p, o_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     still_fine()
     dev_refusals = [(D_, n, p, DO_) for p in bad_params] + [(D_, 1 << 31, pp(), DO_), (None, n, pp(), DO_), (D_, n, pp(), None),
                                                             (D_ + 4, n, pp(), DO_), (D_ + 8, n, pp(mode=1), DO_), (D_, n, pp(), DO_ + 4), (D_, n, pp(mode=1), DO_ + 8)]
     for r_, m, p, o_ in dev_refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_probe_device(gpu.ctx, r_, m, p, o_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
     still_fine()  # after a misaligned pointer as after any other refusal: the next call works
     torch.cuda.synchronize()
     assert (out == -7).all() and bool((d_out == -7).all().item())  # no refused call wrote anything
@@ -468,11 +422,8 @@ def test_an_open_accumulation_session_goes_on_bit_exactly(gpu, monkeypatch):
 def test_render_radiance_and_cast_are_what_they_were_before_probe_calls(gpu, monkeypatch):
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
-    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    for name in ("cornell_200x200_16spp_d4_philox", "fog_96x96_8spp_d12_lcg"):
-        z = np.load(os.path.join(gold, name + ".npz"))
-        scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-        blob = z["blob"].tobytes()
+    for g in map(golden, GOLDEN_PAIR):
+        blob, rng, seed = g.blob, g.rng, g.seed
         gpu.upload_scene(blob)
         rays, _, _ = G.scene_rays(blob, 5, 300)
         rays[:, 6], rays[:, 7] = 1e-6, 1e27
@@ -483,9 +434,7 @@ def test_render_radiance_and_cast_are_what_they_were_before_probe_calls(gpu, mon
         b = gpu.probe(probes, 160, 3, rng_kind=rng, estimator=1)
         c = gpu.probe(probes, 160, 3, rng_kind=rng, mode="occlusion")
         assert np.isfinite(a).all() and np.isfinite(b).all() and a[:, :3].sum() > 0 and 0 < c[:, 0].mean() < 1
-        img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-        assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-        assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+        check_golden_render(gpu, g)
         assert same(gpu.radiance(rays, 24, 6, rng_kind=rng), rad) and same(gpu.probe(probes, 24, 6, rng_kind=rng), a)
         again = gpu.cast(rays)
         assert all(np.array_equal(hits[k].view(np.uint32), again[k].view(np.uint32)) for k in hits)

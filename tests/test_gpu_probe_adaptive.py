@@ -7,7 +7,6 @@ of the batch, chunks, slab ranges and knobs, the torch path, every refusal, grou
 the baker."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -17,42 +16,16 @@ import geometry_ref as G
 import probe_adaptive_ref as PA
 import probe_ref as P
 import radiance_ref as R
+from gpu_common import (BOTH, GOLDEN_PAIR, KNOBS, UPLOADS, check_golden_render, check_stream_order,  # noqa: F401
+                        golden, gpu, left_alone, same3, same_words as same, sentinel_stats, upload)
 from raytracing_weekend_amd import abi, bake
 from raytracing_weekend_amd.torch_probe import probe_adaptive_torch
 
 pytestmark = pytest.mark.gpu
 
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
 MODES = ("irradiance", "occlusion")
 TMAX = {"scene0": 150.0, "scene1": 3.0, "scene3": 150.0, "random_volumes_motion": 70.0}  # test_gpu_probe.py's occlusion distances
 N, CAP, MIN_SPP, DEPTH, KEY, THRESHOLD = 96, 256, 32, 8, 5, 0.02  # the rehearsed inputs (test_probe_adaptive_cpu.py)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def same3(got, want):
-    """(out, spp, err) triples: the counts equal, the floats equal in bits."""
-    return same(got[0], want[0]) and got[1].dtype == np.int32 and np.array_equal(got[1], want[1]) and same(got[2], want[2])
 
 
 def describe(got, want):
@@ -269,8 +242,6 @@ def test_chunks_slab_ranges_lds_and_wrapping_keys_change_no_bit(gpu, monkeypatch
 # ---------------------------------------------------------------- 6. the device path
 def test_probe_adaptive_torch_equals_the_host_path_and_is_ordered_on_the_current_stream(gpu, monkeypatch):
     upload(gpu, monkeypatch, R.scene("scene0"))
-    side = torch.cuda.Stream(device="cuda:0")
-    busy = torch.empty(1 << 26, device="cuda:0")
     for mode in MODES:
         probes = probes_of(gpu, "scene0", mode)
         d_probes = torch.from_numpy(probes).cuda()
@@ -281,28 +252,10 @@ def test_probe_adaptive_torch_equals_the_host_path_and_is_ordered_on_the_current
         assert all(t.is_cuda for t in got) and got[1].dtype == torch.int32 and tuple(got[0].shape) == (N, 4) and tuple(got[1].shape) == (N,)
         assert same3(tuple(t.cpu().numpy() for t in got), want)
         assert (st.segments, st.shadow_rays, st.samples) == (s0.segments, s0.shadow_rays, s0.samples) and st.seconds > 0.0
-        # a side stream: the probes are written on it immediately before the call, behind work that keeps the stream busy
-        stale = torch.zeros_like(d_probes)
-        torch.cuda.synchronize()
-        with torch.cuda.stream(side):
-            for _ in range(8):
-                busy.normal_()
-            stale.copy_(d_probes, non_blocking=True)
-            got = probe_adaptive_torch(gpu, stale, CAP, DEPTH, THRESHOLD, **kw)
-        assert same3(tuple(t.cpu().numpy() for t in got), want)
-        torch.cuda.synchronize()
-        # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-        stale.zero_()
-        torch.cuda.synchronize()
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_probes, non_blocking=True)
-        assert same3(tuple(t.cpu().numpy() for t in probe_adaptive_torch(gpu, stale, CAP, DEPTH, THRESHOLD, **kw)), want)
+        check_stream_order(lambda t: probe_adaptive_torch(gpu, t, CAP, DEPTH, THRESHOLD, **kw), d_probes,
+                           lambda got: same3(tuple(t.cpu().numpy() for t in got), want))
         empty = probe_adaptive_torch(gpu, torch.zeros((0, 8), device="cuda:0"), 64, 4, THRESHOLD, mode=mode)
         assert [tuple(t.shape) for t in empty] == [(0, 4), (0,), (0,)]
-    for bad in (torch.from_numpy(probes), d_probes.double(), d_probes[:, :7]):
-        with pytest.raises(ValueError):
-            probe_adaptive_torch(gpu, bad, CAP, DEPTH, THRESHOLD)
     for cap, mode in ((0, "irradiance"), (64, "ao")):
         with pytest.raises(ValueError):
             probe_adaptive_torch(gpu, d_probes, cap, DEPTH, THRESHOLD, mode=mode)
@@ -351,9 +304,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
     host = [(R_, n, p, a, O_) for p, a in bad] + [(R_, 1 << 31, pp(), ad(), O_), (None, n, pp(), ad(), O_), (R_, n, pp(), ad(), None),
                                                   (R_, n, pp(mode=1), ad(), None)]
     for r_, m, p, a, o_ in host:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_probe_adaptive(gpu.ctx, r_, m, p, a, o_, S_, E_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     still_fine()
     dev = [(D_, n, p, a, DO_, DS_, DE_) for p, a in bad] + [
         (D_, 1 << 31, pp(), ad(), DO_, DS_, DE_), (None, n, pp(), ad(), DO_, DS_, DE_), (D_, n, pp(), ad(), None, DS_, DE_),
@@ -361,9 +314,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
         (D_, n, pp(mode=1), ad(), DO_ + 8, DS_, DE_), (D_, n, pp(), ad(), DO_, DS_ + 2, DE_), (D_, n, pp(), ad(), DO_, DS_, DE_ + 1),
         (D_, n, pp(mode=1), ad(), DO_, DS_ + 1, None)]
     for r_, m, p, a, o_, s_, e_ in dev:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_probe_adaptive_device(gpu.ctx, r_, m, p, a, o_, s_, e_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
     still_fine()  # after a misaligned pointer as after any other refusal: the next call works
     torch.cuda.synchronize()
     assert (out == -7).all() and (spp == -7).all() and (err == -7).all()  # no refused call wrote anything
@@ -432,11 +385,8 @@ def test_probe_radiance_and_render_are_what_they_were_before_adaptive_calls(gpu,
     """The slab is shared: calls beyond 128 spp of the older entry points before and after adaptive calls of both modes."""
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
-    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    for name in ("cornell_200x200_16spp_d4_philox", "fog_96x96_8spp_d12_lcg"):
-        z = np.load(os.path.join(gold, name + ".npz"))
-        scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-        blob = z["blob"].tobytes()
+    for g in map(golden, GOLDEN_PAIR):
+        blob, rng, seed = g.blob, g.rng, g.seed
         gpu.upload_scene(blob)
         rays, _, _ = G.scene_rays(blob, 5, 300)
         rays[:, 6], rays[:, 7] = 1e-6, 1e27
@@ -447,9 +397,7 @@ def test_probe_radiance_and_render_are_what_they_were_before_adaptive_calls(gpu,
         for mode in MODES:
             out, n_i, err = gpu.probe_adaptive(probes, 192, 4, THRESHOLD, min_spp=32, rng_kind=rng, mode=mode)
             assert np.isfinite(out).all() and set(np.unique(n_i)) <= {32, 48, 80, 128, 192} and (err >= 0).all()
-        img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-        assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-        assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+        check_golden_render(gpu, g)
         assert same(gpu.radiance(rays, 160, 4, rng_kind=rng), rad)
         assert same(gpu.probe(probes, 160, 3, rng_kind=rng, estimator=1), a) and same(gpu.probe(probes, 160, 3, rng_kind=rng, mode="occlusion"), b)
 

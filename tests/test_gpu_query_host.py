@@ -14,6 +14,7 @@ import geometry_ref as G
 import probe_ref as P
 import radiance_ref as R
 import view_ref as V
+from gpu_common import same_dict as same  # noqa: F401
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -104,11 +105,6 @@ def run(r, d, env, call):
     with knobs(env):
         out = call(r, d, st)
     return out, st
-
-
-def same(got, want):
-    return list(got) == list(want) and all(got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and got[k].tobytes() == want[k].tobytes()
-                                           for k in want)
 
 
 def counts(st):

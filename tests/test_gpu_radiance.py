@@ -3,7 +3,7 @@ oracle's bits (radiance_ref.py: the ray as the camera of a one-pixel render), th
 of the batch, the chunking and the slab, keys that wrap, the first segment's interval, the torch path, every refusal, groups,
 sessions and rtw_render afterwards."""
 import ctypes as C
-import os
+import functools
 
 import numpy as np
 import pytest
@@ -11,39 +11,14 @@ import torch  # (before the HIP library is loaded, as in a run of the whole suit
 
 import geometry_ref as G
 import radiance_ref as R
+import gpu_common
+from gpu_common import (BOTH, GOLDEN_PAIR, KNOBS, UPLOADS, check_golden_render, check_stream_order, golden, gpu, left_alone, same,  # noqa: F401
+                        sentinel_stats, upload)
 from raytracing_weekend_amd import abi
 from raytracing_weekend_amd.torch_radiance import radiance_torch
 
 pytestmark = pytest.mark.gpu
-
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def first_difference(got, want):
-    bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(1))[0]
-    return f"{len(bad)} rays differ, first {bad[0]}: {got[bad[0]]} != {want[bad[0]]}" if len(bad) else ""
+first_difference = functools.partial(gpu_common.first_difference, what="rays")
 
 
 # ---------------------------------------------------------------- 1. the oracle's bits
@@ -208,29 +183,8 @@ def test_radiance_torch_equals_radiance_and_is_ordered_on_the_current_stream(gpu
     got = radiance_torch(gpu, d_rays, R.SPP, R.DEPTH, stats=st, **kw)
     assert got.is_cuda and tuple(got.shape) == (R.N, 4) and same(got.cpu().numpy(), want)
     assert (st.segments, st.shadow_rays, st.samples) == (seg, shadow, R.N * R.SPP) and st.seconds > 0.0
-    # a side stream: the rays are written on it immediately before the call, behind work that keeps the stream busy
-    side = torch.cuda.Stream(device="cuda:0")
-    stale = torch.zeros_like(d_rays)
-    busy = torch.empty(1 << 26, device="cuda:0")
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_rays, non_blocking=True)
-        got = radiance_torch(gpu, stale, R.SPP, R.DEPTH, **kw)
-    assert same(got.cpu().numpy(), want)
-    torch.cuda.synchronize()
-    # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-    stale.zero_()
-    torch.cuda.synchronize()
-    for _ in range(8):
-        busy.normal_()
-    stale.copy_(d_rays, non_blocking=True)
-    assert same(radiance_torch(gpu, stale, R.SPP, R.DEPTH, **kw).cpu().numpy(), want)
+    check_stream_order(lambda t: radiance_torch(gpu, t, R.SPP, R.DEPTH, **kw), d_rays, lambda got: same(got.cpu().numpy(), want))
     assert tuple(radiance_torch(gpu, torch.zeros((0, 8), device="cuda:0"), 4, 4).shape) == (0, 4)
-    for bad in (torch.from_numpy(rays), d_rays.double(), d_rays[:, :7], d_rays[:, ::1].t().contiguous().t()):
-        with pytest.raises(ValueError):
-            radiance_torch(gpu, bad, R.SPP, R.DEPTH)
     with pytest.raises(ValueError):
         radiance_torch(gpu, d_rays, 0, R.DEPTH)
 
@@ -263,16 +217,16 @@ def test_every_refusal_leaves_the_context_usable(gpu, monkeypatch):
                   rp(sample_offset=-1), rp(sample_offset=2 ** 31 - R.SPP), rp(spp=2 ** 31 - 1, sample_offset=1), rp(reserved=1)]
     refusals = [(R_, n, p, O_) for p in bad_params] + [(R_, 1 << 31, rp(), O_), (None, n, rp(), O_), (R_, n, rp(), None)]
     for r_, m, p, o_ in refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_radiance(gpu.ctx, r_, m, p, o_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     still_fine()
     dev_refusals = [(D_, n, p, DO_) for p in bad_params] + [(D_, 1 << 31, rp(), DO_), (None, n, rp(), DO_), (D_, n, rp(), None),
                                                             (D_ + 4, n, rp(), DO_), (D_ + 8, n, rp(), DO_), (D_, n, rp(), DO_ + 4), (D_, n, rp(), DO_ + 8)]
     for r_, m, p, o_ in dev_refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_radiance_device(gpu.ctx, r_, m, p, o_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
         still_fine()  # after a misaligned pointer as after any other refusal: the next call works
     torch.cuda.synchronize()
     assert (out == -7).all() and bool((d_out == -7).all().item())  # no refused call wrote anything
@@ -328,18 +282,13 @@ def test_an_open_accumulation_session_goes_on_bit_exactly(gpu, monkeypatch):
 def test_rtw_render_after_radiance_calls_still_matches_its_golden_fixture(gpu, monkeypatch):
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
-    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    for name in ("cornell_200x200_16spp_d4_philox", "fog_96x96_8spp_d12_lcg"):
-        z = np.load(os.path.join(gold, name + ".npz"))
-        scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-        blob = z["blob"].tobytes()
+    for g in map(golden, GOLDEN_PAIR):
+        blob, rng, seed = g.blob, g.rng, g.seed
         gpu.upload_scene(blob)
         o, ll = R.pairs(blob, 300)
         rays = R.make_rays(o, ll)
         a = gpu.radiance(rays, 24, 6, rng_kind=rng)
         b = gpu.radiance(rays, 160, 3, rng_kind=rng, estimator=1)
         assert np.isfinite(a).all() and np.isfinite(b).all() and a[:, :3].sum() > 0
-        img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-        assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-        assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+        check_golden_render(gpu, g)
         assert same(gpu.radiance(rays, 24, 6, rng_kind=rng), a)

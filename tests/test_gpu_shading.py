@@ -2,36 +2,22 @@
 nothing with the oracle or the kernels), then against the oracle's bits of the same keys, so that a failure says which side moved.
 Two entries: rtw_radiance on the cases' rays (uploaded as is, with the tree forced, with the tree outside LDS) and rtw_render of
 radiance_ref.ray_blob - every pixel the same ray on its own key - through k_path and through the wavefront kernels."""
+import functools
+
 import numpy as np
 import pytest
 
 import probe_ref
 import radiance_ref as R
 import shading_ref as S
+import gpu_common
+from gpu_common import UPLOADS_LDS as UPLOADS, gpu, same_bits  # noqa: F401
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}, "no_lds": {"RTW_LDS_KB": "0"}}  # both knobs are read at upload
 
-
-def upload(gpu, monkeypatch, blob, how):
-    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
+upload = functools.partial(gpu_common.upload, knobs=gpu_common.UPLOAD_KNOBS)
 
 
 def runs(names, hows, draws):

@@ -3,6 +3,7 @@ frame of the scene with views[v] in its header, which the oracle renders as it s
 units and offsets, the golden fixtures, independence of the call's other views, chunks and slab ranges, the torch path, every
 refusal, groups, sessions, the older entry points afterwards, and the command-line turntable."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -11,44 +12,18 @@ import pytest
 import torch  # (before the HIP library is loaded, as in a run of the whole suite)
 
 import geometry_ref as G
+import gpu_common
 import probe_ref as P
 import radiance_ref as R
 import view_ref as V
+from gpu_common import (BOTH, GOLD, GOLDEN_PAIR, KNOBS, UPLOADS, check_golden_render,  # noqa: F401
+                        check_stream_order, golden, gpu, left_alone, same, sentinel_stats, upload)
 from raytracing_weekend_amd import abi, bake
 from raytracing_weekend_amd.torch_views import views_tensor, views_torch
 
 pytestmark = pytest.mark.gpu
-
 ROOT = abi.REPO_DIR
-GOLD = os.path.join(ROOT, "tests", "golden")
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def first_difference(got, want):
-    bad = np.argwhere((got.view(np.uint32) != want.view(np.uint32)).any(-1))
-    return f"{len(bad)} pixels differ, first (view, y, x) = {tuple(bad[0])}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}" if len(bad) else ""
+first_difference = functools.partial(gpu_common.first_difference, what="pixels (view, y, x)", axes=3)
 
 
 def call(gpu, views, params, stats=None):
@@ -171,34 +146,13 @@ def test_views_torch_equals_views_and_is_ordered_on_the_current_stream(gpu, monk
     upload(gpu, monkeypatch, blob)
     d_views = views_tensor(views, "cuda:0")
     assert tuple(d_views.shape) == (3, 28) and d_views.cpu().numpy().tobytes() == bytes(abi.view_array(views))
-    side = torch.cuda.Stream(device="cuda:0")
-    busy = torch.empty(1 << 26, device="cuda:0")
     st = abi.Stats()
     torch.cuda.synchronize()
     got = views_torch(gpu, d_views, V.W, V.H, V.SPP, V.DEPTH, stats=st)
     assert got.is_cuda and tuple(got.shape) == (3, V.H, V.W, 4) and same(got.cpu().numpy(), want)
     assert (st.segments, st.shadow_rays, st.samples) == (seg, shadow, 3 * V.W * V.H * V.SPP) and st.seconds > 0.0
-    # a side stream: the records are written on it immediately before the call, behind work that keeps the stream busy
-    stale = torch.zeros_like(d_views)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_views, non_blocking=True)
-        got = views_torch(gpu, stale, V.W, V.H, V.SPP, V.DEPTH)
-    assert same(got.cpu().numpy(), want)
-    torch.cuda.synchronize()
-    # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-    stale.zero_()
-    torch.cuda.synchronize()
-    for _ in range(8):
-        busy.normal_()
-    stale.copy_(d_views, non_blocking=True)
-    assert same(views_torch(gpu, stale, V.W, V.H, V.SPP, V.DEPTH).cpu().numpy(), want)
+    check_stream_order(lambda t: views_torch(gpu, t, V.W, V.H, V.SPP, V.DEPTH), d_views, lambda got: same(got.cpu().numpy(), want))
     assert tuple(views_torch(gpu, torch.zeros((0, 28), device="cuda:0"), 4, 3, 4, 4).shape) == (0, 3, 4, 4)
-    for bad in (d_views.cpu(), d_views.double(), d_views[:, :27], d_views.t().contiguous().t()):
-        with pytest.raises(ValueError):
-            views_torch(gpu, bad, V.W, V.H, V.SPP, V.DEPTH)
     for kw in (dict(width=0), dict(height=-1), dict(spp=0)):
         args = dict(width=V.W, height=V.H, spp=V.SPP, max_depth=V.DEPTH)
         args.update(kw)
@@ -259,9 +213,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
     too_many = [(2 ** 31 - 1) // 35 + 1, 1 << 31, 1 << 40, 2 ** 64 - 1]  # n_views * width * height beyond 2^31 - 1, the last ones beyond 64 bits
     refusals = [(V_, n, p, O_) for p in bad_params] + [(V_, m, vp(), O_) for m in too_many] + [(None, n, vp(), O_), (V_, n, vp(), None)]
     for v_, m, p, o_ in refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views(gpu.ctx, v_, m, p, o_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     # the host variant reads the records: a camera type outside 0..2 and a non-zero reserved word, in any view
     for field, value in (("camera_type", 3), ("camera_type", -1), ("camera_type", 7), ("reserved0", 1), ("reserved1", 2 ** 31)):
         bad = abi.view_array([abi.View.from_buffer_copy(bytes(v)) for v in views])
@@ -276,9 +230,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
     dev_refusals = [(D_, n, p, DO_) for p in bad_params] + [(D_, m, vp(), DO_) for m in too_many] + [
         (None, n, vp(), DO_), (D_, n, vp(), None), (D_ + 4, n, vp(), DO_), (D_ + 8, n, vp(), DO_), (D_, n, vp(), DO_ + 4), (D_, n, vp(), DO_ + 8)]
     for v_, m, p, o_ in dev_refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views_device(gpu.ctx, v_, m, p, o_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
     still_fine()  # after a misaligned pointer as after any other refusal: the next call works
     torch.cuda.synchronize()
     assert (out == -7).all() and bool((d_out == -7).all().item())  # no refused call wrote anything
@@ -354,10 +308,8 @@ def test_an_open_accumulation_session_goes_on_bit_exactly(gpu, monkeypatch):
 def test_render_probe_sh_radiance_and_cast_are_what_they_were_before_views_calls(gpu, monkeypatch):
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
-    for name in ("cornell_200x200_16spp_d4_philox", "fog_96x96_8spp_d12_lcg"):
-        z = np.load(os.path.join(GOLD, name + ".npz"))
-        scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-        blob = z["blob"].tobytes()
+    for g in map(golden, GOLDEN_PAIR):
+        blob, rng, seed = g.blob, g.rng, g.seed
         gpu.upload_scene(blob)
         rays, _, _ = G.scene_rays(blob, 5, 300)
         rays[:, 6], rays[:, 7] = 1e-6, 1e27
@@ -369,9 +321,7 @@ def test_render_probe_sh_radiance_and_cast_are_what_they_were_before_views_calls
         a = gpu.views(views, 16, 12, 24, 6, rng_kind=rng)
         b = gpu.views(views, 16, 12, 160, 3, rng_kind=rng, estimator=1)  # the slab the other resolves read as well
         assert np.isfinite(a).all() and np.isfinite(b).all() and a[..., :3].sum() > 0 and b[..., :3].sum() > 0
-        img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-        assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-        assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+        check_golden_render(gpu, g)
         assert same(gpu.radiance(rays, 24, 6, rng_kind=rng), rad) and same(gpu.probe_sh(probes, 160, 3, rng_kind=rng), sh)
         assert same(gpu.views(views, 16, 12, 24, 6, rng_kind=rng), a)
         again = gpu.cast(rays)

@@ -18,42 +18,15 @@ import probe_ref as P
 import radiance_ref as R
 import view_adaptive_ref as VA
 import view_ref as V
+from gpu_common import (BOTH, GOLDEN_PAIR, KNOBS, UPLOADS, check_golden_render, check_stream_order,  # noqa: F401
+                        golden, gpu, left_alone, same3, same_words as same, sentinel_stats, upload)
 from raytracing_weekend_amd import abi, bake
 from raytracing_weekend_amd.torch_views import views_adaptive_torch, views_tensor
 
 pytestmark = pytest.mark.gpu
 
 ROOT = abi.REPO_DIR
-GOLD = os.path.join(ROOT, "tests", "golden")
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
 W, H, CAP, MIN_SPP, DEPTH = 24, 16, 256, 32, 8  # the rehearsed inputs
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def same3(got, want):
-    """(frames, spp, err) triples: the counts equal, the floats equal in bits."""
-    return same(got[0], want[0]) and got[1].dtype == np.int32 and np.array_equal(got[1], want[1]) and same(got[2], want[2])
 
 
 def describe(got, want):
@@ -286,8 +259,6 @@ def test_views_adaptive_torch_equals_the_host_path_and_is_ordered_on_the_current
     views = list(V.cameras("scene0"))
     T = median_threshold(gpu, views, W, H, DEPTH)
     d_views = views_tensor(views, "cuda:0")
-    side = torch.cuda.Stream(device="cuda:0")
-    busy = torch.empty(1 << 26, device="cuda:0")
     kw = dict(min_spp=MIN_SPP, dilate=1)
     s0, st = abi.Stats(), abi.Stats()
     want = gpu.views_adaptive(views, W, H, CAP, DEPTH, T, stats=s0, **kw)
@@ -296,28 +267,10 @@ def test_views_adaptive_torch_equals_the_host_path_and_is_ordered_on_the_current
     assert tuple(got[0].shape) == (3, H, W, 4) and tuple(got[1].shape) == (3, H, W) and tuple(got[2].shape) == (3, H, W)
     assert same3(tuple(t.cpu().numpy() for t in got), want)
     assert (st.segments, st.shadow_rays, st.samples) == (s0.segments, s0.shadow_rays, s0.samples) and st.seconds > 0.0
-    # a side stream: the records are written on it immediately before the call, behind work that keeps the stream busy
-    stale = torch.zeros_like(d_views)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_views, non_blocking=True)
-        got = views_adaptive_torch(gpu, stale, W, H, CAP, DEPTH, T, **kw)
-    assert same3(tuple(t.cpu().numpy() for t in got), want)
-    torch.cuda.synchronize()
-    # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-    stale.zero_()
-    torch.cuda.synchronize()
-    for _ in range(8):
-        busy.normal_()
-    stale.copy_(d_views, non_blocking=True)
-    assert same3(tuple(t.cpu().numpy() for t in views_adaptive_torch(gpu, stale, W, H, CAP, DEPTH, T, **kw)), want)
+    check_stream_order(lambda t: views_adaptive_torch(gpu, t, W, H, CAP, DEPTH, T, **kw), d_views,
+                       lambda got: same3(tuple(t.cpu().numpy() for t in got), want))
     empty = views_adaptive_torch(gpu, torch.zeros((0, 28), device="cuda:0"), 8, 4, 64, 4, T)
     assert [tuple(t.shape) for t in empty] == [(0, 4, 8, 4), (0, 4, 8), (0, 4, 8)]
-    for bad in (d_views.cpu(), d_views.double(), d_views[:, :27]):
-        with pytest.raises(ValueError):
-            views_adaptive_torch(gpu, bad, W, H, CAP, DEPTH, T)
     with pytest.raises(ValueError):
         views_adaptive_torch(gpu, d_views, W, H, 0, DEPTH, T)
 
@@ -367,9 +320,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
     host = [(V_, n, p, a, O_) for p, a in bad] + [(V_, 1 << 31, vp(), ad(), O_), (V_, 1 << 26, vp(), ad(), O_), (None, n, vp(), ad(), O_),
                                                   (V_, n, vp(), ad(), None)]
     for v_, m, p, a, o_ in host:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views_adaptive(gpu.ctx, v_, m, p, a, o_, S_, E_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     # the host entry reads the records
     for field, value in (("camera_type", 3), ("camera_type", -1), ("reserved", (C.c_uint32 * 2)(0, 1))):
         rec = abi.view_array([abi.make_view(v.camera, v.camera_type, v.seed) for v in views])
@@ -383,9 +336,9 @@ def test_every_refusal_leaves_the_context_usable_and_writes_nothing(gpu, monkeyp
         (D_, n, vp(), ad(), DO_ + 8, DS_, DE_), (D_, n, vp(), ad(), DO_, DS_ + 2, DE_), (D_, n, vp(), ad(), DO_, DS_, DE_ + 1),
         (D_, n, vp(), ad(), DO_, DS_ + 1, None)]
     for v_, m, p, a, o_, s_, e_ in dev:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views_adaptive_device(gpu.ctx, v_, m, p, a, o_, s_, e_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
     still_fine()  # after a misaligned pointer as after any other refusal: the next call works
     torch.cuda.synchronize()
     assert (out == -7).all() and (spp == -7).all() and (err == -7).all()  # no refused call wrote anything
@@ -450,10 +403,8 @@ def test_views_probe_adaptive_and_render_are_what_they_were_before_adaptive_view
     """The slab, the staging and the per-entry state are shared: the older entry points before and after adaptive view calls."""
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
-    for name in ("cornell_200x200_16spp_d4_philox", "fog_96x96_8spp_d12_lcg"):
-        z = np.load(os.path.join(GOLD, name + ".npz"))
-        scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-        blob = z["blob"].tobytes()
+    for g in map(golden, GOLDEN_PAIR):
+        blob, rng, seed = g.blob, g.rng, g.seed
         gpu.upload_scene(blob)
         views = bake.orbit_views(blob, 2, seed=seed)
         probes = P.scene_probes(gpu.cast, blob, 300, tmax=100.0)
@@ -462,9 +413,7 @@ def test_views_probe_adaptive_and_render_are_what_they_were_before_adaptive_view
         for dilate in (0, 1):
             out, n_p, err = gpu.views_adaptive(views, 20, 12, 192, 4, 0.02, min_spp=32, dilate=dilate, rng_kind=rng)
             assert np.isfinite(out).all() and set(np.unique(n_p)) <= {32, 48, 80, 128, 192} and (err >= 0).all()
-        img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-        assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-        assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+        check_golden_render(gpu, g)
         assert same(gpu.views(views, 20, 12, 160, 4, rng_kind=rng), frames)
         got = gpu.probe_adaptive(probes, 192, 4, 0.02, min_spp=32, rng_kind=rng)
         assert same(got[0], pa[0]) and np.array_equal(got[1], pa[1]) and same(got[2], pa[2])

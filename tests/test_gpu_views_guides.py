@@ -17,32 +17,15 @@ import oracle
 import radiance_ref as R
 import view_guides_ref as VG
 import view_ref as V
+from gpu_common import (BOTH, KNOBS, UPLOADS, check_golden_render, check_stream_order,  # noqa: F401
+                        golden, gpu, left_alone, sentinel_stats, to_numpy, upload)
 from raytracing_weekend_amd import abi, bake
 from raytracing_weekend_amd.torch_views import denoise_views_torch, views_guides_torch, views_tensor
 
 pytestmark = pytest.mark.gpu
 
 ROOT = abi.REPO_DIR
-GOLD = os.path.join(ROOT, "tests", "golden")
-UPLOADS = {"as_uploaded": {}, "forced_tree": {"RTW_BRUTE_MAX": "0"}}  # the knob is read at upload
-KNOBS = ("RTW_BRUTE_MAX", "RTW_LDS_KB", "RTW_RADIANCE_CHUNK", "RTW_RADIANCE_SLAB_BYTES")
-BOTH = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
 same = VG.same
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    r = abi.Renderer(0)
-    yield r
-    r.close()
-
-
-def upload(gpu, monkeypatch, blob, how="as_uploaded"):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in UPLOADS[how].items():
-        monkeypatch.setenv(k, v)
-    gpu.upload_scene(blob)
 
 
 def all_same(got, want):
@@ -131,37 +114,17 @@ def test_views_guides_torch_equals_views_guides_and_is_ordered_on_the_current_st
     upload(gpu, monkeypatch, blob)
     want = VG.referee_guides(gpu, blob, views, VG.W, VG.H, VG.SPP)
     d_views = views_tensor(views, "cuda:0")
-    side = torch.cuda.Stream(device="cuda:0")
-    busy = torch.empty(1 << 26, device="cuda:0")
     st = abi.Stats()
     torch.cuda.synchronize()
     got = views_guides_torch(gpu, d_views, VG.W, VG.H, VG.SPP, stats=st)
     assert all(t.is_cuda for t in got.values()) and got["prim"].dtype == torch.int32 and tuple(got["depth"].shape) == (3, VG.H, VG.W)
     assert all_same({k: t.cpu().numpy() for k, t in got.items()}, want)
     assert st.samples == st.segments == 3 * VG.W * VG.H * VG.SPP and st.seconds > 0.0 and st.shadow_rays == 0
-    # a side stream: the records are written on it immediately before the call, behind work that keeps the stream busy
-    stale = torch.zeros_like(d_views)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            busy.normal_()
-        stale.copy_(d_views, non_blocking=True)
-        got = views_guides_torch(gpu, stale, VG.W, VG.H, VG.SPP)
-    assert all_same({k: t.cpu().numpy() for k, t in got.items()}, want)
-    torch.cuda.synchronize()
-    # the same under torch's default stream, whose null handle the library reads as "the context's own stream"
-    stale.zero_()
-    torch.cuda.synchronize()
-    for _ in range(8):
-        busy.normal_()
-    stale.copy_(d_views, non_blocking=True)
-    got = views_guides_torch(gpu, stale, VG.W, VG.H, VG.SPP, which=("albedo", "prim"))
-    assert all_same({k: t.cpu().numpy() for k, t in got.items()}, {k: want[k] for k in ("albedo", "prim")})
+    check_stream_order(lambda t: views_guides_torch(gpu, t, VG.W, VG.H, VG.SPP), d_views, lambda got: all_same(to_numpy(got), want),
+                       default=(lambda t: views_guides_torch(gpu, t, VG.W, VG.H, VG.SPP, which=("albedo", "prim")),
+                                lambda got: all_same(to_numpy(got), {k: want[k] for k in ("albedo", "prim")})))
     empty = views_guides_torch(gpu, torch.zeros((0, 28), device="cuda:0"), 4, 3, 4)
     assert tuple(empty["albedo"].shape) == (0, 3, 4, 4) and tuple(empty["prim"].shape) == (0, 3, 4)
-    for bad in (d_views.cpu(), d_views.double(), d_views[:, :27], d_views.t().contiguous().t()):
-        with pytest.raises(ValueError):
-            views_guides_torch(gpu, bad, VG.W, VG.H, VG.SPP)
     for kw in (dict(width=0), dict(height=-1), dict(spp=0), dict(which=()), dict(which=("beauty",))):
         args = dict(width=VG.W, height=VG.H, spp=VG.SPP)
         args.update(kw)
@@ -332,9 +295,9 @@ def test_every_refusal_of_views_guides_leaves_the_context_usable_and_writes_noth
     refusals = ([(V_, n, p, guides(H_)) for p in bad_params] + [(V_, m, vp(), guides(H_)) for m in too_many] +
                 [(None, n, vp(), guides(H_)), (V_, n, vp(), None), (V_, n, vp(), no_buffer)])
     for v_, m, p, g_ in refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views_guides(gpu.ctx, v_, m, p, g_, C.byref(st)) == -1
-        assert lib.rtw_last_error(gpu.ctx) and (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)  # a refused call leaves *stats alone
+        assert lib.rtw_last_error(gpu.ctx) and left_alone(st)  # a refused call leaves *stats alone
     for field, value in (("camera_type", 3), ("camera_type", -1), ("camera_type", 7), ("reserved0", 1), ("reserved1", 2 ** 31)):
         bad = abi.view_array([abi.View.from_buffer_copy(bytes(v)) for v in views])
         if field == "camera_type":
@@ -351,9 +314,9 @@ def test_every_refusal_of_views_guides_leaves_the_context_usable_and_writes_noth
                     [(None, n, vp(), guides(P_)), (D_, n, vp(), None), (D_, n, vp(), no_buffer), (D_ + 4, n, vp(), guides(P_)), (D_ + 8, n, vp(), guides(P_))] +
                     [(D_, n, vp(), g_) for g_ in misaligned])
     for v_, m, p, g_ in dev_refusals:
-        st = abi.Stats(segments=77, shadow_rays=77, seconds=7.0)
+        st = sentinel_stats()
         assert lib.rtw_views_guides_device(gpu.ctx, v_, m, p, g_, None, C.byref(st)) == -1
-        assert (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+        assert left_alone(st)
     still_fine()
     torch.cuda.synchronize()
     assert all((v == -7).all() for v in host.values()) and all(bool((t == -7).all().item()) for t in dev.values())  # no refused call wrote anything
@@ -483,9 +446,8 @@ def test_render_and_views_are_what_they_were_before_the_new_calls(gpu, monkeypat
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
     frames, alb, nrm = three_frames
-    z = np.load(os.path.join(GOLD, "cornell_200x200_16spp_d4_philox.npz"))
-    scene, w, h, spp, depth, rng, seed = (int(v) for v in z["meta"])
-    blob = z["blob"].tobytes()
+    gold = golden("cornell_200x200_16spp_d4_philox")
+    blob, w, h, rng, seed = gold.blob, gold.w, gold.h, gold.rng, gold.seed
     gpu.upload_scene(blob)
     views = bake.orbit_views(blob, 3, seed=seed) + bake.cube_views((278, 278, 278))
     before = gpu.views(views, 16, 12, 24, 6, rng_kind=rng)
@@ -494,9 +456,7 @@ def test_render_and_views_are_what_they_were_before_the_new_calls(gpu, monkeypat
     gpu.views_guides(views, 16, 12, 160, which=("depth",))
     gpu.denoise_views(frames, alb, nrm)
     assert (g["prim"] >= 0).any() and np.isfinite(g["albedo"]).all()
-    img, st = gpu.render(abi.make_params(w, h, spp, depth, seed=seed, rng_kind=rng))
-    assert np.array_equal(img[..., :3], z["rgb"][..., :3]) and np.all(img[..., 3] == 1.0)
-    assert (st.samples, st.segments, st.shadow_rays) == tuple(int(v) for v in z["stats"])
+    check_golden_render(gpu, gold)
     assert same(gpu.views(views, 16, 12, 24, 6, rng_kind=rng), before)
     assert all_same(gpu.render_guides(abi.make_params(w, h, 4, 0, seed=seed)), guides_before)
 

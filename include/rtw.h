@@ -310,7 +310,19 @@ int rtw_upload_scene(rtw_ctx* ctx, const void* scene_blob, size_t bytes);
 /* Replaces optixLaunch + the D2H copy (Director.cpp:982-984, 999-1000).
  * rgba_out: host, rows*width float4 (rows = the rows of [row0,row1) the shard owns: all of them, or every
  * row_stride-th), LINEAR mean radiance of samples [sample_offset, sample_offset+spp), alpha 1; row r of the output is
- * image row row0 + r*max(row_stride,1); image row 0 is the bottom row, like the reference's frame buffer. */
+ * image row row0 + r*max(row_stride,1); image row 0 is the bottom row, like the reference's frame buffer.
+ * A sample is the loop of raygen.cu:28-87 (tests/path_ref.py holds the oracle and every kernel to it):
+ *   At most max_depth segments are traced (max_depth = 0: none, the sample is 0). Every segment adds radiance * T - an emitter's
+ *     or the sky's radiance, a light sample - to the sample, T the throughput, 1 at the camera. A miss, an emitter, a
+ *     cancelled scatter and the max_depth-th segment end the sample; otherwise T *= attenuation of the vertex.
+ *   Russian roulette after the third hit and after every later one (raygen.cu:74-82), on the throughput that already holds
+ *     that hit's attenuation: p = max(T.x, T.y, T.z), under RTW_EST_MIXTURE (whose weights reach 2) capped at 1; one draw xi is
+ *     consumed - also after the last allowed hit, where it decides nothing -, the sample ends when p < xi, else T *= 1 / p. A
+ *     black throughput (p = 0) therefore ends the sample at that hit.
+ *   removeNaNs (raygen.cu:17-24) per sample and per channel: a NaN channel counts as 0, the other channels stay (an infinite
+ *     emitter behind a vertex with a zero channel gives inf, inf, 0), and the sample still counts in spp.
+ *   Spheres: a negative radius is allowed and turns the shading normal (P - C) / radius inwards (a hollow sphere, a room seen
+ *     from inside); the intersection depends on radius * radius alone and the bounds use |radius|. */
 int rtw_render(rtw_ctx* ctx, const rtw_params* params, float* rgba_out, rtw_stats* stats);
 
 /* Same render, result left in device memory (d_rgba: device pointer on device_ids[0], same layout). The work is ordered

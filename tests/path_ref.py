@@ -1,0 +1,799 @@
+"""A float64 numpy reference for what strings the stages of a path together - the loop of the reference's raygen/raygen.cu:28-87: a
+second reading of that loop, of include/rtw.h and of the material, miss and texture programs it calls, written without looking at
+oracle/rtw_oracle.c or the kernels. Shared by test_path_cpu.py (the oracle against this file) and test_gpu_path.py (the kernels against
+this file, then against the oracle's bits and counts). It stands beside four such references: geometry_ref.py (closest hits),
+shading_ref.py (one scatter event, media, textures), lighting_ref.py (direct lighting), camera_ref.py (the camera ray). It imports
+abi's structs and constants, those files' helpers, and the oracle only inside oracle_samples / oracle_frames / oracle_queries.
+
+The loop as read (raygen.cu; `depth` counts from 0, segment j = depth + 1 is the j-th optixTraverse of a sample)
+  :36   while (depth < maxRayDepth): a sample traces at most max_depth segments; max_depth = 0 traces none.
+  :60   sampleRadiance += prd.radiance * throughput: an emitter's or the sky's radiance times the throughput so far.
+  :61   a miss, an emitter (Ray_Finish) or a cancelled scatter ends the sample.
+  :71   throughput *= attenuation, vertex by vertex (Lambertian and metal: the texture's value, lambertianMaterial.cu:66,
+        metalMaterial.cu:52; no pdf ratio: SURVEY Q2).
+  :74   if (2 <= depth): Russian roulette after the third hit and after every later one, on the throughput that already holds
+        that hit's attenuation: p = max(T) (:76), the sample ends when p < rnd (:77), else T /= p (:81; the SDK's float3 / float
+        is a reciprocal and a product: two roundings). The draw is consumed at the last allowed hit too, where it decides nothing.
+        Under RTW_EST_MIXTURE p is capped at 1 (rtw.h): the light list here is empty or dark, so the cap never binds.
+  :144  removeNaNs per channel (:17-24): a NaN channel becomes 0, the others stay.
+
+Law A, the shell (ShellCase): two concentric spheres about the origin, no sky. The wall: a Lambertian sphere of radius -R = -8 (a
+  negative radius turns the shading normal (P - C) / r inwards), albedo rho. The lamp: a diffuse light of radius r = 4, radiance
+  Le, described by no light definition. A ray from between them that meets the wall first. A direction scattered at the wall at
+  angle theta from the inward normal runs at distance R sin(theta) from the centre: it meets the lamp iff sin(theta) < a = r / R,
+  whatever the wall point - so every scattered ray meets the lamp with one probability q (lamp_probability):
+    cosine lobe (the corrected estimators; RTW_EST_MIXTURE with no light to aim at): sin(theta)^2 = r2, uniform: q = a^2 = 1/4;
+    reference lobe (sampling.cuh:49-60): tan(theta)^2 = 4 r2 / (1 - r2) < c = a^2 / (1 - a^2) iff r2 < c / (4 + c): 1/13.
+  A sample that meets the lamp on segment s (2 <= s <= max_depth) is Le rho^(s-1) / prod p_d over the roulettes at depths
+  d = 2 ... s - 2, p_2 = rho_max^3, p_d = rho_max after; its probability is q (1 - q)^(s-2) prod p_d. Every other sample is 0.
+  walk() enumerates the outcomes, their values, probabilities and segment counts; nothing is sampled and nothing is left out.
+  Variants: dark_light (one listed light outside the shell with emission 0 and the header's pdf generator RTW_PDF_RECT_Y on its
+  rectangle: light-sample draws and shadow probes at every wall vertex, every contribution exactly 0; under the reference
+  estimator with Philox this is k_path's one-light instantiation), black wall (rho = 0: p_2 = 0 ends every path at the third
+  hit; Le rho = 0, so every sample is 0), NaN scrub (rho = (0.8, 0.4, 0), Le = +inf: a lamp sample is (inf, inf, inf * 0 = NaN -> 0)).
+Law B, the corridor (CorridorCase): two metal rectangles at fuzz 0 under the sky, y = 0 facing up and y = 1 facing down, x in
+  [-12, 4], z in [-4, 4]. The ray o = (4 - k + 0.25, 0.5, z0), d = (1, 1, dz) bounces exactly k times, at x = 4 - k + j - 0.25, a
+  quarter unit from the edge x = 4 that lets it out to the sky. Nothing is random but the roulette: a sample is 0 or sky(u) prod a_j
+  / prod p_d, the alive share is prod p_d over d = 2 ... k - 1; at max_depth <= k every sample is 0. The sky (miss.cu:8-16) is
+  (1 - t) + t (0.5, 0.7, 1), t = 0.5 (u.y + 1): blue reads the throughput itself. Textured: a_j = shading_ref.texture_value at the
+  bounce points (corridor_walk, float64), p_d = max(T) differs per ray and depth.
+
+The shell from other entries (shell_law; the plain shell, Le = 1)
+  frames        a lens-free perspective and an environment camera at (0, 6, 0), 64 x 64 pixels of 64 samples. Pixels are classified
+                in float64 (classify): a wall pixel's every ray passes the lamp, a lamp pixel's every ray meets it, pixels within
+                one pixel of the silhouette are left out (at most 10 %). Every wall pixel has the law's expectation wherever it
+                lies: z-test of the mean over all of them, chi-square of the per-pixel sums against the law's variance (its
+                variance from the law's kurtosis); lamp pixels are exactly Le (check_frame).
+  rtw_probe     at the wall point (0, -8, 0) with its inward normal: the probe's own ray is segment 1 of max_depth (rtw.h), its
+                direction the cosine lobe whichever estimator, so the irradiance is pi (q Le + (1 - q) L_w), q = a^2, L_w the
+                law's mean of a camera ray that meets the wall first, at the same max_depth: walk() with q_end(1) = a^2.
+  rtw_probe_sh  at (0, 6, 0): the lamp fills a cap of half-angle asin(4 / 6) about -y; c_0 and the first-order coefficient
+                along the axis in closed form, the two across it 0 (check_sh). z-tests, the variance from 64 independent keys.
+
+What is asserted on a sample array (PathCase.check)
+  values        every non-zero sample equals a value of the law within K_FACTOR * MEASURED_CONSTANT_* * 2^-24 * unit relative, per
+                channel; which one names its s; channels the law leaves 0 (or inf) are exactly that; no NaN.
+  distribution  one ray (the shell): Pearson's chi-square of the histogram over (s of the lit samples, dark) against the law, cells
+                pooled from the tail until each expects >= 16 samples, p-value >= ALPHA by the exact survival function (chi2_sf).
+                Many rays (the corridor): the lit count against sum of the rays' alive shares by the binomial rule.
+  means         one ray: per channel, z-test against the law's mean with the law's variance.
+  segments      rtw_stats.segments against the law's mean with the law's variance; exact where the law is deterministic.
+  shadow rays   0 without a listed light; > 0 with the dark light (their number is the oracle's business).
+
+Error units (first-order, in 2^-24 relative to the value): a lit sample that ends on segment s carries s - 1 products T * a, two
+roundings per roulette (depths 2 ... s - 2) and the product radiance * T: unit = (s - 1) + 2 max(0, s - 3) + 1. The corridor's
+red and green add 4 k + 4: k reflections of 8 roundings each on components <= 1, seen through the sky's slope 0.25 / value <= 0.5,
+and 4 for the sky's own operations. A textured vertex adds its texture's own bound relative to its value: shading_ref's image unit
+at (u, v) plus 3 (w ex / 16 + h ez / 8) for the bounce point's own error ex = ez = 2 j (|x| + |z| + 2) after j bounces (two
+roundings of a direction of length <= 1.5 per bounce, carried over a flight of about 1.5, and the point's own rounding), times
+K_FACTOR * MEASURED_CONSTANT_IMAGE of shading_ref; a channel whose texture value is below TEXTURE_FLOOR = 1/64 at any vertex
+would be left out (at least 90 % must be checked; the rays are chosen so that all are). full_walk_error() runs the whole textured
+walk at float32 - points, coordinates, texture fetches, products - against float64: it must stay inside a quarter of the tolerance.
+MEASURED_CONSTANT_SHELL / _CORRIDOR / _TEXTURED are the largest |fp32 - fp64| / (2^-24
+unit value) of THIS FILE's walk at float32 against itself at float64 over the tests' cases (`python tests/path_ref.py` prints
+them; test_path_cpu.py re-measures them). No number here comes from the oracle or the kernels.
+"""
+import functools
+import math
+import os
+import sys
+from collections import namedtuple
+
+import numpy as np
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import camera_ref as CR
+import geometry_ref as G
+import radiance_ref as R
+import shading_ref as S
+from raytracing_weekend_amd import abi
+
+U, K_FACTOR, Z_LIMIT, N_STAT = S.U, S.K_FACTOR, S.Z_LIMIT, S.N_STAT
+REF, CORR, NO_NEE, MIX = abi.RTW_EST_REFERENCE, abi.RTW_EST_CORRECTED, abi.RTW_EST_CORRECTED_NO_NEE, abi.RTW_EST_MIXTURE
+RNGS, DRAWS, SEEDS = S.RNGS, S.DRAWS, S.SEEDS
+# Pearson's statistic over c cells has, under the law, the chi-square distribution of c - 1 degrees of freedom (no parameter is
+# fitted); the case is rejected when P(chi2_{c-1} >= X) < ALPHA = 1e-4, the project's per-case level. The quantile is not tabulated:
+# chi2_sf is the exact survival function - for k = 2 m, e^{-x/2} sum_{i<m} (x/2)^i / i!; for odd k, erfc(sqrt(x/2)) + e^{-x/2}
+# sum_{i=1}^{(k-1)/2} (x/2)^{i-1/2} / Gamma(i + 1/2) - so that P >= ALPHA is the same statement as X <= the 1 - ALPHA quantile
+# (23.51 at 4 degrees of freedom, 35.56 at 10).
+ALPHA = 1e-4
+MIN_EXPECTED = 16.0
+WALL_R, LAMP_R = 8.0, 4.0
+RHO = (0.8, 0.4, 0.2)
+MIRROR = (0.9, 0.6, 0.3)
+SKY_TOP = (0.5, 0.7, 1.0)
+X_MIN, X_MAX, Z_HALF = -12.0, 4.0, 4.0
+TEXTURE_FLOOR = 1.0 / 64.0
+DEPTHS = (1, 2, 3, 4, 5, 50)
+# `python tests/path_ref.py`: walk() at float32 against itself at float64, in the units of the module text
+MEASURED_CONSTANT_SHELL = 0.2292     # every shell case of max_depth >= 3 alike
+MEASURED_CONSTANT_CORRIDOR = 0.2222  # corridor-k2-d3 and -d50
+MEASURED_CONSTANT_TEXTURED = 0.4327  # corridor_image-d6 and -d50 (the walk over the float64 texture values)
+
+Outcome = namedtuple("Outcome", "prob value segments s")  # s: the segment the sample ended on an emitter or the sky, 0: it did not
+
+
+def chi2_sf(x, k):
+    """P(chi-square with k >= 1 degrees of freedom >= x), exact (the finite sums of the module constants' text)."""
+    h = 0.5 * x
+    if k % 2 == 0:
+        term, total = 1.0, 1.0
+        for i in range(1, k // 2):
+            term *= h / i
+            total += term
+        return math.exp(-h) * total
+    total, term = 0.0, math.sqrt(h) / math.gamma(1.5)
+    for i in range(1, (k - 1) // 2 + 1):
+        total += term
+        term *= h / (i + 0.5)
+    return math.erfc(math.sqrt(h)) + math.exp(-h) * total
+
+
+def lamp_probability(reference_lobe, a=LAMP_R / WALL_R):
+    """q: the probability that a direction scattered at the wall meets the lamp (module text), from the lobe's definition."""
+    if not reference_lobe:
+        return a * a                 # sin^2 = r2 < a^2
+    c = a * a / (1.0 - a * a)        # tan^2 = 4 r2 / (1 - r2) < c
+    return c / (4.0 + c)
+
+
+def walk(att, q_end, radiance, depth, ft=np.float64, rr_from=2, p_rule="max", p_before_update=False, rescale=True, depth_shift=0,
+         p_override=None, cap=False):
+    """The outcomes of one camera ray under the loop of the module text. att(j): the (3,) attenuation of hit j = 1, 2, ...;
+    q_end(j): the probability that segment j ends on an emitter or the sky; radiance(j): the (3,) radiance met there. The
+    throughput runs at precision ft, the probabilities in float64. The keyword arguments after ft are the wrong models of the
+    negative controls (p_override(d, T): another p at depth d, or None)."""
+    out, prob, T = [], 1.0, np.ones(3, ft)
+    last = depth + depth_shift
+    for j in range(1, last + 1):
+        qe = float(q_end(j))
+        if qe > 0.0:
+            with np.errstate(invalid="ignore"):
+                v = np.asarray(radiance(j), ft) * T
+            out.append(Outcome(prob * qe, np.where(np.isnan(v), ft(0.0), v), j, j))  # removeNaNs, per channel
+        prob *= 1.0 - qe
+        if prob == 0.0:
+            break
+        before = T
+        T = T * np.asarray(att(j), ft)
+        if j - 1 >= rr_from:
+            base = before if p_before_update else T
+            p = base.mean(dtype=ft) if p_rule == "mean" else base.max()
+            if p_override is not None and p_override(j - 1, T) is not None:
+                p = ft(p_override(j - 1, T))
+            if cap:
+                p = min(p, ft(1.0))
+            live = min(float(p), 1.0)
+            out.append(Outcome(prob * (1.0 - live), np.zeros(3, ft), j, 0))
+            prob *= live
+            if prob == 0.0:
+                break
+            if rescale:
+                T = T * (ft(1.0) / p)
+        if j == last:
+            out.append(Outcome(prob, np.zeros(3, ft), j, 0))
+    return [o for o in out if o.prob > 0.0]
+
+
+def unit_of(s):
+    """The roundings of a sample that ends on segment s (module text)."""
+    return (s - 1) + 2 * max(0, s - 3) + 1
+
+
+class Law:
+    """What the outcomes of one ray say: the lit ends (value != 0) by s, the dark share, the moments of a sample and of its
+    segment count. extra_unit: roundings beside unit_of(s), per channel; tol_extra: a relative tolerance beside the units'."""
+
+    def __init__(self, outcomes, extra_unit=(0.0, 0.0, 0.0), tol_extra=(0.0, 0.0, 0.0), checked=(True, True, True)):
+        self.outcomes = outcomes
+        self.lit = [o for o in outcomes if o.s and o.value.any()]
+        self.s = np.array([o.s for o in self.lit], np.int64)
+        self.values = np.array([o.value for o in self.lit], np.float64).reshape(-1, 3)
+        self.probs = np.array([o.prob for o in self.lit])
+        self.alive = float(self.probs.sum())
+        self.extra_unit, self.tol_extra, self.checked = np.asarray(extra_unit, np.float64), np.asarray(tol_extra, np.float64), np.asarray(checked)
+        total = sum(o.prob for o in outcomes)
+        assert abs(total - 1.0) < 1e-12, total
+        finite = np.isfinite(self.values).all(0) if len(self.lit) else np.ones(3, bool)
+        v = np.where(np.isfinite(self.values), self.values, 0.0)
+        self.finite = finite
+        self.m1, self.m2 = (self.probs[:, None] * v).sum(0), (self.probs[:, None] * v * v).sum(0)
+        seg, pr = np.array([o.segments for o in outcomes], np.float64), np.array([o.prob for o in outcomes])
+        self.seg_mean = float((seg * pr).sum())
+        self.seg_var = max(float((seg * seg * pr).sum()) - self.seg_mean ** 2, 0.0)
+        if self.seg_var < 1e-12:
+            self.seg_var = 0.0
+
+    def tolerance(self, constant):
+        """(ends, 3): the relative tolerance of every lit end's channels."""
+        units = np.array([unit_of(s) for s in self.s], np.float64)[:, None] + self.extra_unit[None, :]
+        return K_FACTOR * constant * U * units + self.tol_extra[None, :]
+
+    def match(self, samples, constant):
+        """For (n, 3) samples: (end index per sample, -1 for a dark one; the largest error / tolerance of the lit ones; the number of
+        samples that are no value of the law). A channel the law has at 0 or inf must be equal; one that is not checked is skipped."""
+        x = np.asarray(samples, np.float64).reshape(-1, 3)
+        idx = np.full(len(x), -1, np.int64)
+        lit = x.any(1) | np.isnan(x).any(1)
+        if not lit.any():
+            return idx, 0.0, 0
+        if not len(self.lit):
+            return idx, np.inf, int(lit.sum())
+        tol = self.tolerance(constant)
+        xs = x[lit][:, None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            plain = np.isfinite(self.values) & (self.values != 0)
+            rel = np.where(plain[None], np.abs(xs / np.where(plain, self.values, 1.0)[None] - 1.0) / tol[None], np.where(xs == self.values[None], 0.0, np.inf))
+        rel = np.where(np.isnan(rel), np.inf, rel)
+        rel = np.where(self.checked[None, None, :], rel, 0.0).max(-1)
+        best = rel.argmin(1)
+        err = rel[np.arange(len(best)), best]
+        idx[lit] = np.where(err <= 1.0, best, -2)
+        return idx, float(err.max()), int((err > 1.0).sum())
+
+    def cells(self, n):
+        """The chi-square cells for n samples: (list of lists of end indices, -1 = dark; expected counts), pooled from the tail (the
+        largest s first) and then from the smallest cell until every cell expects >= MIN_EXPECTED."""
+        groups, expect, by_value = [], [], {}
+        for i in np.argsort(self.s):  # ends of one value (the NaN scrub's: (inf, inf, 0) whatever s) cannot be told apart: one cell
+            key = tuple(self.values[i])
+            if key not in by_value:
+                by_value[key] = len(groups)
+                groups.append([])
+                expect.append(0.0)
+            groups[by_value[key]].append(int(i))
+            expect[by_value[key]] += n * float(self.probs[i])
+        last_lit = len(groups) - 1
+        if 1.0 - self.alive > 0.0:
+            groups.append([-1])
+            expect.append(n * (1.0 - self.alive))
+        while last_lit > 0 and expect[last_lit] < MIN_EXPECTED:  # the tail of s
+            groups[last_lit - 1] += groups.pop(last_lit)
+            expect[last_lit - 1] += expect.pop(last_lit)
+            last_lit -= 1
+        while len(groups) > 1 and min(expect) < MIN_EXPECTED:
+            i = int(np.argmin(expect))
+            k = i - 1 if i > 0 else 1
+            groups[k] += groups.pop(i)
+            expect[k] += expect.pop(i)
+        return groups, expect
+
+
+# ---------------------------------------------------------------- scenes
+def _sphere(radius, material):
+    return S._prim(abi.PRIM_SPHERE, (0.0, 0.0, 0.0, radius), material=material)
+
+
+def shell_blob(rho=RHO, le=1.0, dark_light=False):
+    hdr = S._header(0)
+    lights = []
+    if dark_light:
+        # a y-rectangle [-1, 1]^2 at y = 20, outside the shell, facing down, emission 0; the header's generator on the same rectangle
+        hdr.pdf.gen, hdr.pdf.p0_gen, hdr.pdf.p1_gen = abi.RTW_PDF_RECT_Y, -1, -1
+        for i, e in enumerate((-1.0, 1.0, -1.0, 1.0, 20.0)):
+            hdr.pdf.rect[i] = e
+        lt = abi.Light()
+        for k, (p, u, v, n) in enumerate(zip((-1.0, 20.0, -1.0), (2.0, 0.0, 0.0), (0.0, 0.0, 2.0), (0.0, -1.0, 0.0))):
+            lt.position[k], lt.vec_u[k], lt.vec_v[k], lt.normal[k], lt.emission[k] = p, u, v, n, 0.0
+        lt.area = 4.0
+        lights.append(lt)
+    mats = [abi.Material(type=abi.MAT_LAMBERTIAN, texture=0, fuzz_or_eta=0.0, bsdf_eval=0),
+            abi.Material(type=abi.MAT_DIFFUSE_LIGHT, texture=1, fuzz_or_eta=0.0, bsdf_eval=-1)]
+    return abi.assemble_scene({"header": hdr, "prims": [_sphere(-WALL_R, 0), _sphere(LAMP_R, 1)], "xforms": [G.identity_xform()], "lights": lights,
+                               "materials": mats, "textures": [S._constant(rho), S._constant((le, le, le))], "texdata": b""})
+
+
+def corridor_blob(textures=None, texdata=b""):
+    """The two mirrors; textures: the blob's texture table, texture 0 on both mirrors (default: the constant MIRROR)."""
+    ext = (X_MIN, X_MAX, -Z_HALF, Z_HALF)
+    prims = [S._prim(abi.PRIM_RECT_Y, ext + (0.0,)), S._prim(abi.PRIM_RECT_Y, ext + (1.0,), flip=1)]
+    return S._scene(1, prims, [abi.Material(type=abi.MAT_METAL, texture=0, fuzz_or_eta=0.0, bsdf_eval=2)], textures or [S._constant(MIRROR)], texdata=texdata)
+
+
+def corridor_walk(o, d, k, ft=np.float64, unit_in=True):
+    """The k bounce points (k, 3) and the direction that leaves, at precision ft: the planes y = 1 and y = 0 in turn, the mirror
+    direction of shading_ref.mirror (the reference estimator reflects the direction as it comes and normalises after)."""
+    o, d = np.asarray(o, ft), np.asarray(d, ft)
+    pts = []
+    for j in range(k):
+        up = d[1] > 0
+        t = ((ft(1.0) if up else ft(0.0)) - o[1]) / d[1]
+        o = o + t * d
+        o[1] = ft(1.0) if up else ft(0.0)  # aarecty.cu takes the point on the plane
+        pts.append(o.copy())
+        d = S.mirror(d, np.array([0.0, -1.0 if up else 1.0, 0.0], ft), ft, unit_in=unit_in)
+    return np.array(pts, ft).reshape(k, 3), d
+
+
+def sky(u, ft=np.float64):
+    """miss.cu:8-16 along direction u."""
+    un = S._unit(np.asarray(u, ft))
+    t = ft(0.5) * (un[1] + ft(1.0))
+    return (ft(1.0) - t) * np.ones(3, ft) + t * np.array(SKY_TOP, ft)
+
+
+# ---------------------------------------------------------------- cases
+class PathCase(S.Case):
+    """m rays with keys_per_ray keys each; laws(estimator, **model): one Law per ray; CONSTANT: the measured constant's name."""
+    estimators = (REF, CORR)
+    shadow = "none"  # "none": no probe is traced; "some": probes are traced, their number is the oracle's
+
+    def check(self, samples, estimator, segments=None, shadow_rays=None, **model):
+        samples = np.asarray(samples)
+        laws = self.laws(estimator, **model)
+        constant = globals()["MEASURED_CONSTANT_" + self.CONSTANT]
+        n, kpr = samples.shape[0] * samples.shape[1], samples.shape[1]
+        figs, bad = [], []
+
+        def hold(ok, text):
+            figs.append(text)
+            if not ok:
+                bad.append(text)
+        hold(not np.isnan(samples).any(), f"NaN samples {int(np.isnan(samples).any(-1).sum())}")
+        worst, strangers, lit, idx_of = 0.0, 0, 0, []
+        for j, law in enumerate(laws):
+            idx, err, odd = law.match(samples[j], constant)
+            idx_of.append(idx)
+            worst, strangers, lit = max(worst, err), strangers + odd, lit + int((idx != -1).sum())
+        checked = float(np.mean([law.checked for law in laws]))
+        hold(strangers == 0 and worst <= 1.0, f"{lit} lit of {n}, {strangers} are no value of the law, largest error / tolerance {worst:.3f} "
+             f"(K = {K_FACTOR * constant:.3f}), channels checked {checked:.3f}")
+        hold(checked >= 0.9, f"channels checked {checked:.3f} >= 0.9")
+        if len(laws) == 1:
+            law, idx = laws[0], idx_of[0]
+            groups, expect = law.cells(n)
+            if len(groups) > 1:
+                seen = [int(np.isin(idx, g).sum()) for g in groups]
+                x2 = float(sum((o - e) ** 2 / e for o, e in zip(seen, expect)))
+                pv = chi2_sf(x2, len(groups) - 1)
+                names = ["dark" if g == [-1] else "s=" + "+".join("dark" if i < 0 else str(law.s[i]) for i in g[:3]) + ("+..." if len(g) > 3 else "") for g in groups]
+                hold(pv >= ALPHA, f"chi2 = {x2:.2f} over {len(groups)} cells {dict(zip(names, seen))} (p = {pv:.2e}, level {ALPHA})")
+            else:
+                hold(bool((np.isin(idx, groups[0])).all()), f"one cell {groups[0][:3]}: every sample is in it")
+            for c in range(3):
+                if not law.finite[c]:
+                    continue  # the values' equality covers a channel that holds inf
+                mean, var = float(samples[0][:, c].astype(np.float64).mean()), law.m2[c] - law.m1[c] ** 2
+                if var <= 1e-18:
+                    tol = law.tolerance(constant)[:, c].max() if len(law.lit) else 0.0
+                    hold(abs(mean - law.m1[c]) <= tol * abs(law.m1[c]), f"channel {c}: mean {mean:.6g}, law {law.m1[c]:.6g} (no variance)")
+                else:
+                    z = (mean - law.m1[c]) / math.sqrt(var / n)
+                    hold(abs(z) <= Z_LIMIT, f"channel {c}: mean {mean:.6f}, law {law.m1[c]:.6f}, z = {z:+.2f}")
+            hold(True, f"lit share {lit / n:.4f} (law {law.alive:.4f})")
+        else:
+            p = np.array([law.alive for law in laws])
+            var = kpr * float((p * (1.0 - p)).sum())
+            if var > 0:
+                z = (lit - kpr * p.sum()) / math.sqrt(var)
+                hold(abs(z) <= Z_LIMIT, f"lit share {lit / n:.4f} (law {p.mean():.4f}, z = {z:+.2f})")
+            else:
+                hold(lit == round(kpr * p.sum()), f"lit {lit} (law {kpr * p.sum():.0f}, certain)")
+        if segments is not None:
+            want, var = kpr * sum(law.seg_mean for law in laws), kpr * sum(law.seg_var for law in laws)
+            if var == 0.0:
+                hold(segments == round(want), f"segments {segments} (law {want:.0f}, exact)")
+            else:
+                z = (segments - want) / math.sqrt(var)
+                hold(abs(z) <= Z_LIMIT, f"segments per sample {segments / n:.4f} (law {want / n:.4f}, z = {z:+.2f})")
+        if shadow_rays is not None:
+            hold(shadow_rays == 0 if self.shadow == "none" else shadow_rays > 0, f"shadow rays {shadow_rays} (law: {self.shadow})")
+        fig = "; ".join(figs)
+        assert not bad, "FAILED: " + " | ".join(bad) + " || all figures: " + fig
+        return fig
+
+    def fp32_constant(self):
+        """The largest |value32 - value64| / (2^-24 unit value) of the lit ends over the case's estimators, checked channels only."""
+        worst = 0.0
+        for est in self.estimators:
+            for l64, l32 in zip(self.laws(est), self.laws(est, ft=np.float32)):
+                assert list(l64.s) == list(l32.s)
+                for i, s in enumerate(l64.s):
+                    v64, v32 = l64.values[i], l32.values[i]
+                    ok = np.isfinite(v64) & (v64 != 0) & l64.checked
+                    if ok.any():
+                        worst = max(worst, float((np.abs(v32[ok] / v64[ok] - 1.0) / (U * (unit_of(s) + l64.extra_unit[ok]))).max()))
+        return worst
+
+
+class ShellCase(PathCase):
+    CONSTANT = "SHELL"
+    estimators = (REF, CORR, NO_NEE, MIX)
+
+    def __init__(self, o, d, depth, rho=RHO, le=1.0, dark_light=False):
+        super().__init__(shell_blob(rho, le, dark_light), o, d, N_STAT)
+        self.depth, self.rho, self.le = depth, tuple(float(np.float32(c)) for c in rho), le
+        if dark_light:
+            self.estimators, self.shadow = (REF, CORR), "some"  # the mixture would aim at the light: its q is another
+
+    def laws(self, estimator, ft=np.float64, lobe=None, **model):
+        reference_lobe = (estimator == REF) if lobe is None else lobe == "reference"
+        q = lamp_probability(reference_lobe)
+        le = np.full(3, self.le, ft)
+        return [Law(walk(lambda j: np.asarray(self.rho, ft), lambda j: 0.0 if j == 1 else q, lambda j: le, self.depth, ft,
+                         cap=estimator == MIX, **model))]
+
+    def first_hit_is_the_wall(self):
+        """The input condition, in float64: the ray starts between the spheres and its line passes the lamp (or leaves it behind)."""
+        o, d = self.o[0].astype(np.float64), self.d[0]
+        b, dd = o @ d, d @ d
+        disc = b * b - dd * (o @ o - LAMP_R ** 2)
+        return LAMP_R < np.linalg.norm(o) < WALL_R and (disc < 0 or (-b + math.sqrt(disc)) / dd < 0)
+
+
+class CorridorCase(PathCase):
+    """rays: (k, z0, dz) each; textured: None, or (texture table, texdata) with texture 0 on the mirrors."""
+    CONSTANT = "CORRIDOR"
+
+    def __init__(self, rays, depth, textured=None, keys_per_ray=N_STAT):
+        self.ks = [r[0] for r in rays]
+        o = np.array([(X_MAX - k + 0.25, 0.5, z0) for k, z0, dz in rays])
+        d = np.array([(1.0, 1.0, dz) for k, z0, dz in rays])
+        self.textured = textured is not None
+        if self.textured:
+            self.CONSTANT = "TEXTURED"
+        super().__init__(corridor_blob(*(textured or ())), o, d, keys_per_ray)
+        self.depth = depth
+
+    def vertices(self, j, estimator, ft=np.float64, **texture_model):
+        """Of ray j: (bounce points, direction out, attenuations (k, 3), well-conditioned (k,), error units (k,), texture kinds (k,))."""
+        k = self.ks[j]
+        pts, out = corridor_walk(self.o[j], self.d[j], k, ft, unit_in=estimator != REF)
+        if not self.textured:
+            return pts, out, np.tile(np.array(MIRROR, np.float32).astype(ft), (k, 1)), np.ones(k, bool), np.zeros(k), np.full(k, abi.TEX_CONSTANT)
+        u, v = (pts[:, 0] - ft(X_MIN)) / ft(X_MAX - X_MIN), (pts[:, 2] + ft(Z_HALF)) / ft(2 * Z_HALF)
+        val, ok, unit, kind = S.texture_value(self.blob, 0, u, v, pts, ft, **texture_model)
+        w, h = 64.0, 32.0  # the test image
+        e_pos = 2.0 * (np.arange(k) + 1.0) * (np.abs(pts[:, 0]) + np.abs(pts[:, 2]) + 2.0).astype(np.float64)
+        unit = np.where(kind == abi.TEX_IMAGE, unit + 3.0 * (w * e_pos / (X_MAX - X_MIN) + h * e_pos / (2 * Z_HALF)), 0.0)
+        return pts, out, val, ok, unit, kind
+
+    def laws(self, estimator, ft=np.float64, constant_p=False, **model):
+        laws, model = [], dict(model)
+        for j, k in enumerate(self.ks):
+            pts, out, val, ok, unit, kind = self.vertices(j, estimator, ft)
+            end = sky(out, ft)
+            override = model.get("p_override")
+            if constant_p:  # the wrong model of the textured corridor: the roulette's p from the constant albedo
+                amax = float(np.float32(max(MIRROR)))
+                override = lambda d, T: amax ** 3 if d == 2 else amax  # noqa: E731
+            oc = walk(lambda i: val[i - 1] if i <= k else np.zeros(3, ft), lambda i: 1.0 if i == k + 1 else 0.0, lambda i: end, self.depth, ft,
+                      **dict(model, p_override=override))
+            extra = np.array([4.0 * k + 4.0, 4.0 * k + 4.0, 0.0])
+            tol_extra, checked = np.zeros(3), np.ones(3, bool)
+            if self.textured:
+                v64 = np.asarray(val, np.float64)
+                checked = bool(ok.all()) & (v64 >= TEXTURE_FLOOR).all(0)
+                with np.errstate(divide="ignore"):
+                    tol_extra = np.where(checked, (K_FACTOR * S.MEASURED_CONSTANT_IMAGE * U * unit[:, None] / np.where(v64 > 0, v64, 1.0)).sum(0), 0.0)
+            laws.append(Law(oc, extra, tol_extra, checked))
+        return laws
+
+    def fp32_constant(self):
+        if not self.textured:
+            return super().fp32_constant()
+        # a textured vertex's own error is bounded by shading_ref's constant (tol_extra): what is measured here is the walk over
+        # the float64 texture values, so that the two bounds add and neither is counted twice
+        worst = 0.0
+        for est in self.estimators:
+            for j, k in enumerate(self.ks):
+                val = self.vertices(j, est)[2]
+                v = {}
+                for ft in (np.float64, np.float32):
+                    out = corridor_walk(self.o[j], self.d[j], k, ft, unit_in=est != REF)[1]
+                    v[ft] = walk(lambda i: np.asarray(val[i - 1], ft) if i <= k else np.zeros(3, ft), lambda i: 1.0 if i == k + 1 else 0.0,
+                                 lambda i: sky(out, ft), self.depth, ft)
+                lit = {ft: [o for o in v[ft] if o.s] for ft in v}
+                for a, b in zip(lit[np.float64], lit[np.float32]):
+                    okc = a.value > 0
+                    units = unit_of(a.s) + np.array([4.0 * k + 4.0, 4.0 * k + 4.0, 0.0])
+                    worst = max(worst, float((np.abs(b.value.astype(np.float64)[okc] / a.value[okc] - 1.0) / (U * units[okc])).max()))
+        return worst
+
+    def full_walk_error(self):
+        """The largest error / tolerance of the whole walk at float32 (bounce points, texture coordinates, fetches and products)
+        against the float64 law, over rays, estimators and checked channels: what the tolerance leaves to an implementation."""
+        worst = 0.0
+        constant = globals()["MEASURED_CONSTANT_" + self.CONSTANT]
+        for est in self.estimators:
+            for j, (law, k) in enumerate(zip(self.laws(est), self.ks)):
+                _, out, val, _, _, _ = self.vertices(j, est, np.float32)
+                oc = walk(lambda i: val[i - 1] if i <= k else np.zeros(3, np.float32), lambda i: 1.0 if i == k + 1 else 0.0,
+                          lambda i: sky(out, np.float32), self.depth, np.float32)
+                for o in (o for o in oc if o.s):
+                    _, err, odd = law.match(o.value[None, :], constant)
+                    worst = max(worst, err)
+        return worst
+
+    def well_conditioned(self):
+        """The input conditions: every bounce point a quarter unit from the mirrors' edge in x and inside in z, and (a checker) no
+        |sin| below shading_ref.SIN_EPS there. Returns the smallest margin in x and the share of well-conditioned vertices."""
+        margin, good, total = np.inf, 0, 0
+        for j, k in enumerate(self.ks):
+            pts, _, _, ok, _, _ = self.vertices(j, CORR)
+            assert np.allclose(pts[:, 0], X_MAX - k + np.arange(1, k + 1) - 0.25) and (np.abs(pts[:, 2]) < Z_HALF - 0.25).all()
+            margin = min(margin, float(np.min(np.minimum(X_MAX - pts[:, 0], pts[:, 0] - X_MIN))))
+            good, total = good + int(ok.sum()), total + k
+        return margin, good / total
+
+
+# rays of the shell: exact in float32, between the spheres, the wall first; normal to grazing incidence
+SHELL_RAYS = (((0.0, 6.0, 0.0), (0.5, 1.0, 0.25)), ((0.0, 6.0, 0.0), (0.0, 1.0, 0.0)), ((0.0, 6.0, 0.0), (1.0, 0.0, 0.0)),
+              ((5.0, 0.0, -2.0), (0.25, -0.125, -1.0)))
+CORRIDOR_KS = (1, 2, 3, 4, 7, 12)
+
+
+def _textured(which):
+    import oracle  # the builder of the test image only (pure Python): the oracle library is not loaded here
+    if which == "checker":
+        return [abi.Texture(type=abi.TEX_CHECKER, odd=1, even=2), S._constant((0.9, 0.5, 0.3)), S._constant((0.6, 0.8, 0.7))], b""
+    return [abi.Texture(type=abi.TEX_IMAGE, data=0)], oracle.test_image()
+
+
+def _textured_rays(blob):
+    """32 rays: k from 3 to 8 in turn, z0 on a grid of 1/64 in [-1.5, 2.5], dz in {0, +-1/8, +-1/4}: z stays inside [-2.3, 3.5]. A
+    candidate is taken when every bounce point is well-conditioned (a checker: no |sin| below shading_ref.SIN_EPS) and shows at
+    least 1/16 in every channel (the test image's blue is made of random blocks, some of them black)."""
+    rng = np.random.default_rng(5)
+    out, i = [], 0
+    while len(out) < 32:
+        k = 3 + len(out) % 6
+        dz = (0.0, 0.125, -0.125, 0.25, -0.25)[i % 5]
+        z0 = float(rng.integers(-32, 65)) / 64.0 + (0.0 if dz >= 0 else 1.0)
+        i += 1
+        pts, _ = corridor_walk((X_MAX - k + 0.25, 0.5, z0), (1.0, 1.0, dz), k)
+        val, ok, _, _ = S.texture_value(blob, 0, (pts[:, 0] - X_MIN) / (X_MAX - X_MIN), (pts[:, 2] + Z_HALF) / (2 * Z_HALF), pts)
+        if ok.all() and (val >= 1.0 / 16.0).all():
+            out.append((k, z0, dz))
+    return out
+
+
+def _textured_case(which, depth):
+    textured = _textured(which)
+    return CorridorCase(_textured_rays(corridor_blob(*textured)), depth, textured, keys_per_ray=N_STAT // 32)
+
+
+def _cases():
+    out = {}
+    for r in range(len(SHELL_RAYS)):
+        for depth in DEPTHS:
+            out[f"shell-r{r}-d{depth}"] = lambda r=r, depth=depth: ShellCase(*SHELL_RAYS[r], depth)
+    for depth in (3, 4, 50):
+        out[f"shell_dark_light-d{depth}"] = lambda depth=depth: ShellCase(*SHELL_RAYS[0], depth, dark_light=True)
+    for depth in (2, 3, 4, 50):
+        out[f"shell_black_wall-d{depth}"] = lambda depth=depth: ShellCase(*SHELL_RAYS[0], depth, rho=(0.0, 0.0, 0.0))
+    for depth in (4, 50):
+        out[f"shell_nan_scrub-d{depth}"] = lambda depth=depth: ShellCase(*SHELL_RAYS[0], depth, rho=(0.8, 0.4, 0.0), le=float("inf"))
+    for k in CORRIDOR_KS:
+        for depth in (k, k + 1, 50):
+            out[f"corridor-k{k}-d{depth}"] = lambda k=k, depth=depth: CorridorCase([(k, 0.0, 0.0)], depth)
+    for which in ("checker", "image"):
+        for depth in (6, 50):  # 6: the rays of k >= 6 end at the depth cap, the others go out
+            out[f"corridor_{which}-d{depth}"] = lambda which=which, depth=depth: _textured_case(which, depth)
+    return out
+
+
+CASES = _cases()
+SHELL_MEANS_AT_50 = {False: (0.5, 1.0 / 7.0, 1.0 / 17.0), True: (4.0 / 17.0, 2.0 / 41.0, 1.0 / 53.0)}  # rho q / (1 - rho (1 - q)), by lobe
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    return CASES[name]()
+
+
+def check(name, samples, estimator, **kw):
+    """The assertions of case `name` on a sample array (m, keys_per_ray, 3); returns the figures for the caller to print."""
+    return f"{name}, estimator {estimator}: " + case(name).check(samples, estimator, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_samples(name, rng_kind, estimator, seed, key_base=0):
+    """((m, keys_per_ray, 3) float32, segments, shadow rays): the oracle's samples and counts of case `name`, computed once and left
+    unchanged."""
+    import oracle
+    c = case(name)
+    out = np.empty((c.m, c.keys_per_ray, 3), np.float32)
+    seg = shadow = 0
+    for j in range(c.m):
+        img, st = oracle.render(R.ray_blob(c.blob, c.o[j], c.ll[j]), S.render_params(c, j, rng_kind, estimator, seed, key_base), threads=4)
+        out[j] = img[..., :3].reshape(c.keys_per_ray, 3)
+        seg, shadow = seg + int(st.segments), shadow + int(st.shadow_rays)
+    out.setflags(write=False)
+    return out, seg, shadow
+
+
+# ---------------------------------------------------------------- the shell seen by a camera, a probe and a light probe
+def shell_law(estimator, depth, first="wall"):
+    """The law of one sample in the plain shell whose first segment meets the wall ("wall"), leaves a wall point along rtw_probe's
+    cosine lobe ("cosine": the lamp with probability a^2 whichever estimator, rtw.h) or meets the lamp with probability `first`."""
+    q = lamp_probability(estimator == REF)
+    q1 = {"wall": 0.0, "cosine": lamp_probability(False)}.get(first, first)
+    rho = np.array(RHO, np.float32).astype(np.float64)
+    return Law(walk(lambda j: rho, lambda j: q1 if j == 1 else q, lambda j: np.ones(3), depth, cap=estimator == MIX))
+
+
+def _moments(law):
+    """(mean, variance, fourth central moment) of a sample per channel, the dark share included."""
+    v, p = law.values, law.probs[:, None]
+    m = law.m1
+    dark = 1.0 - law.alive
+    return m, (p * (v - m) ** 2).sum(0) + dark * m ** 2, (p * (v - m) ** 4).sum(0) + dark * m ** 4
+
+
+FRAME_SIDE = FRAME_SPP = 64
+FRAME_EYE = (0.0, 6.0, 0.0)
+MAX_LEFT_OUT = 0.10
+
+
+@functools.lru_cache(maxsize=None)
+def frame_views():
+    """A lens-free perspective camera (60 degrees, looking down along the lamp's rim) and an environment camera, both at
+    (0, 6, 0) inside the shell; seeds SEEDS[0] and SEEDS[1]."""
+    persp = CR.io_perspective(FRAME_EYE, (6.0, 2.0, 0.0), (0.0, 1.0, 0.0), 60.0, 1.0).astype(np.float32)
+    env = CR.io_environment(FRAME_EYE, (6.0, 6.0, 0.0), (0.0, 1.0, 0.0)).astype(np.float32)
+    return (abi.make_view(persp, abi.RTW_CAM_PERSPECTIVE, SEEDS[0]), abi.make_view(env, abi.RTW_CAM_ENVIRONMENT, SEEDS[1]))
+
+
+def frame_blob(view):
+    """The plain shell with the view's camera in its header."""
+    import ctypes as C
+    blob = shell_blob()
+    n = C.sizeof(abi.SceneHeader)
+    h = abi.SceneHeader.from_buffer_copy(blob[:n])
+    h.camera, h.camera_type = abi.Camera.from_buffer_copy(bytes(view.camera)), view.camera_type
+    return bytes(h) + blob[n:]
+
+
+@functools.lru_cache(maxsize=None)
+def classify(which):
+    """(FRAME_SIDE, FRAME_SIDE) int: 0 where every ray through the pixel and through its eight neighbours passes the lamp (a wall
+    pixel), 1 where every one meets it (a lamp pixel), -1 elsewhere (within one pixel of the lamp's silhouette: left out). In
+    float64 from the camera's float32 record (camera_ref.camera_rays), on a 7 x 7 lattice of jitters from -1 to 2."""
+    view = frame_views()[which]
+    cam = np.frombuffer(bytes(view.camera), np.float32)
+    frame = CR.Frame(FRAME_SIDE, FRAME_SIDE, 0, FRAME_SIDE, 0)
+    zero = np.zeros((FRAME_SIDE, FRAME_SIDE))
+    hits = []
+    for a in np.linspace(-1.0, 2.0, 7):
+        for b in np.linspace(-1.0, 2.0, 7):
+            o, d, _, _ = CR.camera_rays(cam, view.camera_type, frame, {"r0": zero + a, "r1": zero + b, "r2": zero, "r3": zero})
+            bq, dd = S._dot(o, d), S._dot(d, d)
+            disc = bq * bq - dd * (S._dot(o, o) - LAMP_R ** 2)
+            hits.append((disc > 0) & (bq < 0))
+    hits = np.array(hits)
+    return np.where(hits.all(0), 1, np.where(hits.any(0), -1, 0))
+
+
+def check_frame(pixels, which, estimator, depth):
+    """The assertions on view `which`'s (FRAME_SIDE, FRAME_SIDE, 4) frame of FRAME_SPP samples: lamp pixels are exactly Le, every
+    wall pixel has the law's expectation - the mean over all wall pixels by z-test, the per-pixel sums by chi-square against the
+    law's variance. The statistic sum (S_p - n m)^2 / (n var) over N pixels of n samples has mean N and variance N (2 + kappa / n),
+    kappa the law's excess kurtosis: held to Z_LIMIT as a normal deviate (N > 3000)."""
+    px = np.asarray(pixels, np.float64)
+    cls = classify(which)
+    wall, lamp = cls == 0, cls == 1
+    m, var, m4 = _moments(shell_law(estimator, depth))
+    n_w, figs, ok = int(wall.sum()), [], True
+    left = float((cls < 0).mean())
+    exact = bool(np.array_equal(np.asarray(pixels)[lamp], np.broadcast_to(np.float32(1.0), (int(lamp.sum()), 4)))) and bool((px[..., 3] == 1.0).all())
+    figs.append(f"{n_w} wall pixels, {int(lamp.sum())} lamp pixels (exactly Le: {exact}), left out {left:.4f}")
+    ok = ok and exact and left <= MAX_LEFT_OUT and lamp.sum() > 0 and n_w > 0
+    for c in range(3):
+        x = px[..., c][wall]
+        z = (x.mean() - m[c]) / math.sqrt(var[c] / (n_w * FRAME_SPP))
+        x2 = float((FRAME_SPP * (x - m[c]) ** 2 / var[c]).sum())
+        kappa = m4[c] / var[c] ** 2 - 3.0
+        zx = (x2 - n_w) / math.sqrt(n_w * (2.0 + kappa / FRAME_SPP))
+        figs.append(f"channel {c}: mean {x.mean():.6f} (law {m[c]:.6f}, z = {z:+.2f}), chi2 of the pixel sums {x2:.1f} over {n_w} (z = {zx:+.2f})")
+        ok = ok and abs(z) <= Z_LIMIT and abs(zx) <= Z_LIMIT
+    fig = "; ".join(figs)
+    assert ok, "FAILED: " + fig
+    return fig
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_frames(rng_kind, estimator, depth):
+    """((2, side, side, 4) float32 frames, [segments per view], [shadow rays per view]) of frame_views(), from the oracle, once."""
+    import oracle
+    frames, seg, shadow = np.empty((2, FRAME_SIDE, FRAME_SIDE, 4), np.float32), [], []
+    for i, v in enumerate(frame_views()):
+        p = abi.make_params(FRAME_SIDE, FRAME_SIDE, FRAME_SPP, depth, seed=v.seed, rng_kind=rng_kind, estimator=estimator)
+        frames[i], st = oracle.render(frame_blob(v), p, threads=8)
+        seg.append(int(st.segments))
+        shadow.append(int(st.shadow_rays))
+    frames.setflags(write=False)
+    return frames, seg, shadow
+
+
+QUERY_N, QUERY_SPP = 64, 64   # 64 independent keys: the variance of a z-test is estimated from them
+WALL_PROBE = (0.0, -WALL_R, 0.0, 0.0, 1.0, 0.0, 1e-3, 1e27)   # a wall point with its inward normal
+FREE_POINT = (0.0, 6.0, 0.0, 0.0, 0.0, 0.0, 1e-3, 1e27)       # 6 from the centre: the lamp is a cap about -y
+SH_Y0, SH_Y1 = 0.282094792, 0.488602512
+
+
+def _z_keys(x, want):
+    """(mean, z) of the mean of x (n,) against `want`, the variance estimated from the n independent keys."""
+    x = np.asarray(x, np.float64)
+    sd = x.std(ddof=1) / math.sqrt(len(x))
+    return float(x.mean()), (float((x.mean() - want) / sd) if sd > 0 else (0.0 if x.mean() == want else math.inf))
+
+
+def check_irradiance(out, estimator, depth):
+    """(QUERY_N, 4) irradiance probes at WALL_PROBE: pi (q Le + (1 - q) L_w) with q = a^2 of the probe's cosine lobe and L_w the
+    law's mean at the probe's depth convention (rtw.h: the probe's own ray is segment 1 of max_depth)."""
+    want = math.pi * shell_law(estimator, depth, "cosine").m1
+    figs, ok = [], bool((np.asarray(out)[:, 3] == 1.0).all())
+    for c in range(3):
+        mean, z = _z_keys(np.asarray(out)[:, c], want[c])
+        figs.append(f"channel {c}: irradiance {mean:.5f} (law {want[c]:.5f}, z = {z:+.2f})")
+        ok = ok and abs(z) <= Z_LIMIT
+    fig = "; ".join(figs)
+    assert ok, "FAILED: " + fig
+    return fig
+
+
+def check_sh(out, estimator, depth):
+    """(QUERY_N, 9, 4) coefficients at FREE_POINT. The lamp fills the cap of half-angle alpha about -y, sin(alpha) = 4 / 6: a share
+    f = (1 - cos(alpha)) / 2 of the sphere; every other direction meets the wall. c_0 = 4 pi Y0 (f Le + (1 - f) L_w) = 2 sqrt(pi)
+    (...); the integral of y over the cap is -pi sin(alpha)^2 and over the whole sphere 0, so c_1 (Y1 = K1 y) = -K1 pi
+    sin(alpha)^2 (Le - L_w) and the two other first-order coefficients (z, x) are 0."""
+    lw = shell_law(estimator, depth).m1 if depth > 0 else np.zeros(3)
+    sin2 = (LAMP_R / 6.0) ** 2
+    f = 0.5 * (1.0 - math.sqrt(1.0 - sin2))
+    want = {0: 4.0 * math.pi * SH_Y0 * (f + (1.0 - f) * lw), 1: -SH_Y1 * math.pi * sin2 * (1.0 - lw), 2: np.zeros(3), 3: np.zeros(3)}
+    figs, ok = [], bool((np.asarray(out)[..., 3] == 0.0).all())
+    for j, w in want.items():
+        zs = []
+        for c in range(3):
+            mean, z = _z_keys(np.asarray(out)[:, j, c], w[c])
+            zs.append(z)
+            ok = ok and abs(z) <= Z_LIMIT
+        figs.append(f"c_{j}: red {np.asarray(out)[:, j, 0].astype(np.float64).mean():+.5f} (law {w[0]:+.5f}), z = " + " ".join(f"{z:+.2f}" for z in zs))
+    fig = "; ".join(figs)
+    assert ok, "FAILED: " + fig
+    return fig
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_queries(rng_kind, estimator, depth):
+    """((QUERY_N, 4) irradiance probes, (QUERY_N, 9, 4) coefficients) assembled from the oracle's samples along rtw_probe's and
+    rtw_probe_sh's own directions (probe_ref, sh_ref) in the library's summation order."""
+    import probe_ref
+    import sh_ref
+    blob = shell_blob()
+
+    def samples(points, dirs):
+        out = np.empty((QUERY_SPP, QUERY_N, 3), np.float32)
+        for s in range(QUERY_SPP):
+            rays = probe_ref.rays_of(points, dirs, s)
+            pix, _, _ = R.expect(blob, rays[:, :3], (rays[:, :3] + rays[:, 3:6]).astype(np.float32), 1, depth, rng_kind=rng_kind,
+                                 sample_offset=s, estimator=estimator)
+            out[s] = pix[:, :3]
+        return out
+    probes = np.tile(np.array(WALL_PROBE, np.float32), (QUERY_N, 1))
+    rad = samples(probes, probe_ref.directions(probes, QUERY_SPP, rng_kind=rng_kind))
+    irr = np.ones((QUERY_N, 4), np.float32)
+    for i in range(QUERY_N):
+        irr[i, :3] = R.sum_in_order(rad[:, i], QUERY_SPP) * np.float32(3.14159265)
+    points = np.tile(np.array(FREE_POINT, np.float32), (QUERY_N, 1))
+    dirs = sh_ref.directions(QUERY_N, QUERY_SPP, rng_kind=rng_kind)
+    return irr, sh_ref.project(samples(points, dirs), dirs, QUERY_SPP)
+
+
+# ---------------------------------------------------------------- the measurement behind the MEASURED_CONSTANT_* values
+def measure_constants(verbose=False):
+    out = {"SHELL": 0.0, "CORRIDOR": 0.0, "TEXTURED": 0.0}
+    for name in CASES:
+        c = case(name)
+        k = c.fp32_constant()
+        if verbose:
+            print(f"{name:28s} {c.CONSTANT:9s} {k:.4f}")
+        out[c.CONSTANT] = max(out[c.CONSTANT], k)
+    return out
+
+
+if __name__ == "__main__":
+    for k_, v_ in measure_constants(verbose=True).items():
+        print(f"MEASURED_CONSTANT_{k_} = {v_:.4f}")

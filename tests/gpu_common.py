@@ -1,12 +1,15 @@
 """What the GPU test files of the query family and of the float64 checks share: the renderer fixture, the upload under chosen knobs,
-the bit-equality helpers, the golden fixtures, the stream-order check of a *_torch call and the sentinel Stats of the refusal tests.
+the bit-equality helpers, the golden fixtures, the stream-order check of a *_torch call, the sentinel Stats of the refusal tests and
+the GPU half of law_common.py: a case observed through rtw_radiance and rtw_render, held to its float64 law and to the oracle.
 A plain module (not a conftest): a test file imports what it uses by name, the `gpu` fixture included."""
+import functools
 import os
 import types
 
 import numpy as np
 import pytest
 
+import law_common
 from raytracing_weekend_amd import abi
 
 GOLD = os.path.join(abi.REPO_DIR, "tests", "golden")
@@ -33,6 +36,9 @@ def upload(gpu, monkeypatch, blob, how="as_uploaded", knobs=KNOBS, env=None):
     for k, v in dict(UPLOADS_LDS[how], **(env or {})).items():
         monkeypatch.setenv(k, v)
     gpu.upload_scene(blob)
+
+
+upload_lds = functools.partial(upload, knobs=UPLOAD_KNOBS)  # for the files that set no knob but the two read at upload
 
 
 # ---------------------------------------------------------------- the same bits
@@ -135,3 +141,46 @@ def sentinel_stats():
 
 def left_alone(st):
     return (st.segments, st.shadow_rays, st.seconds) == (77, 77, 7.0)
+
+
+# ---------------------------------------------------------------- a law_common.Case on the GPU: observed, then checked
+def radiance_observed(gpu, monkeypatch, case, how, rng, est, seed, base):
+    """The case through rtw_radiance under upload `how`: one sample per ray, ray j's keys by key_offset; alpha is 1."""
+    upload_lds(gpu, monkeypatch, case.blob, how)
+    st = abi.Stats()
+    out = gpu.radiance(case.rays(est), 1, case.depth, seed=seed, rng_kind=rng, estimator=est, key_offset=base, stats=st)
+    assert np.array_equal(out[:, 3], np.ones(len(out), np.float32))
+    return law_common.Observed(out[:, :3].reshape(case.m, case.keys_per_ray, 3), int(st.segments), int(st.shadow_rays))
+
+
+def render_observed(gpu, monkeypatch, case, path, rng, est, seed, base):
+    """The case through rtw_render of each ray's own blob, uploaded as is, by k_path (RTW_PATH=1) or the wavefront kernels (0)."""
+    for k in UPLOAD_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("RTW_PATH", path)
+
+    def render(blob, params):
+        gpu.upload_scene(blob)
+        return gpu.render(params)
+    return law_common.observe(render, case, rng, est, seed, base)
+
+
+def check_both(module, name, observed, run, counts):
+    """The float64 law of case `name` of `module` first (it takes the counts named in `counts` beside the samples), then the oracle's
+    bits on the keys of run = (rng, est, seed, base), then the oracle's counts: a failure says which side moved."""
+    rng, est, seed, base = run
+    print(module.check(name, observed.samples, est, **{k: getattr(observed, k) for k in counts}))
+    want = law_common.oracle_samples(module.case(name), rng, est, seed, base)
+    differ = int((words(np.asarray(observed.samples, np.float32)) != words(want.samples)).any(-1).sum())
+    assert same_bits(observed.samples, want.samples), f"{name}: {differ} samples differ from the oracle's"
+    for k in counts:
+        assert getattr(observed, k) == getattr(want, k), f"{name}: {k} {getattr(observed, k)}, the oracle's {getattr(want, k)}"
+
+
+def probe_is_pi_times_radiance(gpu, probes, out, rng, est, n=1024):
+    """Each of the first n irradiance probes `out` of one sample and one segment is, bit for bit, pi times rtw_radiance along
+    probe_ref.directions on the same key (the keys count from 0, so the first probes are the first rays)."""
+    import probe_ref
+    rays = probe_ref.rays_of(probes[:n], probe_ref.directions(probes[:n], 1, rng_kind=rng), 0)
+    rad = gpu.radiance(rays, 1, 1, rng_kind=rng, estimator=est, key_offset=0)
+    assert same_bits(out[:n, :3], rad[:, :3] * law_common.PI32)

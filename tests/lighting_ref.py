@@ -71,7 +71,6 @@ Nothing is left out of any case (the printed share is 0): the conditions above a
 Statistical limits are shading_ref's KS_LIMIT and Z_LIMIT; n = 16384 keys in every case, the deterministic ones too (a draw that
 leaked into some lanes' samples would show), 65536 where a channel's hit probability is below 0.05.
 """
-import functools
 import os
 import sys
 
@@ -80,13 +79,12 @@ import numpy as np
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import geometry_ref as G
-import radiance_ref as R
+import law_common as C
 import shading_ref as S
+from law_common import CORR, DRAWS, K_FACTOR, KS_LIMIT, MIX, N_STAT, NO_NEE, PI32, REF, RNGS, SEEDS, U, Z_LIMIT, _dot  # noqa: F401
 from raytracing_weekend_amd import abi
 
-REF, CORR, NO_NEE, MIX = abi.RTW_EST_REFERENCE, abi.RTW_EST_CORRECTED, abi.RTW_EST_CORRECTED_NO_NEE, abi.RTW_EST_MIXTURE
-U, K_FACTOR, KS_LIMIT, Z_LIMIT = S.U, S.K_FACTOR, S.KS_LIMIT, S.Z_LIMIT
-N_STAT, N_RARE = S.N_STAT, 4 * S.N_STAT
+N_RARE = 4 * N_STAT
 GRID = 2048
 QUANTILES = 16385
 COS_EPS = 1e-6                                        # DENOMINATOR_EPSILON, rectPdf.cu:14
@@ -102,10 +100,6 @@ MEASURED_CONSTANT_LIGHT = 4.0104  # the reference estimator at (1, 2, -0.5); the
 MEASURED_GRID_RANGE = 3.58e-7
 RANGE_SLACK = K_FACTOR * MEASURED_CONSTANT_LIGHT * U + MEASURED_GRID_RANGE  # relative: the fp32 bound of a sample plus the grid's
 LATTICE_NUDGE = 2.0 ** -30
-
-
-def _dot(a, b):
-    return (a * b).sum(-1)
 
 
 # ---------------------------------------------------------------- scene description (the law reads these, the blob is built from them)
@@ -423,7 +417,7 @@ def _constant(rgb):
     return S._constant(rgb)
 
 
-class LightCase(S.Case):
+class LightCase(C.Case):
     """One scene at one depth. lights: Light definitions; rects: the Rect primitives, the receiver first; pdf_rect: (axis, (a0, a1,
     b0, b1), k) of the header's rtw_pdf; media: shading_ref.media_scene's tuples."""
 
@@ -577,6 +571,7 @@ class ExactCase(LightCase):
     def __init__(self, *a, value=None, units=0.0, **kw):
         super().__init__(*a, **kw)
         self.value, self.units = value, units
+        self.drawn = bool(self.media)  # without a medium the case is deterministic: it runs once per generator
 
     def check(self, samples, estimator, shadow_rays=None, value_factor=1.0, **model):
         s = np.asarray(samples, np.float64).reshape(-1, 3)
@@ -684,34 +679,14 @@ CASES = {
     "through_medium-d1": lambda: _point_case(*MEDIUM_LIGHT, media=(MEDIUM,)),
 }
 CASES.update({f"point{i:02d}-d1": (lambda p=p, nrm=nrm: _point_case(p, nrm)) for i, (p, nrm) in enumerate(POINT_LIGHTS)})
-RNGS, DRAWS, SEEDS = S.RNGS, S.DRAWS, S.SEEDS
+COUNTS = ("shadow_rays",)  # what check takes beside the samples
+case, check = C.registry(CASES, "{name}, estimator {est}: ")
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    return CASES[name]()
-
-
-def drawn(name):
-    """Whether the case's samples depend on the draws (a deterministic case runs once per generator)."""
-    c = case(name)
-    return not isinstance(c, ExactCase) or bool(c.media)
-
-
-def check(name, samples, estimator, **kw):
-    """The assertions of case `name` on its samples (any shape (..., 3)); returns the figures for the caller to print."""
-    return f"{name}, estimator {estimator}: " + case(name).check(samples, estimator, **kw)
-
-
-@functools.lru_cache(maxsize=None)
 def oracle_samples(name, rng_kind, estimator, seed, key_base=0):
     """((1, keys_per_ray, 3) float32 samples, shadow rays): the oracle's answer for case `name`, computed once and left unchanged."""
-    import oracle
-    c = case(name)
-    img, st = oracle.render(R.ray_blob(c.blob, c.o[0], c.ll[0]), S.render_params(c, 0, rng_kind, estimator, seed, key_base), threads=4)
-    out = img[..., :3].reshape(1, c.keys_per_ray, 3).copy()
-    out.setflags(write=False)
-    return out, int(st.shadow_rays)
+    out = C.oracle_samples(case(name), rng_kind, estimator, seed, key_base)
+    return out.samples, out.shadow_rays
 
 
 def irradiance_law(name):
@@ -722,7 +697,7 @@ def irradiance_law(name):
     return {int(np.nonzero(c.rects[j].color)[0][0]): (float(c.rects[j].color.max()), hits.visible[j]) for j in hits.emitters}
 
 
-def check_irradiance(name, samples, pi32=np.float32(3.14159265)):
+def check_irradiance(name, samples, pi32=PI32):
     """The assertions on (n, 3) float32 irradiance probes of one sample and one segment each at the receiver point of case `name`:
     every probe is exactly 0 or float32(pi) * Le in the emitter's channel, the hit count per channel is binomial with p = the
     visible form factor, the mean is pi * Le * F by z-test."""

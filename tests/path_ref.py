@@ -85,13 +85,12 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import camera_ref as CR
 import geometry_ref as G
+import law_common as C
 import radiance_ref as R
 import shading_ref as S
+from law_common import CORR, DRAWS, K_FACTOR, MIX, N_STAT, NO_NEE, PI32, REF, RNGS, SEEDS, U, Z_LIMIT, _dot, _unit  # noqa: F401
 from raytracing_weekend_amd import abi
 
-U, K_FACTOR, Z_LIMIT, N_STAT = S.U, S.K_FACTOR, S.Z_LIMIT, S.N_STAT
-REF, CORR, NO_NEE, MIX = abi.RTW_EST_REFERENCE, abi.RTW_EST_CORRECTED, abi.RTW_EST_CORRECTED_NO_NEE, abi.RTW_EST_MIXTURE
-RNGS, DRAWS, SEEDS = S.RNGS, S.DRAWS, S.SEEDS
 # Pearson's statistic over c cells has, under the law, the chi-square distribution of c - 1 degrees of freedom (no parameter is
 # fitted); the case is rejected when P(chi2_{c-1} >= X) < ALPHA = 1e-4, the project's per-case level. The quantile is not tabulated:
 # chi2_sf is the exact survival function - for k = 2 m, e^{-x/2} sum_{i<m} (x/2)^i / i!; for odd k, erfc(sqrt(x/2)) + e^{-x/2}
@@ -308,13 +307,13 @@ def corridor_walk(o, d, k, ft=np.float64, unit_in=True):
 
 def sky(u, ft=np.float64):
     """miss.cu:8-16 along direction u."""
-    un = S._unit(np.asarray(u, ft))
+    un = _unit(np.asarray(u, ft))
     t = ft(0.5) * (un[1] + ft(1.0))
     return (ft(1.0) - t) * np.ones(3, ft) + t * np.array(SKY_TOP, ft)
 
 
 # ---------------------------------------------------------------- cases
-class PathCase(S.Case):
+class PathCase(C.Case):
     """m rays with keys_per_ray keys each; laws(estimator, **model): one Law per ray; CONSTANT: the measured constant's name."""
     estimators = (REF, CORR)
     shadow = "none"  # "none": no probe is traced; "some": probes are traced, their number is the oracle's
@@ -578,30 +577,14 @@ CASES = _cases()
 SHELL_MEANS_AT_50 = {False: (0.5, 1.0 / 7.0, 1.0 / 17.0), True: (4.0 / 17.0, 2.0 / 41.0, 1.0 / 53.0)}  # rho q / (1 - rho (1 - q)), by lobe
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    return CASES[name]()
+COUNTS = ("segments", "shadow_rays")  # what check takes beside the samples
+case, check = C.registry(CASES, "{name}, estimator {est}: ")
 
 
-def check(name, samples, estimator, **kw):
-    """The assertions of case `name` on a sample array (m, keys_per_ray, 3); returns the figures for the caller to print."""
-    return f"{name}, estimator {estimator}: " + case(name).check(samples, estimator, **kw)
-
-
-@functools.lru_cache(maxsize=None)
 def oracle_samples(name, rng_kind, estimator, seed, key_base=0):
     """((m, keys_per_ray, 3) float32, segments, shadow rays): the oracle's samples and counts of case `name`, computed once and left
     unchanged."""
-    import oracle
-    c = case(name)
-    out = np.empty((c.m, c.keys_per_ray, 3), np.float32)
-    seg = shadow = 0
-    for j in range(c.m):
-        img, st = oracle.render(R.ray_blob(c.blob, c.o[j], c.ll[j]), S.render_params(c, j, rng_kind, estimator, seed, key_base), threads=4)
-        out[j] = img[..., :3].reshape(c.keys_per_ray, 3)
-        seg, shadow = seg + int(st.segments), shadow + int(st.shadow_rays)
-    out.setflags(write=False)
-    return out, seg, shadow
+    return tuple(C.oracle_samples(case(name), rng_kind, estimator, seed, key_base))
 
 
 # ---------------------------------------------------------------- the shell seen by a camera, a probe and a light probe
@@ -659,8 +642,8 @@ def classify(which):
     for a in np.linspace(-1.0, 2.0, 7):
         for b in np.linspace(-1.0, 2.0, 7):
             o, d, _, _ = CR.camera_rays(cam, view.camera_type, frame, {"r0": zero + a, "r1": zero + b, "r2": zero, "r3": zero})
-            bq, dd = S._dot(o, d), S._dot(d, d)
-            disc = bq * bq - dd * (S._dot(o, o) - LAMP_R ** 2)
+            bq, dd = _dot(o, d), _dot(d, d)
+            disc = bq * bq - dd * (_dot(o, o) - LAMP_R ** 2)
             hits.append((disc > 0) & (bq < 0))
     hits = np.array(hits)
     return np.where(hits.all(0), 1, np.where(hits.any(0), -1, 0))
@@ -776,7 +759,7 @@ def oracle_queries(rng_kind, estimator, depth):
     rad = samples(probes, probe_ref.directions(probes, QUERY_SPP, rng_kind=rng_kind))
     irr = np.ones((QUERY_N, 4), np.float32)
     for i in range(QUERY_N):
-        irr[i, :3] = R.sum_in_order(rad[:, i], QUERY_SPP) * np.float32(3.14159265)
+        irr[i, :3] = R.sum_in_order(rad[:, i], QUERY_SPP) * PI32
     points = np.tile(np.array(FREE_POINT, np.float32), (QUERY_N, 1))
     dirs = sh_ref.directions(QUERY_N, QUERY_SPP, rng_kind=rng_kind)
     return irr, sh_ref.project(samples(points, dirs), dirs, QUERY_SPP)

@@ -103,21 +103,15 @@ import numpy as np
 if __name__ == "__main__":  # `python tests/shading_ref.py` from anywhere: the package lies one directory up
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import geometry_ref as G
-import radiance_ref as R
+import law_common as C
+# the limits, the draws, Case and render_params lived here first: they keep their names in this module (S.N_STAT, S.Case, ...)
+from law_common import CORR, DRAWS, K_FACTOR, KEY_SHIFT, KS_LIMIT, N_STAT, REF, RNGS, SEEDS, SIDE, U, Z_LIMIT  # noqa: F401
+from law_common import Case, _dot, _unit, render_params  # noqa: F401
 from raytracing_weekend_amd import abi
 
-U = 2.0 ** -24
-K_FACTOR = 4.0
-KS_LIMIT = 2.23       # Kolmogorov: P(D sqrt(n) > 2.23) = 2 exp(-2 * 2.23^2) = 0.96e-4
-Z_LIMIT = 3.89        # normal, two-sided: P(|z| > 3.89) = 1.0e-4
-SEEDS = (0x6314759, 0x0BADC0DE)  # the project's default seed and one more; both fixed
-KEY_SHIFT = 1 << 20              # TEA+LCG takes no seed (include/rtw.h rtw_rng_kind): its second sample comes from other stream keys
-SIDE = 128
-N_STAT = SIDE * SIDE  # samples of a statistical case: 128 x 128 keys, one sample each
 CRITICAL_EPS = 1e-3   # incidences with |ratio * sin_i - 1| below this are left out
 SIN_EPS = 1e-3        # checker points with a |sin| below this are left out
 NOISE_GRADIENT = 3.0  # bound of |grad noise|: the smoothstep's slope 1.5 times the corner dots' range, plus the unit gradient
-REF, CORR = abi.RTW_EST_REFERENCE, abi.RTW_EST_CORRECTED
 
 # `python tests/shading_ref.py`: this file at float32 against itself at float64, in the units of the module text
 MEASURED_CONSTANT_MIRROR = 0.2579   # direction-mirror_above, reference estimator
@@ -128,14 +122,6 @@ MEASURED_CONSTANT_IMAGE = 0.1511    # texture-checker_noise_image (the image chi
 
 
 # ---------------------------------------------------------------- small algebra, at the precision of its arguments
-def _dot(a, b):
-    return (a * b).sum(-1)
-
-
-def _unit(v):
-    return v / np.sqrt(_dot(v, v))[..., None]
-
-
 def sky_red(u, ft=np.float64):
     """Red of the sky along direction u (miss.cu:8-16): (1 - t) * 1 + t * 0.5 with t = 0.5 (unit(u).y + 1)."""
     un = _unit(np.asarray(u, ft))
@@ -517,28 +503,6 @@ def strip_points(blob, n, grid, seed):
 
 
 # ---------------------------------------------------------------- cases
-class Case:
-    """m rays (o, d), each traced on keys_per_ray consecutive stream keys with one sample per key: ray j owns the keys
-    j * keys_per_ray ...; a sample array has the shape (m, keys_per_ray, 3)."""
-    depth = 2
-    estimators = (REF, CORR)
-
-    def __init__(self, blob, o, d, keys_per_ray):
-        self.blob, self.keys_per_ray = blob, keys_per_ray
-        self.o = np.atleast_2d(np.asarray(o, np.float32))
-        self.ll = (self.o + np.atleast_2d(np.asarray(d, np.float32))).astype(np.float32)
-        self.d = ((np.float32(0) + self.ll) - self.o).astype(np.float64)  # the bits the camera ray carries
-        assert np.array_equal(self.d, np.atleast_2d(np.asarray(d, np.float64))), "the direction is not exact in float32"
-        self.m = len(self.o)
-
-    def rays(self, estimator):
-        """(m * keys_per_ray, 8) float32 for rtw_radiance: ray j repeated keys_per_ray times, tmin = the estimator's start distance."""
-        return np.repeat(R.make_rays(self.o, self.ll, estimator), self.keys_per_ray, axis=0)
-
-    def tmin(self, estimator):
-        return float(np.float32(1e-6 if estimator == REF else 1e-3))
-
-
 def lost_count(red):
     return int((np.asarray(red) == 0).sum())
 
@@ -719,6 +683,7 @@ class EmitterCase(Case):
     colour exactly where dot(n, d) < 0 and black elsewhere (diffuseLight.cu:54-62); RTW_MAT_NORMAL (color None) ends the path with
     its colour 0.5 n + 0.5 in the attenuation, which never reaches the radiance (normalMaterial.cu:29-30): black."""
     depth = 1
+    drawn = False
 
     def __init__(self, mat, flip, color):
         d = np.array([(0.0, -1.0, 0.0), (0.5, -1.0, 0.25), (-3.0, -1.0, 2.0), (0.0, 1.0, 0.0), (0.5, 1.0, 0.25), (-3.0, 1.0, 2.0)])
@@ -737,6 +702,7 @@ class TextureCase(Case):
     """Rays along -y from one above to exactly representable points of emitters that carry a texture, max_depth = 1: the sample is
     the texture's value at the point."""
     depth = 1
+    drawn = False
 
     def __init__(self, blob, points, strips, noise_constant=0.0, classes=None):
         super().__init__(blob, points + np.array([0.0, 1.0, 0.0]), np.broadcast_to(np.array([0.0, -1.0, 0.0]), points.shape), 1)
@@ -912,43 +878,13 @@ CASES = {}
 for _family, _cases in (("direction", DIRECTION_CASES), ("lambert", LAMBERT_CASES), ("fuzz", FUZZ_CASES), ("slab", SLAB_CASES),
                         ("media", MEDIA_CASES), ("emitter", EMITTER_CASES), ("texture", TEXTURE_CASES), ("texture32", TEXTURE_SUBSETS)):
     CASES.update({f"{_family}-{k}": v for k, v in _cases.items()})
-RNGS = (abi.RTW_RNG_PHILOX, abi.RTW_RNG_TEA_LCG)
-# generator -> the (seed, key base) of its two independent samples
-DRAWS = {abi.RTW_RNG_PHILOX: ((SEEDS[0], 0), (SEEDS[1], 0)), abi.RTW_RNG_TEA_LCG: ((SEEDS[0], 0), (SEEDS[0], KEY_SHIFT))}
+COUNTS = ()  # check takes the samples alone
+case, check = C.registry(CASES, "{name}: ")
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    return CASES[name]()
-
-
-def check(name, samples, estimator, **model):
-    """The assertions of case `name` on a sample array (m, keys_per_ray, 3); returns the figures for the caller to print."""
-    return f"{name}: " + case(name).check(np.asarray(samples), estimator, **model)
-
-
-def render_params(c, j, rng_kind, estimator, seed, key_base=0):
-    """The rtw_params under which a render of radiance_ref.ray_blob(c.blob, c.o[j], c.ll[j]) gives ray j's samples on ray j's keys,
-    key_base + j * keys_per_ray ...: min(keys_per_ray, 128) pixels wide, the rows from key_base / width + j * rows - a render's
-    stream key is width * y + x."""
-    w = min(c.keys_per_ray, SIDE)
-    rows = c.keys_per_ray // w
-    assert key_base % w == 0
-    r0 = key_base // w + j * rows
-    return abi.make_params(w, r0 + rows, 1, c.depth, seed=seed, row0=r0, row1=r0 + rows, rng_kind=rng_kind, estimator=estimator)
-
-
-@functools.lru_cache(maxsize=None)
 def oracle_samples(name, rng_kind, estimator, seed, key_base=0):
     """(m, keys_per_ray, 3) float32: the oracle's samples of case `name`, computed once and left unchanged."""
-    import oracle
-    c = case(name)
-    out = np.empty((c.m, c.keys_per_ray, 3), np.float32)
-    for j in range(c.m):
-        img, _ = oracle.render(R.ray_blob(c.blob, c.o[j], c.ll[j]), render_params(c, j, rng_kind, estimator, seed, key_base))
-        out[j] = img[..., :3].reshape(c.keys_per_ray, 3)
-    out.setflags(write=False)
-    return out
+    return C.oracle_samples(case(name), rng_kind, estimator, seed, key_base).samples
 
 
 # ---------------------------------------------------------------- the measurement behind the MEASURED_CONSTANT_* values

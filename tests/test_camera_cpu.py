@@ -13,6 +13,7 @@ import pytest
 
 import camera_ref as L
 import view_ref as V
+from law_common import measured_band
 from raytracing_weekend_amd import abi, bake
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -220,9 +221,9 @@ def test_measured_constants_hold_and_the_law_alone_stays_inside_the_cap():
     build = L.measure_builder_constant()
     print(dirs, depth, build, {k: round(100 * v, 2) for k, v in left.items()})
     for kind, got in dirs.items():
-        assert L.MEASURED_CONSTANT_DIR[kind] * 0.9 <= got <= L.MEASURED_CONSTANT_DIR[kind] * 1.0005, (kind, got)
-    assert L.MEASURED_CONSTANT_DEPTH * 0.9 <= depth <= L.MEASURED_CONSTANT_DEPTH * 1.0005, depth
-    assert L.MEASURED_CONSTANT_BUILD * 0.9 <= build <= L.MEASURED_CONSTANT_BUILD * 1.0005, build
+        measured_band(got, L.MEASURED_CONSTANT_DIR[kind], f"MEASURED_CONSTANT_DIR[{kind!r}]")
+    measured_band(depth, L.MEASURED_CONSTANT_DEPTH, "MEASURED_CONSTANT_DEPTH")
+    measured_band(build, L.MEASURED_CONSTANT_BUILD, "MEASURED_CONSTANT_BUILD")
     assert max(left.values()) <= L.MAX_LEFT_OUT, left
     assert abs(L.sum_units(L.MEAN_SPP) - 14.3264) < 1e-4
 

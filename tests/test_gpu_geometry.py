@@ -10,14 +10,11 @@ import pytest
 import geometry_ref as G
 import guides_ref
 import oracle
-import gpu_common
 from gpu_common import UPLOADS_LDS as UPLOADS, gpu, same_bits  # noqa: F401
+from gpu_common import upload_lds as upload
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
-
-
-upload = functools.partial(gpu_common.upload, knobs=gpu_common.UPLOAD_KNOBS)
 
 
 # ---------------------------------------------------------------- (a) closest hits against the float64 reference

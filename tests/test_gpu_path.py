@@ -4,70 +4,33 @@ counts of the same keys, so that a failure says which side moved. Entries: rtw_r
 tree forced, with the tree outside LDS); rtw_render of radiance_ref.ray_blob - every pixel the same ray on its own key - through
 k_path and through the wavefront kernels; whole frames from a camera inside the shell through rtw_render (both pipelines) and
 rtw_views; rtw_probe and rtw_probe_sh in the shell."""
-import functools
-
 import numpy as np
 import pytest
 
+import law_common as C
 import path_ref as P
 import radiance_ref as R
 import shading_ref as S
-import gpu_common
-from gpu_common import UPLOADS_LDS as UPLOADS, gpu, same_bits  # noqa: F401
+from gpu_common import UPLOADS_LDS as UPLOADS, check_both, gpu, radiance_observed, render_observed  # noqa: F401
+from gpu_common import upload_lds as upload
 from raytracing_weekend_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-upload = functools.partial(gpu_common.upload, knobs=gpu_common.UPLOAD_KNOBS)
-
-
-def runs(hows, draws):
-    """draws: which of the generator's independent samples (shading_ref.DRAWS: a second seed for Philox, other keys for TEA+LCG)."""
-    out = []
-    for name in P.CASES:
-        for est in P.case(name).estimators:
-            out += [pytest.param(name, how, rng, est, seed, base, id=f"{name}-{how}-rng{rng}-est{est}-seed{seed:x}-key{base}")
-                    for how in hows for rng in P.RNGS for seed, base in P.DRAWS[rng][draws]]
-    return out
-
-
-def both(name, got, segments, shadow_rays, rng, est, seed, base):
-    """The float64 law first, the oracle's bits and counts second."""
-    print(P.check(name, got, est, segments=segments, shadow_rays=shadow_rays))
-    want, want_segments, want_shadow = P.oracle_samples(name, rng, est, seed, base)
-    differ = int((np.asarray(got, np.float32).view(np.uint32) != want.view(np.uint32)).any(-1).sum())
-    print(f"{name}: {differ} samples differ from the oracle's; segments {segments} (oracle {want_segments}), shadow rays {shadow_rays} (oracle {want_shadow})")
-    assert same_bits(got, want), f"{name}: {differ} samples differ from the oracle's"
-    assert (segments, shadow_rays) == (want_segments, want_shadow), f"{name}: counts {(segments, shadow_rays)}, the oracle's {(want_segments, want_shadow)}"
-
 
 # ---------------------------------------------------------------- entry 1: rtw_radiance, one sample per ray, keys by key_offset
-@pytest.mark.parametrize("name,how,rng,est,seed,base", runs(list(UPLOADS), slice(0, 1)) + runs(["as_uploaded"], slice(1, 2)))
+# (the second of the generator's independent samples as uploaded only)
+@pytest.mark.parametrize("name,how,rng,est,seed,base", C.runs(P, hows=list(UPLOADS), draws=slice(0, 1)) + C.runs(P, hows=["as_uploaded"], draws=slice(1, 2)))
 def test_radiance_meets_the_law_and_the_oracle(gpu, monkeypatch, name, how, rng, est, seed, base):
-    c = P.case(name)
-    upload(gpu, monkeypatch, c.blob, how)
-    st = abi.Stats()
-    out = gpu.radiance(c.rays(est), 1, c.depth, seed=seed, rng_kind=rng, estimator=est, key_offset=base, stats=st)
-    assert np.array_equal(out[:, 3], np.ones(len(out), np.float32))
-    both(name, out[:, :3].reshape(c.m, c.keys_per_ray, 3), int(st.segments), int(st.shadow_rays), rng, est, seed, base)
+    """The float64 law first, the oracle's bits and counts second."""
+    check_both(P, name, radiance_observed(gpu, monkeypatch, P.case(name), how, rng, est, seed, base), (rng, est, seed, base), P.COUNTS)
 
 
 # ---------------------------------------------------------------- entry 2: rtw_render of the ray's own blob, one upload per ray
 @pytest.mark.parametrize("path", ["1", "0"])  # k_path (the default) / the wavefront kernels
-@pytest.mark.parametrize("name,how,rng,est,seed,base", runs(["as_uploaded"], slice(0, 1)))
+@pytest.mark.parametrize("name,how,rng,est,seed,base", C.runs(P, hows=["as_uploaded"], draws=slice(0, 1)))
 def test_render_meets_the_law_and_the_oracle(gpu, monkeypatch, name, how, rng, est, seed, base, path):
-    for k in ("RTW_BRUTE_MAX", "RTW_LDS_KB"):
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("RTW_PATH", path)
-    c = P.case(name)
-    got = np.empty((c.m, c.keys_per_ray, 3), np.float32)
-    segments = shadow_rays = 0
-    for j in range(c.m):
-        gpu.upload_scene(R.ray_blob(c.blob, c.o[j], c.ll[j]))
-        img, st = gpu.render(S.render_params(c, j, rng, est, seed, base))
-        got[j] = img[..., :3].reshape(c.keys_per_ray, 3)
-        segments, shadow_rays = segments + int(st.segments), shadow_rays + int(st.shadow_rays)
-    both(name, got, segments, shadow_rays, rng, est, seed, base)
+    check_both(P, name, render_observed(gpu, monkeypatch, P.case(name), path, rng, est, seed, base), (rng, est, seed, base), P.COUNTS)
 
 
 def test_dark_light_render_runs_the_one_light_route(gpu, monkeypatch):

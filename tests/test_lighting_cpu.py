@@ -3,27 +3,18 @@ material programs that shares nothing with the oracle: the light sample alone (m
 estimator), emitter hits after it (max_depth = 2, the three corrected estimators), point lights held to a float64 value. Thresholds
 come from lighting_ref and shading_ref alone: 4 x the measured fp32-against-float64 constant for deterministic values, Kolmogorov
 and binomial limits at alpha = 1e-4 for the laws."""
+import functools
+
 import numpy as np
 import pytest
 
+import law_common as C
 import lighting_ref as L
-from raytracing_weekend_amd import abi
 
 REF, CORR, NO_NEE, MIX = L.REF, L.CORR, L.NO_NEE, L.MIX
 
 
-def runs():
-    """(case, generator, estimator, seed, key base): every case under the estimators it is defined for, both generators, both of
-    the generator's independent samples (shading_ref.DRAWS) where the samples depend on draws at all."""
-    out = []
-    for name in L.CASES:
-        for est in L.case(name).estimators:
-            out += [pytest.param(name, rng, est, seed, base, id=f"{name}-rng{rng}-est{est}-seed{seed:x}-key{base}")
-                    for rng in L.RNGS for seed, base in L.DRAWS[rng][:2 if L.drawn(name) else 1]]
-    return out
-
-
-@pytest.mark.parametrize("name,rng,est,seed,base", runs())
+@pytest.mark.parametrize("name,rng,est,seed,base", C.runs(L))
 def test_oracle_matches_float64_reference(name, rng, est, seed, base):
     samples, shadow_rays = L.oracle_samples(name, rng, est, seed, base)
     print(L.check(name, samples, est, shadow_rays=shadow_rays))
@@ -40,7 +31,7 @@ def test_oracle_irradiance_is_pi_times_the_emitters_form_factors(name, rng):
     probes = np.tile(np.array([0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1e-3, 1e27], np.float32), (L.N_RARE, 1))
     rays = probe_ref.rays_of(probes, probe_ref.directions(probes, 1, rng_kind=rng), 0)
     pix, _, _ = R.expect(c.blob, rays[:, :3], (rays[:, :3] + rays[:, 3:6]).astype(np.float32), 1, 1, rng_kind=rng, estimator=CORR)
-    print(L.check_irradiance(name, pix[:, :3] * np.float32(3.14159265)))
+    print(L.check_irradiance(name, pix[:, :3] * C.PI32))
 
 
 def test_the_cases_are_what_their_names_say():
@@ -78,7 +69,7 @@ def test_the_cases_are_what_their_names_say():
 def test_measured_constant_holds():
     got = L.measure_constant()
     print(got)
-    assert L.MEASURED_CONSTANT_LIGHT * 0.9 <= got <= L.MEASURED_CONSTANT_LIGHT * 1.0005
+    C.measured_band(got, L.MEASURED_CONSTANT_LIGHT, "MEASURED_CONSTANT_LIGHT")
 
 
 def test_grids_agree_with_the_closed_forms_and_with_themselves():
@@ -90,16 +81,11 @@ def test_grids_agree_with_the_closed_forms_and_with_themselves():
         assert err < 1e-5, what
         if what.endswith("extremes"):
             extremes = max(extremes, err)
-    assert 0.9 * L.MEASURED_GRID_RANGE <= extremes <= 1.0005 * L.MEASURED_GRID_RANGE, f"MEASURED_GRID_RANGE: measured {extremes:.3e}"
+    C.measured_band(extremes, L.MEASURED_GRID_RANGE, "MEASURED_GRID_RANGE")
 
 
 # ---------------------------------------------------------------- negative controls: the laws reject wrong models
-def rejected(name, est, rng=abi.RTW_RNG_PHILOX, **wrong):
-    samples, shadow_rays = L.oracle_samples(name, rng, est, L.SEEDS[0])
-    L.check(name, samples, est, shadow_rays=shadow_rays)  # the right model passes on these very samples
-    with pytest.raises(AssertionError) as e:
-        L.check(name, samples, est, shadow_rays=shadow_rays, **wrong)
-    print(f"{name}, estimator {est}, with {wrong}: rejected, {str(e.value).split(' || ')[0]}")
+rejected = functools.partial(C.rejected, L)
 
 
 @pytest.mark.parametrize("est", [REF, CORR])

@@ -4,11 +4,13 @@ closed-form law for every sample), the corridor (a deterministic one, plain and 
 shell, irradiance and light probes there. Then the negative controls - the same checkers must reject the loops one could have
 written instead -, the measured fp32 constants, and the input conditions the GPU tests rely on. Thresholds come from path_ref and
 shading_ref alone."""
+import functools
 import math
 
 import numpy as np
 import pytest
 
+import law_common as C
 import path_ref as P
 import radiance_ref as R
 from raytracing_weekend_amd import abi
@@ -16,16 +18,7 @@ from raytracing_weekend_amd import abi
 REF, CORR, NO_NEE, MIX = P.REF, P.CORR, P.NO_NEE, P.MIX
 
 
-def runs():
-    out = []
-    for name in P.CASES:
-        for est in P.case(name).estimators:
-            out += [pytest.param(name, rng, est, seed, base, id=f"{name}-rng{rng}-est{est}-seed{seed:x}-key{base}")
-                    for rng in P.RNGS for seed, base in P.DRAWS[rng]]
-    return out
-
-
-@pytest.mark.parametrize("name,rng,est,seed,base", runs())
+@pytest.mark.parametrize("name,rng,est,seed,base", C.runs(P))
 def test_oracle_meets_the_law(name, rng, est, seed, base):
     samples, segments, shadow_rays = P.oracle_samples(name, rng, est, seed, base)
     print(P.check(name, samples, est, segments=segments, shadow_rays=shadow_rays))
@@ -93,8 +86,7 @@ def test_measured_constants_hold():
     got = P.measure_constants()
     print(got)
     for k, v in got.items():
-        rec = getattr(P, "MEASURED_CONSTANT_" + k)
-        assert 0.0 < v <= rec * 1.0005 and v >= rec * 0.9, f"MEASURED_CONSTANT_{k}: measured {v:.4f}, recorded {rec}"
+        C.measured_band(v, getattr(P, "MEASURED_CONSTANT_" + k), f"MEASURED_CONSTANT_{k}")
 
 
 def test_input_conditions_hold():
@@ -143,12 +135,7 @@ def test_scene_preparation_accepts_the_scenes(tmp_path):
 
 
 # ---------------------------------------------------------------- negative controls: the checkers reject the other loops
-def rejected(name, est, rng=abi.RTW_RNG_PHILOX, **wrong):
-    samples, segments, shadow_rays = P.oracle_samples(name, rng, est, P.SEEDS[0])
-    P.check(name, samples, est, segments=segments, shadow_rays=shadow_rays)  # the right law passes on these very samples
-    with pytest.raises(AssertionError) as e:
-        P.check(name, samples, est, segments=segments, shadow_rays=shadow_rays, **wrong)
-    print(f"{name}, estimator {est}, with {sorted(wrong)}: rejected, {str(e.value)[:300]}")
+rejected = functools.partial(C.rejected, P)
 
 
 RHO_MAX = float(np.float32(max(P.RHO)))
@@ -200,19 +187,14 @@ def test_control_the_oracle_without_roulette_is_rejected(name, est):
     """The other way round: a renderer that is wrong, under the right law. rtwo_set_debug(1) switches the oracle's roulette off (the
     hook of test_oracle_physics.py: the draws are consumed, nobody dies, nothing is rescaled)."""
     import oracle
-    import shading_ref as S
-    c = P.case(name)
     lib = oracle.load()
     lib.rtwo_set_debug(1)
     try:
-        got, segments = np.empty((c.m, c.keys_per_ray, 3), np.float32), 0
-        for j in range(c.m):
-            img, st = oracle.render(R.ray_blob(c.blob, c.o[j], c.ll[j]), S.render_params(c, j, abi.RTW_RNG_PHILOX, est, P.SEEDS[0]))
-            got[j], segments = img[..., :3].reshape(c.keys_per_ray, 3), segments + int(st.segments)
+        got = C.observe(oracle.render, P.case(name), abi.RTW_RNG_PHILOX, est, P.SEEDS[0], 0)
     finally:
         lib.rtwo_set_debug(0)
     with pytest.raises(AssertionError) as e:
-        P.check(name, got, est, segments=segments)
+        P.check(name, got.samples, est, segments=got.segments)
     print(f"{name}, estimator {est}: rejected, {str(e.value)[:300]}")
 
 

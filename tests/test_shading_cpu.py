@@ -2,36 +2,21 @@
 shares nothing with the oracle: single scatter events observed through the sky (max_depth = 2), free flights observed through an
 emitter behind the medium (max_depth = 1), textures observed on an emitter (max_depth = 1). Thresholds come from shading_ref alone:
 4 x its own fp32-against-float64 constants for deterministic values, Kolmogorov and binomial limits at alpha = 1e-4 for the laws."""
+import functools
+
 import numpy as np
 import pytest
 
+import law_common as C
 import shading_ref as S
 from raytracing_weekend_amd import abi
 
 REF, CORR = S.REF, S.CORR
 
 
-def runs(names, draws=2):
-    """(case, generator, estimator, seed, key base) of every case of the list, for the estimators the case is defined for and the
-    first `draws` of the generator's independent samples (shading_ref.DRAWS: a second seed for Philox, other keys for TEA+LCG)."""
-    out = []
-    for name in names:
-        for est in S.case(name).estimators:
-            out += [pytest.param(name, rng, est, seed, base, id=f"{name}-rng{rng}-est{est}-seed{seed:x}-key{base}")
-                    for rng in S.RNGS for seed, base in S.DRAWS[rng][:draws]]
-    return out
-
-
-def family(prefix):
-    return [n for n in S.CASES if n.startswith(prefix + "-")]
-
-
-STATISTICAL = family("direction") + family("lambert") + family("fuzz") + family("slab") + family("media")
-# a case without draws gives the same samples whatever the seed and the keys: both generators, once
-DRAW_FREE = family("emitter") + family("texture") + family("texture32")
-
-
-@pytest.mark.parametrize("name,rng,est,seed,base", runs(STATISTICAL) + runs(DRAW_FREE, 1))
+# the statistical families on both of the generator's independent samples; a case without draws (emitter, texture, texture32) gives
+# the same samples whatever the seed and the keys: both generators, once
+@pytest.mark.parametrize("name,rng,est,seed,base", C.runs(S))
 def test_oracle_matches_float64_reference(name, rng, est, seed, base):
     print(S.check(name, S.oracle_samples(name, rng, est, seed, base), est))
 
@@ -45,7 +30,7 @@ def test_measured_constants_hold():
     got.update({"NOISE " + k: v for k, v in got.pop("NOISE").items()})
     assert set(got) == set(recorded)
     for k, v in got.items():
-        assert 0.0 < v <= recorded[k] * 1.0005 and v >= recorded[k] * 0.9, f"MEASURED_CONSTANT_{k}: measured {v:.4f}, recorded {recorded[k]}"
+        C.measured_band(v, recorded[k], f"MEASURED_CONSTANT_{k}")
 
 
 def test_quadratures_are_accurate_to_1e_6():
@@ -55,12 +40,7 @@ def test_quadratures_are_accurate_to_1e_6():
 
 
 # ---------------------------------------------------------------- negative controls: the checkers reject wrong expectations
-def rejected(name, est, rng=abi.RTW_RNG_PHILOX, samples=None, **wrong):
-    samples = S.oracle_samples(name, rng, est, S.SEEDS[0]) if samples is None else samples
-    S.check(name, samples, est)  # the right expectation passes on these very samples
-    with pytest.raises(AssertionError) as e:
-        S.check(name, samples, est, **wrong)
-    print(f"{name} with {wrong}: rejected, {e.value}")
+rejected = functools.partial(C.rejected, S)
 
 
 @pytest.mark.parametrize("name", ["lambert-normal_up", "lambert-tangent_x", "lambert-tangent_z"])
@@ -88,14 +68,14 @@ def more_samples(name, est, n):
     import oracle
     import radiance_ref as R
     c = S.case(name)
-    img, _ = oracle.render(R.ray_blob(c.blob, c.o[0], c.ll[0]), abi.make_params(S.SIDE, n // S.SIDE, 1, c.depth, estimator=est))
-    return img[..., :3].reshape(1, n, 3)
+    img, st = oracle.render(R.ray_blob(c.blob, c.o[0], c.ll[0]), abi.make_params(S.SIDE, n // S.SIDE, 1, c.depth, estimator=est))
+    return C.Observed(img[..., :3].reshape(1, n, 3), int(st.segments), int(st.shadow_rays))
 
 
 @pytest.mark.parametrize("name", ["media-box_normal", "media-sphere_off_centre"])
 def test_control_density_5_percent_off_is_rejected(name):
     for est in (REF, CORR):
-        rejected(name, est, samples=more_samples(name, est, CONTROL_N), density_factor=1.05)
+        rejected(name, est, observed=more_samples(name, est, CONTROL_N), density_factor=1.05)
 
 
 @pytest.mark.parametrize("name", ["media-box_normal", "media-sphere_off_centre", "media-box_xformed"])

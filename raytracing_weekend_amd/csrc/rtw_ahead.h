@@ -23,6 +23,12 @@
 #ifndef RTW_PATH_NEE1
 #define RTW_PATH_NEE1 1
 #endif
+// The fixed-shape walk (DESIGN.md 4.1 "The metric scene's list shape is a compile-time fact"): 1: k_path<..., NEE1 = 1, SHAPE> walks the
+// LDS lists with the shape's groups and counts compiled in (rtw_device.h walk_lds<ANY_HIT, SHAPE>); 0: those instantiations are the
+// one-light instantiation's text
+#ifndef RTW_PATH_SHAPE
+#define RTW_PATH_SHAPE 1
+#endif
 
 namespace rtwk {
 

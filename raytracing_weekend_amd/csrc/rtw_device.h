@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 #include "../../include/rtw.h"
 
 #define RTW_DEV __device__ __forceinline__
@@ -944,14 +946,8 @@ RTW_DEV void traverse_brute(const DScene& sc, v3 o, v3 d, float tmin, float tmax
 struct WalkRec { u32x4 q0, q1; };
 RTW_DEV bool in_range(float a, uint32_t lo, uint32_t hi) { return __builtin_amdgcn_fmed3f(a, __uint_as_float(lo), __uint_as_float(hi)) == a; }
 
-template <bool ANY_HIT>
-RTW_DEV void walk_lds(const u32x4* __restrict__ w, const int n_groups, const v3 o, const v3 d, const float tmin, const float tmax, float& best_t, int& best_prim) {
-    // closest hit: key = bits(best_t) << 32 | best_prim + 1; any hit: key_lo = 1 once occluded
-    uint32_t key_hi = __float_as_uint(tmax), key_lo = 0u;
-    const u32x4* xf = w + 2 * n_groups;
-    const u32x4* r = w + 5 * n_groups;  // the record stream: groups follow each other without gaps
-    WalkRec A, B;
-    A.q0 = r[0]; A.q1 = r[1];
+// The walk's tests, shared by its two forms below. They read the ray (oo, dd, inv; tmin, tmax) and update the key (key_hi, key_lo) of
+// the function they stand in.
 #define RTW_RECT_TEST(R_, OK_, IK_, OA_, DA_, OB_, DB_)                                              \
     {                                                                                                \
         const float t = (__uint_as_float(R_.q1.x) - (OK_)) * (IK_);                                  \
@@ -967,6 +963,101 @@ RTW_DEV void walk_lds(const u32x4* __restrict__ w, const int n_groups, const v3 
             key_lo = take ? R_.q1.y : key_lo;                                                        \
         }                                                                                            \
     }
+#define RTW_TEST_X(R_) RTW_RECT_TEST(R_, oo.x, inv.x, oo.y, dd.y, oo.z, dd.z)   /* shaders/aarectx.cu:8-22 */
+#define RTW_TEST_Y(R_) RTW_RECT_TEST(R_, oo.y, inv.y, oo.x, dd.x, oo.z, dd.z)   /* shaders/aarecty.cu:8-22 */
+#define RTW_TEST_Z(R_) RTW_RECT_TEST(R_, oo.z, inv.z, oo.x, dd.x, oo.y, dd.y)   /* shaders/aarectz.cu:9-23 */
+#define RTW_TEST_SPH(R_)                                                                             \
+    {                                                                                                \
+        float t = 0.f;                                                                               \
+        const bool hit = sphere_roots(oo, dd, V(__uint_as_float(R_.q0.x), __uint_as_float(R_.q0.y), __uint_as_float(R_.q0.z)), \
+                                      __uint_as_float(R_.q0.w), tmin, RTW_FLT_MAX, t);               \
+        if (ANY_HIT) {                                                                               \
+            key_lo = (hit & (t < tmax)) ? 1u : key_lo;                                               \
+        } else {                                                                                     \
+            const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | R_.q1.y; \
+            const bool take = hit & (key < (((unsigned long long)key_hi << 32) | key_lo));           \
+            key_hi = take ? __float_as_uint(t) : key_hi;                                             \
+            key_lo = take ? R_.q1.y : key_lo;                                                        \
+        }                                                                                            \
+    }
+// the rows of a group's world->object matrix -> the ray in the group's frame
+RTW_DEV void walk_xform(const u32x4* __restrict__ xg, const v3 o, const v3 d, v3& oo, v3& dd) {
+    const u32x4 r0 = xg[0], r1 = xg[1], r2 = xg[2];
+    float m[12];
+    m[0] = __uint_as_float(r0.x); m[1] = __uint_as_float(r0.y); m[2] = __uint_as_float(r0.z); m[3] = __uint_as_float(r0.w);
+    m[4] = __uint_as_float(r1.x); m[5] = __uint_as_float(r1.y); m[6] = __uint_as_float(r1.z); m[7] = __uint_as_float(r1.w);
+    m[8] = __uint_as_float(r2.x); m[9] = __uint_as_float(r2.y); m[10] = __uint_as_float(r2.z); m[11] = __uint_as_float(r2.w);
+    oo = xf_point(m, o);
+    dd = xf_vector(m, d);
+}
+
+// The walk of a list shape known at compile time (rtw_scene.h WalkShape; the host's path_kernel vouches that the uploaded image has
+// it): the same image, records, order, tests and key as the walk below, with everything that walk reads from the group headers - the
+// number of groups, whether a group has a transform, the four counts - folded into the instruction stream. No header reads, no
+// uniform values to broadcast, no counted loops and no copy after an odd list: record ri of the image is tested from register set
+// ri mod 2 while record ri + 1 loads into the other; of a record's second word only the plane and the tie key are read.
+// What keeps this form inside k_path's 80 registers (without it: 220 B of scratch):
+//   - recip3 and sphere_roots branch, so the walk is several basic blocks. The tests are pure arithmetic whose only result, the key,
+//     is read at the end, and the optimiser sinks them below every such branch; the reads stay where they are, so all seven records
+//     of the first group were live at once. An empty asm that "modifies" the key ahead of each branch (after the last rectangle
+//     before a sphere, after a sphere, at the end of a group) holds the tests in place.
+//   - all reads share one base register; as a constant it was hoisted out of the kernel's loop and held a register for the whole
+//     launch. It is made opaque here, so it lives as long as the walk.
+template <int... I, class F>
+RTW_DEV void walk_each(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <bool ANY_HIT, int SHAPE>
+RTW_DEV void walk_lds_shape(const u32x4* __restrict__ w, const v3 o, const v3 d, const float tmin, const float tmax, float& best_t, int& best_prim) {
+    static_assert(SHAPE == WALK_SHAPE_CORNELL, "a compiled list shape");
+    constexpr WalkShape S = kShapeCornell;
+    constexpr int NG = S.n_groups, NR = walk_shape_recs(S, NG);
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    uint32_t key_hi = __float_as_uint(tmax), key_lo = 0u;
+    uint32_t base = 0u;
+    asm volatile("" : "+v"(base));
+    const u32x4* r = (const u32x4*)((const char*)(w + 5 * NG) + base);  // the record stream; the matrices lie 3 words per group before it
+    const u32x4* xf = r - 3 * NG;
+    WalkRec R[2];
+#define RTW_WALK_LOAD(I_)                                                                            \
+    {                                                                                                \
+        const u32x2 h_ = *(const u32x2*)(r + 2 * (I_) + 1);                                          \
+        R[(I_) & 1].q0 = r[2 * (I_)];                                                                \
+        R[(I_) & 1].q1 = u32x4{h_.x, h_.y, 0u, 0u};                                                  \
+    }
+    RTW_WALK_LOAD(0)
+    v3 oo = o, dd = d, inv = o;
+    walk_each(std::make_integer_sequence<int, NR>{}, [&](auto ri_) {
+        constexpr int ri = decltype(ri_)::value;
+        constexpr int gi = walk_shape_group(S, ri), kind = walk_shape_kind(S, ri);
+        if constexpr (ri == walk_shape_recs(S, gi)) {  // the group's first record: the ray in its frame
+            if constexpr (S.g[gi].xform) walk_xform(xf + 3 * gi, o, d, oo, dd);
+            else { oo = o; dd = d; }
+            if constexpr (S.g[gi].n[0] + S.g[gi].n[1] + S.g[gi].n[2] > 0) inv = recip3(dd);
+        }
+        if constexpr (ri + 1 < NR) RTW_WALK_LOAD(ri + 1)
+        const WalkRec C = R[ri & 1];
+        if constexpr (kind == 0) RTW_TEST_X(C)
+        else if constexpr (kind == 1) RTW_TEST_Y(C)
+        else if constexpr (kind == 2) RTW_TEST_Z(C)
+        else RTW_TEST_SPH(C)
+        if constexpr (kind == 3 || ri + 1 == NR || walk_shape_kind(S, ri + 1) == 3 || walk_shape_group(S, ri + 1) != gi) {  // a branch follows
+            if (ANY_HIT) asm volatile("" : "+v"(key_lo));
+            else asm volatile("" : "+v"(key_hi), "+v"(key_lo));
+        }
+    });
+#undef RTW_WALK_LOAD
+    best_t = ANY_HIT ? tmax : __uint_as_float(key_hi);
+    best_prim = (int)key_lo - 1;
+}
+
+template <bool ANY_HIT, int SHAPE = 0>
+RTW_DEV void walk_lds(const u32x4* __restrict__ w, const int n_groups, const v3 o, const v3 d, const float tmin, const float tmax, float& best_t, int& best_prim) {
+    if constexpr (SHAPE != 0) { walk_lds_shape<ANY_HIT, SHAPE>(w, o, d, tmin, tmax, best_t, best_prim); return; }
+    // closest hit: key = bits(best_t) << 32 | best_prim + 1; any hit: key_lo = 1 once occluded
+    uint32_t key_hi = __float_as_uint(tmax), key_lo = 0u;
+    const u32x4* xf = w + 2 * n_groups;
+    const u32x4* r = w + 5 * n_groups;  // the record stream: groups follow each other without gaps
+    WalkRec A, B;
+    A.q0 = r[0]; A.q1 = r[1];
 // n records of one kind: A holds the first on entry and the first record after the list on exit
 #define RTW_REC_LIST(N_, TEST_)                                                                      \
     {                                                                                                \
@@ -1002,38 +1093,21 @@ RTW_DEV void walk_lds(const u32x4* __restrict__ w, const int n_groups, const v3 
         }
         if (n_rx + n_ry + n_rz > 0) {
             const v3 inv = recip3(dd);
-#define RTW_TEST_X(R_) RTW_RECT_TEST(R_, oo.x, inv.x, oo.y, dd.y, oo.z, dd.z)   /* shaders/aarectx.cu:8-22 */
-#define RTW_TEST_Y(R_) RTW_RECT_TEST(R_, oo.y, inv.y, oo.x, dd.x, oo.z, dd.z)   /* shaders/aarecty.cu:8-22 */
-#define RTW_TEST_Z(R_) RTW_RECT_TEST(R_, oo.z, inv.z, oo.x, dd.x, oo.y, dd.y)   /* shaders/aarectz.cu:9-23 */
             RTW_REC_LIST(n_rx, RTW_TEST_X)
             RTW_REC_LIST(n_ry, RTW_TEST_Y)
             RTW_REC_LIST(n_rz, RTW_TEST_Z)
-#undef RTW_TEST_X
-#undef RTW_TEST_Y
-#undef RTW_TEST_Z
-        }
-#define RTW_TEST_SPH(R_)                                                                             \
-        {                                                                                            \
-            float t = 0.f;                                                                           \
-            const bool hit = sphere_roots(oo, dd, V(__uint_as_float(R_.q0.x), __uint_as_float(R_.q0.y), __uint_as_float(R_.q0.z)), \
-                                          __uint_as_float(R_.q0.w), tmin, RTW_FLT_MAX, t);           \
-            if (ANY_HIT) {                                                                           \
-                key_lo = (hit & (t < tmax)) ? 1u : key_lo;                                           \
-            } else {                                                                                 \
-                const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | R_.q1.y; \
-                const bool take = hit & (key < (((unsigned long long)key_hi << 32) | key_lo));       \
-                key_hi = take ? __float_as_uint(t) : key_hi;                                         \
-                key_lo = take ? R_.q1.y : key_lo;                                                    \
-            }                                                                                        \
         }
         RTW_REC_LIST(n_sph, RTW_TEST_SPH)
-#undef RTW_TEST_SPH
     }
 #undef RTW_REC_LIST
-#undef RTW_RECT_TEST
     best_t = ANY_HIT ? tmax : __uint_as_float(key_hi);
     best_prim = (int)key_lo - 1;
 }
+#undef RTW_TEST_SPH
+#undef RTW_TEST_X
+#undef RTW_TEST_Y
+#undef RTW_TEST_Z
+#undef RTW_RECT_TEST
 
 // Closest / any hit (optixTraverse at raygen.cu:41-54 and closehit.cu:27-40).
 // Candidate order (observable only through volume RNG draws and exact ties in t): volume

@@ -102,6 +102,8 @@ extern template __global__ void k_path<RTW_RNG_PHILOX, 1, 1>(const KArgs);
 extern template __global__ void k_path<RTW_RNG_TEA_LCG, 1, 1>(const KArgs);
 extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>(const KArgs);
 extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1>(const KArgs);
+extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1, WALK_SHAPE_CORNELL>(const KArgs);
+extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1, WALK_SHAPE_CORNELL>(const KArgs);
 RTW_EXT(k_first)
 RTW_EXT(k_shade)
 RTW_EXT(k_bounce)
@@ -350,9 +352,14 @@ bool path_nee1(int rng_kind, const DScene& sc) {
     return rng_kind == RTW_RNG_PHILOX && sc.has_tex == 0 && sc.estimator == RTW_EST_REFERENCE && sc.n_lights == 1 &&
            (gen == RTW_PDF_RECT_X || gen == RTW_PDF_RECT_Y || gen == RTW_PDF_RECT_Z);
 }
-Kernel path_kernel(int rng_kind, const DScene& sc, bool list = false) {
+// The one-light twin in turn has a fixed-shape twin (rtw_kernels.h k_path SHAPE) for the scenes whose candidate lists have a compiled
+// shape: walk_shape is what prepare_scene found for the uploaded scene (SceneInfo::walk_shape; 0: none).
+Kernel path_kernel(int rng_kind, const DScene& sc, int walk_shape, bool list = false) {
     const int feat = sc.has_tex, n_vol = sc.n_vol;
-    if (path_nee1(rng_kind, sc)) return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>;
+    if (path_nee1(rng_kind, sc)) {
+        if (walk_shape == WALK_SHAPE_CORNELL) return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1, WALK_SHAPE_CORNELL> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1, WALK_SHAPE_CORNELL>;
+        return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>;
+    }
 #define RTW_PK(R_, L_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1, L_> : feat == 2 ? k_path<R_, 2, 0, L_> : feat == 1 ? k_path<R_, 1, 0, L_> : k_path<R_, 0, 0, L_>)
     if (list) return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 1) : RTW_PK(RTW_RNG_PHILOX, 1);
     return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 0) : RTW_PK(RTW_RNG_PHILOX, 0);
@@ -365,14 +372,15 @@ Kernel first_list_kernel(int rng_kind, int feat) {
 #undef RTW_FK
 }
 
-// which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH. list: k_first / k_path over a.list (LIST = 1)
-void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock, bool list = false) {
+// which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH. list: k_first / k_path over a.list (LIST = 1).
+// walk_shape: k_path only, the uploaded scene's SceneInfo::walk_shape
+void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock, bool list = false, int walk_shape = 0) {
     const bool lcg = rng_kind == RTW_RNG_TEA_LCG;
     // kernels that shade exist in six instantiations: RNG kind x feature level
     const int feat = a.sc.has_tex;  // 0 hot, 1 cold features, 2 cold features + the mixture estimator (rtw_kernels.h shade_a)
     if (list) {
         if (which == RTW_K_FIRST) hipLaunchKernelGGL(first_list_kernel(rng_kind, feat), dim3(grid), dim3(kBlock), lds, s, a);
-        else hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, true), dim3(grid), dim3(kBlock), lds, s, a);
+        else hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, walk_shape, true), dim3(grid), dim3(kBlock), lds, s, a);
         return;
     }
 #define RTW_LAUNCH_SHADING_R(K_, LDS_, R_)                                                                        \
@@ -393,7 +401,7 @@ void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipSt
         else if (a.sc.n_generic == 0) hipLaunchKernelGGL((k_trace<true>), dim3(grid), dim3(kBlock), lds, s, a);
         else hipLaunchKernelGGL((k_trace<false>), dim3(grid), dim3(kBlock), lds, s, a);
         break;
-    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, a.sc), dim3(grid), dim3(kBlock), lds, s, a); break;
+    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, walk_shape), dim3(grid), dim3(kBlock), lds, s, a); break;
     default: RTW_LAUNCH_SHADING(k_bounce, lds); break;
 #undef RTW_LAUNCH_SHADING
 #undef RTW_LAUNCH_SHADING_R
@@ -789,7 +797,7 @@ int issue_path_pass(rtw_ctx* c, CallLog& log, const KArgs& base, const PathPass&
         a.block0 = target.blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
         hipStream_t ls = part == 0 ? s : c->stream2;
         if (part == 1) HIP_TRY(c, hipStreamWaitEvent(ls, ev_a, 0));
-        launch(RTW_K_PATH, target.rng_kind, a, l.grid, 0, ls, kBlock, target.list);
+        launch(RTW_K_PATH, target.rng_kind, a, l.grid, 0, ls, kBlock, target.list, c->info.walk_shape);
         log.launches++;
         if (part == 1) {
             HIP_TRY(c, hipEventRecord(ev_b, ls));
@@ -952,7 +960,7 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)P->spp;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
     const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, cull.live_groups);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     if ((rc = grow_order(c, plan.n_groups)) != RTW_OK) return rc;
@@ -1284,7 +1292,7 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
     // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
     Tuning t = tune;
     if (t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, true), 0, t.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape, true), 0, t.path_grid_mult);
     const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     int rc = grow_blocksum(c, plan.need_slots * n_list);
@@ -1465,7 +1473,7 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)(n_to - n_from);
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
     const size_t n_groups = (npix + 63) / 64;
     if ((rc = grow_order(c, n_groups)) != RTW_OK) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));

@@ -18,6 +18,7 @@ namespace rtwk {
 #if !defined(RTW_INST_KIND) || RTW_INST_KIND == 0
 RTW_INST(RTW_RNG_PHILOX)
 template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1>(const KArgs);  // the one-light instantiation (NEE1)
+template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1, WALK_SHAPE_CORNELL>(const KArgs);  // and its fixed-shape twin (SHAPE)
 #endif
 #if !defined(RTW_INST_KIND) || RTW_INST_KIND == 1
 RTW_INST(RTW_RNG_TEA_LCG)

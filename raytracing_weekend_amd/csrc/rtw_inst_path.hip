@@ -17,6 +17,7 @@ RTW_INST(k_path)
 template __global__ void k_path<RTW_RNG_PHILOX, 1, 1>(const KArgs);
 template __global__ void k_path<RTW_RNG_TEA_LCG, 1, 1>(const KArgs);
 template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>(const KArgs);  // the one-light instantiation (NEE1)
+template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1, WALK_SHAPE_CORNELL>(const KArgs);  // and its fixed-shape twin (SHAPE)
 template __global__ void k_classify<true>(const KArgs, uint32_t*, uint32_t*, uint32_t);
 template __global__ void k_classify<false>(const KArgs, uint32_t*, uint32_t*, uint32_t);
 }  // namespace rtwk

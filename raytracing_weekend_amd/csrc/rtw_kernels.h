@@ -1380,8 +1380,12 @@ RTW_DEV constexpr int rtw_phase_id(const char* n) { return n[0] == 'r' && n[2] =
 // are free and s_usum[0] holds each lane's list position. Everything after the refill is the same code.
 // NEE1 = 1 (hot instantiation, Philox): the scene lists exactly one light, a rectangle, under the reference estimator - facts of
 // rtw_upload_scene that the host's path_kernel() checks (rtw_hip.hip path_nee1) - and shade_a compiles that light sample alone.
-template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0, int NEE1 = 0>
+// SHAPE != 0 (with NEE1 = 1): the scene's candidate lists have that compiled shape (rtw_scene.h walk_shape, checked by path_kernel() as
+// well), and both walks are the shape's straight-line code.
+template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0, int NEE1 = 0, int SHAPE = 0>
 __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVES) : RTW_PATH_WAVES) k_path(const KArgs A) {
+    static_assert(SHAPE == 0 || (NEE1 && !TEX), "the fixed-shape walks belong to the one-light instantiation");
+    constexpr int WSHAPE = RTW_PATH_SHAPE ? SHAPE : 0;
     RTW_NOISE_SHARED
     __shared__ u32x4 s_hitrec[kPathMaxPrims * 6];
     const uint32_t tid = threadIdx.x;
@@ -1446,6 +1450,8 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
     uint32_t gk = 0, rng_b = 0, nee_prev = 0;
     float ray_time = 0.f;
     v3 o = V(0.f, 0.f, 0.f), d = o, T = o, L = o;
+    // (segments and shadow probes: each lane's own count, summed over the wave at the end; the fixed-shape instantiation, which has no
+    // register to spare for them, counts per wave in scalar registers, from the ballots of the lanes that trace)
     uint32_t n_seg = 0, n_shadow = 0;
 #ifdef RTW_PHASE_TIMERS
     unsigned long long ph_cyc[6] = {0, 0, 0, 0, 0, 0}, ph_t0 = __builtin_amdgcn_s_memtime();
@@ -1555,18 +1561,20 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
 #endif
             if (busy) {
                 if (TEX) traverse_brute<Rng<KIND>, false, false>(A.sc, o, d, A.sc.ray_tmin, 1.e27f, ray_time, gt, g, th, prim);
-                else walk_lds<false>(s_walk, A.sc.n_groups, o, d, A.sc.ray_tmin, 1.e27f, th, prim);
+                else walk_lds<false, WSHAPE>(s_walk, A.sc.n_groups, o, d, A.sc.ray_tmin, 1.e27f, th, prim);
             }
         }
         RTW_MARK("shade_a");
 #ifdef RTW_SUBPHASE_TIMERS
         rtw_sub_stamp(8);   // 8: shade_a entry (miss test, branch to the hit code)
 #endif
+        bool probed = false;
+        if constexpr (WSHAPE != 0) n_seg += (uint32_t)__popcll(__ballot(busy));  // (the counters are the wave's there: see their declaration)
         if (busy) {
             v3 so, sd, att, radiance;
             Nee nee;
             const int ev = shade_a<KIND, TEX, NEE1 && RTW_PATH_NEE1>(A.sc, g, o, d, gt, th, prim, so, sd, att, radiance, nee, noise_lds, nee_prev, s_hitrec, &s_pc);
-            n_seg++;
+            if constexpr (WSHAPE == 0) n_seg++;
 #ifdef RTW_SUBPHASE_TIMERS
             rtw_sub_stamp(0);  // 0: everything outside the closest-hit program
 #endif
@@ -1575,8 +1583,9 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                 float st;
                 int sprim;
                 if (TEX) traverse_brute<Rng<KIND>, true, false>(A.sc, so, nee.dir, nee.tmin, nee.tmax, 0.0f, gt, g, st, sprim);
-                else walk_lds<true>(s_walk, A.sc.n_groups, so, nee.dir, nee.tmin, nee.tmax, st, sprim);
-                n_shadow++;
+                else walk_lds<true, WSHAPE>(s_walk, A.sc.n_groups, so, nee.dir, nee.tmin, nee.tmax, st, sprim);
+                if constexpr (WSHAPE == 0) n_shadow++;
+                else probed = true;
                 if (sprim < 0) radiance = vadd(radiance, nee.rad);
             }
             RTW_MARK("shade_b");
@@ -1615,15 +1624,17 @@ __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVE
                 }
             }
         }
+        if constexpr (WSHAPE != 0) n_shadow += (uint32_t)__popcll(__ballot(probed));
     }
 #ifdef RTW_PHASE_TIMERS
     RTW_MARK("refill");
     if (lane == 0) for (int q = 0; q < 6; q++) atomicAdd(&A.stats[kStatRows * 8 + q], ph_cyc[q]);
 #endif
-    for (int off = 32; off > 0; off >>= 1) {
-        n_seg += __shfl_down(n_seg, off);
-        n_shadow += __shfl_down(n_shadow, off);
-    }
+    if constexpr (WSHAPE == 0)
+        for (int off = 32; off > 0; off >>= 1) {
+            n_seg += __shfl_down(n_seg, off);
+            n_shadow += __shfl_down(n_shadow, off);
+        }
     if (lane == 0) {
         unsigned long long* row = stat_row(A);
         if (n_seg) { atomicAdd(&row[0], (unsigned long long)n_seg); atomicAdd(&row[2 + RTW_K_PATH], (unsigned long long)n_seg); }

@@ -57,6 +57,39 @@ struct BruteRec {
 
 constexpr int kWalkMaxWords = 400;  // k_path's walk image (rtw_device.h walk_lds): 6.4 KB of LDS; scenes whose lists are larger use the wavefront kernels
 
+// List shapes k_path has a walk compiled for (rtw_device.h walk_lds<ANY_HIT, SHAPE>, DESIGN.md 4.1 "The metric scene's list
+// shape is a compile-time fact"): the number of groups and, per group, whether it has a transform and its four counts - everything the
+// walk's control flow depends on. Shape id 0 is "none": the walk that reads the image's group headers.
+struct WalkShapeGroup { bool xform; int n[4]; };  // n: x-, y-, z-rectangles, spheres
+struct WalkShape { int n_groups; WalkShapeGroup g[2]; };
+enum { WALK_SHAPE_NONE = 0, WALK_SHAPE_CORNELL = 1 };
+// the reference's Cornell box (host/ioScene.h CornellBox): walls, floor, ceiling, light and the sphere; then the rotated box
+constexpr WalkShape kShapeCornell = {2, {{false, {2, 3, 1, 1}}, {true, {2, 2, 2, 0}}}};
+constexpr int walk_shape_recs(const WalkShape& s, int n_groups) {  // records in the first n_groups groups
+    int n = 0;
+    for (int g = 0; g < n_groups; g++) for (int k = 0; k < 4; k++) n += s.g[g].n[k];
+    return n;
+}
+constexpr int walk_shape_group(const WalkShape& s, int ri) {  // the group record ri (of the image's record stream) lies in
+    int g = 0;
+    while (g + 1 < s.n_groups && ri >= walk_shape_recs(s, g + 1)) g++;
+    return g;
+}
+constexpr int walk_shape_kind(const WalkShape& s, int ri) {   // and its list there: 0, 1, 2: x-, y-, z-rectangles, 3: spheres
+    const int g = walk_shape_group(s, ri);
+    int k = 0, first = walk_shape_recs(s, g);
+    while (k < 3 && ri >= first + s.g[g].n[k]) first += s.g[g].n[k++];
+    return k;
+}
+static_assert(5 * kShapeCornell.n_groups + 2 * walk_shape_recs(kShapeCornell, kShapeCornell.n_groups) + 4 <= kWalkMaxWords, "a compiled shape has a walk image");
+constexpr bool walk_shape_is(const WalkShape& s, const BruteGroup* groups, size_t n_groups) {
+    if (n_groups != (size_t)s.n_groups) return false;
+    for (int g = 0; g < s.n_groups; g++) {
+        const BruteGroup& G = groups[g];
+        if ((G.xform != 0) != s.g[g].xform || G.n_rx != s.g[g].n[0] || G.n_ry != s.g[g].n[1] || G.n_rz != s.g[g].n[2] || G.n_sph != s.g[g].n[3]) return false;
+    }
+    return true;
+}
 }  // namespace rtwdev
 
 namespace rtwk {
@@ -79,6 +112,7 @@ struct SceneInfo {
     size_t lds_bytes;                   // dynamic LDS of k_first and the tree walks at kBlock threads: stacks + staged nodes and leaf records
     bool cull_ok;                       // cull_bmin / cull_bmax hold the bounds the empty-pixel cull projects (rtw_plan.h cull_bounds)
     float cull_bmin[3], cull_bmax[3];
+    int walk_shape;                     // WALK_SHAPE_*: the compiled list shape of the walk image (walk_shape below); 0: none, no walk image, or cold features
 };
 struct PreparedScene {
     std::vector<char> image;            // one device allocation's worth: 256-byte aligned tables, zero padding
@@ -285,6 +319,11 @@ inline std::vector<uint32_t> walk_image(const Tables& s, const std::vector<Brute
     return walk;
 }
 
+// ---- 6b: the id of the compiled shape (WalkShape above) the group table matches exactly (groups, their order, identity or transformed, all four counts), else 0
+inline int walk_shape(const std::vector<BruteGroup>& groups) {
+    return walk_shape_is(kShapeCornell, groups.data(), groups.size()) ? WALK_SHAPE_CORNELL : WALK_SHAPE_NONE;
+}
+
 // ---- 7: the wave-coherent walk's nodes: fp32 child boxes, padded for its plane arithmetic. It computes a plane's distance as
 // fma(plane, 1/d, -(o * 1/d)): the rounding of o * 1/d displaces a plane by about ulp(|o|) in space, so the boxes grow by
 // 2^-19 of the largest coordinate around (`big`: scene bounds, camera origin; the primitives' own bounds carry 1e-4 already)
@@ -383,6 +422,8 @@ inline int prepare_scene(const void* blob, size_t bytes, const Tuning& tune, Pre
     // selects the kernel instantiations that contain the cold features: textures, media, (k_path) moving spheres in the brute lists,
     // camera kinds other than the reference's lens-free perspective camera
     sc.has_tex = (dyn_tex || facts.n_vol > 0 || sc.n_generic > 0 || h.camera_type != RTW_CAM_PERSPECTIVE || h.camera.lens_radius != 0.0f) ? 1 : 0;
+    // (only k_path's instantiation without the cold features has fixed-shape walks)
+    out.info.walk_shape = (walk.empty() || sc.has_tex != 0) ? WALK_SHAPE_NONE : walk_shape(groups);
     sc.noise_lds_data = -1;  // the first noise texture some primitive shows gets its tables staged in LDS
     for (uint32_t i = 0; i < h.n_prims && sc.noise_lds_data < 0; i++) {
         int ti = s.mats[s.prims[i].material].texture;

@@ -73,8 +73,11 @@ if __name__ == "__main__":
     print(f"# {len(theirs)} kernels in the other checkout, {len(ours)} here; per kernel: {', '.join(cols)}")
     for key in sorted(theirs):
         a, b = theirs[key], ours.get(key)
-        if b is None:  # k_path gained a fifth template argument (NEE1): the other checkout's <a, b, c, d> is <a, b, c, d, 0> here
-            b = ours.get((key[0], re.sub(r"(6k_pathILi\d+ELi\d+ELi\d+ELi\d+E)E", r"\1Li0EE", key[1])))
+        # k_path gained template arguments (NEE1, then SHAPE): the other checkout's <a, b, c, d> or <a, b, c, d, e> is <a, b, c, d, e, 0> here
+        if b is None:
+            b = ours.get((key[0], re.sub(r"(6k_pathILi\d+ELi\d+ELi\d+ELi\d+ELi\d+E)E", r"\1Li0EE", key[1])))
+        if b is None:
+            b = ours.get((key[0], re.sub(r"(6k_pathILi\d+ELi\d+ELi\d+ELi\d+E)E", r"\1Li0ELi0EE", key[1])))
         label = f"{key[0]:24s} {demangle(key[1]):72s}"
         if b is None:
             bad += 1
@@ -85,7 +88,7 @@ if __name__ == "__main__":
             bad += 1
             print(f"{label} DIFFERS  " + "; ".join(f"{c}: {x} -> {y}" for c, x, y in zip(cols, a, b) if x != y))
     print("# kernels only this tree has")
-    for key in sorted(k for k in set(ours) - set(theirs) if not re.search(r"6k_pathILi\d+ELi\d+ELi\d+ELi\d+ELi0EE", k[1])):
+    for key in sorted(k for k in set(ours) - set(theirs) if not re.search(r"6k_pathILi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi0EE", k[1])):
         b = ours[key]
         print(f"{key[0]:24s} {demangle(key[1]):72s} new   {b[0]:6d} {b[1]:4d} {b[2]:4d} {b[3]:5d} {b[4]:6d} {b[5]}")
     print(f"# {len(theirs) - bad} of {len(theirs)} kernels of the other checkout are the same here, {bad} differ or are missing")

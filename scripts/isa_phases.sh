@@ -1,11 +1,13 @@
 #!/bin/bash
-# usage: [NEE1=0|1] scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0,NEE1> per phase
-# (between the phase-fence comments; NEE1 = 1, the default, is the one-light instantiation the headline scene runs). Compiles
+# usage: [NEE1=0|1] [SHAPE=0|1] scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0,NEE1,SHAPE>
+# per phase (between the phase-fence comments; NEE1 = 1 with SHAPE = 1, the defaults, is the one-light instantiation with the Cornell box's
+# fixed-shape walks that the headline scene runs; SHAPE = 0 with NEE1 = 1 the one-light instantiation other one-light scenes run). Compiles
 # rtw_inst_path.hip the way __graft_entry__.build() does (HIP_FLAGS + that unit's UNIT_FLAGS) and prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
 # divisions (v_div_fixup_f32, fallbacks of the short forms included), sqrt = its roots (v_sqrt_f32), rcp_short / rsq_short = the
 # short forms of rtw_math.h (a v_rcp_f32 without a v_div_fixup_f32; v_rsq_f32). Exits 1 when the kernel is not found.
 R=$(cd "$(dirname "$0")/.." && pwd)
-K=_ZN4rtwk6k_pathILi0ELi0ELi0ELi0ELi${NEE1:-1}EEEvNS_5KArgsE
+NEE1=${NEE1:-1}
+K=_ZN4rtwk6k_pathILi0ELi0ELi0ELi0ELi${NEE1}ELi${SHAPE:-$NEE1}EEEvNS_5KArgsE
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 FLAGS=$(cd "$R" && python3 -c "

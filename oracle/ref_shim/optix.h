@@ -1,0 +1,2 @@
+// Stand-in for <optix.h>: see ref_shim_core.h (test infrastructure, no reference text).
+#include "ref_shim_core.h"

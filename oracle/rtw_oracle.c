@@ -5,13 +5,16 @@
  * cpu_baseline leg may load this file's library; the product (librtw_hip.so, Director) never does.
  *
  * PINNING STATUS.  The reference holds no tests, golden images or known-answer vectors for this path
- *  and its device code needs OptiX 8 + nvcc, so it cannot be built here:
+ *  and its device code needs OptiX 8 + nvcc, so it cannot be built as it is:
  *   - RNG (tea / xorshift32 / randf) IS pinned: oracle/Makefile compiles the reference's own
  *     lib/random.cuh where it lies into oracle/_ref/ and tests/golden/rng_kat.json holds its outputs;
  *     the OptiX-SDK lcg/rnd (not in tree) is restated from its published definition;
  *     Philox4x32-10 is pinned by the Random123 known-answer vectors.
- *   - Everything else (pixels) is PARITY UNPINNED against OptiX: the checker is this restatement,
- *     function by function, each citing the reference file:line it follows.
+ *   - The first segment of a path (camera ray, traversal, intersection, closest hit, material, texture, light sample, shadow
+ *     probe, miss) IS pinned: oracle/ref_programs_wrap.cpp runs the reference's own device programs on the CPU behind stand-in
+ *     headers, tests/golden/ref_programs/*.npz holds what they compute (DESIGN.md "Pinning", tests/ref_programs.py).
+ *   - Everything behind it (deeper pixels) is PARITY UNPINNED against OptiX - the reference does not agree with itself there -:
+ *     the checker is this restatement, function by function, each citing the reference file:line it follows.
  *   - rtw_params.estimator != 0 (corrected estimators) and rtwo_denoise are this build's own definitions, not the
  *     reference's: there the file is the CPU twin of the HIP code, nothing more.
  *

@@ -301,6 +301,14 @@ def camera_rays(cam, camera_type, frame, d, ft=np.float64, swap_jitter=False, ro
     return origin, direction, np.broadcast_to(e_o, s.shape), np.broadcast_to(e_d, s.shape)
 
 
+def fp32_ray_units(origin, direction, e_o, e_d):
+    """The units (2^-24) in which a float32 ray is compared with camera_rays' float64 origin and direction, per pixel: the forward
+    bounds e_o, e_d, and no less than the size of the value itself - a bound of 0 (an origin that is a copy of the camera's) still
+    leaves the rounding of the float64 value to float32, half an ulp of its largest component."""
+    return (np.maximum(e_o, np.abs(np.asarray(origin, np.float64)).max(-1)),
+            np.maximum(e_d, np.abs(np.asarray(direction, np.float64)).max(-1)))
+
+
 def times(cam, d, ft=np.float64, times_swapped=False, ray_time_over_shutter=False, gather_raw=False):
     """(gather time, first ray time) at precision ft. The keyword flags are negative controls."""
     cam = np.asarray(cam, np.float32).astype(ft)

@@ -25,7 +25,7 @@
 //
 //   the query family (rtw_cast, rtw_radiance, rtw_probe, rtw_probe_sh, rtw_views, rtw_views_guides, rtw_denoise_views, rtw_probe_adaptive,
 //     rtw_views_adaptive, each with a _device variant): the caller's rays, probes, points or cameras through kernels of their own
-//     translation units. On the host they share one scaffold: grow_buffer for every buffer a context grows on demand, QueryCall
+//     translation units. On the host they share one scaffold: QueryCall
 //     (query_open / query_close: device context, stream, the two timing events, the control words), query_chunks for the host
 //     variants' upload / issue / copy-back loop through one staging slab (laid out by rtw_stage_plan.h), query_stats for the tail,
 //     and adaptive_issue, the checkpoint loop of the two adaptive families
@@ -35,6 +35,9 @@
 // schedules they share with the adaptive renderer and the sessions (issue_path_pass, run_batches).
 // rtw_upload_scene prepares the blob once on the host (rtw_scene.h prepare_scene: validation, hit records, candidate lists, tree, one
 // staged image, likewise checked on the CPU) and copies the image to each device.
+//
+// Device memory has one owner type, DevBuf (rtw_devbuf.h: grow on demand, freed with its owner): every buffer of a context, grown where a call
+// first needs it and kept until rtw_destroy, and every call's own scratch, freed on whichever path the call returns.
 //
 // No OptiX, no CUDA shims, no Triton, no MFMA (divergent scalar fp32). Results do not depend on
 // scheduling: every path owns a counter-based RNG stream and every (pixel, block) its own sum.
@@ -56,6 +59,7 @@
 
 #include "../../include/rtw.h"
 #include "rtw_bvh.h"
+#include "rtw_devbuf.h"
 #include "rtw_scene.h"
 #include "rtw_device.h"
 #include "rtw_plan.h"
@@ -131,7 +135,7 @@ struct rtw_ctx {
     // scene
     bool has_scene = false;
     DScene sc{};
-    void* d_scene = nullptr;   // one allocation holding all scene tables
+    DevBuf d_scene;            // one allocation holding all scene tables
     SceneInfo info{};          // its host-side facts, overwritten as a whole by every upload (rtw_scene.h)
     // render pool
     // Two independent "lanes" (stream + path pool): consecutive batches alternate between them so that the
@@ -141,39 +145,32 @@ struct rtw_ctx {
         hipEvent_t ev_done = nullptr, ev_free = nullptr;
         PathBuf buf[2] = {};
         uint2* hit[2] = {nullptr, nullptr};
-        void* slab[2] = {nullptr, nullptr};  // one allocation per ping-pong set: six planes + hit records
-        float4* lbuf = nullptr;
-        uint32_t* cnt = nullptr;
-        size_t cnt_words = 0;
+        DevBuf slab[2];        // one allocation per ping-pong set: six planes + hit records
+        DevBuf lbuf;           // float4 per path
+        DevBuf cnt;            // the region counters, in words
         size_t paths = 0;
         bool probes = false;   // the slabs hold the planes of scenes with listed lights (p2, a full p5) as well
     } lane[4];
-    float4* accum = nullptr;   // per pixel: sum of the finished sample blocks
-    float4* part = nullptr;    // per pixel: running sum of the current block (wavefront pipeline)
-    float4* upart = nullptr;   // per pixel: running sum of the current summation unit's finished blocks (wavefront pipeline)
-    size_t accum_pix = 0;
-    float4* blocksum = nullptr;  // k_path: [block][pixel] unit sums of one pass
-    size_t blocksum_elems = 0;
-    uint32_t* d_queue = nullptr; // k_path: job counter [0], k_classify's two counters [1], [2]
-    uint32_t* d_order = nullptr; // k_path: job order of the pixel groups
+    DevBuf accum;              // float4 per pixel: sum of the finished sample blocks
+    DevBuf part;               // float4 per pixel: running sum of the current block (wavefront pipeline)
+    DevBuf upart;              // float4 per pixel: running sum of the current summation unit's finished blocks (wavefront pipeline)
+    DevBuf blocksum;           // k_path: [block][pixel] float4 unit sums of one pass
+    DevBuf d_queue;            // k_path: 16 words, job counter [0], k_classify's two counters [1], [2]
+    DevBuf d_order;            // k_path: job order of the pixel groups (k_classify's three lists), in groups of 64 pixels
     hipStream_t stream2 = nullptr;  // k_path: the stream of the fine-grained end-game launch
-    size_t order_groups = 0;
     std::vector<hipEvent_t> ev_pool;  // timing events, reused across launches and calls
-    unsigned long long* d_stats = nullptr;
-    float4* d_out = nullptr;
-    size_t out_pix = 0;
+    DevBuf d_stats;            // kStatRows + 1 rows of 8 counters
+    DevBuf d_out;              // float4 per pixel: the frame of a call that returns it to the host
     int n_cu = 256;
     // n_devices > 1: this context is a group; kids[g] renders the g-th interleaved sub-shard on device_ids[g], the
     // shards are gathered on device_ids[0] (this->device) into `stage` and interleaved into the caller's frame
     std::vector<rtw_ctx*> kids;
-    float4* stage = nullptr;
-    size_t stage_pix = 0;
+    DevBuf stage;              // in pixels: the gathered shards, then the shards' row offsets
     size_t pool_cap = ~(size_t)0;  // paths in flight this device has room for (halved when a pool allocation fails: render_wavefront)
     struct Worker* worker = nullptr;  // a kid's host thread: created with the group, lives until rtw_destroy
     // rtw_render_adaptive's per-pixel state (rtw_adaptive.h), one allocation made on first use: accum, upart, part, moments, n, err,
     // two active lists (a length word, then the pixels) and the compaction's masks and offsets (one per 64 pixels)
-    void* adapt = nullptr;
-    size_t adapt_pix = 0;
+    DevBuf adapt;
     // the accumulation session (rtw.h rtw_accum_*; a group's lives in kids[0]). It owns its per-pixel state, one allocation: accum,
     // upart, part (rtw_accum.h), with RTW_ACCUM_ERROR mom and the error map a read computes. An add borrows the context's scratch
     // (blocksum, job order, queue, lanes, stats rows: all dead again when the add returns), never its accum / upart / part / adapt.
@@ -184,27 +181,22 @@ struct rtw_ctx {
         int32_t done = 0;
         uint64_t samples = 0, segments = 0, shadow_rays = 0;
         size_t npix = 0;
-        void* slab = nullptr;
+        DevBuf slab;
         float4 *accum = nullptr, *upart = nullptr, *part = nullptr;
         double2* mom = nullptr;
         float* err = nullptr;
     } acc;
-    // The query family's scratch (rtw_cast ... rtw_views_adaptive), each grown on demand (grow_buffer) and kept until rtw_destroy.
+    // The query family's scratch (rtw_cast ... rtw_views_adaptive), each grown on demand and kept until rtw_destroy.
     // The host variants' staging slab: one chunk's inputs and results, laid out per call by rtw_stage_plan.h. Every call that uses it
     // returns synchronised, so one slab serves them all.
-    void* stage_slab = nullptr;
-    size_t stage_bytes = 0;
-    void* rad_slab = nullptr;  // the unit sums [unit][ray] of calls beyond 128 spp; the block sums of an adaptive pass
-    size_t rad_slab_bytes = 0;
-    void* view_buf = nullptr;  // the view records of a host call
-    size_t view_bytes = 0;
-    void* dn_buf = nullptr;  // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
-    size_t dn_bytes = 0;
-    unsigned long long* rad_ctl = nullptr;  // the control words: kStatRows rows of 8 counters, then the queue word (query_open)
+    DevBuf stage_slab;         // (in bytes, like the next three)
+    DevBuf rad_slab;           // the unit sums [unit][ray] of calls beyond 128 spp; the block sums of an adaptive pass
+    DevBuf view_buf;           // the view records of a host call
+    DevBuf dn_buf;             // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
+    DevBuf rad_ctl;            // the control words: kStatRows rows of 8 counters, then the queue word (query_open)
     // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept;
     // rtw_views_adaptive's per-pixel state as well (the same layout over the pixels of a call or batch: a call initialises what it uses)
-    void* padapt = nullptr;
-    size_t padapt_probes = 0;
+    DevBuf padapt;             // (in probes)
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
 };
 
@@ -240,23 +232,24 @@ int fail(rtw_ctx* c, int code, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
 
+constexpr size_t kQueueBytes = 64;                                                   // rtw_ctx::d_queue
+constexpr size_t kStatsBytes = (kStatRows + 1) * 8 * sizeof(unsigned long long);      // rtw_ctx::d_stats
+constexpr size_t kCtlBytes = (kStatRows * 8 + 2) * sizeof(unsigned long long);        // rtw_ctx::rad_ctl
+
 void free_lane(rtw_ctx::Lane& L) {
     for (int b = 0; b < 2; b++) {
-        if (L.slab[b]) (void)hipFree(L.slab[b]);
-        L.slab[b] = nullptr;
+        L.slab[b].release();
         L.buf[b] = PathBuf{};
         L.hit[b] = nullptr;
     }
-    if (L.lbuf) (void)hipFree(L.lbuf);
-    L.lbuf = nullptr;
+    L.lbuf.release();
     L.paths = 0;
     L.probes = false;
 }
 void free_pool(rtw_ctx* c) {
     for (auto& L : c->lane) {
         free_lane(L);
-        if (L.cnt) (void)hipFree(L.cnt);
-        L.cnt = nullptr; L.cnt_words = 0;
+        L.cnt.release();
     }
 }
 
@@ -292,22 +285,17 @@ int ensure_lane(rtw_ctx* c, rtw_ctx::Lane& L, size_t paths, size_t cnt_words, bo
         size_t off[8] = {0};
         for (int k = 0; k < 7; k++) off[k + 1] = off[k] + sz[k];
         for (int b = 0; b < 2; b++) {
-            HIP_TRY(c, hipMalloc(&L.slab[b], off[7] + 4096));
-            char* base = (char*)L.slab[b];
+            HIP_TRY(c, L.slab[b].grow(paths, off[7] + 4096));
+            char* base = L.slab[b].as<char>();
             L.buf[b].p0 = (float4*)(base + off[0]); L.buf[b].p1 = (float4*)(base + off[1]); L.buf[b].p2 = (float4*)(base + off[2]);
             L.buf[b].p3 = (float4*)(base + off[3]); L.buf[b].p4 = (float4*)(base + off[4]); L.buf[b].p5 = (uint4*)(base + off[5]);
             L.hit[b] = (uint2*)(base + off[6]);
         }
-        HIP_TRY(c, hipMalloc(&L.lbuf, paths * sizeof(float4)));
+        HIP_TRY(c, L.lbuf.grow(paths, paths * sizeof(float4)));
         L.paths = paths;
         L.probes = probes;
     }
-    if (cnt_words > L.cnt_words) {
-        if (L.cnt) (void)hipFree(L.cnt);
-        L.cnt = nullptr; L.cnt_words = 0;
-        HIP_TRY(c, hipMalloc(&L.cnt, cnt_words * sizeof(uint32_t)));
-        L.cnt_words = cnt_words;
-    }
+    HIP_TRY(c, L.cnt.grow(cnt_words, cnt_words * sizeof(uint32_t)));
     return RTW_OK;
 }
 
@@ -316,20 +304,9 @@ int ensure_pool(rtw_ctx* c, int n_lanes, size_t paths, size_t npix, size_t cnt_w
         int rc = ensure_lane(c, c->lane[l], paths, cnt_words, probes);
         if (rc) return rc;
     }
-    if (n_lanes == 0 && !c->d_queue) HIP_TRY(c, hipMalloc(&c->d_queue, 64));
-    if (npix > c->accum_pix) {
-        if (c->accum) (void)hipFree(c->accum);
-        c->accum = nullptr; c->accum_pix = 0;
-        HIP_TRY(c, hipMalloc(&c->accum, npix * sizeof(float4)));
-        if (c->part) (void)hipFree(c->part);
-        c->part = nullptr;
-        HIP_TRY(c, hipMalloc(&c->part, npix * sizeof(float4)));
-        if (c->upart) (void)hipFree(c->upart);
-        c->upart = nullptr;
-        HIP_TRY(c, hipMalloc(&c->upart, npix * sizeof(float4)));
-        c->accum_pix = npix;
-    }
-    if (!c->d_stats) HIP_TRY(c, hipMalloc(&c->d_stats, (kStatRows + 1) * 8 * sizeof(unsigned long long)));
+    if (n_lanes == 0) HIP_TRY(c, c->d_queue.grow(kQueueBytes, kQueueBytes));
+    for (DevBuf* b : {&c->accum, &c->part, &c->upart}) HIP_TRY(c, b->grow(npix, npix * sizeof(float4)));
+    HIP_TRY(c, c->d_stats.grow(kStatsBytes, kStatsBytes));
     return RTW_OK;
 }
 
@@ -518,34 +495,15 @@ int impl_destroy(rtw_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    accum_free(c);
-    free_pool(c);
     for (auto& L : c->lane) {
         if (L.ev_done) (void)hipEventDestroy(L.ev_done);
         if (L.ev_free) (void)hipEventDestroy(L.ev_free);
         if (L.st) (void)hipStreamDestroy(L.st);
     }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->accum) (void)hipFree(c->accum);
-    if (c->part) (void)hipFree(c->part);
-    if (c->upart) (void)hipFree(c->upart);
-    if (c->blocksum) (void)hipFree(c->blocksum);
-    if (c->adapt) (void)hipFree(c->adapt);
-    if (c->d_queue) (void)hipFree(c->d_queue);
-    if (c->d_order) (void)hipFree(c->d_order);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stage) (void)hipFree(c->stage);
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->stage_slab) (void)hipFree(c->stage_slab);
-    if (c->rad_slab) (void)hipFree(c->rad_slab);
-    if (c->padapt) (void)hipFree(c->padapt);
-    if (c->view_buf) (void)hipFree(c->view_buf);
-    if (c->dn_buf) (void)hipFree(c->dn_buf);
-    if (c->rad_ctl) (void)hipFree(c->rad_ctl);
-    if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // its buffers go with it, while its device is the current one
     return RTW_OK;
 }
 
@@ -554,12 +512,12 @@ int upload_prepared(rtw_ctx* c, const PreparedScene& ps) {
     test_fault("upload");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_scene) { (void)hipFree(c->d_scene); c->d_scene = nullptr; }
+    c->d_scene.release();
     c->has_scene = false;
     accum_free(c);  // a session belongs to the scene it was begun with
-    HIP_TRY(c, hipMalloc(&c->d_scene, ps.image.size()));
-    HIP_TRY(c, hipMemcpy(c->d_scene, ps.image.data(), ps.image.size(), hipMemcpyHostToDevice));
-    const char* d = (const char*)c->d_scene;
+    HIP_TRY(c, c->d_scene.grow(ps.image.size(), ps.image.size()));
+    HIP_TRY(c, hipMemcpy(c->d_scene.as<void>(), ps.image.data(), ps.image.size(), hipMemcpyHostToDevice));
+    const char* d = c->d_scene.as<char>();
     const SceneScalars& v = ps.sc;
     const SceneFacts& f = ps.info.facts;
     DScene sc{};
@@ -693,6 +651,18 @@ struct CallLog {
     }
 };
 
+// the context's two timing events, out of its pool (no event is created once a context has timed anything)
+hipError_t timing_events(rtw_ctx* d, hipEvent_t ev[2]) {
+    while (d->ev_pool.size() < 2) {
+        hipEvent_t n = nullptr;
+        const hipError_t e = hipEventCreate(&n);
+        if (e != hipSuccess) return e;
+        d->ev_pool.push_back(n);
+    }
+    ev[0] = d->ev_pool[0]; ev[1] = d->ev_pool[1];
+    return hipSuccess;
+}
+
 // ---- the launch schedules that rtw_render, rtw_render_adaptive and rtw_accum_add share. Each renderer plans its own launches (rtw_plan.h)
 // and resolves them with its own kernel; how a planned pass or batch is issued, how the pool is fitted and how a call's counters
 // become rtw_stats is written once, here.
@@ -705,25 +675,6 @@ int path_wg_per_cu(const void* kernel, size_t lds, int override) {
     int nb = 0;
     const hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, lds);
     return (qe == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
-}
-
-// k_path's unit sums of one pass, at least `elems` of them
-int grow_blocksum(rtw_ctx* c, size_t elems) {
-    if (elems <= c->blocksum_elems) return RTW_OK;
-    if (c->blocksum) (void)hipFree(c->blocksum);
-    c->blocksum = nullptr; c->blocksum_elems = 0;
-    HIP_TRY(c, hipMalloc(&c->blocksum, elems * sizeof(float4)));
-    c->blocksum_elems = elems;
-    return RTW_OK;
-}
-// k_classify's three job lists, for at least n_groups groups of 64 pixels
-int grow_order(rtw_ctx* c, size_t n_groups) {
-    if (n_groups <= c->order_groups) return RTW_OK;
-    if (c->d_order) (void)hipFree(c->d_order);
-    c->d_order = nullptr; c->order_groups = 0;
-    HIP_TRY(c, hipMalloc(&c->d_order, 3 * n_groups * sizeof(uint32_t)));
-    c->order_groups = n_groups;
-    return RTW_OK;
 }
 
 // Groups of 64 pixels that certainly see nothing get no job: a miss adds +0 (no sky light), so their pixels stay at 0 and their
@@ -743,10 +694,12 @@ PathCull path_cull(const rtw_ctx* c, const rtw_params* P, const Tuning& tune, KA
 
 // job order: longest units first (k_classify), into c->d_order with the lists' lengths at c->d_queue + 1
 int classify_jobs(rtw_ctx* c, const KArgs& base, size_t n_groups, hipStream_t s) {
-    HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 64, s));
+    uint32_t* const order = c->d_order.as<uint32_t>();
+    uint32_t* const counts = c->d_queue.as<uint32_t>() + 1;
+    HIP_TRY(c, hipMemsetAsync(c->d_queue.as<void>(), 0, kQueueBytes, s));
     const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
-    if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
-    else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, c->d_order, c->d_queue + 1, (uint32_t)n_groups);
+    if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, order, counts, (uint32_t)n_groups);
+    else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, order, counts, (uint32_t)n_groups);
     return RTW_OK;
 }
 
@@ -767,12 +720,13 @@ struct PathTarget {
 int issue_path_pass(rtw_ctx* c, CallLog& log, const KArgs& base, const PathPass& ps, bool unit_sums, const PathTarget& target, hipStream_t s) {
     // render_path and accum_add_path have d_queue from ensure_pool before they point target.order_counts into it; only the list caller,
     // whose order_counts is null, can arrive here without one. A caller that needs the counts must allocate d_queue first.
-    if (!c->d_queue) HIP_TRY(c, hipMalloc(&c->d_queue, 64));
+    HIP_TRY(c, c->d_queue.grow(kQueueBytes, kQueueBytes));
+    uint32_t* const queue = c->d_queue.as<uint32_t>();
     // low priority: it fills the slots the bulk launch vacates. Created by a context's first pass, after the call's begin event: that
     // one call's stats.seconds includes the stream's creation
     if (!c->stream2) HIP_TRY(c, create_stream(&c->stream2, 2));
-    HIP_TRY(c, hipMemsetAsync(c->d_queue, 0, 4, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_queue + 4, 0, 4, s));
+    HIP_TRY(c, hipMemsetAsync(queue, 0, 4, s));
+    HIP_TRY(c, hipMemsetAsync(queue + 4, 0, 4, s));
     hipEvent_t ev_a = nullptr, ev_b = nullptr;  // (from the call's event pool, like the wavefront lanes' start event)
     HIP_TRY(c, log.event(ev_a));
     HIP_TRY(c, log.event(ev_b));
@@ -785,13 +739,13 @@ int issue_path_pass(rtw_ctx* c, CallLog& log, const KArgs& base, const PathPass&
         const PathLaunch& l = ps.part[part];
         if (l.count == 0) continue;
         KArgs a = base;
-        a.stats = c->d_stats;
+        a.stats = c->d_stats.as<unsigned long long>();
         a.sample0 = target.sample0;
         a.spp = target.spp_end;
-        a.queue = c->d_queue + (part == 0 ? 0 : 4);
+        a.queue = queue + (part == 0 ? 0 : 4);
         a.order = target.order;
         a.order_counts = target.order_counts;
-        a.blocksum = c->blocksum + (part == 0 ? 0 : ps.slots_coarse) * target.n_items;
+        a.blocksum = c->blocksum.as<float4>() + (part == 0 ? 0 : ps.slots_coarse) * target.n_items;
         a.unit_sums = (part == 0 && unit_sums) ? 1u : 0u;
         a.n_jobs = (uint32_t)l.n_jobs; a.n_ranges = (uint32_t)l.n_ranges; a.units_per_job = (uint32_t)l.jb;
         a.block0 = target.blk0 + (uint32_t)(ps.b0 + l.first); a.n_blocks_pass = (uint32_t)l.count; a.unit_blocks = (uint32_t)l.unit_blocks;
@@ -815,9 +769,10 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
     const size_t lds = c->info.lds_bytes;
     const uint32_t regions = w.grid_for(paths);
     HIP_TRY(c, hipStreamWaitEvent(L.st, ready, 0));
-    HIP_TRY(c, hipMemsetAsync(L.cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
-    a.lbuf = L.lbuf;
-    a.stats = c->d_stats;
+    uint32_t* const cnt = L.cnt.as<uint32_t>();
+    HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)regions * (w.sched.size() + 2) * sizeof(uint32_t), L.st));
+    a.lbuf = L.lbuf.as<float4>();
+    a.stats = c->d_stats.as<unsigned long long>();
     a.n_regions = regions;
     a.n_paths = (uint32_t)paths;
     a.region_cap = (uint32_t)w.cap_for(paths);
@@ -829,7 +784,7 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
     size_t ci = 0;  // index of the region-counter row describing buffer `cur`
     a.out = L.buf[0];
     a.hit_out = L.hit[0];
-    a.cnt_out = L.cnt;
+    a.cnt_out = cnt;
     a.depth = 0; a.n_iter = 1;
     log.launches++;
     // every compacting launch uses exactly this grid: workgroup b owns region b
@@ -838,7 +793,7 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
         a.in = L.buf[cur];
         a.hit = L.hit[cur];
         a.hit_out = L.hit[cur];  // k_trace fills the records of the buffer it reads
-        a.cnt_in = L.cnt + ci * regions;
+        a.cnt_in = cnt + ci * regions;
         a.depth = (uint32_t)st.depth;
         a.n_iter = (uint32_t)st.n_iter;
         if (st.kind == RTW_K_TRACE) {
@@ -852,7 +807,7 @@ int issue_batch(rtw_ctx* c, const WavefrontPlan& w, const Tuning& tune, KArgs a,
         } else {
             a.out = L.buf[cur ^ 1];
             a.hit_out = L.hit[cur ^ 1];
-            a.cnt_out = L.cnt + (ci + 1) * regions;
+            a.cnt_out = cnt + (ci + 1) * regions;
             HIP_TRY(c, log.launch(L.st, st.kind, a, (int)regions, st.kind == RTW_K_BOUNCE ? lds : 0));
             cur ^= 1;
             ci++;
@@ -963,25 +918,27 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
     const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, cull.live_groups);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
-    if ((rc = grow_order(c, plan.n_groups)) != RTW_OK) return rc;
-    if ((rc = grow_blocksum(c, plan.need_slots * npix)) != RTW_OK) return rc;
+    HIP_TRY(c, c->d_order.grow(plan.n_groups, 3 * plan.n_groups * sizeof(uint32_t)));  // k_classify's three job lists
+    HIP_TRY(c, c->blocksum.grow(plan.need_slots * npix, plan.need_slots * npix * sizeof(float4)));
+    float4* const accum = c->accum.as<float4>();
+    const float4* const blocksum = c->blocksum.as<float4>();
     HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(accum, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
     if ((rc = classify_jobs(c, base, plan.n_groups, s)) != RTW_OK) return rc;
     const unsigned pix_grid = pixel_grid(c, npix);
-    const PathTarget target{npix, c->d_order, c->d_queue + 1, false, 0u, (uint32_t)P->spp, P->rng_kind, (uint32_t)P->sample_offset};
+    const PathTarget target{npix, c->d_order.as<uint32_t>(), c->d_queue.as<uint32_t>() + 1, false, 0u, (uint32_t)P->spp, P->rng_kind, (uint32_t)P->sample_offset};
     for (const PathPass& ps : plan.passes) {
         if (cull.live_groups == 0) break;  // the frame looks past everything: black, nothing to launch
         if ((rc = issue_path_pass(c, log, base, ps, plan.unit_sums, target, s)) != RTW_OK) return rc;
         // coarse region: whole unit sums (unit_sums) or block sums from block b0 on; fine region: block sums from b0 + nb_coarse on
         if (plan.unit_sums)
-            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, blocksum, accum, (uint32_t)npix, (uint32_t)ps.slots_coarse,
                                (uint32_t)(ps.nb - ps.nb_coarse), (uint32_t)(ps.b0 + ps.nb_coarse), cull.rcull);
         else
-            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, c->accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0, cull.rcull);
+            hipLaunchKernelGGL(k_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, blocksum, accum, (uint32_t)npix, 0u, (uint32_t)ps.nb, (uint32_t)ps.b0, cull.rcull);
     }
-    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
+    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)accum, (const float4*)nullptr, (const float4*)nullptr, out, (uint32_t)npix, (float)P->spp);
     return RTW_OK;
 }
 
@@ -993,18 +950,19 @@ int render_wavefront(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const 
                                 [&] { return plan_wavefront(tune, npix, P->spp, P->samples_per_pass, P->max_depth, c->pool_cap, c->n_cu, c->info.facts); },
                                 [](const WavefrontPlan& p) { return (size_t)p.regions_max * p.region_cap_max; }, w);
     if (rc) return rc;
+    float4 *const accum = c->accum.as<float4>(), *const upart = c->upart.as<float4>(), *const part = c->part.as<float4>();
     HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->accum, 0, npix * sizeof(float4), s));
-    HIP_TRY(c, hipMemsetAsync(c->part, 0, npix * sizeof(float4), s));
-    HIP_TRY(c, hipMemsetAsync(c->upart, 0, npix * sizeof(float4), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(accum, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(part, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(upart, 0, npix * sizeof(float4), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
     const unsigned pix_grid = pixel_grid(c, npix);
     // the lanes start once the accumulators are cleared
     rc = run_batches(c, w, tune, base, npix, (size_t)P->spp, P->sample_offset, nullptr, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
-        hipLaunchKernelGGL(k_resolve, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, c->accum, c->upart, c->part, (uint32_t)npix, (uint32_t)Sb, (uint32_t)s0);
+        hipLaunchKernelGGL(k_resolve, dim3(pix_grid), dim3(kBlock), 0, s, L.lbuf.as<const float4>(), accum, upart, part, (uint32_t)npix, (uint32_t)Sb, (uint32_t)s0);
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->accum, (const float4*)c->upart, (const float4*)c->part, out, (uint32_t)npix, (float)P->spp);
+    hipLaunchKernelGGL(k_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)accum, (const float4*)upart, (const float4*)part, out, (uint32_t)npix, (float)P->spp);
     return RTW_OK;
 }
 
@@ -1014,7 +972,7 @@ int print_diagnostics(rtw_ctx* c, bool path, const unsigned long long* hs) {
 #ifdef RTW_PHASE_TIMERS
     if (path) {
         unsigned long long ph[8];
-        HIP_TRY(c, hipMemcpy(ph, c->d_stats + kStatRows * 8, sizeof ph, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(ph, c->d_stats.as<unsigned long long>() + kStatRows * 8, sizeof ph, hipMemcpyDeviceToHost));
         double tot = 0;
         for (int q = 0; q < 6; q++) tot += (double)ph[q];
         const char* nm[6] = {"refill", "regen", "walk_r", "shade_a", "walk_s", "shade_b"};
@@ -1042,7 +1000,7 @@ int print_diagnostics(rtw_ctx* c, bool path, const unsigned long long* hs) {
 #ifdef RTW_TRACE_COUNT
     {
         unsigned long long w[7];
-        HIP_TRY(c, hipMemcpy(w, c->d_stats + kStatRows * 8, sizeof w, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(w, c->d_stats.as<unsigned long long>() + kStatRows * 8, sizeof w, hipMemcpyDeviceToHost));
         const double rays = (double)w[6];
         fprintf(stderr, "[rtw] k_trace_bvh: rays %.4g; per ray: node visits %.2f, primitive tests %.2f; wave steps per 64 rays: inner %.2f (lanes busy %.2f), leaf %.2f (lanes busy %.2f), outer %.2f\n",
                 rays, (double)hs[6] / rays, (double)hs[7] / rays, (double)w[0] * 64.0 / rays, (double)hs[6] / ((double)w[0] * 64.0), (double)w[1] * 64.0 / rays,
@@ -1093,7 +1051,7 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
     HIP_TRY(c, hipEventSynchronize(log.end));
 
     unsigned long long hs[8];
-    if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
+    if ((rc = sum_stat_rows(c, c->d_stats.as<unsigned long long>(), hs)) != RTW_OK) return rc;
     rc = print_diagnostics(c, use_path, hs);
     if (rc) return rc;
     if (stats) return fill_stats(c, log, hs, (uint64_t)npix * (uint64_t)P->spp, hs[0] + log.culled_segments, stats);
@@ -1119,15 +1077,10 @@ int run_shard(rtw_ctx* kc, Worker& w) {
     test_fault("worker");
     if (hipSetDevice(kc->device) != hipSuccess) return fail(kc, RTW_ERR_DEVICE, "hipSetDevice failed");
     if (w.npix == 0) return RTW_OK;
-    if (w.npix > kc->out_pix) {
-        if (kc->d_out) (void)hipFree(kc->d_out);
-        kc->d_out = nullptr; kc->out_pix = 0;
-        if (hipMalloc(&kc->d_out, w.npix * sizeof(float4)) != hipSuccess) return fail(kc, RTW_ERR_OOM, "shard buffer");
-        kc->out_pix = w.npix;
-    }
-    const int rc = render_single(kc, &w.P, kc->d_out, nullptr, w.want_stats ? &w.st : nullptr);
+    if (kc->d_out.grow(w.npix, w.npix * sizeof(float4)) != hipSuccess) return fail(kc, RTW_ERR_OOM, "shard buffer");
+    const int rc = render_single(kc, &w.P, kc->d_out.as<void>(), nullptr, w.want_stats ? &w.st : nullptr);
     if (rc) return rc;
-    HIP_TRY(kc, hipMemcpyPeerAsync(w.gather_dst, w.gather_dev, kc->d_out, kc->device, w.npix * sizeof(float4), kc->stream));
+    HIP_TRY(kc, hipMemcpyPeerAsync(w.gather_dst, w.gather_dev, kc->d_out.as<void>(), kc->device, w.npix * sizeof(float4), kc->stream));
     HIP_TRY(kc, hipStreamSynchronize(kc->stream));
     return RTW_OK;
 }
@@ -1170,12 +1123,7 @@ int render_group(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, r
     HIP_TRY(c, hipSetDevice(c->device));
     if (!s) s = c->stream;
     const size_t npix = rows * (size_t)P->width;
-    if (npix > c->stage_pix) {
-        if (c->stage) (void)hipFree(c->stage);
-        c->stage = nullptr; c->stage_pix = 0;
-        HIP_TRY(c, hipMalloc(&c->stage, npix * sizeof(float4) + (n + 1) * sizeof(uint32_t) + 256));
-        c->stage_pix = npix;
-    }
+    HIP_TRY(c, c->stage.grow(npix, npix * sizeof(float4) + (n + 1) * sizeof(uint32_t) + 256));
     std::vector<uint32_t> off(n + 1, 0);
     std::vector<size_t> krows(n, 0);
     for (size_t g = 0; g < n; g++) {
@@ -1191,7 +1139,7 @@ int render_group(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, r
         w.P.row_stride = (int32_t)(k * n);
         if (w.P.row0 > w.P.row1) w.P.row0 = w.P.row1;
         w.npix = krows[g] * (size_t)P->width;
-        w.gather_dst = c->stage + (size_t)off[g] * P->width;
+        w.gather_dst = c->stage.as<float4>() + (size_t)off[g] * P->width;
         w.gather_dev = c->device;
         w.want_stats = stats != nullptr;
         memset(&w.st, 0, sizeof w.st);
@@ -1209,9 +1157,9 @@ int render_group(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, r
     if (first_rc != RTW_OK)
         return fail(c, first_rc, std::string("device ") + std::to_string(c->kids[first_bad]->device) + ": " + c->kids[first_bad]->err);
     HIP_TRY(c, hipSetDevice(c->device));
-    uint32_t* d_off = (uint32_t*)((char*)c->stage + ((npix * sizeof(float4) + 255) & ~(size_t)255));
+    uint32_t* d_off = (uint32_t*)(c->stage.as<char>() + ((npix * sizeof(float4) + 255) & ~(size_t)255));
     HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_interleave, dim3((unsigned)std::min<size_t>((npix + 255) / 256, (size_t)c->n_cu * 8)), dim3(256), 0, s, (const float4*)c->stage,
+    hipLaunchKernelGGL(k_interleave, dim3((unsigned)std::min<size_t>((npix + 255) / 256, (size_t)c->n_cu * 8)), dim3(256), 0, s, c->stage.as<const float4>(),
                        (float4*)d_rgba, (uint32_t)P->width, (uint32_t)rows, (uint32_t)n, (const uint32_t*)d_off);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -1247,15 +1195,10 @@ int impl_render(rtw_ctx* c, const rtw_params* P, float* rgba_out, rtw_stats* sta
     if (P->width <= 0 || P->row0 < 0 || P->row1 < P->row0) return fail(c, RTW_ERR_INVALID_ARG, "bad render params");
     const size_t npix = shard_rows(P) * (size_t)P->width;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (npix > c->out_pix) {
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_pix = 0;
-        HIP_TRY(c, hipMalloc(&c->d_out, std::max<size_t>(npix, 1) * sizeof(float4)));
-        c->out_pix = npix;
-    }
-    int rc = impl_render_device(c, P, c->d_out, nullptr, stats);
+    HIP_TRY(c, c->d_out.grow(npix, std::max<size_t>(npix, 1) * sizeof(float4)));
+    int rc = impl_render_device(c, P, c->d_out.as<void>(), nullptr, stats);
     if (rc) return rc;
-    if (npix) HIP_TRY(c, hipMemcpy(rgba_out, c->d_out, npix * sizeof(float4), hipMemcpyDeviceToHost));  // Director.cpp:999-1000
+    if (npix) HIP_TRY(c, hipMemcpy(rgba_out, c->d_out.as<void>(), npix * sizeof(float4), hipMemcpyDeviceToHost));  // Director.cpp:999-1000
     return RTW_OK;
 }
 
@@ -1273,13 +1216,8 @@ int ensure_adapt(rtw_ctx* c, size_t npix, AdaptState& st) {
     const size_t sz[10] = {npix * 16, npix * 16, npix * 16, npix * 16, npix * 4, npix * 4 + 4, npix * 4 + 4, npix * 4, nw * 8, nw * 4};
     size_t off[11] = {0};
     for (int k = 0; k < 10; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
-    if (npix > c->adapt_pix) {
-        if (c->adapt) (void)hipFree(c->adapt);
-        c->adapt = nullptr; c->adapt_pix = 0;
-        HIP_TRY(c, hipMalloc(&c->adapt, off[10]));
-        c->adapt_pix = npix;
-    }
-    char* b = (char*)c->adapt;  // (the layout for npix fits in an allocation made for more pixels)
+    HIP_TRY(c, c->adapt.grow(npix, off[10]));
+    char* b = c->adapt.as<char>();  // (the layout for npix fits in an allocation made for more pixels)
     st.accum = (float4*)(b + off[0]); st.upart = (float4*)(b + off[1]); st.part = (float4*)(b + off[2]); st.mom = (double2*)(b + off[3]);
     st.n = (uint32_t*)(b + off[4]); st.list[0] = (uint32_t*)(b + off[5]); st.list[1] = (uint32_t*)(b + off[6]); st.err = (float*)(b + off[7]);
     st.masks = (unsigned long long*)(b + off[8]); st.offsets = (uint32_t*)(b + off[9]);
@@ -1295,13 +1233,13 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
     const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape, true), 0, t.path_grid_mult);
     const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
-    int rc = grow_blocksum(c, plan.need_slots * n_list);
-    if (rc) return rc;
+    HIP_TRY(c, c->blocksum.grow(plan.need_slots * n_list, plan.need_slots * n_list * sizeof(float4)));
+    int rc;
     const uint32_t blk0 = (uint32_t)n_from / kSumBlock;
     const PathTarget target{n_list, list, nullptr, true, blk0, (uint32_t)n_to, P->rng_kind, (uint32_t)P->sample_offset};
     for (const PathPass& ps : plan.passes) {
         if ((rc = issue_path_pass(c, log, base, ps, false, target, s)) != RTW_OK) return rc;
-        hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(c, n_list)), dim3(kBlock), 0, s, (const float4*)c->blocksum, list, (uint32_t)n_list,
+        hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(c, n_list)), dim3(kBlock), 0, s, c->blocksum.as<const float4>(), list, (uint32_t)n_list,
                            (uint32_t)ps.nb, blk0 + (uint32_t)ps.b0, st.accum, st.upart, st.mom);
     }
     return RTW_OK;
@@ -1327,7 +1265,7 @@ int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune,
     const unsigned grid = pixel_grid(c, n_list);
     // the lanes start after the previous checkpoint's decision (the list) on s
     return run_batches(c, w, tune, base, n_list, step, P->sample_offset + n_from, list, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
-        hipLaunchKernelGGL(k_adapt_resolve_samples, dim3(grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, list, (uint32_t)n_list, (uint32_t)npix,
+        hipLaunchKernelGGL(k_adapt_resolve_samples, dim3(grid), dim3(kBlock), 0, s, L.lbuf.as<const float4>(), list, (uint32_t)n_list, (uint32_t)npix,
                            (uint32_t)Sb, (uint32_t)(n_from + (int)s0), st.accum, st.upart, st.part, st.mom);
     });
 }
@@ -1350,17 +1288,12 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
     AdaptState st{};
     int rc = ensure_adapt(c, npix, st);
     if (rc) return rc;
-    if (!c->d_stats) HIP_TRY(c, hipMalloc(&c->d_stats, (kStatRows + 1) * 8 * sizeof(unsigned long long)));
-    if (npix > c->out_pix) {
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_pix = 0;
-        HIP_TRY(c, hipMalloc(&c->d_out, npix * sizeof(float4)));
-        c->out_pix = npix;
-    }
+    HIP_TRY(c, c->d_stats.grow(kStatsBytes, kStatsBytes));
+    HIP_TRY(c, c->d_out.grow(npix, npix * sizeof(float4)));
     const unsigned pix_grid = pixel_grid(c, npix);
     const uint32_t n_waves = (uint32_t)((npix + 63) / 64);
     HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
     hipLaunchKernelGGL(k_adapt_init, dim3(pix_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.part, st.mom, st.n, st.err, (uint32_t)npix);
     size_t n_active = npix;
     uint64_t samples = 0;
@@ -1395,10 +1328,10 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
         n_prev = n_k;
     }
     hipLaunchKernelGGL(k_adapt_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
-                       c->d_out, (uint32_t)npix);
+                       c->d_out.as<float4>(), (uint32_t)npix);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(log.end, s));
-    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, npix * sizeof(float4), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out.as<void>(), npix * sizeof(float4), hipMemcpyDeviceToHost, s));
     if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out, st.n, npix * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (error_out) HIP_TRY(c, hipMemcpyAsync(error_out, st.err, npix * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -1411,7 +1344,7 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
     }
     if (stats) {
         unsigned long long hs[8];
-        if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
+        if ((rc = sum_stat_rows(c, c->d_stats.as<unsigned long long>(), hs)) != RTW_OK) return rc;
         return fill_stats(c, log, hs, samples, hs[0], stats);
     }
     return RTW_OK;
@@ -1434,11 +1367,8 @@ int impl_render_adaptive(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* AD
 // ---- accumulation sessions (rtw.h rtw_accum_*): the uniform launches of render_path / render_wavefront over samples [done, done + spp),
 // resolved into the session's own state by the kernels of rtw_accum.h, which keep the summation unit open from add to add
 void accum_free(rtw_ctx* c) {
-    if (c->acc.slab) {
-        (void)hipSetDevice(c->device);
-        (void)hipFree(c->acc.slab);
-    }
-    c->acc = rtw_ctx::Accum{};
+    if (c->acc.slab) (void)hipSetDevice(c->device);
+    c->acc = rtw_ctx::Accum{};  // (the slab with it)
 }
 
 // the session's allocation for npix pixels: accum, upart, part, with RTW_ACCUM_ERROR mom and err
@@ -1449,14 +1379,14 @@ int accum_alloc(rtw_ctx* c, size_t npix, uint32_t flags) {
     size_t off[6] = {0};
     for (int k = 0; k < 5; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMalloc(&A.slab, off[5]));
-    char* b = (char*)A.slab;
+    HIP_TRY(c, A.slab.grow(off[5], off[5]));
+    char* b = A.slab.as<char>();
     A.accum = (float4*)(b + off[0]); A.upart = (float4*)(b + off[1]); A.part = (float4*)(b + off[2]);
     A.mom = em ? (double2*)(b + off[3]) : nullptr;
     A.err = em ? (float*)(b + off[4]) : nullptr;
     A.npix = npix;
     A.flags = flags;
-    const hipError_t e = hipMemsetAsync(A.slab, 0, off[5], c->stream);
+    const hipError_t e = hipMemsetAsync(b, 0, off[5], c->stream);
     if (e != hipSuccess) { accum_free(c); return fail(c, RTW_ERR_DEVICE, std::string("rtw_accum: ") + hipGetErrorString(e)); }
     return RTW_OK;
 }
@@ -1475,9 +1405,9 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)(n_to - n_from);
     const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
     const size_t n_groups = (npix + 63) / 64;
-    if ((rc = grow_order(c, n_groups)) != RTW_OK) return rc;
+    HIP_TRY(c, c->d_order.grow(n_groups, 3 * n_groups * sizeof(uint32_t)));
     HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
     if (cull.live_groups == 0) return RTW_OK;  // the frame looks past everything: the state stays black
     if ((rc = classify_jobs(c, base, n_groups, s)) != RTW_OK) return rc;  // once per add
     const unsigned pix_grid = pixel_grid(c, npix);
@@ -1494,18 +1424,18 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
         if (plans[k].unit_sums && !runs.run[k].units_ok) return fail(c, RTW_ERR_UNSUPPORTED, "rtw_accum_add: unit sums off a unit boundary");
         need_slots = std::max(need_slots, plans[k].need_slots);
     }
-    if ((rc = grow_blocksum(c, need_slots * npix)) != RTW_OK) return rc;
+    HIP_TRY(c, c->blocksum.grow(need_slots * npix, need_slots * npix * sizeof(float4)));
     for (int k = 0; k < runs.n; k++) {
         const PathPlan& plan = plans[k];
         const uint32_t blk0 = (uint32_t)runs.run[k].n_from / kSumBlock;
-        const PathTarget target{npix, c->d_order, c->d_queue + 1, false, blk0, (uint32_t)runs.run[k].n_to, P->rng_kind, (uint32_t)P->sample_offset};
+        const PathTarget target{npix, c->d_order.as<uint32_t>(), c->d_queue.as<uint32_t>() + 1, false, blk0, (uint32_t)runs.run[k].n_to, P->rng_kind, (uint32_t)P->sample_offset};
         for (const PathPass& ps : plan.passes) {
             if ((rc = issue_path_pass(c, log, base, ps, plan.unit_sums, target, s)) != RTW_OK) return rc;
             // coarse region: whole unit sums (unit_sums) or block sums from block b0 of the run on; fine region: block sums
             const uint32_t n_unit = plan.unit_sums ? (uint32_t)ps.slots_coarse : 0u;
             const uint32_t n_blk = plan.unit_sums ? (uint32_t)(ps.nb - ps.nb_coarse) : (uint32_t)ps.nb;
             const uint32_t first = blk0 + (uint32_t)(plan.unit_sums ? ps.b0 + ps.nb_coarse : ps.b0);
-            hipLaunchKernelGGL(k_accum_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)c->blocksum, (uint32_t)npix, n_unit, n_blk, first,
+            hipLaunchKernelGGL(k_accum_resolve_blocks, dim3(pix_grid), dim3(kBlock), 0, s, c->blocksum.as<const float4>(), (uint32_t)npix, n_unit, n_blk, first,
                                A.accum, A.upart, A.mom, cull.rcull);
         }
     }
@@ -1524,10 +1454,10 @@ int accum_add_wavefront(rtw_ctx* c, const Tuning& tune, const KArgs& base, int n
                                       [](const WavefrontPlan& p) { return (size_t)p.regions_max * p.region_cap_max; }, w);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(log.begin, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, (kStatRows + 1) * 8 * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
     const unsigned pix_grid = pixel_grid(c, npix);
     return run_batches(c, w, tune, base, npix, step, P->sample_offset + n_from, nullptr, s, log, [&](rtw_ctx::Lane& L, size_t Sb, size_t s0) {
-        hipLaunchKernelGGL(k_accum_resolve_samples, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)L.lbuf, (uint32_t)npix, (uint32_t)Sb,
+        hipLaunchKernelGGL(k_accum_resolve_samples, dim3(pix_grid), dim3(kBlock), 0, s, L.lbuf.as<const float4>(), (uint32_t)npix, (uint32_t)Sb,
                            (uint32_t)(n_from + (int)s0), A.accum, A.upart, A.part, A.mom);
     });
 }
@@ -1551,7 +1481,7 @@ int accum_add_single(rtw_ctx* c, int32_t spp, rtw_stats* stats) {
     HIP_TRY(c, hipEventRecord(log.end, s));
     HIP_TRY(c, hipEventSynchronize(log.end));
     unsigned long long hs[8];
-    if ((rc = sum_stat_rows(c, c->d_stats, hs)) != RTW_OK) return rc;
+    if ((rc = sum_stat_rows(c, c->d_stats.as<unsigned long long>(), hs)) != RTW_OK) return rc;
     const uint64_t samples = (uint64_t)npix * (uint64_t)spp, segments = hs[0] + log.culled_segments;
     if (stats && (rc = fill_stats(c, log, hs, samples, segments, stats)) != RTW_OK) return rc;
     A.done = n_to;
@@ -1636,15 +1566,10 @@ int impl_accum_read(rtw_ctx* c, float* rgba_out, float* error_out) {
     if (rc) return rc;
     const size_t npix = d->acc.npix;
     HIP_TRY(c, hipSetDevice(d->device));
-    if (npix > d->out_pix) {
-        if (d->d_out) (void)hipFree(d->d_out);
-        d->d_out = nullptr; d->out_pix = 0;
-        HIP_TRY(c, hipMalloc(&d->d_out, npix * sizeof(float4)));
-        d->out_pix = npix;
-    }
-    rc = accum_read_single(d, d->d_out, error_out != nullptr, nullptr);
+    HIP_TRY(c, d->d_out.grow(npix, npix * sizeof(float4)));
+    rc = accum_read_single(d, d->d_out.as<float4>(), error_out != nullptr, nullptr);
     if (rc) return accum_up(c, d, rc);
-    HIP_TRY(c, hipMemcpy(rgba_out, d->d_out, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(rgba_out, d->d_out.as<void>(), npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (error_out) HIP_TRY(c, hipMemcpy(error_out, d->acc.err, npix * sizeof(float), hipMemcpyDeviceToHost));
     return RTW_OK;
 }
@@ -1726,10 +1651,12 @@ int denoise_passes(rtw_ctx* c, const char* what, const float* rgba_in, const flo
     const size_t bytes = (size_t)width * height * sizeof(float4);
     const float* src[4] = {rgba_in, nullptr, albedo, normal};
     const int n_buf = albedo ? 4 : 2;
-    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};  // ping, pong, albedo, normal
-    auto cleanup = [&]() { for (float4* p : d) if (p) (void)hipFree(p); };
-    for (int k = 0; k < n_buf; k++)
-        if (hipMalloc(&d[k], bytes) != hipSuccess) { d[k] = nullptr; cleanup(); return fail(c, RTW_ERR_OOM, std::string(what) + ": device allocation failed"); }
+    DevBuf buf[4];  // ping, pong, albedo, normal
+    float4* d[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < n_buf; k++) {
+        HIP_TRY(c, buf[k].grow(bytes, bytes));
+        d[k] = buf[k].as<float4>();
+    }
     hipError_t e = hipSuccess;
     for (int k = 0; k < n_buf && e == hipSuccess; k++)
         if (src[k]) e = hipMemcpyAsync(d[k], src[k], bytes, hipMemcpyHostToDevice, c->stream);
@@ -1744,7 +1671,6 @@ int denoise_passes(rtw_ctx* c, const char* what, const float* rgba_in, const flo
     }
     if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, d[cur], bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     return RTW_OK;
 }
@@ -1779,14 +1705,11 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
     const size_t sz[4] = {G->albedo ? npix * 16 : 0, G->normal ? npix * 16 : 0, G->depth ? npix * 4 : 0, G->prim ? npix * 4 : 0};
     size_t off[5] = {0};
     for (int k = 0; k < 4; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
-    char* slab = nullptr;
+    DevBuf buf;
+    HIP_TRY(c, buf.grow(off[4], off[4]));
+    char* const slab = buf.as<char>();
     hipEvent_t ev[2] = {nullptr, nullptr};
-    auto cleanup = [&]() {
-        if (slab) (void)hipFree(slab);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    };
-    hipError_t e = hipMalloc(&slab, off[4]);
-    if (e != hipSuccess) { slab = nullptr; return fail(c, RTW_ERR_OOM, "rtw_render_guides: device allocation failed"); }
+    hipError_t e = hipSuccess;
     GuideOut g;
     g.albedo = sz[0] ? (float4*)(slab + off[0]) : nullptr;
     g.normal = sz[1] ? (float4*)(slab + off[1]) : nullptr;
@@ -1794,8 +1717,7 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
     g.prim = sz[3] ? (int32_t*)(slab + off[3]) : nullptr;
     g.rng_kind = P->rng_kind;
     if (stats) {
-        e = hipEventCreate(&ev[0]);
-        if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+        e = timing_events(d, ev);
         if (e == hipSuccess) e = hipEventRecord(ev[0], d->stream);
     }
     if (e == hipSuccess) {
@@ -1813,7 +1735,6 @@ int impl_render_guides(rtw_ctx* c, const rtw_params* P, const rtw_guides* G, rtw
         stats->samples = stats->segments = (uint64_t)npix * (uint64_t)P->spp;
         stats->seconds = ms * 1e-3;
     }
-    cleanup();
     if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_render_guides: ") + hipGetErrorString(e));
     return RTW_OK;
 }
@@ -1840,29 +1761,21 @@ int impl_debug_intersect(rtw_ctx* c, const float* rays, const float* ray_time, c
     if (n < 0 || (n > 0 && (!rays || !out_t || !out_prim))) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
     if (n == 0) return RTW_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    float *d_rays = nullptr, *d_rt = nullptr, *d_gt = nullptr, *d_t = nullptr;
-    int32_t* d_p = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_rays); (void)hipFree(d_rt); (void)hipFree(d_gt); (void)hipFree(d_t); (void)hipFree(d_p); };
-#define HIP_TRY_D(expr)                                                                             \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) { cleanup(); return fail(c, RTW_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-    } while (0)
-    HIP_TRY_D(hipMalloc(&d_rays, (size_t)n * 8 * sizeof(float)));
-    HIP_TRY_D(hipMalloc(&d_t, (size_t)n * sizeof(float)));
-    HIP_TRY_D(hipMalloc(&d_p, (size_t)n * sizeof(int32_t)));
-    HIP_TRY_D(hipMemcpy(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
-    if (ray_time) { HIP_TRY_D(hipMalloc(&d_rt, (size_t)n * sizeof(float))); HIP_TRY_D(hipMemcpy(d_rt, ray_time, (size_t)n * sizeof(float), hipMemcpyHostToDevice)); }
-    if (gather_time) { HIP_TRY_D(hipMalloc(&d_gt, (size_t)n * sizeof(float))); HIP_TRY_D(hipMemcpy(d_gt, gather_time, (size_t)n * sizeof(float), hipMemcpyHostToDevice)); }
+    const size_t words = (size_t)n * 4;  // the bytes of n floats or n int32
+    DevBuf d_rays, d_rt, d_gt, d_t, d_p;  // (d_rt, d_gt: null unless given)
+    HIP_TRY(c, d_rays.grow(8 * words, 8 * words));
+    HIP_TRY(c, d_t.grow(words, words));
+    HIP_TRY(c, d_p.grow(words, words));
+    HIP_TRY(c, hipMemcpy(d_rays.as<void>(), rays, 8 * words, hipMemcpyHostToDevice));
+    if (ray_time) { HIP_TRY(c, d_rt.grow(words, words)); HIP_TRY(c, hipMemcpy(d_rt.as<void>(), ray_time, words, hipMemcpyHostToDevice)); }
+    if (gather_time) { HIP_TRY(c, d_gt.grow(words, words)); HIP_TRY(c, hipMemcpy(d_gt.as<void>(), gather_time, words, hipMemcpyHostToDevice)); }
     const size_t lds = c->info.lds_bytes;
-    hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, c->stream, c->sc, (const float*)d_rays,
-                       (const float*)d_rt, (const float*)d_gt, n, d_t, d_p, (uint32_t)kBlock);
-    HIP_TRY_D(hipGetLastError());
-    HIP_TRY_D(hipStreamSynchronize(c->stream));
-    HIP_TRY_D(hipMemcpy(out_t, d_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY_D(hipMemcpy(out_prim, d_p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    cleanup();
-#undef HIP_TRY_D
+    hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, c->stream, c->sc, d_rays.as<const float>(),
+                       d_rt.as<const float>(), d_gt.as<const float>(), n, d_t.as<float>(), d_p.as<int32_t>(), (uint32_t)kBlock);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_t, d_t.as<void>(), words, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_prim, d_p.as<void>(), words, hipMemcpyDeviceToHost));
     return RTW_OK;
 }
 
@@ -1900,36 +1813,6 @@ int cast_check(rtw_ctx* c, const char* what, const float* rays, size_t n, int32_
 // scope of one call (device context, stream, the two timing events, the control words, the staging slab), the chunk loop of the host
 // variants, the view records and the stats tail. What is specific to an entry point is its checks, what it stages and what it issues.
 
-// A device buffer that a context grows on demand and keeps until rtw_destroy: at least `need` of the capacity's unit (bytes; probes
-// for padapt), `bytes` large when it has to be made anew. drain: the stream whose pending work may still read the old buffer and is
-// waited for before that is freed, or null where every use has been waited for. A failed allocation leaves the pointer null and the
-// capacity 0.
-hipError_t grow_buffer(void*& buf, size_t& cap, size_t need, size_t bytes, const hipStream_t* drain) {
-    if (need <= cap) return hipSuccess;
-    if (drain) {
-        const hipError_t e = hipStreamSynchronize(*drain);
-        if (e != hipSuccess) return e;
-    }
-    if (buf) (void)hipFree(buf);
-    buf = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(&buf, bytes);
-    if (e != hipSuccess) { buf = nullptr; return e; }
-    cap = need;
-    return hipSuccess;
-}
-
-// the context's two timing events, out of its pool (no event is created once a context has timed anything)
-hipError_t timing_events(rtw_ctx* d, hipEvent_t ev[2]) {
-    while (d->ev_pool.size() < 2) {
-        hipEvent_t n = nullptr;
-        const hipError_t e = hipEventCreate(&n);
-        if (e != hipSuccess) return e;
-        d->ev_pool.push_back(n);
-    }
-    ev[0] = d->ev_pool[0]; ev[1] = d->ev_pool[1];
-    return hipSuccess;
-}
-
 // One call of the family, from the last refusal to the return.
 struct QueryCall {
     rtw_ctx* d = nullptr;     // the device context it runs on (a group's first device)
@@ -1947,12 +1830,12 @@ int query_open(rtw_ctx* c, QueryCall& q, void* hip_stream, size_t stage_bytes, b
     rtw_ctx* const d = q.d = c->kids.empty() ? c : c->kids[0];
     HIP_TRY(c, hipSetDevice(d->device));
     q.s = hip_stream ? (hipStream_t)hip_stream : d->stream;
-    HIP_TRY(c, grow_buffer(d->stage_slab, d->stage_bytes, stage_bytes, stage_bytes, nullptr));
-    q.stage = (char*)d->stage_slab;
+    HIP_TRY(c, d->stage_slab.grow(stage_bytes, stage_bytes));
+    q.stage = d->stage_slab.as<char>();
     HIP_TRY(c, timing_events(d, q.ev));
-    if (ctl && !d->rad_ctl) HIP_TRY(c, hipMalloc((void**)&d->rad_ctl, (kStatRows * 8 + 2) * sizeof(unsigned long long)));
+    if (ctl) HIP_TRY(c, d->rad_ctl.grow(kCtlBytes, kCtlBytes));
     if (timed) HIP_TRY(c, hipEventRecord(q.ev[0], q.s));
-    if (ctl) HIP_TRY(c, hipMemsetAsync(d->rad_ctl, 0, kStatRows * 8 * sizeof(unsigned long long), q.s));
+    if (ctl) HIP_TRY(c, hipMemsetAsync(d->rad_ctl.as<void>(), 0, kStatRows * 8 * sizeof(unsigned long long), q.s));
     return RTW_OK;
 }
 
@@ -2003,8 +1886,8 @@ int view_records_check(rtw_ctx* c, const char* what, const rtw_view* views, size
 // ... and their copy to the context's record buffer, on the call's stream (after ev[0]: the upload is part of the call's time)
 int view_records_upload(rtw_ctx* c, QueryCall& q, const rtw_view* views, size_t n_views) {
     const size_t bytes = n_views * sizeof(rtw_view);
-    HIP_TRY(c, grow_buffer(q.d->view_buf, q.d->view_bytes, bytes, bytes, nullptr));
-    HIP_TRY(c, hipMemcpyAsync(q.d->view_buf, views, bytes, hipMemcpyHostToDevice, q.s));
+    HIP_TRY(c, q.d->view_buf.grow(bytes, bytes));
+    HIP_TRY(c, hipMemcpyAsync(q.d->view_buf.as<void>(), views, bytes, hipMemcpyHostToDevice, q.s));
     return RTW_OK;
 }
 
@@ -2020,7 +1903,7 @@ int query_stats(rtw_ctx* c, QueryCall& q, rtw_stats* stats, uint64_t samples, bo
         stats->shadow_rays = samples;
     } else {
         unsigned long long hs[8];
-        if ((rc = sum_stat_rows(c, q.d->rad_ctl, hs)) != RTW_OK) return rc;
+        if ((rc = sum_stat_rows(c, q.d->rad_ctl.as<unsigned long long>(), hs)) != RTW_OK) return rc;
         stats->segments = hs[0]; stats->shadow_rays = hs[1];
         stats->algorithmic_bytes = 128ull * stats->segments + 32ull * stats->samples;
     }
@@ -2139,7 +2022,7 @@ int radiance_check(rtw_ctx* c, const char* what, const float* rays, size_t n, co
 
 // the context's unit slab, at least `need` bytes: grown after the stream's pending work, which may still read the old one
 int radiance_slab(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
-    HIP_TRY(c, grow_buffer(d->rad_slab, d->rad_slab_bytes, (size_t)need, (size_t)need, &s));
+    HIP_TRY(c, d->rad_slab.grow((size_t)need, (size_t)need, &s));
     return RTW_OK;
 }
 
@@ -2162,7 +2045,7 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
         OcclusionArgs a{};
         a.probes = (const float4*)d_probes + 2 * rg.first;
         a.out = d_out + rg.first;
-        a.counts = (uint32_t*)d->rad_slab;
+        a.counts = d->rad_slab.as<uint32_t>();
         a.n = (uint32_t)rg.count; a.units_per_probe = units; a.n_units = (uint32_t)(rg.count * units);
         magic_div(a.n, a.divn_m, a.divn_s1, a.divn_s2);
         a.spp = (uint32_t)RP->spp; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed;
@@ -2171,7 +2054,7 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, d->sc, a);
         HIP_TRY(c, hipGetLastError());
         if (units > 1) {
-            hipLaunchKernelGGL(k_probe_occlusion_resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, d_out + rg.first, a.n,
+            hipLaunchKernelGGL(k_probe_occlusion_resolve, dim3(pixel_grid(d, rg.count)), dim3(kBlock), 0, s, d->rad_slab.as<const uint32_t>(), d_out + rg.first, a.n,
                                units, (float)RP->spp);
             HIP_TRY(c, hipGetLastError());
         }
@@ -2187,7 +2070,7 @@ int occlusion_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_p
 int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_rays, size_t n, const rtw_radiance_params* RP, uint32_t key_offset,
                    float4* d_out, hipStream_t s, int query, const ViewFrame* vf = nullptr) {
     if (query == RTW_PROBE_OCCLUSION) return occlusion_issue(c, d, tune, d_rays, n, RP, key_offset, d_out, s);
-    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    uint32_t* const queue = (uint32_t*)(d->rad_ctl.as<unsigned long long>() + kStatRows * 8);
     const bool sh = query == kQueryProbeSh;
     const size_t stride = query_stride(query);
     if (RP->max_depth == 0 && sh) {  // no segment is traced: every coefficient is 0 (n <= 2^31 - 1: the launch goes by ranges as well)
@@ -2226,9 +2109,9 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         const RadianceRange rg = radiance_range(n, per, r);
         RadianceArgs a{};
         a.rays = views ? (const float4*)d_rays : (const float4*)d_rays + 2 * rg.first;
-        a.out = units > 1 ? (float4*)d->rad_slab : d_out + rg.first * stride;
+        a.out = units > 1 ? d->rad_slab.as<float4>() : d_out + rg.first * stride;
         a.queue = queue;
-        a.stats = d->rad_ctl;
+        a.stats = d->rad_ctl.as<unsigned long long>();
         a.n = (uint32_t)rg.count; a.units_per_ray = units; a.n_units = (uint32_t)(rg.count * units);
         const size_t grid = std::min<size_t>(((size_t)a.n_units + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
         a.job_units = radiance_job_units(RP->spp, a.n_units, grid * (kBlock / 64));
@@ -2249,7 +2132,7 @@ int radiance_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_ra
         }
         HIP_TRY(c, hipGetLastError());
         if (units > 1) {
-            hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count * stride)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, d_out + rg.first * stride, a.n, units,
+            hipLaunchKernelGGL(resolve, dim3(pixel_grid(d, rg.count * stride)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), d_out + rg.first * stride, a.n, units,
                                (float)RP->spp);
             HIP_TRY(c, hipGetLastError());
         }
@@ -2404,7 +2287,7 @@ int impl_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view
         c, q, n, chunk, no_upload,
         [&](size_t i0, size_t m) {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
             const ViewFrame vf{VP->width, VP->height, (uint64_t)i0};
-            return radiance_issue(c, q.d, tune, (const float*)q.d->view_buf, m, &rp, 0u, st_out, q.s, kQueryViews, &vf);
+            return radiance_issue(c, q.d, tune, q.d->view_buf.as<const float>(), m, &rp, 0u, st_out, q.s, kQueryViews, &vf);
         },
         [&](size_t i0, size_t m) -> int {
             HIP_TRY(c, hipMemcpyAsync(rgba_out + 4 * i0, st_out, m * 16, hipMemcpyDeviceToHost, q.s));
@@ -2480,7 +2363,7 @@ int impl_views_guides(rtw_ctx* c, const rtw_view* views, size_t n_views, const r
     rc = query_chunks(
         c, q, n, chunk, no_upload,
         [&](size_t i0, size_t m) -> int {  // a chunk may begin and end mid-row and mid-view: a pixel knows its own index
-            HIP_TRY(c, views_guides_launch(q.d, q.d->view_buf, VP, (uint64_t)i0, m, g, q.s));
+            HIP_TRY(c, views_guides_launch(q.d, q.d->view_buf.as<void>(), VP, (uint64_t)i0, m, g, q.s));
             return RTW_OK;
         },
         [&](size_t i0, size_t m) -> int {
@@ -2513,9 +2396,9 @@ int denoise_views_check(rtw_ctx* c, const char* what, const float* rgba_in, cons
 
 // the context's denoiser scratch, at least `need` bytes: grown after the stream's pending work, which may still read the old one
 int denoise_views_scratch(rtw_ctx* c, rtw_ctx* d, uint64_t need, hipStream_t s) {
-    if (need <= d->dn_bytes) return RTW_OK;
+    if (need <= d->dn_buf.cap()) return RTW_OK;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (grow_buffer(d->dn_buf, d->dn_bytes, (size_t)need, (size_t)need, nullptr) != hipSuccess)
+    if (d->dn_buf.grow((size_t)need, (size_t)need) != hipSuccess)
         return fail(c, RTW_ERR_OOM, "rtw_denoise_views: device allocation failed");
     return RTW_OK;
 }
@@ -2554,7 +2437,7 @@ int impl_denoise_views_device(rtw_ctx* c, const float* rgba_in, const float* alb
     QueryCall q;  // (untimed: ev[1] is the completion wait alone)
     if ((rc = query_open(c, q, hip_stream, 0, false, false)) != RTW_OK) return rc;
     if ((rc = denoise_views_scratch(c, q.d, denoise_views_scratch_bytes(n, iterations, false), q.s)) != RTW_OK) return rc;
-    HIP_TRY(c, denoise_views_issue(q.d, (const float4*)rgba_in, (const float4*)albedo, (const float4*)normal, (float4*)rgba_out, (float4*)q.d->dn_buf, n,
+    HIP_TRY(c, denoise_views_issue(q.d, (const float4*)rgba_in, (const float4*)albedo, (const float4*)normal, (float4*)rgba_out, q.d->dn_buf.as<float4>(), n,
                                    width, height, iterations, sigma, sigma_albedo, sigma_normal, q.s));
     return query_close(c, q, nullptr);
 }
@@ -2570,7 +2453,7 @@ int impl_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, co
     HIP_TRY(c, hipSetDevice(d->device));
     if ((rc = denoise_views_scratch(c, d, denoise_views_scratch_bytes(n, iterations, true), d->stream)) != RTW_OK) return rc;
     const size_t each = (size_t)denoise_views_buffer_bytes(n);
-    char* const b = (char*)d->dn_buf;  // colour, albedo, normal, output, then the ping-pong buffer
+    char* const b = d->dn_buf.as<char>();  // colour, albedo, normal, output, then the ping-pong buffer
     const float* const src[3] = {rgba_in, albedo, normal};
     for (int k = 0; k < 3; k++) HIP_TRY(c, hipMemcpyAsync(b + k * each, src[k], n * 16, hipMemcpyHostToDevice, d->stream));
     HIP_TRY(c, denoise_views_issue(d, (const float4*)b, (const float4*)(b + each), (const float4*)(b + 2 * each), (float4*)(b + 3 * each),
@@ -2595,8 +2478,8 @@ struct ProbeAdaptState {
 // the context's per-probe state for at least n probes: grown after the stream's pending work, kept until rtw_destroy
 int ensure_probe_adapt(rtw_ctx* c, rtw_ctx* d, size_t n, hipStream_t s, ProbeAdaptState& st) {
     const ProbeAdaptiveLayout l = probe_adaptive_layout(n);  // (the layout for n fits in an allocation made for more probes)
-    HIP_TRY(c, grow_buffer(d->padapt, d->padapt_probes, n, (size_t)l.bytes(), &s));
-    char* b = (char*)d->padapt;
+    HIP_TRY(c, d->padapt.grow(n, (size_t)l.bytes(), &s));
+    char* b = d->padapt.as<char>();
     typedef ProbeAdaptiveLayout PL;
     st.accum = (float4*)(b + l.off[PL::kAccum]); st.upart = (float4*)(b + l.off[PL::kUpart]); st.mom = (double2*)(b + l.off[PL::kMom]);
     st.n = (uint32_t*)(b + l.off[PL::kN]); st.err = (float*)(b + l.off[PL::kErr]); st.total = (uint32_t*)(b + l.off[PL::kTotal]);
@@ -2632,7 +2515,7 @@ int adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, size_t n, const v
     int rc = ensure_probe_adapt(c, d, n, s, st);
     if (rc) return rc;
     const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu(kernel, d->info.lds_bytes, 0);
-    uint32_t* const queue = (uint32_t*)(d->rad_ctl + kStatRows * 8);
+    uint32_t* const queue = (uint32_t*)(d->rad_ctl.as<unsigned long long>() + kStatRows * 8);
     const unsigned all_grid = pixel_grid(d, n);
     const uint32_t n_waves = (uint32_t)((n + 63) / 64);
     hipLaunchKernelGGL(k_probe_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.mom, st.n, st.err, st.total, (uint32_t)n);
@@ -2650,13 +2533,13 @@ int adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, size_t n, const v
             const RadianceRange rg = radiance_range(n_active, per, r);
             const uint32_t* const list = st.list[cur] + rg.first;
             if (zero_depth) {
-                HIP_TRY(c, hipMemsetAsync(d->rad_slab, 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
+                HIP_TRY(c, hipMemsetAsync(d->rad_slab.as<void>(), 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
             } else {
                 ListPass p{};
                 p.list = list;
-                p.out = (float4*)d->rad_slab;
+                p.out = d->rad_slab.as<float4>();
                 p.queue = queue;
-                p.stats = d->rad_ctl;
+                p.stats = d->rad_ctl.as<unsigned long long>();
                 p.n = (uint32_t)rg.count; p.n_blocks = nb; p.run_blocks = run_blocks; p.n_units = (uint32_t)(rg.count * runs);
                 p.grid = (unsigned)std::min<size_t>(((size_t)p.n_units + kBlock - 1) / kBlock, max_grid);
                 p.job_units = probe_adaptive_job_units(run_blocks, p.n_units, (size_t)p.grid * (kBlock / 64));
@@ -2711,10 +2594,10 @@ int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float
         },
         [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
             if (occ)
-                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const uint32_t*)d->rad_slab, list, count, nb,
+                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const uint32_t>(), list, count, nb,
                                    st.total, st.mom);
             else
-                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, count, nb, blk0,
+                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), list, count, nb, blk0,
                                    st.accum, st.upart, st.mom);
         },
         [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // rtw_render_adaptive's rule over a frame of n x 1, dilate 0
@@ -2837,7 +2720,7 @@ int view_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const rtw_vi
             hipLaunchKernelGGL(k, dim3(p.grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
         },
         [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
-            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, (const float4*)d->rad_slab, list, count, nb, blk0, st.accum,
+            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), list, count, nb, blk0, st.accum,
                                st.upart, st.mom);
         },
         [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // the rule dilated inside each view
@@ -2908,7 +2791,7 @@ int impl_adaptive_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const
     rc = query_chunks(
         c, q, n, chunk, no_upload,
         [&](size_t i0, size_t m) {  // a batch's pixels start at its first view's first
-            return view_adaptive_issue(c, q.d, tune, (const rtw_view*)q.d->view_buf + i0 / frame, m / frame, VP, &rp, AD, cps, (float4*)base,
+            return view_adaptive_issue(c, q.d, tune, q.d->view_buf.as<const rtw_view>() + i0 / frame, m / frame, VP, &rp, AD, cps, (float4*)base,
                                        (int32_t*)(base + o_spp), (float*)(base + o_err), q.s, samples);
         },
         [&](size_t i0, size_t m) -> int {
@@ -2925,10 +2808,11 @@ int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
-    unsigned long long* d = nullptr;
     const unsigned long long init[3] = {0ull, 0ull, ~0ull};
     unsigned long long got[3];
-    HIP_TRY(c, hipMalloc(&d, sizeof init));
+    DevBuf buf;
+    HIP_TRY(c, buf.grow(sizeof init, sizeof init));
+    unsigned long long* const d = buf.as<unsigned long long>();
     hipError_t e = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         // 2^16 blocks of 256 threads: 256 patterns per thread
@@ -2937,7 +2821,6 @@ int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(got, d, sizeof got, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(c, RTW_ERR_DEVICE, std::string("rtw_debug_math: ") + hipGetErrorString(e));
     for (int i = 0; i < 3; i++) out[i] = got[i];
     return RTW_OK;

@@ -53,6 +53,11 @@ struct MathHw {
     static RTW_DEV float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
     static RTW_DEV bool all(bool ok) { return __builtin_amdgcn_ballot_w64(!ok) == 0ull; }
 };
+// the policy for code that takes one (rtw_nee.h): with RTW_SHORT_FORMS = 0 no range test passes, so every call takes the compiler's form
+struct MathIeee : MathHw {
+    static RTW_DEV bool all(bool) { return false; }
+};
+using MathSel = std::conditional_t<RTW_SHORT_FORMS != 0, MathHw, MathIeee>;
 // 1.0f / x, sqrtf(x), and sqrtf(x) for an x that the code around the call keeps inside rtw_math.h's window (no range test)
 RTW_DEV float rcp_(float x) { return RTW_SHORT_FORMS ? rtwmath::rcp<MathHw>(x) : 1.0f / x; }
 RTW_DEV float sqrt_(float x) { return RTW_SHORT_FORMS ? rtwmath::sqrt<MathHw>(x) : __builtin_sqrtf(x); }

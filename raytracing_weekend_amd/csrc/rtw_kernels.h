@@ -27,6 +27,7 @@
 #pragma once
 #include "rtw_ahead.h"
 #include "rtw_device.h"
+#include "rtw_nee.h"
 #include "rtw_plan.h"
 
 namespace rtwk {
@@ -248,6 +249,8 @@ struct NoRng {
 };
 
 // ------------------------------------------------------------------ shading
+// k_path's one-light instantiation with RTW_PATH_FLAT_NEE (rtw_nee.h) sets `has` always and the other fields only where has holds: they are
+// unspecified otherwise, and read only under has
 struct Nee {
     bool has;
     v3 dir, rad;  // rad = f * Le * (w * (wL.n) / pdfL), not yet multiplied by the throughput
@@ -296,7 +299,10 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
     radiance = V(0.f, 0.f, 0.f);
     att = V(0.f, 0.f, 0.f);
     so = origin; sd = dir;
+    constexpr bool FLAT = NEE1 && RTW_PATH_FLAT_NEE != 0;  // the light sample and the Lambertian's event without control flow (rtw_nee.h)
     nee.has = false;
+    // (FLAT overwrites these with unspecified values where has stays false. Leaving them out there saves 25 more VALU instructions and
+    // costs 28 B of scratch, three accesses of it inside the probe walk: kept)
     nee.dir = V(0.f, 0.f, 0.f); nee.rad = V(0.f, 0.f, 0.f); nee.tmin = 0.f; nee.tmax = -1.f;
     if (prim < 0) {
         if (sc.sky_light) {  // miss.cu:8-21
@@ -358,9 +364,15 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
         sdir = normalize3(sdir);
         so = hp; sd = sdir;
         float cosine = dot3(hn, sdir);
-        ev = EV_HIT;
-        if (cosine <= 0.0f || pdf <= 0.0f) ev = EV_CANCEL;
-        else att = tex;
+        if constexpr (FLAT) {
+            // att is read only where ev == EV_HIT (the light sample below, shade_b): no merge of att, ev by a select
+            att = tex;
+            ev = ((cosine <= 0.0f) | (pdf <= 0.0f)) ? EV_CANCEL : EV_HIT;
+        } else {
+            ev = EV_HIT;
+            if (cosine <= 0.0f || pdf <= 0.0f) ev = EV_CANCEL;
+            else att = tex;
+        }
     RTW_MARK2("sa_light");
     } else if (mtype == RTW_MAT_DIFFUSE_LIGHT) {
         // diffuseLight.cu:48-69
@@ -523,6 +535,19 @@ RTW_DEV int shade_a(const DScene& sc, Rng<KIND>& g, const v3 origin, const v3 di
             gen = sc.pdf.gen;
             if (gen == RTW_PDF_MIXTURE || gen == RTW_PDF_MIXTURE_BIAS) gen = sc.pdf.p1_gen;
             rc0 = sc.pdf.rect[0]; rc1 = sc.pdf.rect[1]; rc2 = sc.pdf.rect[2]; rc3 = sc.pdf.rect[3]; rc4 = sc.pdf.rect[4];
+        }
+        if constexpr (FLAT) {
+            float ra, rb;
+            if (KIND == RTW_RNG_PHILOX) {
+                ra = g.block_draw(2); rb = g.block_draw(3);  // draws 2 and 3 of the vertex's block, as below
+                g.a += 2u;
+            } else {
+                ra = g.next1();
+                rb = g.next1();
+            }
+            nee.has = rtwnee::rect_sample_flat<MathSel>(ra, rb, rc0, rc1, rc2, rc3, rc4, gen, lnrm, lemi, larea, so, hn, att, (int)hr.bsdf_eval,
+                                                        sc.probe_eps, nee.dir, nee.tmin, nee.tmax, nee.rad);
+            return ev;
         }
         float lpdf = 0.0f, ldist = 0.0f;
         v3 ldir = V(0.f, 0.f, 0.f), lem = V(0.f, 0.f, 0.f);

@@ -101,6 +101,18 @@ RTW_MATH_FN float rcp_sqrt(float x) {
     if (__builtin_expect(P::all(sqrt_window(x)), 1)) return rcp_sqrt_short<P>(x);
     return 1.0f / __builtin_sqrtf(x);
 }
+// root = sqrtf(x) and inv = 1.0f / root, the length of a vector and the factor that normalises it: one test for both, by the
+// argument of rcp_sqrt (the root of an x inside the window is inside it). The sequences are sqrt's and rcp's own.
+template <class P>
+RTW_MATH_FN void sqrt_rcp(float x, float& root, float& inv) {
+    if (__builtin_expect(P::all(sqrt_window(x)), 1)) {
+        root = sqrt_short<P>(x);
+        inv = rcp_short<P>(root);
+    } else {
+        root = __builtin_sqrtf(x);
+        inv = 1.0f / root;
+    }
+}
 // (1/x, 1/y, 1/z) in place, one test
 template <class P>
 RTW_MATH_FN void rcp3(float& x, float& y, float& z) {

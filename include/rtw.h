@@ -869,6 +869,101 @@ int rtw_denoise_views_device(rtw_ctx* ctx, const float* rgba_in, const float* al
                              int32_t width, int32_t height, int32_t iterations, float sigma, float sigma_albedo, float sigma_normal,
                              void* hip_stream);
 
+/* Path records: replay samples and return every vertex of their paths (which of a pixel's 4096 samples is the firefly and what it
+ * bounced off; direct against indirect light, per-bounce layers, per-light contributions and path-length histograms as folds over the
+ * vertices; (position, direction, throughput, contribution) tuples for path guiding, left on the device). Every other entry point
+ * reduces a path to three floats and the samples to a mean; these return the samples themselves, one head per sample and one vertex
+ * per traced segment.
+ *   Same path as rtw_radiance: sample s of ray i is the rtw_radiance sample of that ray (rtw_cast's eight floats; tmin and tmax bound
+ *     the first segment only) at stream key key_offset + i (mod 2^32) and sample index sample_offset + s: the same draws, media,
+ *     light sampling, shadow probe, roulette and depth limit, operation for operation. rtw_paths_views replays rtw_views' samples
+ *     in the same way: pixels [first, first + count) of rtw_views' flattened index (view * height + y) * width + x, the camera ray
+ *     generated on the device from the pixel's view record, the stream key width * y + x, the seed the view's own. To replay sample
+ *     s of pixel (x, y) of view v: first = (v * height + y) * width + x, count = 1, sample_offset = s, spp = 1.
+ *   Head: radiance carries the bits rtw_radiance (rtw_views) returns in rgb for spp = 1 at that sample index - the sample after
+ *     removeNaNs, added to +0 as that call's sums add it, so a -0 comes back as +0. Hence the sum of a ray's head radiances in the
+ *     order of RTW_SUM_BLOCK / RTW_SUM_UNIT_BLOCKS counted from sample_offset, divided by (float)spp, is rtw_radiance's result for
+ *     that spp. segments counts the segments traced (it may exceed max_records), shadow_rays the light-sample probes traced,
+ *     gather_time is the sample's gather time, key and sample its stream key and its absolute sample index.
+ *   Vertices: vertex j is segment j of the path. o and d are the segment's origin and direction as traced (d is not normalised;
+ *     record 0 of rtw_paths carries the caller's o and d), t the hit parameter (the segment's tmax on a miss: the caller's tmax for
+ *     segment 0 of rtw_paths, else 1e27f), prim the primitive hit, volume primitives included, -1 on a miss. throughput is the
+ *     path's throughput T that weighted this segment ((1, 1, 1) at the first), contribution the term the segment added to the
+ *     sample: (emitted or sky radiance + the light sample where its probe came back unoccluded) * T. ray_time is the segment's ray
+ *     time. flags = the segment's event (RTW_PATH_MISS: nothing hit, the path ends; RTW_PATH_SCATTER: the material scattered, the
+ *     path goes on unless the roulette or the depth limit ends it; RTW_PATH_END: an emitter or an absorbing event, the path ends;
+ *     RTW_PATH_CANCEL: the material cancelled the path) | RTW_PATH_LIGHT_SAMPLED where a light-sample probe was traced from this
+ *     segment's hit | RTW_PATH_LIGHT_ADDED where that probe came back unoccluded. Whenever segments <= max_records: adding the
+ *     contributions in float32 in order from +0 and replacing NaN channels by 0 gives head.radiance bit for bit, and the number of
+ *     RTW_PATH_LIGHT_SAMPLED records is head.shadow_rays.
+ *   Layout: heads_out[i * spp + s]; vertices_out[(i * spp + s) * max_records + j] for j < min(segments, max_records). Entries
+ *     beyond that are not written. i counts rays, or pixels from `first`.
+ *   max_depth = 0 gives segments = 0, radiance 0 and no records. max_records = 0 returns the heads alone - the cheap way to find
+ *     an outlier among thousands of samples - and vertices_out must then be NULL.
+ *   Independence: a head and its records depend on the ray (or the pixel and its view record), the key and the params alone: not on
+ *     n, count, how the call is cut into chunks, the launch geometry or tuning knobs.
+ *   rtw_paths / rtw_paths_views: host pointers. Rays, heads and records are staged through rtw_radiance's staging slab in chunks of
+ *     whole rays (pixels): as many as keep a chunk's heads and records within RTW_PATHS_CHUNK_BYTES (an environment variable read
+ *     per call, csrc/rtw_plan.h), at least one; chunk c runs with the key of its first ray, or from its first pixel. A chunk's
+ *     records come back whole, so the caller's bytes go up first: vertices_out is read, and an entry that is not written keeps
+ *     what it held. rtw_paths_views reads and checks its records as rtw_views does.
+ *   rtw_paths_device / rtw_paths_views_device: device pointers on the context's device, all 16-byte aligned. Ordered on hip_stream
+ *     exactly as rtw_radiance_device is; returns when the results are written. NULL selects the context's own non-blocking stream,
+ *     NOT the legacy default stream. One persistent launch: a lane owns one (ray, sample) pair at a time. It allocates nothing per
+ *     call. rtw_paths_views_device does not read the records back (rtw_views_device's rule for camera_type and `reserved`).
+ *   Groups (n_devices > 1): the call runs on device_ids[0]; the bits are a single-device context's.
+ *   An accumulation session on the context is not disturbed.
+ *   stats (may be NULL): samples = n * spp (count * spp), segments = the sum of head.segments, shadow_rays = the sum of
+ *     head.shadow_rays, algorithmic_bytes and seconds as rtw_radiance reports them; the per-kernel arrays are 0.
+ *   Errors: rtw_radiance's list (rtw_paths_views: rtw_views' list, for the params built from view_params and the whole of
+ *     n_views * width * height) and RTW_ERR_INVALID_ARG for max_records < 0 or > max_depth, a non-zero reserved word,
+ *     n * spp > 2^31 - 1 (count * spp), with n > 0 a NULL heads_out, a NULL vertices_out with max_records > 0 or a non-NULL one
+ *     with max_records = 0, first + count beyond the call's pixels, and (the device variants) a misaligned pointer. A refused call
+ *     writes nothing and leaves *stats alone. n = 0 (count = 0) is RTW_OK and launches nothing. The context stays usable after an
+ *     error. */
+enum { RTW_PATH_MISS = 0, RTW_PATH_SCATTER = 1, RTW_PATH_END = 2, RTW_PATH_CANCEL = 3 };
+enum { RTW_PATH_EVENT_MASK = 3, RTW_PATH_LIGHT_SAMPLED = 4, RTW_PATH_LIGHT_ADDED = 8 };
+
+typedef struct rtw_path_vertex {
+    float o[3];            /* the segment's origin                                                   */
+    float t;               /* the hit parameter; the segment's tmax on a miss                        */
+    float d[3];            /* its direction as traced (not normalised)                               */
+    int32_t prim;          /* the primitive hit (volumes included), -1: miss                         */
+    float contribution[3]; /* radiance * T: what the segment added to the sample                     */
+    uint32_t flags;        /* event | RTW_PATH_LIGHT_*                                               */
+    float throughput[3];   /* T that weighted this segment, (1, 1, 1) at the first                   */
+    float ray_time;        /* the segment's ray time                                                 */
+} rtw_path_vertex;         /* 64 B */
+
+typedef struct rtw_path_head {
+    float radiance[3];     /* the sample after removeNaNs: what joins the block sum                  */
+    int32_t segments;      /* segments traced (may exceed max_records)                               */
+    float gather_time;
+    int32_t shadow_rays;   /* light-sample probes traced                                             */
+    uint32_t key, sample;  /* the stream key and the absolute sample index                           */
+} rtw_path_head;           /* 32 B */
+
+typedef struct rtw_paths_params {
+    int32_t spp;            /* samples per ray (pixel), > 0                                  */
+    int32_t max_depth;      /* as rtw_radiance_params.max_depth                              */
+    uint32_t seed;          /* (rtw_paths_views: unused, the seed is the view's)             */
+    int32_t rng_kind;       /* rtw_rng_kind                                                  */
+    int32_t sample_offset;  /* first sample index; sample_offset + spp <= INT32_MAX          */
+    int32_t estimator;      /* rtw_estimator                                                 */
+    uint32_t key_offset;    /* ray i draws from the stream of key_offset + i (mod 2^32)      */
+    int32_t max_records;    /* vertices kept per sample, 0 .. max_depth (0: heads only)      */
+    uint32_t reserved[2];   /* 0, else RTW_ERR_INVALID_ARG                                   */
+} rtw_paths_params;         /* 40 B */
+
+int rtw_paths(rtw_ctx* ctx, const float* rays, size_t n, const rtw_paths_params* params, rtw_path_head* heads_out,
+              rtw_path_vertex* vertices_out, rtw_stats* stats);
+int rtw_paths_device(rtw_ctx* ctx, const float* rays, size_t n, const rtw_paths_params* params, void* d_heads, void* d_vertices,
+                     void* hip_stream, rtw_stats* stats);
+int rtw_paths_views(rtw_ctx* ctx, const rtw_view* views, size_t n_views, const rtw_view_params* view_params, uint64_t first, uint64_t count,
+                    int32_t max_records, rtw_path_head* heads_out, rtw_path_vertex* vertices_out, rtw_stats* stats);
+int rtw_paths_views_device(rtw_ctx* ctx, const rtw_view* d_views, size_t n_views, const rtw_view_params* view_params, uint64_t first,
+                           uint64_t count, int32_t max_records, void* d_heads, void* d_vertices, void* hip_stream, rtw_stats* stats);
+
 /* Test hooks (no reference counterpart): one closest-hit query per ray on the GPU accel structure,
  * used by the parity tests to compare BVH traversal with the oracle's brute force.
  * rays: n*8 floats (ox,oy,oz,dx,dy,dz,tmin,tmax); ray_time: n floats or NULL;

@@ -138,6 +138,34 @@ class ViewParams(C.Structure):
                 ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class PathVertex(C.Structure):
+    """rtw_path_vertex (include/rtw.h): one traced segment of a replayed path."""
+    _fields_ = [("o", C.c_float * 3), ("t", C.c_float), ("d", C.c_float * 3), ("prim", C.c_int32), ("contribution", C.c_float * 3),
+                ("flags", C.c_uint32), ("throughput", C.c_float * 3), ("ray_time", C.c_float)]
+
+
+class PathHead(C.Structure):
+    """rtw_path_head (include/rtw.h): one replayed sample."""
+    _fields_ = [("radiance", C.c_float * 3), ("segments", C.c_int32), ("gather_time", C.c_float), ("shadow_rays", C.c_int32),
+                ("key", C.c_uint32), ("sample", C.c_uint32)]
+
+
+class PathsParams(C.Structure):
+    """rtw_paths_params (include/rtw.h): rtw_radiance's sampling and the number of vertices kept per sample."""
+    _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint32), ("rng_kind", C.c_int32),
+                ("sample_offset", C.c_int32), ("estimator", C.c_int32), ("key_offset", C.c_uint32), ("max_records", C.c_int32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+# the two records as numpy sees them: structured dtypes with rtw.h's field names, sizes and offsets
+PATH_VERTEX = np.dtype([("o", np.float32, 3), ("t", np.float32), ("d", np.float32, 3), ("prim", np.int32), ("contribution", np.float32, 3),
+                        ("flags", np.uint32), ("throughput", np.float32, 3), ("ray_time", np.float32)])
+PATH_HEAD = np.dtype([("radiance", np.float32, 3), ("segments", np.int32), ("gather_time", np.float32), ("shadow_rays", np.int32),
+                      ("key", np.uint32), ("sample", np.uint32)])
+# rtw_path_vertex.flags: the event in the low two bits, then the light sample's two bits
+RTW_PATH_MISS, RTW_PATH_SCATTER, RTW_PATH_END, RTW_PATH_CANCEL = range(4)
+RTW_PATH_EVENT_MASK, RTW_PATH_LIGHT_SAMPLED, RTW_PATH_LIGHT_ADDED = 3, 4, 8
+
 _PTR, _STATS = C.c_void_p, C.POINTER(Stats)
 _DENOISE = [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float]  # two sizes, iterations, the three sigmas
 
@@ -181,7 +209,9 @@ for _name, _sig in (("rtw_radiance", _query([RadianceParams], _PTR)), ("rtw_prob
                     ("rtw_probe_sh", _query([RadianceParams], _PTR)), ("rtw_views", _query([ViewParams], _PTR)),
                     ("rtw_probe_adaptive", _query([ProbeParams, Adaptive], _PTR, _PTR, _PTR)),
                     ("rtw_views_guides", _query([ViewParams, Guides])),
-                    ("rtw_views_adaptive", _query([ViewParams, Adaptive], _PTR, _PTR, _PTR))):
+                    ("rtw_views_adaptive", _query([ViewParams, Adaptive], _PTR, _PTR, _PTR)),
+                    ("rtw_paths", _query([PathsParams], _PTR, _PTR)),
+                    ("rtw_paths_views", _query([ViewParams], C.c_uint64, C.c_uint64, C.c_int32, _PTR, _PTR))):
     HIP_SIGNATURES[_name], HIP_SIGNATURES[_name + "_device"] = _sig
 HIP_SYMBOLS = list(HIP_SIGNATURES)
 PROBE_MODES = {"irradiance": 0, "occlusion": 1}  # RTW_PROBE_IRRADIANCE, RTW_PROBE_OCCLUSION
@@ -367,6 +397,41 @@ def make_probe_params(spp, max_depth, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, s
     if mode not in PROBE_MODES:
         raise ValueError(f"probe: mode {mode!r} is neither 'irradiance' nor 'occlusion'")
     return ProbeParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, PROBE_MODES[mode])
+
+
+def make_paths_params(spp, max_depth, max_records=None, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0):
+    """rtw_paths_params; spp must be a positive integer and max_records (None: max_depth, every vertex) an integer in 0 .. max_depth."""
+    _positive("paths", "spp", spp)
+    k = _max_records("paths", max_records, max_depth)
+    return PathsParams(int(spp), int(max_depth), seed & 0xffffffff, rng_kind, sample_offset, estimator, key_offset & 0xffffffff, k, (C.c_uint32 * 2)(0, 0))
+
+
+def _max_records(prefix, max_records, max_depth):
+    if max_records is None:
+        return max(int(max_depth), 0)
+    if isinstance(max_records, bool) or not isinstance(max_records, (int, np.integer)) or not 0 <= max_records <= max(int(max_depth), 0):
+        raise ValueError(f"{prefix}: max_records = {max_records!r}, expected an integer in 0 .. max_depth")
+    return int(max_records)
+
+
+def _check_pairs(prefix, n, spp):
+    if n * int(spp) > 0x7fffffff:
+        raise ValueError(f"{prefix}: more than 2^31 - 1 samples in one call")
+
+
+def _path_window(prefix, first, count, total):
+    """`first` of a window [first, first + count) of `total` flattened pixels, refused when it does not lie inside them."""
+    for name, v in (("first", first), ("count", count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"{prefix}: {name} = {v!r}, expected a non-negative integer")
+    if first + count > total:
+        raise ValueError(f"{prefix}: pixels [{first}, {first + count}) of {total}")
+    return int(first)
+
+
+def _path_buffers(n, spp, k):
+    """(heads (n, spp), vertices (n, spp, k), zeroed: the library writes the first min(segments, k) of a sample alone)"""
+    return np.zeros((n, int(spp)), dtype=PATH_HEAD), np.zeros((n, int(spp), k), dtype=PATH_VERTEX)
 
 
 def make_view(camera, camera_type=RTW_CAM_PERSPECTIVE, seed=0x6314759):
@@ -721,6 +786,56 @@ class Renderer:
         self._check(self.lib.rtw_views_adaptive_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), C.byref(ad), C.c_void_p(out_ptr),
                                                        C.c_void_p(spp_ptr), C.c_void_p(err_ptr), C.c_void_p(stream_ptr),
                                                        _ref(stats)), "rtw_views_adaptive_device")
+
+    # ---- replayed samples and the vertices of their paths (include/rtw.h rtw_paths / rtw_paths_views and their _device variants)
+    def paths(self, rays, spp, max_depth, max_records=None, seed=0x6314759, rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, key_offset=0,
+              stats=None):
+        """rtw_paths on (n, 8) float32 rays: (heads, vertices), structured arrays of dtype PATH_HEAD, shape (n, spp), and PATH_VERTEX,
+        shape (n, spp, max_records). Sample s of ray i is radiance()'s sample of that ray at key key_offset + i and sample index
+        sample_offset + s; heads["radiance"][i, s] carries the bits radiance(spp=1, sample_offset=sample_offset + s) returns.
+        vertices[i, s, j] is segment j of that path, written for j < min(heads["segments"][i, s], max_records); the rest stays zero.
+        max_records None keeps every vertex (max_depth of them), 0 returns the heads alone. `stats`: a Stats to fill, or None."""
+        rays = _batch("paths", "rays", rays)
+        pp = make_paths_params(spp, max_depth, max_records, seed, rng_kind, sample_offset, estimator, key_offset)
+        n = rays.shape[0]
+        _check_pairs("paths", n, spp)
+        heads, vertices = _path_buffers(n, spp, pp.max_records)
+        self._check(self.lib.rtw_paths(self.ctx, rays.ctypes.data, n, C.byref(pp), heads.ctypes.data, vertices.ctypes.data if pp.max_records else None,
+                                       _ref(stats)), "rtw_paths")
+        return heads, vertices
+
+    def paths_device(self, n, rays_ptr, heads_ptr, vertices_ptr, spp, max_depth, max_records=None, seed=0x6314759, rng_kind=RTW_RNG_PHILOX,
+                     sample_offset=0, estimator=0, key_offset=0, stream_ptr=0, stats=None):
+        """rtw_paths_device on raw device pointers, as radiance_device takes them: n rays at rays_ptr, n * spp heads (32 B) written at
+        heads_ptr and up to max_records vertices (64 B) per sample at vertices_ptr (0 with max_records = 0), all 16-byte aligned,
+        stream_ptr a hipStream_t (0: the context's own stream)."""
+        pp = make_paths_params(spp, max_depth, max_records, seed, rng_kind, sample_offset, estimator, key_offset)
+        self._check(self.lib.rtw_paths_device(self.ctx, C.c_void_p(rays_ptr), n, C.byref(pp), C.c_void_p(heads_ptr), C.c_void_p(vertices_ptr),
+                                              C.c_void_p(stream_ptr), _ref(stats)), "rtw_paths_device")
+
+    def paths_views(self, views, width, height, first, count, spp, max_depth, max_records=None, rng_kind=RTW_RNG_PHILOX, sample_offset=0,
+                    estimator=0, stats=None):
+        """rtw_paths_views on View records: paths()'s two arrays, shapes (count, spp) and (count, spp, max_records), for pixels
+        [first, first + count) of views()'s flattened (view, y, x) index: the samples views() averages, one by one. Pixel (x, y) of
+        view v is first = (v * height + y) * width + x. `stats`: a Stats to fill, or None."""
+        arr, vp = _view_batch("paths_views", views, width, height, spp, max_depth, rng_kind, sample_offset, estimator)
+        first = _path_window("paths_views", first, count, len(arr) * int(width) * int(height))
+        count, k = int(count), _max_records("paths_views", max_records, max_depth)
+        _check_pairs("paths_views", count, spp)
+        heads, vertices = _path_buffers(count, spp, k)
+        self._check(self.lib.rtw_paths_views(self.ctx, C.cast(arr, C.c_void_p), len(arr), C.byref(vp), first, count, k, heads.ctypes.data,
+                                             vertices.ctypes.data if k else None, _ref(stats)), "rtw_paths_views")
+        return heads, vertices
+
+    def paths_views_device(self, n, views_ptr, heads_ptr, vertices_ptr, width, height, first, count, spp, max_depth, max_records=None,
+                           rng_kind=RTW_RNG_PHILOX, sample_offset=0, estimator=0, stream_ptr=0, stats=None):
+        """rtw_paths_views_device on raw device pointers: n rtw_view records at views_ptr, count * spp heads at heads_ptr and up to
+        max_records vertices per sample at vertices_ptr (0 with max_records = 0), all 16-byte aligned, stream_ptr a hipStream_t (0:
+        the context's own stream)."""
+        vp = make_view_params(width, height, spp, max_depth, rng_kind, sample_offset, estimator)
+        k = _max_records("paths_views", max_records, max_depth)
+        self._check(self.lib.rtw_paths_views_device(self.ctx, C.c_void_p(views_ptr), n, C.byref(vp), int(first), int(count), k, C.c_void_p(heads_ptr),
+                                                    C.c_void_p(vertices_ptr), C.c_void_p(stream_ptr), _ref(stats)), "rtw_paths_views_device")
 
     # ---- guides of batched views and their denoiser (include/rtw.h rtw_views_guides / rtw_denoise_views)
     def views_guides(self, views, width, height, spp=16, which=GUIDES, rng_kind=RTW_RNG_PHILOX, sample_offset=0, stats=None):

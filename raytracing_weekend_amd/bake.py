@@ -1,7 +1,8 @@
 """Baking on top of rtw_probe and rtw_probe_sh (include/rtw.h): the probes at the texel centres of an axis-aligned rectangle primitive
 and the baked map - irradiance or ambient occlusion - in the layout of an RTW_TEX_IMAGE of that primitive; the points of an
 irradiance volume, the spherical-harmonic basis of rtw_probe_sh and the irradiance its nine coefficients give for a normal.
-Cameras for rtw_views: look_at (the host description's perspective camera), the six faces of a cube map and a turntable."""
+Cameras for rtw_views: look_at (the host description's perspective camera), the six faces of a cube map and a turntable.
+The polylines of the paths rtw_paths recorded (path_segments)."""
 import math
 
 import numpy as np
@@ -203,4 +204,28 @@ def orbit_views(blob, n, seed=0x6314759):
             else:
                 cam += rot(x)
         out.append(abi.make_view(np.array(cam + c[21:24], np.float64).astype(np.float32), base.camera_type, seeds[k]))
+    return out
+
+
+def path_segments(heads, vertices, miss_length=None):
+    """The world-space polylines of the paths Renderer.paths / paths_views recorded, for plotting: one (m + 1, 3) float32 array per
+    sample, in the arrays' order (ray-major), m = min(segments, max_records) the records the library wrote - the origins of its
+    segments and then the end point o + t * d of the last one (float32, one rounding per operation). A sample without records gives
+    a (0, 3) array. A path that leaves the scene ends on a miss, whose t is the segment's tmax (1e27 after the first segment):
+    miss_length, where given, is the ray parameter such a last segment is drawn to instead."""
+    heads, vertices = np.asarray(heads), np.asarray(vertices)
+    if heads.dtype != abi.PATH_HEAD or vertices.dtype != abi.PATH_VERTEX or vertices.shape[:-1] != heads.shape:
+        raise ValueError("path_segments: expected the (heads, vertices) pair of Renderer.paths or Renderer.paths_views")
+    k = vertices.shape[-1]
+    out = []
+    for h, v in zip(heads.reshape(-1), vertices.reshape(-1, k)):
+        m = min(int(h["segments"]), k)
+        if m == 0:
+            out.append(np.zeros((0, 3), np.float32))
+            continue
+        last = v[m - 1]
+        t = np.float32(miss_length) if miss_length is not None and last["prim"] < 0 else last["t"]
+        with np.errstate(over="ignore", invalid="ignore"):
+            end = (last["o"] + (t * last["d"]).astype(np.float32)).astype(np.float32)
+        out.append(np.concatenate([v["o"][:m], end[None, :]]).astype(np.float32))
     return out

@@ -24,7 +24,7 @@
 //     (rtw_accum.h) that keeps the summation unit open between adds; splitting and the saved form: rtw_accum_state.h
 //
 //   the query family (rtw_cast, rtw_radiance, rtw_probe, rtw_probe_sh, rtw_views, rtw_views_guides, rtw_denoise_views, rtw_probe_adaptive,
-//     rtw_views_adaptive, each with a _device variant): the caller's rays, probes, points or cameras through kernels of their own
+//     rtw_views_adaptive, rtw_paths, rtw_paths_views, each with a _device variant): the caller's rays, probes, points or cameras through kernels of their own
 //     translation units. On the host they share one scaffold: QueryCall
 //     (query_open / query_close: device context, stream, the two timing events, the control words), query_chunks for the host
 //     variants' upload / issue / copy-back loop through one staging slab (laid out by rtw_stage_plan.h), query_stats for the tail,
@@ -79,6 +79,8 @@
 #include "rtw_probe_adaptive_plan.h"
 #include "rtw_view_adaptive.h"
 #include "rtw_view_adaptive_plan.h"
+#include "rtw_paths.h"
+#include "rtw_paths_plan.h"
 #include "rtw_accum.h"
 #ifndef RTW_SPLIT_BUILD
 #include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
@@ -89,6 +91,7 @@
 #include "rtw_view.hip"  // (likewise)
 #include "rtw_probe_adaptive.hip"  // (likewise)
 #include "rtw_view_adaptive.hip"  // (likewise)
+#include "rtw_paths.hip"  // (likewise)
 #endif
 
 using namespace rtwdev;
@@ -2804,6 +2807,173 @@ int impl_adaptive_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const
     return query_stats(c, q, stats, samples, false);
 }
 
+// ---- rtw_paths / rtw_paths_device / rtw_paths_views / rtw_paths_views_device (rtw.h): rtw_radiance's (rtw_views') samples replayed
+// one by one through k_paths, a head per sample and a vertex per segment
+typedef void (*PathsKernel)(const DScene, const PathsArgs);
+// k_paths by its source, under names RTW_PICK can instantiate
+template <int KIND, int TEX> constexpr PathsKernel k_paths_rays = k_paths<KIND, TEX, kPathsRays>;
+template <int KIND, int TEX> constexpr PathsKernel k_paths_views = k_paths<KIND, TEX, kPathsViews>;
+
+// n rays at d_src (device), or with vf n pixels from flattened pixel vf->first of the view records at d_src -> their n * spp heads
+// and, K > 0, records, issued on stream s of device context d and not waited for: one persistent k_paths launch sized as k_cast's,
+// ray i on the stream of key0 + i. The counters add up in d->rad_ctl's rows, which the caller zeroed on s. n * spp <= 2^31 - 1.
+int paths_issue(rtw_ctx* c, rtw_ctx* d, const void* d_src, size_t n, const rtw_radiance_params* RP, uint32_t key0, int32_t K, float4* d_heads,
+                float4* d_vertices, hipStream_t s, const ViewFrame* vf) {
+    DScene sc = d->sc;
+    apply_estimator(sc, RP->estimator);
+    const PathsKernel k = vf ? RTW_PICK(k_paths_views, RP->rng_kind, sc.has_tex) : RTW_PICK(k_paths_rays, RP->rng_kind, sc.has_tex);
+    PathsArgs a{};
+    if (vf) a.v = view_frame_args(d_src, vf->width, vf->height, vf->first);
+    else a.v.rays = (const float4*)d_src;
+    a.v.stats = d->rad_ctl.as<unsigned long long>();
+    a.v.n = (uint32_t)n; a.v.spp = (uint32_t)RP->spp; a.v.sample0 = (uint32_t)RP->sample_offset; a.v.seed = RP->seed;
+    a.v.max_depth = (uint32_t)RP->max_depth; a.v.key0 = key0;
+    a.heads = d_heads; a.vertices = d_vertices;
+    a.n_pairs = (uint32_t)((uint64_t)n * (uint64_t)RP->spp); a.max_records = (uint32_t)K;
+    magic_div(a.v.spp, a.divs_m, a.divs_s1, a.divs_s2);
+    const size_t lds = d->info.lds_bytes;
+    const size_t per_cu = (size_t)path_wg_per_cu((const void*)k, lds, 0);
+    const size_t grid = std::min<size_t>(((size_t)a.n_pairs + kBlock - 1) / kBlock, (size_t)d->n_cu * per_cu);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, s, sc, a);
+    HIP_TRY(c, hipGetLastError());
+    return RTW_OK;
+}
+
+// what the four variants check after rtw_radiance's (rtw_views') own list, in rtw.h's order; n counts rays, or the pixels asked for
+int paths_check(rtw_ctx* c, const char* what, size_t n, const rtw_radiance_params& rp, int32_t K, const uint32_t* reserved, const void* heads,
+                const void* vertices, bool device) {
+    if (K < 0 || K > rp.max_depth) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": max_records outside 0 .. max_depth");
+    if (reserved && (reserved[0] != 0u || reserved[1] != 0u)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": reserved must be 0");
+    if (!paths_pairs_ok(n, rp.spp)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": more than 2^31 - 1 samples");
+    if (n == 0) return RTW_OK;
+    if (!heads) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": null heads");
+    if ((K > 0) != (vertices != nullptr)) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": vertices must be NULL exactly when max_records is 0");
+    if (device && (((uintptr_t)heads & 15) || ((uintptr_t)vertices & 15)))
+        return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": heads and vertices must be 16-byte aligned");
+    return RTW_OK;
+}
+
+// rtw_paths_params' sampling fields as rtw_radiance's params (the two reserved words are checked by paths_check)
+const rtw_radiance_params* paths_sampling(const rtw_paths_params* PP, rtw_radiance_params& rp) {
+    if (!PP) return nullptr;
+    rp = rtw_radiance_params{PP->spp, PP->max_depth, PP->seed, PP->rng_kind, PP->sample_offset, PP->estimator, PP->key_offset, 0u};
+    return &rp;
+}
+
+// the window [first, first + count) of a views call lies inside its pixels (views_check has bounded their number)
+int paths_window_check(rtw_ctx* c, const char* what, size_t n_views, const rtw_view_params* VP, uint64_t first, uint64_t count) {
+    const uint64_t total = view_pixels(n_views, VP->width, VP->height);
+    if (first > total || count > total - first) return fail(c, RTW_ERR_INVALID_ARG, std::string(what) + ": first + count beyond the call's pixels");
+    return RTW_OK;
+}
+
+// the device variants: d_src holds the rays, or with vf the view records
+int paths_device(rtw_ctx* c, const void* d_src, size_t n, const rtw_radiance_params& rp, int32_t K, void* d_heads, void* d_vertices, void* hip_stream,
+                 rtw_stats* stats, const ViewFrame* vf) {
+    if (stats) memset(stats, 0, sizeof *stats);  // (after every refusal: a refused call leaves *stats alone)
+    if (n == 0) return RTW_OK;
+    QueryCall q;
+    int rc;
+    if ((rc = query_open(c, q, hip_stream, 0, true)) != RTW_OK) return rc;
+    if ((rc = paths_issue(c, q.d, d_src, n, &rp, rp.key_offset, K, (float4*)d_heads, (float4*)d_vertices, q.s, vf)) != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * (uint64_t)rp.spp, false);
+}
+
+// the host variants: chunks of whole rays (rtw_paths_plan.h) through the staging slab - a chunk's rays (not for views, whose records
+// are uploaded once), heads and records
+int paths_host(rtw_ctx* c, const float* rays, size_t n, const rtw_radiance_params& rp, int32_t K, rtw_path_head* heads_out, rtw_path_vertex* vertices_out,
+               rtw_stats* stats, const rtw_view* views, size_t n_views, const ViewFrame* vf) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTW_OK;
+    const PathsPlan pl = paths_plan(n, rp.spp, K, read_tuning().paths_chunk_bytes);
+    const uint64_t spp = (uint64_t)rp.spp;
+    const uint64_t width[3] = {32, spp * sizeof(rtw_path_head), spp * (uint64_t)K * sizeof(rtw_path_vertex)};
+    const bool want[3] = {views == nullptr, true, K > 0};
+    const StagePlan st = stage_plan(pl.rays, 3, width, want);
+    QueryCall q;
+    int rc;
+    if ((rc = query_open(c, q, nullptr, (size_t)st.bytes, true)) != RTW_OK) return rc;
+    if (views && (rc = view_records_upload(c, q, views, n_views)) != RTW_OK) return rc;
+    float* const st_rays = (float*)(q.stage + st.off[0]);
+    float4* const st_heads = (float4*)(q.stage + st.off[1]);
+    float4* const st_vertices = K > 0 ? (float4*)(q.stage + st.off[2]) : nullptr;
+    rc = query_chunks(
+        c, q, n, (size_t)pl.rays,
+        [&](size_t i0, size_t m) -> int {
+            if (!views) HIP_TRY(c, hipMemcpyAsync(st_rays, rays + 8 * i0, m * 32, hipMemcpyHostToDevice, q.s));
+            // the kernel writes a sample's first min(segments, K) records alone and the chunk comes back whole: the caller's own
+            // bytes go up first, so that what is not written comes back as it was
+            if (K > 0) {
+                const PathsChunk ch = paths_chunk(n, rp.spp, K, pl, i0 / pl.rays);
+                HIP_TRY(c, hipMemcpyAsync(st_vertices, (const char*)vertices_out + ch.vertex_off, m * width[2], hipMemcpyHostToDevice, q.s));
+            }
+            return RTW_OK;
+        },
+        // chunk c runs with the key of its first ray, or from its first pixel: the bits do not depend on the chunk size
+        [&](size_t i0, size_t m) -> int {
+            if (!views) return paths_issue(c, q.d, st_rays, m, &rp, radiance_key(rp.key_offset, i0), K, st_heads, st_vertices, q.s, nullptr);
+            const ViewFrame f{vf->width, vf->height, vf->first + (uint64_t)i0};
+            return paths_issue(c, q.d, q.d->view_buf.as<const void>(), m, &rp, 0u, K, st_heads, st_vertices, q.s, &f);
+        },
+        [&](size_t i0, size_t m) -> int {
+            const PathsChunk ch = paths_chunk(n, rp.spp, K, pl, i0 / pl.rays);
+            HIP_TRY(c, hipMemcpyAsync((char*)heads_out + ch.head_off, st_heads, m * width[1], hipMemcpyDeviceToHost, q.s));
+            if (K > 0) HIP_TRY(c, hipMemcpyAsync((char*)vertices_out + ch.vertex_off, st_vertices, m * width[2], hipMemcpyDeviceToHost, q.s));
+            return RTW_OK;
+        });
+    if (rc != RTW_OK) return rc;
+    return query_stats(c, q, stats, (uint64_t)n * spp, false);
+}
+
+int impl_paths_device(rtw_ctx* c, const float* rays, size_t n, const rtw_paths_params* PP, void* d_heads, void* d_vertices, void* hip_stream,
+                      rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    static const char some = 0;  // radiance_check's null test of the output is made by paths_check, on heads and vertices
+    int rc = radiance_check(c, "rtw_paths_device", rays, n, paths_sampling(PP, rp), &some);
+    if (rc || (rc = paths_check(c, "rtw_paths_device", n, rp, PP->max_records, PP->reserved, d_heads, d_vertices, true))) return rc;
+    if (n > 0 && ((uintptr_t)rays & 15)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_paths_device: rays must be 16-byte aligned");
+    return paths_device(c, rays, n, rp, PP->max_records, d_heads, d_vertices, hip_stream, stats, nullptr);
+}
+
+int impl_paths(rtw_ctx* c, const float* rays, size_t n, const rtw_paths_params* PP, rtw_path_head* heads_out, rtw_path_vertex* vertices_out,
+               rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    static const char some = 0;
+    int rc = radiance_check(c, "rtw_paths", rays, n, paths_sampling(PP, rp), &some);
+    if (rc || (rc = paths_check(c, "rtw_paths", n, rp, PP->max_records, PP->reserved, heads_out, vertices_out, false))) return rc;
+    return paths_host(c, rays, n, rp, PP->max_records, heads_out, vertices_out, stats, nullptr, 0, nullptr);
+}
+
+int impl_paths_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, uint64_t first, uint64_t count,
+                            int32_t K, void* d_heads, void* d_vertices, void* hip_stream, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    static const char some = 0;
+    int rc = views_check(c, "rtw_paths_views_device", d_views, n_views, VP, &some, rp);
+    if (rc || (rc = paths_window_check(c, "rtw_paths_views_device", n_views, VP, first, count)) ||
+        (rc = paths_check(c, "rtw_paths_views_device", (size_t)count, rp, K, nullptr, d_heads, d_vertices, true)))
+        return rc;
+    if (count > 0 && ((uintptr_t)d_views & 15)) return fail(c, RTW_ERR_INVALID_ARG, "rtw_paths_views_device: views must be 16-byte aligned");
+    const ViewFrame vf{VP->width, VP->height, first};
+    return paths_device(c, d_views, (size_t)count, rp, K, d_heads, d_vertices, hip_stream, stats, &vf);
+}
+
+int impl_paths_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, uint64_t first, uint64_t count, int32_t K,
+                     rtw_path_head* heads_out, rtw_path_vertex* vertices_out, rtw_stats* stats) {
+    if (!c) return RTW_ERR_INVALID_ARG;
+    rtw_radiance_params rp;
+    static const char some = 0;
+    int rc = views_check(c, "rtw_paths_views", views, n_views, VP, &some, rp);
+    if (rc || (rc = view_records_check(c, "rtw_paths_views", views, n_views)) ||
+        (rc = paths_window_check(c, "rtw_paths_views", n_views, VP, first, count)) ||
+        (rc = paths_check(c, "rtw_paths_views", (size_t)count, rp, K, nullptr, heads_out, vertices_out, false)))
+        return rc;
+    const ViewFrame vf{VP->width, VP->height, first};
+    return paths_host(c, nullptr, (size_t)count, rp, K, heads_out, vertices_out, stats, views, n_views, &vf);
+}
+
 int impl_debug_math(rtw_ctx* c, int op, uint64_t* out) {
     if (!c) return RTW_ERR_INVALID_ARG;
     if (op < 0 || op > 6 || !out) return fail(c, RTW_ERR_INVALID_ARG, "bad arguments");
@@ -2933,6 +3103,21 @@ int rtw_denoise_views_device(rtw_ctx* c, const float* rgba_in, const float* albe
     return guarded(c, [&] {
         return impl_denoise_views_device(c, rgba_in, albedo, normal, rgba_out, n_views, width, height, iterations, sigma, sigma_albedo, sigma_normal, hip_stream);
     });
+}
+
+int rtw_paths(rtw_ctx* c, const float* rays, size_t n, const rtw_paths_params* PP, rtw_path_head* heads_out, rtw_path_vertex* vertices_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_paths(c, rays, n, PP, heads_out, vertices_out, stats); });
+}
+int rtw_paths_device(rtw_ctx* c, const float* rays, size_t n, const rtw_paths_params* PP, void* d_heads, void* d_vertices, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_paths_device(c, rays, n, PP, d_heads, d_vertices, hip_stream, stats); });
+}
+int rtw_paths_views(rtw_ctx* c, const rtw_view* views, size_t n_views, const rtw_view_params* VP, uint64_t first, uint64_t count, int32_t max_records,
+                    rtw_path_head* heads_out, rtw_path_vertex* vertices_out, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_paths_views(c, views, n_views, VP, first, count, max_records, heads_out, vertices_out, stats); });
+}
+int rtw_paths_views_device(rtw_ctx* c, const rtw_view* d_views, size_t n_views, const rtw_view_params* VP, uint64_t first, uint64_t count,
+                           int32_t max_records, void* d_heads, void* d_vertices, void* hip_stream, rtw_stats* stats) {
+    return guarded(c, [&] { return impl_paths_views_device(c, d_views, n_views, VP, first, count, max_records, d_heads, d_vertices, hip_stream, stats); });
 }
 
 }  // extern "C"

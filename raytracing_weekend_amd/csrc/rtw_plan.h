@@ -73,6 +73,9 @@ inline void magic_div(uint32_t d, uint32_t& m, uint32_t& s1, uint32_t& s2) {
 //                        Chunk c runs with the stream key of its first ray: the results do not depend on it.
 //   RTW_RADIANCE_SLAB_BYTES  cap of rtw_radiance's unit-sum slab (calls beyond 128 spp: 16 B per ray and 128 samples; default 1 GiB). A
 //                        larger batch runs as consecutive ray ranges (csrc/rtw_radiance_plan.h). The results do not depend on it.
+//   RTW_PATHS_CHUNK_BYTES  what rtw_paths / rtw_paths_views (the host variants) stage of heads and records at a time (default 256 MiB; at
+//                        least 1): a chunk is the most whole rays that fit, and at least one (csrc/rtw_paths_plan.h). Chunk c runs with
+//                        the stream key of its first ray: the results do not depend on it.
 // Two measured-slower alternatives were removed from the code: k_path_tree for tree scenes and the paired batch
 // schedule; their knobs are no longer read.
 struct Tuning {
@@ -109,6 +112,7 @@ struct Tuning {
     int cast_grid_mult = 0;               // k_cast workgroups per CU; 0 = the occupancy query's answer
     size_t radiance_chunk = (size_t)1 << 20;        // rtw_radiance: rays per staged chunk
     size_t radiance_slab_bytes = (size_t)1 << 30;   // rtw_radiance: cap of the unit-sum slab
+    size_t paths_chunk_bytes = (size_t)256 << 20;   // rtw_paths: heads and records per staged chunk
     bool verbose = false;  // RTW_VERBOSE=1: table sizes at upload (stderr)
 };
 inline Tuning read_tuning() {
@@ -146,6 +150,7 @@ inline Tuning read_tuning() {
     if (geti("RTW_CAST_GRID_MULT", v)) t.cast_grid_mult = (int)std::max<long long>(0, std::min<long long>(4096, v));
     if (geti("RTW_RADIANCE_CHUNK", v)) t.radiance_chunk = (size_t)std::max<long long>(1, std::min<long long>(0x7fffffffll, v));
     if (geti("RTW_RADIANCE_SLAB_BYTES", v)) t.radiance_slab_bytes = (size_t)std::max<long long>(16, v);
+    if (geti("RTW_PATHS_CHUNK_BYTES", v)) t.paths_chunk_bytes = (size_t)std::max<long long>(1, v);
     if (geti("RTW_VERBOSE", v)) t.verbose = v != 0;
     return t;
 }

@@ -4,12 +4,14 @@
 //   Director::renderFrame   Director.cpp:971-1008 -> rtw_render (optixLaunch + D2H copy; no AI denoiser), or an accumulation
 //                                                    session (rtw_accum_*: what the accum_buffer left commented out at :485-488 was for)
 //   Director::renderOrbit   (no counterpart)      -> rtw_views: n frames of a turntable in one call (rtw_views_adaptive with -adaptive)
+//   Director::writePaths    (no counterpart)      -> rtw_paths_views: the samples of one pixel of the frame, replayed, as text
 //   Director::printPPM      Director.cpp:1010-1031
 //   Director::destroy       Director.cpp:66-104   -> rtw_destroy
 #include "Director.h"
 
 #include <cmath>
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -399,6 +401,61 @@ bool Director::writeBinaryPPM(const std::string& path) const {
 
 bool Director::writePFM(const std::string& path) const {
     return rtwhost::writePfm(path, m_hostBuffer.data(), m_Nx, m_Ny, 4, 3);  // linear radiance, little-endian, rows bottom-up
+}
+
+// One text line per sample and per vertex; every float as the 8 hex digits of its bits, then %.9g.
+bool Director::writePaths(int x, int y, const std::string& path) {
+    if (x < 0 || x >= m_Nx || y < 0 || y >= m_Ny) {
+        std::cerr << "ERROR: -paths pixel (" << x << ", " << y << ") outside the " << m_Nx << 'x' << m_Ny << " frame" << std::endl;
+        return false;
+    }
+    rtw_view view{};
+    view.camera = m_camera;
+    view.camera_type = m_blobCameraType;
+    view.seed = m_seed;
+    rtw_view_params vp{};
+    vp.width = m_Nx; vp.height = m_Ny; vp.spp = m_Ns; vp.max_depth = m_maxRayDepth;
+    vp.rng_kind = m_rngKind; vp.sample_offset = 0; vp.estimator = m_estimator;
+    const size_t K = static_cast<size_t>(m_maxRayDepth);
+    std::vector<rtw_path_head> heads(static_cast<size_t>(m_Ns));
+    std::vector<rtw_path_vertex> vertices(heads.size() * K);
+    const uint64_t first = static_cast<uint64_t>(y) * static_cast<uint64_t>(m_Nx) + static_cast<uint64_t>(x);
+    const int rc = rtw_paths_views(m_ctx, &view, 1, &vp, first, 1, m_maxRayDepth, heads.data(), vertices.data(), nullptr);
+    if (rc != RTW_OK) die(m_ctx, "rtw_paths_views", rc);
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    auto put = [&](const char* name, const float* v, int n) {
+        std::fprintf(f, " %s", name);
+        for (int i = 0; i < n; i++) {
+            uint32_t bits;
+            std::memcpy(&bits, v + i, sizeof bits);
+            std::fprintf(f, " %08x %.9g", bits, static_cast<double>(v[i]));
+        }
+    };
+    size_t brightest = 0;
+    float top = -1.f;
+    for (size_t s = 0; s < heads.size(); s++) {
+        const rtw_path_head& h = heads[s];
+        std::fprintf(f, "sample %u key %u segments %d shadow_rays %d", h.sample, h.key, h.segments, h.shadow_rays);
+        put("gather_time", &h.gather_time, 1);
+        put("radiance", h.radiance, 3);
+        std::fputc('\n', f);
+        const size_t m = std::min(static_cast<size_t>(std::max(h.segments, 0)), K);
+        for (size_t j = 0; j < m; j++) {
+            const rtw_path_vertex& v = vertices[s * K + j];
+            std::fprintf(f, "vertex %u %zu prim %d flags %u", h.sample, j, v.prim, v.flags);
+            put("o", v.o, 3); put("t", &v.t, 1); put("d", v.d, 3); put("contribution", v.contribution, 3);
+            put("throughput", v.throughput, 3); put("ray_time", &v.ray_time, 1);
+            std::fputc('\n', f);
+        }
+        const float lum = 0.2126f * h.radiance[0] + 0.7152f * h.radiance[1] + 0.0722f * h.radiance[2];
+        if (lum > top) { top = lum; brightest = s; }
+    }
+    const bool ok = std::fclose(f) == 0;
+    if (_verbose)
+        std::cerr << "INFO: Pixel (" << x << ", " << y << "): the brightest of " << heads.size() << " samples is sample " << heads[brightest].sample
+                  << " (luminance " << top << ", " << heads[brightest].segments << " segments)" << std::endl;
+    return ok;
 }
 
 bool Director::writeGuides(const std::string& prefix) const {

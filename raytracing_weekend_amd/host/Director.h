@@ -70,6 +70,12 @@ public:
     // PREFIX_albedo.pfm, PREFIX_normal.pfm (PF, rgb) and PREFIX_depth.pfm (Pf), rows bottom-up as writePFM; after an adaptive
     // frame also PREFIX_spp.pfm and PREFIX_error.pfm (Pf: each pixel's sample count and error estimate)
     bool writeGuides(const std::string& prefix) const;
+    // the samples [0, Ns) of pixel (x, y) (row 0 the bottom row) of the frame renderFrame renders, replayed through rtw_paths_views
+    // with the blob's own view and the frame's seed, generator, estimator and depth: one text line per sample ("sample S key K
+    // segments N shadow_rays M gather_time .. radiance ..") followed by one per recorded vertex ("vertex S J prim P flags F o .. t ..
+    // d .. contribution .. throughput .. ray_time .."), every float as the 8 hex digits of its bits followed by %.9g. Verbose: the
+    // sample with the largest luminance is named on stderr.
+    bool writePaths(int x, int y, const std::string& path);
     const rtw_stats& stats() const { return m_stats; }
     const std::vector<float>& hostBuffer() const { return m_hostBuffer; }  // linear RGBA, row 0 = bottom row
 

@@ -4,6 +4,7 @@
 //   -d depth (reference: 20, Director.cpp:42)   -seed N   -rng philox|lcg   -gpu id   -gpus N   -o file.ppm|file.png|file.pfm
 //   -progressive N   -checkpoint file   -resume file   (accumulation sessions: previews, checkpoints, resumed renders)
 //   -orbit N   (a turntable of N views through rtw_views, or rtw_views_adaptive with -adaptive, one file per view)
+//   -paths X Y FILE   (the samples of one pixel of the frame replayed through rtw_paths_views, as text)
 // The reference's resolution / sample clamps (main.cpp:21-27) are widened so that 200x200 and
 // 7680x4320 are reachable, and its scene range bug (only scene 4 selectable, main.cpp:69) is not kept.
 #include <chrono>
@@ -85,6 +86,12 @@ int main(int argc, char* argv[]) {
                    [-step N] every view is sampled to the noise target (rtw_views_adaptive) and -aov PREFIX also writes
                    PREFIX_000_spp.pfm and PREFIX_000_error.pfm, ... It does not combine with -denoise without -guided,
                    -progressive, -checkpoint or -resume
+    -paths X Y F   After the render, replay the -ns samples of pixel (X, Y) of the frame (Y counts rows from the bottom, as a PFM
+                   does) and write them to F (rtw_paths_views): one line per sample - its index, stream key, segment and shadow-ray
+                   counts, gather time and radiance - and one per vertex of its path; every float as the 8 hex digits of its bits
+                   and in decimal. The samples' radiances, added in the library's order and divided by -ns, are the frame's
+                   pixel. With -v the brightest sample is named. It does not combine with -orbit, -adaptive, -denoise or the
+                   session flags
     -gpu N         Device ordinal (the first one with -gpus)
     -gpus N        Render on N GPUs of this node: interleaved row shards, one gather onto the first device (default 1)
     -o FILE        Write FILE instead of ASCII P3 on stdout: *.ppm = binary P6, *.png = 8-bit PNG, *.pfm = linear float PFM
@@ -202,6 +209,32 @@ int main(int argc, char* argv[]) {
         if (cl_input.cmdOptionExists("-aov") && aovPrefix.empty()) { std::cerr << "ERROR: -aov needs a prefix" << std::endl; return EXIT_FAILURE; }
     }
 
+    int pathsX = 0, pathsY = 0;
+    std::string pathsFile;
+    if (cl_input.cmdOptionExists("-paths")) {
+        // -paths X Y FILE: three values after the flag
+        int at = 0;
+        for (int i = 1; i < argc; i++)
+            if (std::string(argv[i]) == "-paths") at = i;
+        bool ok = at > 0 && at + 3 < argc && argv[at + 3][0] != '\0';
+        if (ok) {
+            try {
+                pathsX = std::stoi(argv[at + 1], nullptr, 0);
+                pathsY = std::stoi(argv[at + 2], nullptr, 0);
+                pathsFile = argv[at + 3];
+            } catch (const std::exception&) {
+                ok = false;
+            }
+        }
+        if (!ok) { std::cerr << "ERROR: -paths needs a pixel and a file name: -paths X Y FILE" << std::endl; return EXIT_FAILURE; }
+        for (const char* flag : {"-orbit", "-adaptive", "-denoise", "-progressive", "-checkpoint", "-resume"})
+            if (cl_input.cmdOptionExists(flag)) { std::cerr << "ERROR: -paths does not combine with " << flag << std::endl; return EXIT_FAILURE; }
+        if (pathsX < 0 || pathsX >= Nx || pathsY < 0 || pathsY >= Ny) {
+            std::cerr << "ERROR: -paths pixel (" << pathsX << ", " << pathsY << ") outside the " << Nx << 'x' << Ny << " frame" << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     auto start = std::chrono::system_clock::now();
     director.init(Nx, Ny, Ns);
     if (Qverbose) {
@@ -243,6 +276,11 @@ int main(int argc, char* argv[]) {
             director.destroy();
             return EXIT_FAILURE;
         }
+    }
+    if (!pathsFile.empty() && !director.writePaths(pathsX, pathsY, pathsFile)) {
+        std::cerr << "ERROR: cannot write " << pathsFile << std::endl;
+        director.destroy();
+        return EXIT_FAILURE;
     }
     if (!aovPrefix.empty() && !director.writeGuides(aovPrefix)) {
         std::cerr << "ERROR: cannot write the guide files " << aovPrefix << "_*.pfm" << std::endl;

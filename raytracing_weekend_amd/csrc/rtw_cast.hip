@@ -1,14 +1,11 @@
-// rtw_cast.hip - the ray-query kernel (rtw_cast.h), a translation unit of its own under __graft_entry__.build(); a single-file
-// build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_cast.hip - the ray-query kernel (rtw_cast.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_cast<ANY_HIT, ATTR>  the caller's rays through traverse<NoRng, ANY_HIT, true> (the candidate lists of small scenes or the
 //                          4-wide tree, whichever the scene was uploaded with; volumes skipped), then - ATTR only - the closest-hit
 //                          code's hit record, shading normal and texture coordinates of the hit
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

@@ -996,7 +996,7 @@ RTW_DEV void walk_xform(const u32x4* __restrict__ xg, const v3 o, const v3 d, v3
     dd = xf_vector(m, d);
 }
 
-// The walk of a list shape known at compile time (rtw_scene.h WalkShape; the host's path_kernel vouches that the uploaded image has
+// The walk of a list shape known at compile time (rtw_scene.h WalkShape; the host's path_row (rtw_variants.h) vouches that the uploaded image has
 // it): the same image, records, order, tests and key as the walk below, with everything that walk reads from the group headers - the
 // number of groups, whether a group has a transform, the four counts - folded into the instruction stream. No header reads, no
 // uniform values to broadcast, no counted loops and no copy after an odd list: record ri of the image is tested from register set

@@ -1,5 +1,4 @@
-// rtw_guides.hip - the guide kernels (rtw_guides.h), a translation unit of their own under __graft_entry__.build(); a single-file
-// build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_guides.hip - the guide kernels (rtw_guides.h), a translation unit of their own (__graft_entry__.py UNITS).
 //
 //   k_guides         first-hit albedo / normal means, depth and primitive of the first sample: the beauty's own camera rays
 //                    (raygen<>), closest hit through traverse<> with volumes skipped, the closest-hit code's hit record,
@@ -8,9 +7,7 @@
 //   k_atrous_guided_views  k_atrous_guided over the frames of a batch of views, every tap inside its pixel's frame
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

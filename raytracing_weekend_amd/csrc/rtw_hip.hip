@@ -82,52 +82,27 @@
 #include "rtw_paths.h"
 #include "rtw_paths_plan.h"
 #include "rtw_accum.h"
-#ifndef RTW_SPLIT_BUILD
-#include "rtw_guides.hip"  // (under __graft_entry__.build() a translation unit of its own)
-#include "rtw_cast.hip"    // (likewise)
-#include "rtw_radiance.hip"  // (likewise)
-#include "rtw_probe.hip"  // (likewise)
-#include "rtw_probe_sh.hip"  // (likewise)
-#include "rtw_view.hip"  // (likewise)
-#include "rtw_probe_adaptive.hip"  // (likewise)
-#include "rtw_view_adaptive.hip"  // (likewise)
-#include "rtw_paths.hip"  // (likewise)
-#endif
+#include "rtw_variants.h"
 
 using namespace rtwdev;
 using namespace rtwk;
 
-#ifdef RTW_SPLIT_BUILD
-// __graft_entry__.build() compiles the shading kernels in translation units of their own, in parallel (rtw_inst_path.hip,
-// rtw_inst_shade.hip): here they are only declared
+// The template kernels' rows (rtw_variants.h) are instantiated in translation units of their own (rtw_inst_*.hip) and only declared
+// here; k_trace and k_trace_bvh are instantiated by this unit. Each list once more as the rows' addresses, indexed by the row (the
+// null address behind the last row: what a selector that finds no row picks, a launch error)
 namespace rtwk {
-#define RTW_EXT(K_) \
-    extern template __global__ void K_<RTW_RNG_PHILOX, 0>(const KArgs); extern template __global__ void K_<RTW_RNG_PHILOX, 1>(const KArgs); extern template __global__ void K_<RTW_RNG_PHILOX, 2>(const KArgs); \
-    extern template __global__ void K_<RTW_RNG_TEA_LCG, 0>(const KArgs); extern template __global__ void K_<RTW_RNG_TEA_LCG, 1>(const KArgs); extern template __global__ void K_<RTW_RNG_TEA_LCG, 2>(const KArgs);
-RTW_EXT(k_path)
-extern template __global__ void k_path<RTW_RNG_PHILOX, 1, 1>(const KArgs);
-extern template __global__ void k_path<RTW_RNG_TEA_LCG, 1, 1>(const KArgs);
-extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>(const KArgs);
-extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1>(const KArgs);
-extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 0, 1, WALK_SHAPE_CORNELL>(const KArgs);
-extern template __global__ void k_path<RTW_RNG_PHILOX, 0, 0, 1, 1, WALK_SHAPE_CORNELL>(const KArgs);
-RTW_EXT(k_first)
-RTW_EXT(k_shade)
-RTW_EXT(k_bounce)
-#undef RTW_EXT
-extern template __global__ void k_classify<true>(const KArgs, uint32_t*, uint32_t*, uint32_t);
-extern template __global__ void k_classify<false>(const KArgs, uint32_t*, uint32_t*, uint32_t);
-// the list instantiations of rtw_render_adaptive (rtw_inst_list.hip)
-#define RTW_EXT_LIST(R_) \
-    extern template __global__ void k_path<R_, 0, 0, 1>(const KArgs); extern template __global__ void k_path<R_, 1, 0, 1>(const KArgs); \
-    extern template __global__ void k_path<R_, 2, 0, 1>(const KArgs); extern template __global__ void k_path<R_, 1, 1, 1>(const KArgs); \
-    extern template __global__ void k_first<R_, 0, 1>(const KArgs); extern template __global__ void k_first<R_, 1, 1>(const KArgs); \
-    extern template __global__ void k_first<R_, 2, 1>(const KArgs);
-RTW_EXT_LIST(RTW_RNG_PHILOX)
-RTW_EXT_LIST(RTW_RNG_TEA_LCG)
-#undef RTW_EXT_LIST
+#define RTW_DECL(K_, name, ...) extern template __global__ void K_<__VA_ARGS__> RTW_SIG_##K_;
+RTW_K_PATH_ROWS(RTW_DECL) RTW_K_FIRST_ROWS(RTW_DECL) RTW_K_SHADE_ROWS(RTW_DECL) RTW_K_BOUNCE_ROWS(RTW_DECL) RTW_K_CLASSIFY_ROWS(RTW_DECL)
+#undef RTW_DECL
+typedef void (*Kernel)(const KArgs);
+typedef void (*ClassifyKernel)(const KArgs, uint32_t*, uint32_t*, uint32_t);
+#define RTW_ADDR(K_, name, ...) K_<__VA_ARGS__>,
+const Kernel kPathKernels[] = {RTW_K_PATH_ROWS(RTW_ADDR) nullptr}, kFirstKernels[] = {RTW_K_FIRST_ROWS(RTW_ADDR) nullptr},
+             kShadeKernels[] = {RTW_K_SHADE_ROWS(RTW_ADDR) nullptr}, kBounceKernels[] = {RTW_K_BOUNCE_ROWS(RTW_ADDR) nullptr},
+             kTraceKernels[] = {RTW_K_TRACE_ROWS(RTW_ADDR) nullptr}, kTraceBvhKernels[] = {RTW_K_TRACE_BVH_ROWS(RTW_ADDR) nullptr};
+const ClassifyKernel kClassifyKernels[] = {RTW_K_CLASSIFY_ROWS(RTW_ADDR) nullptr};
+#undef RTW_ADDR
 }  // namespace rtwk
-#endif
 
 // =============================================================================================
 // host side of the library
@@ -313,79 +288,18 @@ int ensure_pool(rtw_ctx* c, int n_lanes, size_t paths, size_t npix, size_t cnt_w
     return RTW_OK;
 }
 
-// k_trace_bvh's instantiation for a workgroup size and a tree (mode: see the kernel)
-typedef void (*Kernel)(const KArgs);
-int trace_bvh_mode(const DScene& sc) { return sc.stack_wide ? 0 : sc.n_lds_nodes >= sc.n_nodes ? 2 : 1; }
-Kernel trace_bvh_kernel(int block, int mode) {
-#define RTW_TB(B_) (mode == 0 ? k_trace_bvh<B_, 0> : mode == 1 ? k_trace_bvh<B_, 1> : k_trace_bvh<B_, 2>)
-    return block == 1024 ? RTW_TB(1024) : block == 512 ? RTW_TB(512) : RTW_TB(256);
-#undef RTW_TB
-}
-
-// k_path's instantiation: RNG kind x feature level (0 hot, 1 cold features, 2 cold features + the mixture estimator); media scenes
-// take the cold instantiation allocated for 5 waves (rtw_kernels.h k_path MEDIA5). list: the LIST = 1 twin (rtw_render_adaptive)
-// The hot instantiation with Philox has a one-light twin (rtw_kernels.h k_path NEE1), for scenes whose light sample is always the same
-// case of shade_a: exactly one listed light, the reference estimator (feature level 0 has no other), a rectangle generator.
-bool path_nee1(int rng_kind, const DScene& sc) {
-    int gen = sc.pdf.gen;
-    if (gen == RTW_PDF_MIXTURE || gen == RTW_PDF_MIXTURE_BIAS) gen = sc.pdf.p1_gen;
-    return rng_kind == RTW_RNG_PHILOX && sc.has_tex == 0 && sc.estimator == RTW_EST_REFERENCE && sc.n_lights == 1 &&
-           (gen == RTW_PDF_RECT_X || gen == RTW_PDF_RECT_Y || gen == RTW_PDF_RECT_Z);
-}
-// The one-light twin in turn has a fixed-shape twin (rtw_kernels.h k_path SHAPE) for the scenes whose candidate lists have a compiled
-// shape: walk_shape is what prepare_scene found for the uploaded scene (SceneInfo::walk_shape; 0: none).
-Kernel path_kernel(int rng_kind, const DScene& sc, int walk_shape, bool list = false) {
-    const int feat = sc.has_tex, n_vol = sc.n_vol;
-    if (path_nee1(rng_kind, sc)) {
-        if (walk_shape == WALK_SHAPE_CORNELL) return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1, WALK_SHAPE_CORNELL> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1, WALK_SHAPE_CORNELL>;
-        return list ? k_path<RTW_RNG_PHILOX, 0, 0, 1, 1> : k_path<RTW_RNG_PHILOX, 0, 0, 0, 1>;
-    }
-#define RTW_PK(R_, L_) (feat == 1 && n_vol > 0 ? k_path<R_, 1, 1, L_> : feat == 2 ? k_path<R_, 2, 0, L_> : feat == 1 ? k_path<R_, 1, 0, L_> : k_path<R_, 0, 0, L_>)
-    if (list) return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 1) : RTW_PK(RTW_RNG_PHILOX, 1);
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_PK(RTW_RNG_TEA_LCG, 0) : RTW_PK(RTW_RNG_PHILOX, 0);
-#undef RTW_PK
-}
-// k_first's list twin (rtw_render_adaptive's wavefront passes)
-Kernel first_list_kernel(int rng_kind, int feat) {
-#define RTW_FK(R_) (feat == 2 ? k_first<R_, 2, 1> : feat == 1 ? k_first<R_, 1, 1> : k_first<R_, 0, 1>)
-    return rng_kind == RTW_RNG_TEA_LCG ? RTW_FK(RTW_RNG_TEA_LCG) : RTW_FK(RTW_RNG_PHILOX);
-#undef RTW_FK
-}
-
 // which: RTW_K_FIRST, RTW_K_SHADE, RTW_K_TRACE, RTW_K_BOUNCE or RTW_K_PATH. list: k_first / k_path over a.list (LIST = 1).
-// walk_shape: k_path only, the uploaded scene's SceneInfo::walk_shape
+// walk_shape: k_path only, the uploaded scene's SceneInfo::walk_shape. The row is rtw_variants.h's choice.
 void launch(int which, int rng_kind, const KArgs& a, int grid, size_t lds, hipStream_t s, int block = kBlock, bool list = false, int walk_shape = 0) {
-    const bool lcg = rng_kind == RTW_RNG_TEA_LCG;
-    // kernels that shade exist in six instantiations: RNG kind x feature level
-    const int feat = a.sc.has_tex;  // 0 hot, 1 cold features, 2 cold features + the mixture estimator (rtw_kernels.h shade_a)
-    if (list) {
-        if (which == RTW_K_FIRST) hipLaunchKernelGGL(first_list_kernel(rng_kind, feat), dim3(grid), dim3(kBlock), lds, s, a);
-        else hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, walk_shape, true), dim3(grid), dim3(kBlock), lds, s, a);
-        return;
-    }
-#define RTW_LAUNCH_SHADING_R(K_, LDS_, R_)                                                                        \
-    do {                                                                                                          \
-        if (feat == 2) hipLaunchKernelGGL((K_<R_, 2>), dim3(grid), dim3(kBlock), LDS_, s, a);                     \
-        else if (feat == 1) hipLaunchKernelGGL((K_<R_, 1>), dim3(grid), dim3(kBlock), LDS_, s, a);                \
-        else hipLaunchKernelGGL((K_<R_, 0>), dim3(grid), dim3(kBlock), LDS_, s, a);                               \
-    } while (0)
-#define RTW_LAUNCH_SHADING(K_, LDS_)                                                                              \
-    do {                                                                                                          \
-        if (lcg) RTW_LAUNCH_SHADING_R(K_, LDS_, RTW_RNG_TEA_LCG); else RTW_LAUNCH_SHADING_R(K_, LDS_, RTW_RNG_PHILOX); \
-    } while (0)
+    Kernel k;
     switch (which) {
-    case RTW_K_FIRST: RTW_LAUNCH_SHADING(k_first, lds); break;
-    case RTW_K_SHADE: RTW_LAUNCH_SHADING(k_shade, 0); break;
-    case RTW_K_TRACE:
-        if (a.sc.use_bvh) hipLaunchKernelGGL(trace_bvh_kernel(block, trace_bvh_mode(a.sc)), dim3(grid), dim3(block), lds, s, a);
-        else if (a.sc.n_generic == 0) hipLaunchKernelGGL((k_trace<true>), dim3(grid), dim3(kBlock), lds, s, a);
-        else hipLaunchKernelGGL((k_trace<false>), dim3(grid), dim3(kBlock), lds, s, a);
-        break;
-    case RTW_K_PATH: hipLaunchKernelGGL(path_kernel(rng_kind, a.sc, walk_shape), dim3(grid), dim3(kBlock), lds, s, a); break;
-    default: RTW_LAUNCH_SHADING(k_bounce, lds); break;
-#undef RTW_LAUNCH_SHADING
-#undef RTW_LAUNCH_SHADING_R
+    case RTW_K_FIRST: k = kFirstKernels[first_row(rng_kind, a.sc.has_tex, list)]; break;
+    case RTW_K_SHADE: k = kShadeKernels[shade_row(rng_kind, a.sc.has_tex)]; lds = 0; break;
+    case RTW_K_TRACE: k = a.sc.use_bvh ? kTraceBvhKernels[trace_bvh_row(block, trace_bvh_mode(a.sc))] : kTraceKernels[trace_row(a.sc)]; break;
+    case RTW_K_PATH: k = kPathKernels[path_row(rng_kind, a.sc, walk_shape, list)]; break;
+    default: k = kBounceKernels[bounce_row(rng_kind, a.sc.has_tex)]; break;
     }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(which == RTW_K_TRACE && a.sc.use_bvh ? block : kBlock), lds, s, a);
 }
 
 // ---- the exception barrier of the C ABI (include/rtw.h: "no exceptions cross this ABI") -------------------------------
@@ -701,8 +615,7 @@ int classify_jobs(rtw_ctx* c, const KArgs& base, size_t n_groups, hipStream_t s)
     uint32_t* const counts = c->d_queue.as<uint32_t>() + 1;
     HIP_TRY(c, hipMemsetAsync(c->d_queue.as<void>(), 0, kQueueBytes, s));
     const dim3 cg((unsigned)std::min<size_t>((n_groups + 3) / 4, (size_t)c->n_cu * 8));
-    if (c->sc.n_walk_words > 0) hipLaunchKernelGGL(k_classify<true>, cg, dim3(kBlock), 0, s, base, order, counts, (uint32_t)n_groups);
-    else hipLaunchKernelGGL(k_classify<false>, cg, dim3(kBlock), 0, s, base, order, counts, (uint32_t)n_groups);
+    hipLaunchKernelGGL(kClassifyKernels[classify_row(c->sc)], cg, dim3(kBlock), 0, s, base, order, counts, (uint32_t)n_groups);
     return RTW_OK;
 }
 
@@ -828,7 +741,7 @@ int fit_wavefront_pool(rtw_ctx* c, const Tuning& tune, int samples_per_pass, siz
         if (w.trace_lds > 48 * 1024) {  // beyond the default dynamic-LDS limit of a launch
             DScene ts = c->sc;
             ts.n_lds_nodes = w.trace_nodes;
-            const void* f = (const void*)trace_bvh_kernel(w.trace_block, trace_bvh_mode(ts));
+            const void* f = (const void*)kTraceBvhKernels[trace_bvh_row(w.trace_block, trace_bvh_mode(ts))];
             HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.trace_lds));
         }
         const int rc = ensure_pool(c, w.n_lanes, paths_fn(w), npix, w.cnt_words, c->sc.n_lights > 0);
@@ -903,13 +816,6 @@ int fill_stats(rtw_ctx* c, const CallLog& log, const unsigned long long hs[8], u
     return RTW_OK;
 }
 
-// the corrected estimators live in the cold-feature instantiations
-void apply_estimator(DScene& sc, int estimator) {
-    if (estimator == RTW_EST_REFERENCE) return;
-    sc.estimator = estimator; sc.has_tex = estimator == RTW_EST_MIXTURE ? 2 : 1;
-    sc.ray_tmin = 1.0e-3f; sc.probe_eps = 1.0e-3f;
-}
-
 // ---- k_path: paths in registers, lanes regenerate; only the unit sums (16 B per pixel and 64 samples) reach HBM
 int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base_in, float4* out, hipStream_t s, CallLog& log) {
     const size_t npix = base_in.npix;
@@ -918,7 +824,7 @@ int render_path(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)P->spp;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)kPathKernels[path_row(P->rng_kind, base.sc, c->info.walk_shape, false)], 0, tune.path_grid_mult);
     const PathPlan plan = plan_path(tune, npix, P->spp, c->n_cu, wg_per_cu, cull.live_groups);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     HIP_TRY(c, c->d_order.grow(plan.n_groups, 3 * plan.n_groups * sizeof(uint32_t)));  // k_classify's three job lists
@@ -1024,13 +930,6 @@ KArgs render_args(const rtw_ctx* c, const rtw_params* P, size_t npix) {
     apply_estimator(base.sc, P->estimator);
     return base;
 }
-// k_path: scenes walked with the brute lists; it packs a unit's pixel as x | y << 16, so frames wider or taller than 65535
-// take the wavefront kernels
-bool path_pipeline(const rtw_ctx* c, const rtw_params* P, const Tuning& tune) {
-    const bool path_small = !c->sc.use_bvh && c->sc.n_prims <= kPathMaxPrims && (c->sc.n_walk_words > 0 || c->sc.has_tex);
-    const bool fits16 = P->width <= 65535 && P->height <= 65535;
-    return P->max_depth > 0 && tune.path != 0 && fits16 && path_small;
-}
 
 // One device: the whole render of the shard P describes, result in d_rgba (device memory of c->device).
 int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, rtw_stats* stats) {
@@ -1046,7 +945,7 @@ int render_single(rtw_ctx* c, const rtw_params* P, void* d_rgba, hipStream_t s, 
     HIP_TRY(c, log.event(log.begin));
     HIP_TRY(c, log.event(log.end));
     const KArgs base = render_args(c, P, npix);
-    const bool use_path = path_pipeline(c, P, tune);
+    const bool use_path = path_pipeline(c->sc, P->width, P->height, P->max_depth, tune);
     int rc = use_path ? render_path(c, P, tune, base, (float4*)d_rgba, s, log) : render_wavefront(c, P, tune, base, (float4*)d_rgba, s, log);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
@@ -1233,7 +1132,7 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
     // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
     Tuning t = tune;
     if (t.path_unit_blocks % (int)kSumUnitBlocks == 0) t.path_unit_blocks = 4;
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape, true), 0, t.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)kPathKernels[path_row(P->rng_kind, base.sc, c->info.walk_shape, true)], 0, t.path_grid_mult);
     const PathPlan plan = plan_path(t, n_list, n_to - n_from, c->n_cu, wg_per_cu);
     if (plan.too_many_jobs) return fail(c, RTW_ERR_UNSUPPORTED, "too many k_path jobs");
     HIP_TRY(c, c->blocksum.grow(plan.need_slots * n_list, plan.need_slots * n_list * sizeof(float4)));
@@ -1287,7 +1186,7 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
     HIP_TRY(c, log.event(log.begin));
     HIP_TRY(c, log.event(log.end));
     const KArgs base = render_args(c, P, npix);
-    const bool use_path = path_pipeline(c, P, tune);
+    const bool use_path = path_pipeline(c->sc, P->width, P->height, P->max_depth, tune);
     AdaptState st{};
     int rc = ensure_adapt(c, npix, st);
     if (rc) return rc;
@@ -1406,7 +1305,7 @@ int accum_add_path(rtw_ctx* c, const Tuning& tune, const KArgs& base_in, int n_f
     KArgs base = base_in;
     const PathCull cull = path_cull(c, P, tune, base, npix);
     log.culled_segments = (uint64_t)cull.culled_pixels * (uint64_t)(n_to - n_from);
-    const int wg_per_cu = path_wg_per_cu((const void*)path_kernel(P->rng_kind, base.sc, c->info.walk_shape), 0, tune.path_grid_mult);
+    const int wg_per_cu = path_wg_per_cu((const void*)kPathKernels[path_row(P->rng_kind, base.sc, c->info.walk_shape, false)], 0, tune.path_grid_mult);
     const size_t n_groups = (npix + 63) / 64;
     HIP_TRY(c, c->d_order.grow(n_groups, 3 * n_groups * sizeof(uint32_t)));
     HIP_TRY(c, hipEventRecord(log.begin, s));
@@ -1476,7 +1375,7 @@ int accum_add_single(rtw_ctx* c, int32_t spp, rtw_stats* stats) {
     HIP_TRY(c, log.event(log.begin));
     HIP_TRY(c, log.event(log.end));
     const KArgs base = render_args(c, &A.P, npix);
-    const bool use_path = path_pipeline(c, &A.P, tune);
+    const bool use_path = path_pipeline(c->sc, A.P.width, A.P.height, A.P.max_depth, tune);
     const int n_from = A.done, n_to = A.done + spp;
     int rc = use_path ? accum_add_path(c, tune, base, n_from, n_to, s, log) : accum_add_wavefront(c, tune, base, n_from, n_to, s, log);
     if (rc) return rc;

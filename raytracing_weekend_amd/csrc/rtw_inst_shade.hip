@@ -1,27 +1,17 @@
-// rtw_inst_shade.hip - the instantiations of the wavefront kernels that shade (k_first, k_shade, k_bounce), compiled as a
-// translation unit of their own (see rtw_inst_path.hip).
+// rtw_inst_shade.hip - the rows of the wavefront kernels that shade (k_first's frame rows, k_shade, k_bounce: rtw_variants.h),
+// instantiated in a translation unit of their own. It is the longest of the units, so __graft_entry__.py UNITS compiles it twice,
+// side by side: -DRTW_INST_KIND=0 / 1 leaves the rows of one generator (rtw_variants.h RTW_IF_<generator>).
 #include <hip/hip_runtime.h>
 
 #define RTW_TEMPLATES_ONLY
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"
+#include "rtw_variants.h"
 
 namespace rtwk {
-// -DRTW_INST_KIND=0 / 1: only the Philox / only the TEA+LCG instantiations (__graft_entry__.build() compiles this file twice, side
-// by side: it is the longest of the translation units); without the macro, both
-#if !defined(RTW_INST_KIND) || RTW_INST_KIND == 0
-#define RTW_INST(K_) template __global__ void K_<RTW_RNG_PHILOX, 0>(const KArgs); template __global__ void K_<RTW_RNG_PHILOX, 1>(const KArgs); template __global__ void K_<RTW_RNG_PHILOX, 2>(const KArgs);
-RTW_INST(k_first)
-RTW_INST(k_shade)
-RTW_INST(k_bounce)
-#undef RTW_INST
-#endif
-#if !defined(RTW_INST_KIND) || RTW_INST_KIND == 1
-#define RTW_INST(K_) template __global__ void K_<RTW_RNG_TEA_LCG, 0>(const KArgs); template __global__ void K_<RTW_RNG_TEA_LCG, 1>(const KArgs); template __global__ void K_<RTW_RNG_TEA_LCG, 2>(const KArgs);
-RTW_INST(k_first)
-RTW_INST(k_shade)
-RTW_INST(k_bounce)
-#undef RTW_INST
-#endif
+#define RTW_INST(K_, name, KIND, ...) RTW_IF_##KIND(template __global__ void K_<KIND, __VA_ARGS__> RTW_SIG_##K_;)
+RTW_K_FIRST_FRAME_ROWS(RTW_INST)
+RTW_K_SHADE_ROWS(RTW_INST)
+RTW_K_BOUNCE_ROWS(RTW_INST)
 }  // namespace rtwk

@@ -1404,8 +1404,8 @@ RTW_DEV constexpr int rtw_phase_id(const char* n) { return n[0] == 'r' && n[2] =
 // position i goes to slot [b][i] (stride n_list). The host runs these passes with block sums (unit_sums = 0), so the LDS unit sums
 // are free and s_usum[0] holds each lane's list position. Everything after the refill is the same code.
 // NEE1 = 1 (hot instantiation, Philox): the scene lists exactly one light, a rectangle, under the reference estimator - facts of
-// rtw_upload_scene that the host's path_kernel() checks (rtw_hip.hip path_nee1) - and shade_a compiles that light sample alone.
-// SHAPE != 0 (with NEE1 = 1): the scene's candidate lists have that compiled shape (rtw_scene.h walk_shape, checked by path_kernel() as
+// rtw_upload_scene that the host's path_row() checks (rtw_variants.h path_nee1) - and shade_a compiles that light sample alone.
+// SHAPE != 0 (with NEE1 = 1): the scene's candidate lists have that compiled shape (rtw_scene.h walk_shape, checked by path_row() as
 // well), and both walks are the shape's straight-line code.
 template <int KIND, int TEX, int MEDIA5 = 0, int LIST = 0, int NEE1 = 0, int SHAPE = 0>
 __global__ void __launch_bounds__(kBlock, TEX ? (MEDIA5 ? 5 : RTW_PATH_COLD_WAVES) : RTW_PATH_WAVES) k_path(const KArgs A) {

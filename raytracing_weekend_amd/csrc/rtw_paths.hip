@@ -1,5 +1,4 @@
-// rtw_paths.hip - the path-record kernel (rtw_paths.h), a translation unit of its own under __graft_entry__.build(); a single-file
-// build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_paths.hip - the path-record kernel (rtw_paths.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_paths<KIND, TEX, SRC>  samples replayed one by one: the path of sample s of ray (pixel) i is k_radiance's (k_view's) - the
 //                            regeneration step is radiance_raygen<> or view_raygen<> of rtw_radiance_body.h, a segment the
@@ -10,9 +9,7 @@
 //                            whose body is one segment (a lane whose path ended starts its next pair at once).
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

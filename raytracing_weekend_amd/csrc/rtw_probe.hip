@@ -1,5 +1,4 @@
-// rtw_probe.hip - the probe kernels (rtw_probe.h), a translation unit of its own under __graft_entry__.build(); a single-file build
-// of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_probe.hip - the probe kernels (rtw_probe.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_probe<KIND, TEX>         irradiance at surface points: k_radiance's loop (rtw_radiance_body.h: the same job queue, units, path
 //                              segments - traverse<>, shade_a, shade_b - and sums) whose regeneration step draws the first direction
@@ -10,9 +9,7 @@
 //   k_probe_occlusion_resolve  the units' counts of calls beyond 128 spp, added as integers
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

@@ -1,5 +1,4 @@
-// rtw_probe_adaptive.hip - the kernels of rtw_probe_adaptive (rtw_probe_adaptive.h), a translation unit of its own under
-// __graft_entry__.build(); a single-file build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_probe_adaptive.hip - the kernels of rtw_probe_adaptive (rtw_probe_adaptive.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_probe_list<KIND, TEX>            k_probe's samples for the probes of an active list, blocks [n_from / 16, n_to / 16) of each: the
 //                                      unit of work is (list position, run of R whole blocks), every block's sum goes to the slab
@@ -10,9 +9,7 @@
 //   k_probe_adapt_finish[_occlusion]   the results, the sample counts and the errors
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

@@ -1,5 +1,4 @@
-// rtw_probe_sh.hip - the spherical-harmonic probe kernels (rtw_probe_sh.h), a translation unit of its own under
-// __graft_entry__.build(); a single-file build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_probe_sh.hip - the spherical-harmonic probe kernels (rtw_probe_sh.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_probe_sh<KIND, TEX>  light probes at free points: k_radiance's loop (rtw_radiance_body.h: the same job queue, units, path
 //                          segments - traverse<>, shade_a, shade_b - and summation order) whose regeneration step draws the first
@@ -9,9 +8,7 @@
 //   k_probe_sh_resolve     the unit sums of calls beyond 128 spp, added in order; the mean times 4 pi
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

@@ -1,5 +1,4 @@
-// rtw_radiance.hip - the radiance-query kernels (rtw_radiance.h), a translation unit of its own under __graft_entry__.build(); a
-// single-file build of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_radiance.hip - the radiance-query kernels (rtw_radiance.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_radiance<KIND, TEX>  whole paths along the caller's rays: a camera path of rtw_render whose camera ray is replaced. The draws
 //                          are raygen<>'s for a perspective camera path of pixel key0 + ray, the segments k_bounce's inner loop
@@ -9,9 +8,7 @@
 //   k_radiance_resolve     the unit sums of renders beyond 128 spp, added in order
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

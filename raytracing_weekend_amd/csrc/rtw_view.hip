@@ -1,5 +1,4 @@
-// rtw_view.hip - the view kernel (rtw_view.h), a translation unit of its own under __graft_entry__.build(); a single-file build
-// of rtw_hip.hip (scripts/build_variant.sh) includes this file instead.
+// rtw_view.hip - the view kernel (rtw_view.h), a translation unit of its own (__graft_entry__.py UNITS).
 //
 //   k_view<KIND, TEX>  frames from the caller's cameras: k_radiance's loop (rtw_radiance_body.h: the same job queue, units, path
 //                      segments - traverse<>, shade_a, shade_b - and summation order) whose "ray" is a pixel of the flattened
@@ -10,9 +9,7 @@
 //                      path is view_raygen<>'s, from the pixel's view record
 #include <hip/hip_runtime.h>
 
-#ifndef RTW_TEMPLATES_ONLY
 #define RTW_TEMPLATES_ONLY  // (the plain kernels of rtw_kernels.h belong to rtw_hip.hip)
-#endif
 #include "../../include/rtw.h"
 #include "rtw_device.h"
 #include "rtw_kernels.h"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Are the kernels of two checkouts the same machine code? Every translation unit of __graft_entry__.build() is compiled with
-`hipcc -S` and the build's flags (no GPU needed) in this tree and in another checkout, and every kernel is compared: instruction
+"""Are the kernels of two checkouts the same machine code? Every unit of __graft_entry__.UNITS is compiled with `hipcc -S` and
+the build's flags (no GPU needed) in this tree and in another checkout - each by its own checkout's recipe - and every kernel is compared: instruction
 count, next_free_vgpr, next_free_sgpr, scratch bytes, static LDS, and a hash of its instruction text (labels, directives and
 comments left out).
 
@@ -10,6 +10,7 @@ figures. Exit status 1 if a kernel of the other checkout differs or is missing h
 output for the parent of rtw_probe_adaptive."""
 import concurrent.futures
 import hashlib
+import importlib.util
 import os
 import re
 import subprocess
@@ -21,19 +22,25 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 
-def units_of(root):
-    """(source, object name, extra flags) of every unit in that checkout's build(): read from its own __graft_entry__.py."""
+def recipe_of(root):
+    """That checkout's own build recipe: its __graft_entry__ imported by path. -> (UNITS, flags of a unit)"""
+    spec = importlib.util.spec_from_file_location("entry_" + hashlib.sha256(root.encode()).hexdigest()[:8], os.path.join(root, "__graft_entry__.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    if hasattr(mod, "UNITS"):
+        return mod.UNITS, mod.unit_flags
+    # a checkout from before UNITS: the list literal and the common flags cut out of build()'s text (they name UNIT_FLAGS and HIP_FLAGS)
     text = open(os.path.join(root, "__graft_entry__.py")).read()
     body = text[text.index("units = ["):text.index("cflags = ")]
-    env = {"UNIT_FLAGS": entry.UNIT_FLAGS}
-    return eval(body.split("=", 1)[1].strip(), env)  # (a list literal of tuples that names UNIT_FLAGS)
+    units = eval(body.split("=", 1)[1].strip(), {"UNIT_FLAGS": mod.UNIT_FLAGS})
+    cflags = eval(text[text.index("cflags = "):].split("\n")[0].split("=", 1)[1], {"HIP_FLAGS": mod.HIP_FLAGS})
+    return units, lambda unit, extra: cflags + extra + mod.UNIT_FLAGS.get(unit, [])
 
 
-def kernels(root, unit, obj, extra):
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")] + ["-DRTW_SPLIT_BUILD"] + extra + entry.UNIT_FLAGS.get(unit, [])
+def kernels(root, flags_of, unit, obj, extra):
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "unit.s")
-        subprocess.check_call([entry.HIPCC] + flags + ["--cuda-device-only", "-S", "-o", out,
+        subprocess.check_call([entry.HIPCC] + flags_of(unit, extra) + ["--cuda-device-only", "-S", "-o", out,
                                os.path.join(root, "raytracing_weekend_amd", "csrc", unit)], stderr=subprocess.DEVNULL)
         text = open(out).read()
     rows = {}
@@ -55,7 +62,8 @@ def kernels(root, unit, obj, extra):
 def all_kernels(root, jobs):
     out = {}
     with concurrent.futures.ThreadPoolExecutor(jobs) as ex:
-        for rows in ex.map(lambda u: kernels(root, *u), units_of(root)):
+        units, flags_of = recipe_of(root)
+        for rows in ex.map(lambda u: kernels(root, flags_of, *u), units):
             out.update(rows)
     return out
 
@@ -73,11 +81,6 @@ if __name__ == "__main__":
     print(f"# {len(theirs)} kernels in the other checkout, {len(ours)} here; per kernel: {', '.join(cols)}")
     for key in sorted(theirs):
         a, b = theirs[key], ours.get(key)
-        # k_path gained template arguments (NEE1, then SHAPE): the other checkout's <a, b, c, d> or <a, b, c, d, e> is <a, b, c, d, e, 0> here
-        if b is None:
-            b = ours.get((key[0], re.sub(r"(6k_pathILi\d+ELi\d+ELi\d+ELi\d+ELi\d+E)E", r"\1Li0EE", key[1])))
-        if b is None:
-            b = ours.get((key[0], re.sub(r"(6k_pathILi\d+ELi\d+ELi\d+ELi\d+E)E", r"\1Li0ELi0EE", key[1])))
         label = f"{key[0]:24s} {demangle(key[1]):72s}"
         if b is None:
             bad += 1
@@ -88,7 +91,7 @@ if __name__ == "__main__":
             bad += 1
             print(f"{label} DIFFERS  " + "; ".join(f"{c}: {x} -> {y}" for c, x, y in zip(cols, a, b) if x != y))
     print("# kernels only this tree has")
-    for key in sorted(k for k in set(ours) - set(theirs) if not re.search(r"6k_pathILi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi0EE", k[1])):
+    for key in sorted(set(ours) - set(theirs)):
         b = ours[key]
         print(f"{key[0]:24s} {demangle(key[1]):72s} new   {b[0]:6d} {b[1]:4d} {b[2]:4d} {b[3]:5d} {b[4]:6d} {b[5]}")
     print(f"# {len(theirs) - bad} of {len(theirs)} kernels of the other checkout are the same here, {bad} differ or are missing")

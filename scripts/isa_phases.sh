@@ -2,7 +2,7 @@
 # usage: [NEE1=0|1] [SHAPE=0|1] scripts/isa_phases.sh [extra flags] : static instruction counts of the shipped k_path<PHILOX,0,0,0,NEE1,SHAPE>
 # per phase (between the phase-fence comments; NEE1 = 1 with SHAPE = 1, the defaults, is the one-light instantiation with the Cornell box's
 # fixed-shape walks that the headline scene runs; SHAPE = 0 with NEE1 = 1 the one-light instantiation other one-light scenes run). Compiles
-# rtw_inst_path.hip the way __graft_entry__.build() does (HIP_FLAGS + that unit's UNIT_FLAGS) and prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
+# rtw_inst_path.hip with __graft_entry__.unit_flags (HIP_FLAGS + that unit's UNIT_FLAGS) and prints, per phase, the instruction classes and the reciprocal / root sequences: div = the compiler's correctly rounded
 # divisions (v_div_fixup_f32, fallbacks of the short forms included), sqrt = its roots (v_sqrt_f32), rcp_short / rsq_short = the
 # short forms of rtw_math.h (a v_rcp_f32 without a v_div_fixup_f32; v_rsq_f32). Exits 1 when the kernel is not found.
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -12,7 +12,7 @@ T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 FLAGS=$(cd "$R" && python3 -c "
 import __graft_entry__ as g
-print(' '.join([f for f in g.HIP_FLAGS if f != '-shared'] + ['-DRTW_SPLIT_BUILD'] + g.UNIT_FLAGS['rtw_inst_path.hip']))") || exit 1
+print(' '.join(g.unit_flags('rtw_inst_path.hip')))") || exit 1
 ${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS "$@" -S --cuda-device-only -o "$T/rtw.s" "$R/raytracing_weekend_amd/csrc/rtw_inst_path.hip" || exit 1
 awk '/^'$K':/{f=1} f{print} /s_endpgm/{if(f){exit}}' "$T/rtw.s" > "$T/kpath.s"
 if [ ! -s "$T/kpath.s" ]; then echo "isa_phases: no $K in the assembly" >&2; exit 1; fi

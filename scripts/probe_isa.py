@@ -19,7 +19,7 @@ import __graft_entry__ as entry  # noqa: E402
 
 
 def counts(unit):
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")] + ["-DRTW_SPLIT_BUILD"] + entry.UNIT_FLAGS.get(os.path.basename(unit), [])
+    flags = entry.unit_flags(os.path.basename(unit), next((extra for u, _, extra in entry.UNITS if u == os.path.basename(unit)), []))
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "unit.s")
         subprocess.check_call([entry.HIPCC] + flags + ["--cuda-device-only", "-S", "-o", out, unit])

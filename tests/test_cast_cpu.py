@@ -64,7 +64,7 @@ def test_the_kernel_is_a_unit_of_the_build_with_the_common_flags():
     entry = open(os.path.join(abi.REPO_DIR, "__graft_entry__.py")).read()
     assert '("rtw_cast.hip", "rtw_cast.o", [])' in entry and '"rtw_cast.hip"' not in entry.split("UNIT_FLAGS = ")[1].split("\n")[0]
     hip = open(os.path.join(abi.PKG_DIR, "csrc", "rtw_hip.hip")).read()
-    assert '#include "rtw_cast.hip"' in hip.split("#ifndef RTW_SPLIT_BUILD")[1].split("#endif")[0]  # the single-file variant build
+    assert '#include "rtw_cast.hip"' not in hip  # (a translation unit of its own, in no other)
 
 
 # ---------------------------------------------------------------- the Python surface

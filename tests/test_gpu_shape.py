@@ -4,7 +4,7 @@ groups; 2 + 3 + 1 rectangles and a sphere, then the transformed box's 2 + 2 + 2 
 through render_adaptive's list twin. Scenes that still run the one-light instantiation but have other lists must take the walk that
 reads the group headers: a one-light scene of three rectangles, the box's rectangles moved into the identity group (one group), and
 a wall retyped so that the counts are 1, 3, 2. Chosen wrongly, the fixed walk would test records as the wrong kind, or read records
-that are not there, and every pixel would differ. TEA + LCG runs the generic kernel. The oracle's frames are rendered once per case
+that are not there, and every pixel would differ. (TEA + LCG runs the generic kernel: tests/test_gpu_variants.py renders that frame.) The oracle's frames are rendered once per case
 and shared."""
 import numpy as np
 import pytest
@@ -130,7 +130,3 @@ def test_edited_cornell_lists_fall_back(gpu, scene):
     """the Cornell box with one group instead of two, and with the identity group's counts 1, 3, 2 instead of 2, 3, 1"""
     counts = check(gpu, scene, W, H, 16, 4)
     assert counts[2] > 0
-
-
-def test_cornell_tea_lcg_runs_the_generic_kernel(gpu):
-    check(gpu, 0, W, H, 16, 4, rng_kind=abi.RTW_RNG_TEA_LCG)

@@ -54,7 +54,7 @@ def test_the_kernels_are_a_unit_of_the_build_and_share_the_body():
     assert '("rtw_probe_sh.hip", "rtw_probe_sh.o", [])' in entry and '"rtw_probe_sh.hip"' not in entry.split("UNIT_FLAGS = ")[1].split("\n")[0]
     csrc = os.path.join(abi.PKG_DIR, "csrc")
     hip, body, sh = (open(os.path.join(csrc, f)).read() for f in ("rtw_hip.hip", "rtw_radiance_body.h", "rtw_probe_sh.hip"))
-    assert '#include "rtw_probe_sh.hip"' in hip.split("#ifndef RTW_SPLIT_BUILD")[1].split("#endif")[0]  # the single-file variant build
+    assert '#include "rtw_probe_sh.hip"' not in hip  # (a translation unit of its own, in no other)
     assert hip.count("return guarded(c, [&] { return impl_sh_probe") == 2
     assert "RTW_RADIANCE_BODY(2)" in sh and "shade_a<" not in sh and "shade_b<" not in sh
     assert body.count("shade_a<KIND, TEX>") == 1 and body.count("shade_b<KIND>") == 1

@@ -1,29 +1,36 @@
-// rtw_adaptive.h — the per-pixel kernels of rtw_render_adaptive (include/rtw.h): running sums and error moments of the listed
-// pixels, the stop rule and the compaction of the next active list, the final image. The passes themselves are k_path / k_first
-// with LIST = 1 (rtw_kernels.h). Included by rtw_hip.hip.
+// rtw_adaptive.h — the per-entry kernels of the adaptive family (include/rtw.h: rtw_render_adaptive, rtw_probe_adaptive,
+// rtw_views_adaptive): the start of a call, running sums and error moments of the listed entries, the stop rule and the compaction of
+// the next active list, the results. An entry is a shard pixel, a probe or a pixel of a batch of views; the passes themselves are the
+// families' own (k_path / k_first with LIST = 1, rtw_kernels.h; k_probe_list, k_view_list). Included by rtw_hip.hip, whose
+// adaptive_run launches them.
 //
-// Per shard pixel p the state is: accum (sum of finished summation units), upart (running sum of the current unit's finished
-// blocks), part (running sum of the current block: wavefront pipeline only), mom = (M1, M2) in fp64, n (0 while active, else the
-// sample count the pixel stopped at) and err. A list of active pixels is list[0] = n, list[1 + i] = the pixel of position i (the
-// layout k_path / k_first read with LIST = 1), in ascending pixel order. Checkpoints fall on block boundaries but not on unit boundaries, so a pass leaves the
-// unit open (upart) and only k_adapt_finish closes it - the order in which k_resolve_blocks / k_resolve + k_finish close it.
+// Per entry p the state (rtw_adaptive_plan.h) is: accum (sum of finished summation units), upart (running sum of the current unit's
+// finished blocks), part (running sum of the current block: wavefront pipeline only), mom = (M1, M2) in fp64, n (0 while active, else
+// the sample count the entry stopped at), err, and total (occlusion probes only). A list of active entries is list[0] = n,
+// list[1 + i] = the entry of position i (the layout k_path / k_first read with LIST = 1), in ascending order. Checkpoints fall on
+// block boundaries but not on unit boundaries, so a pass leaves the unit open (upart) and only k_adapt_finish closes it - the order
+// in which k_resolve_blocks / k_resolve + k_finish close it.
 #pragma once
 #include "rtw_adaptive_stat.h"
+#include "rtw_kernels.h"
+#include "rtw_probe.h"
 
 namespace rtwk {
 
-// the start of an adaptive render: every pixel active (identity list), sums and moments zero
+// the start of a call: every entry active (identity list), sums and moments zero; part and total where the family keeps them (not null)
 __global__ void __launch_bounds__(kBlock) k_adapt_init(uint32_t* __restrict__ list, float4* __restrict__ accum, float4* __restrict__ upart,
                                                        float4* __restrict__ part, double2* __restrict__ mom, uint32_t* __restrict__ n,
-                                                       float* __restrict__ err, uint32_t npix) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+                                                       float* __restrict__ err, uint32_t* __restrict__ total, uint32_t n_entries) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_entries; i += gridDim.x * blockDim.x) {
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         list[1u + i] = i;
-        if (i == 0u) list[0] = npix;
-        accum[i] = z; upart[i] = z; part[i] = z;
+        if (i == 0u) list[0] = n_entries;
+        accum[i] = z; upart[i] = z;
+        if (part) part[i] = z;
         mom[i] = make_double2(0.0, 0.0);
         n[i] = 0u;
         err[i] = 0.f;
+        if (total) total[i] = 0u;
     }
 }
 
@@ -77,29 +84,41 @@ __global__ void __launch_bounds__(kBlock) k_adapt_resolve_samples(const float4* 
     }
 }
 
-// Checkpoint n_k = 16 B: err of every active pixel (n == 0) and the stop rule (rtw.h), dilation against the current active set
-// (a neighbour's err is recomputed from its moments: no pass over the frame has to finish first). One wave per 64 consecutive
-// pixels; masks[w] = the ballot of the pixels of wave w that stay active. n is only read here (k_adapt_compact writes it).
+// Checkpoint n_k = 16 B: err of every active entry (n == 0) and the stop rule (rtw.h), dilation against the current active set (a
+// neighbour's err is recomputed from its moments: no pass over the frame has to finish first). The entries are n_views frames of
+// width x height: the renderer's shard is one view of width x rows, a probe batch one view of n x 1 with dilate 0. One wave per 64
+// consecutive flattened pixels (a wave may span two views), p -> (view, y, x) by the exact divisions of view_split, the 3x3
+// neighbourhood clamped to the pixel's own frame: neighbour (xx, yy) is pixel view * width * height + yy * width + xx, so a tap never
+// reads another view (rtw_view_adaptive_plan.h view_adaptive_neighbour). masks[w] = the ballot of the pixels of wave w that stay
+// active. n is only read here (k_adapt_compact writes it).
+struct AdaptDecideArgs {
+    uint32_t width, height, npix;  // npix = n_views * width * height
+    uint32_t divw_m, divw_s1, divw_s2;  // exact division by width (magic_div)
+    uint32_t divf_m, divf_s1, divf_s2;  // exact division by width * height
+    uint32_t B, at_cap, dilate;
+    float threshold;
+};
 __global__ void __launch_bounds__(kBlock) k_adapt_decide(const double2* __restrict__ mom, const uint32_t* __restrict__ n, float* __restrict__ err,
-                                                         unsigned long long* __restrict__ masks, uint32_t width, uint32_t rows, uint32_t B,
-                                                         uint32_t at_cap, float threshold, uint32_t dilate) {
-    const uint32_t npix = width * rows, n_waves = (npix + 63u) / 64u;
+                                                         unsigned long long* __restrict__ masks, const AdaptDecideArgs a) {
+    const uint32_t n_waves = (a.npix + 63u) / 64u;
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t w = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); w < n_waves; w += gridDim.x * (kBlock / 64u)) {
         const uint32_t p = w * 64u + lane;
         bool keep = false;
-        if (p < npix && n[p] == 0u) {
-            const float e = adapt_err(mom[p], B);
+        if (p < a.npix && n[p] == 0u) {
+            const float e = adapt_err(mom[p], a.B);
             err[p] = e;
-            bool stop = at_cap != 0u || e < threshold;
-            if (stop && at_cap == 0u && dilate != 0u) {
-                const int y = (int)(p / width), x = (int)(p - (uint32_t)y * width);
+            bool stop = a.at_cap != 0u || e < a.threshold;
+            if (stop && a.at_cap == 0u && a.dilate != 0u) {
+                const uint32_t view = fastdiv(p, a.divf_m, a.divf_s1, a.divf_s2);
+                const uint32_t base = view * (a.width * a.height), in = p - base;  // the view's first pixel, p's index inside its frame
+                const int y = (int)fastdiv(in, a.divw_m, a.divw_s1, a.divw_s2), x = (int)(in - (uint32_t)y * a.width);
                 for (int dy = -1; dy <= 1; dy++) {
-                    const int yy = min(max(y + dy, 0), (int)rows - 1);
+                    const int yy = min(max(y + dy, 0), (int)a.height - 1);
                     for (int dx = -1; dx <= 1; dx++) {
-                        const int xx = min(max(x + dx, 0), (int)width - 1);
-                        const uint32_t q = (uint32_t)yy * width + (uint32_t)xx;
-                        if (q != p && n[q] == 0u && !(adapt_err(mom[q], B) < threshold)) stop = false;
+                        const int xx = min(max(x + dx, 0), (int)a.width - 1);
+                        const uint32_t q = base + (uint32_t)yy * a.width + (uint32_t)xx;  // (inside view's frame: < npix)
+                        if (q != p && n[q] == 0u && !(adapt_err(mom[q], a.B) < a.threshold)) stop = false;
                     }
                 }
             }
@@ -146,15 +165,22 @@ __global__ void __launch_bounds__(kBlock) k_adapt_compact(const unsigned long lo
     }
 }
 
-// mean radiance: the open unit joins the total (as k_resolve_blocks / k_finish close the last unit), then the division by (float)n_p
+// the results: the open unit joins the total (as k_resolve_blocks / k_finish close the last unit), then the division by (float)n_p,
+// alpha 1; times_pi (launch-uniform: the irradiance probe's estimate, rtw_probe.h kProbePi) multiplies the quotient afterwards.
+// spp_out and err_out where they are not null.
 __global__ void __launch_bounds__(kBlock) k_adapt_finish(const float4* __restrict__ accum, const float4* __restrict__ upart, const uint32_t* __restrict__ n,
-                                                         float4* __restrict__ out, uint32_t npix) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+                                                         const float* __restrict__ err, float4* __restrict__ out, int32_t* __restrict__ spp_out,
+                                                         float* __restrict__ err_out, uint32_t n_entries, uint32_t times_pi) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_entries; i += gridDim.x * blockDim.x) {
         float4 a = accum[i];
         const float4 u = upart[i];
         a.x += u.x; a.y += u.y; a.z += u.z;
         const float spp = (float)n[i];
-        out[i] = make_float4(a.x / spp, a.y / spp, a.z / spp, 1.0f);
+        float4 r = make_float4(a.x / spp, a.y / spp, a.z / spp, 1.0f);
+        if (times_pi != 0u) { r.x *= kProbePi; r.y *= kProbePi; r.z *= kProbePi; }
+        out[i] = r;
+        if (spp_out) spp_out[i] = (int32_t)n[i];
+        if (err_out) err_out[i] = err[i];
     }
 }
 

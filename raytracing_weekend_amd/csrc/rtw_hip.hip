@@ -28,7 +28,10 @@
 //     translation units. On the host they share one scaffold: QueryCall
 //     (query_open / query_close: device context, stream, the two timing events, the control words), query_chunks for the host
 //     variants' upload / issue / copy-back loop through one staging slab (laid out by rtw_stage_plan.h), query_stats for the tail,
-//     and adaptive_issue, the checkpoint loop of the two adaptive families
+//     and list_pass, a pass of the two adaptive queries
+//
+//   the adaptive family (rtw_render_adaptive, rtw_probe_adaptive, rtw_views_adaptive): one per-entry state (rtw_adaptive_plan.h) and one
+//     checkpoint loop, adaptive_run, over the kernels of rtw_adaptive.h; a family hands in its pass and its results
 //
 // render_single picks the pipeline; render_path and render_wavefront issue what rtw_plan.h's plan_path / plan_wavefront decide
 // (unit and batch sizes, passes, lanes, trace workgroup, launch schedule: host arithmetic on sizes, checked on the CPU), through the
@@ -146,8 +149,8 @@ struct rtw_ctx {
     DevBuf stage;              // in pixels: the gathered shards, then the shards' row offsets
     size_t pool_cap = ~(size_t)0;  // paths in flight this device has room for (halved when a pool allocation fails: render_wavefront)
     struct Worker* worker = nullptr;  // a kid's host thread: created with the group, lives until rtw_destroy
-    // rtw_render_adaptive's per-pixel state (rtw_adaptive.h), one allocation made on first use: accum, upart, part, moments, n, err,
-    // two active lists (a length word, then the pixels) and the compaction's masks and offsets (one per 64 pixels)
+    // rtw_render_adaptive's per-pixel state, one allocation made on first use: the adaptive family's layout with `part`
+    // (rtw_adaptive_plan.h adaptive_layout(npix, true))
     DevBuf adapt;
     // the accumulation session (rtw.h rtw_accum_*; a group's lives in kids[0]). It owns its per-pixel state, one allocation: accum,
     // upart, part (rtw_accum.h), with RTW_ACCUM_ERROR mom and the error map a read computes. An add borrows the context's scratch
@@ -172,7 +175,7 @@ struct rtw_ctx {
     DevBuf view_buf;           // the view records of a host call
     DevBuf dn_buf;             // rtw_denoise_views: the ping-pong buffer, and the host variant's colour, guides and output beside it
     DevBuf rad_ctl;            // the control words: kStatRows rows of 8 counters, then the queue word (query_open)
-    // rtw_probe_adaptive's per-probe state (rtw_probe_adaptive_plan.h probe_adaptive_layout), one allocation grown on demand and kept;
+    // rtw_probe_adaptive's per-probe state (rtw_adaptive_plan.h adaptive_layout(n, false)), one allocation grown on demand and kept;
     // rtw_views_adaptive's per-pixel state as well (the same layout over the pixels of a call or batch: a call initialises what it uses)
     DevBuf padapt;             // (in probes)
     uint64_t scene_fp = 0;  // accum_fingerprint of the uploaded blob (on the context the caller holds)
@@ -1104,30 +1107,94 @@ int impl_render(rtw_ctx* c, const rtw_params* P, float* rgba_out, rtw_stats* sta
     return RTW_OK;
 }
 
-// ---- rtw_render_adaptive (rtw.h): passes from checkpoint to checkpoint over the list of active pixels (rtw_adaptive.h)
-struct AdaptState {
-    float4 *accum, *upart, *part;
+// ---- the adaptive family (rtw.h: rtw_render_adaptive, rtw_probe_adaptive, rtw_views_adaptive): one state, one checkpoint loop
+// (rtw_adaptive.h, rtw_adaptive_plan.h). An entry is a shard pixel, a probe or a pixel of the views at hand.
+struct AdaptiveState {
+    float4 *accum, *upart, *part;  // part: null unless the layout has it
     double2* mom;
-    uint32_t *n, *list[2], *offsets;
+    uint32_t *n, *total, *list[2], *offsets;
     float* err;
     unsigned long long* masks;
 };
 
-int ensure_adapt(rtw_ctx* c, size_t npix, AdaptState& st) {
-    const size_t nw = (npix + 63) / 64;
-    const size_t sz[10] = {npix * 16, npix * 16, npix * 16, npix * 16, npix * 4, npix * 4 + 4, npix * 4 + 4, npix * 4, nw * 8, nw * 4};
-    size_t off[11] = {0};
-    for (int k = 0; k < 10; k++) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
-    HIP_TRY(c, c->adapt.grow(npix, off[10]));
-    char* b = c->adapt.as<char>();  // (the layout for npix fits in an allocation made for more pixels)
-    st.accum = (float4*)(b + off[0]); st.upart = (float4*)(b + off[1]); st.part = (float4*)(b + off[2]); st.mom = (double2*)(b + off[3]);
-    st.n = (uint32_t*)(b + off[4]); st.list[0] = (uint32_t*)(b + off[5]); st.list[1] = (uint32_t*)(b + off[6]); st.err = (float*)(b + off[7]);
-    st.masks = (unsigned long long*)(b + off[8]); st.offsets = (uint32_t*)(b + off[9]);
+// the state for n entries in `buf`, a context-owned allocation grown on demand and kept (the layout for n fits in an allocation made
+// for more entries); drain: DevBuf::grow's
+int adaptive_state(rtw_ctx* c, DevBuf& buf, size_t n, bool want_part, const hipStream_t* drain, AdaptiveState& st) {
+    typedef AdaptiveLayout AL;
+    const AL l = adaptive_layout(n, want_part);
+    HIP_TRY(c, buf.grow(n, (size_t)l.bytes(), drain));
+    char* b = buf.as<char>();
+    st.accum = (float4*)(b + l.off[AL::kAccum]); st.upart = (float4*)(b + l.off[AL::kUpart]); st.part = want_part ? (float4*)(b + l.off[AL::kPart]) : nullptr;
+    st.mom = (double2*)(b + l.off[AL::kMom]); st.n = (uint32_t*)(b + l.off[AL::kN]); st.err = (float*)(b + l.off[AL::kErr]);
+    st.total = (uint32_t*)(b + l.off[AL::kTotal]); st.list[0] = (uint32_t*)(b + l.off[AL::kList0]); st.list[1] = (uint32_t*)(b + l.off[AL::kList1]);
+    st.masks = (unsigned long long*)(b + l.off[AL::kMasks]); st.offsets = (uint32_t*)(b + l.off[AL::kOffsets]);
     return RTW_OK;
 }
 
+// the stop rule's frames: n_views views of width x height (the renderer: one view of width x rows; probes: one view of n x 1, dilate 0)
+AdaptDecideArgs adaptive_frames(uint32_t width, uint32_t height, size_t n_views, float threshold, int dilate) {
+    AdaptDecideArgs da{};
+    da.width = width; da.height = height; da.npix = (uint32_t)(n_views * width * height);
+    magic_div(width, da.divw_m, da.divw_s1, da.divw_s2);
+    magic_div(width * height, da.divf_m, da.divf_s1, da.divf_s2);
+    da.dilate = (uint32_t)dilate; da.threshold = threshold;
+    return da;
+}
+
+// RTW_VERBOSE=1, rtw_render_adaptive: a row of the pass table, timed from before the pass to after the compaction
+struct AdaptivePassRec { int n_from, n_to; size_t active; hipEvent_t a, b; };
+
+// The checkpoint loop over the da.npix entries of state st, on stream s of device context d (c: the context the caller holds, for
+// errors): the start, then per checkpoint one pass over the list of the active entries, the decision, the compaction and one count
+// read-back - the next pass is planned on the active count - and at last the results. It returns when `finish` has been issued.
+// `samples` receives the sum of the entries' sample counts. What a family hands in:
+//   pass(list, n_active, n_from, n_to)   samples [n_from, n_to) of the n_active entries of `list`, resolved into the state; -> RTW_OK or an error
+//   finish(grid)                         the results
+// table: where not null, every pass leaves a row, its events taken from log.
+template <class Pass, class Finish>
+int adaptive_run(rtw_ctx* c, rtw_ctx* d, const AdaptiveState& st, AdaptDecideArgs da, const std::vector<int>& cps, hipStream_t s, uint64_t& samples,
+                 CallLog* log, std::vector<AdaptivePassRec>* table, Pass pass, Finish finish) {
+    const size_t n = da.npix;
+    const unsigned all_grid = pixel_grid(d, n);
+    const uint32_t n_waves = (uint32_t)((n + 63) / 64);
+    hipLaunchKernelGGL(k_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.part, st.mom, st.n, st.err, st.total, (uint32_t)n);
+    HIP_TRY(c, hipGetLastError());
+    size_t n_active = n;
+    int cur = 0, n_prev = 0;
+    for (size_t k = 0; k < cps.size() && n_active > 0; k++) {
+        const int n_k = cps[k];
+        if (table) {
+            table->push_back(AdaptivePassRec{n_prev, n_k, n_active, nullptr, nullptr});
+            HIP_TRY(c, log->event(table->back().a));
+            HIP_TRY(c, log->event(table->back().b));
+            HIP_TRY(c, hipEventRecord(table->back().a, s));
+        }
+        const int rc = pass(st.list[cur], n_active, n_prev, n_k);
+        if (rc) return rc;
+        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
+        da.B = (uint32_t)n_k / kSumBlock; da.at_cap = k + 1 == cps.size() ? 1u : 0u;
+        hipLaunchKernelGGL(k_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
+                           (const uint32_t*)st.n, st.err, st.masks, da);
+        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
+        hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
+                           st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
+        HIP_TRY(c, hipGetLastError());
+        if (table) HIP_TRY(c, hipEventRecord(table->back().b, s));
+        uint32_t cnt = 0;  // one read-back, one host synchronisation per checkpoint
+        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        n_active = cnt;
+        cur ^= 1;
+        n_prev = n_k;
+    }
+    finish(all_grid);
+    HIP_TRY(c, hipGetLastError());
+    return RTW_OK;
+}
+
+// ---- rtw_render_adaptive (rtw.h): the family's loop over the shard's pixels; a pass is k_path's or the wavefront pipeline's
 // k_path over the n_list pixels of `list` (length word, then the pixels: rtw_adaptive.h): blocks [n_from / 16, n_to / 16) of each, resolved into the state
-int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptState& st, const uint32_t* list,
+int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptiveState& st, const uint32_t* list,
                        size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
     // every block's sum must reach memory (the moments are taken over blocks): no lane unit may be a whole summation unit
     Tuning t = tune;
@@ -1150,7 +1217,7 @@ int adaptive_path_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, cons
 // the wavefront pipeline over the n_list pixels of `list`: samples [n_from, n_to) of each. Path ids keep the shard's stride
 // (slot * npix + pixel), so a batch's radiance buffer needs Sb * npix slots: a list batch takes at most the samples per pixel that a
 // full-frame batch would (the pool's share per lane over npix), and the lane's buffers are sized for that many slots.
-int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptState& st, const uint32_t* list,
+int adaptive_wavefront_pass(rtw_ctx* c, const rtw_params* P, const Tuning& tune, const KArgs& base, const AdaptiveState& st, const uint32_t* list,
                             size_t n_list, int n_from, int n_to, hipStream_t s, CallLog& log) {
     const size_t npix = base.npix;
     const size_t step = (size_t)(n_to - n_from);
@@ -1187,51 +1254,26 @@ int render_adaptive_single(rtw_ctx* c, const rtw_params* P, const rtw_adaptive* 
     HIP_TRY(c, log.event(log.end));
     const KArgs base = render_args(c, P, npix);
     const bool use_path = path_pipeline(c->sc, P->width, P->height, P->max_depth, tune);
-    AdaptState st{};
-    int rc = ensure_adapt(c, npix, st);
+    AdaptiveState st{};
+    int rc = adaptive_state(c, c->adapt, npix, true, nullptr, st);
     if (rc) return rc;
     HIP_TRY(c, c->d_stats.grow(kStatsBytes, kStatsBytes));
     HIP_TRY(c, c->d_out.grow(npix, npix * sizeof(float4)));
-    const unsigned pix_grid = pixel_grid(c, npix);
-    const uint32_t n_waves = (uint32_t)((npix + 63) / 64);
     HIP_TRY(c, hipEventRecord(log.begin, s));
     HIP_TRY(c, hipMemsetAsync(c->d_stats.as<void>(), 0, kStatsBytes, s));
-    hipLaunchKernelGGL(k_adapt_init, dim3(pix_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.part, st.mom, st.n, st.err, (uint32_t)npix);
-    size_t n_active = npix;
     uint64_t samples = 0;
-    int cur = 0, n_prev = 0;
-    struct PassRec { int n_from, n_to; size_t active; hipEvent_t a, b; };
-    std::vector<PassRec> passes;  // RTW_VERBOSE=1: the pass table, printed to stderr at the end
-    for (size_t k = 0; k < cps.size() && n_active > 0; k++) {
-        const int n_k = cps[k];
-        if (tune.verbose) {
-            passes.push_back(PassRec{n_prev, n_k, n_active, nullptr, nullptr});
-            HIP_TRY(c, log.event(passes.back().a));
-            HIP_TRY(c, log.event(passes.back().b));
-            HIP_TRY(c, hipEventRecord(passes.back().a, s));
-        }
-        rc = use_path ? adaptive_path_pass(c, P, tune, base, st, st.list[cur], n_active, n_prev, n_k, s, log)
-                      : adaptive_wavefront_pass(c, P, tune, base, st, st.list[cur], n_active, n_prev, n_k, s, log);
-        if (rc) return rc;
-        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
-        hipLaunchKernelGGL(k_adapt_decide, dim3(std::min<unsigned>((n_waves + 3) / 4, (unsigned)c->n_cu * 8)), dim3(kBlock), 0, s, (const double2*)st.mom,
-                           (const uint32_t*)st.n, st.err, st.masks, (uint32_t)P->width, (uint32_t)rows, (uint32_t)n_k / kSumBlock,
-                           k + 1 == cps.size() ? 1u : 0u, AD->threshold, (uint32_t)AD->dilate);
-        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
-        hipLaunchKernelGGL(k_adapt_compact, dim3(pix_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
-                           st.list[cur ^ 1], (uint32_t)npix, (uint32_t)n_k);
-        HIP_TRY(c, hipGetLastError());
-        if (tune.verbose) HIP_TRY(c, hipEventRecord(passes.back().b, s));
-        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
-        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        n_active = cnt;
-        cur ^= 1;
-        n_prev = n_k;
-    }
-    hipLaunchKernelGGL(k_adapt_finish, dim3(pix_grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
-                       c->d_out.as<float4>(), (uint32_t)npix);
-    HIP_TRY(c, hipGetLastError());
+    std::vector<AdaptivePassRec> passes;  // RTW_VERBOSE=1: the pass table, printed to stderr at the end
+    rc = adaptive_run(
+        c, c, st, adaptive_frames((uint32_t)P->width, (uint32_t)rows, 1, AD->threshold, AD->dilate), cps, s, samples, &log, tune.verbose ? &passes : nullptr,
+        [&](const uint32_t* list, size_t n_active, int n_from, int n_to) {
+            return use_path ? adaptive_path_pass(c, P, tune, base, st, list, n_active, n_from, n_to, s, log)
+                            : adaptive_wavefront_pass(c, P, tune, base, st, list, n_active, n_from, n_to, s, log);
+        },
+        [&](unsigned grid) {  // (n and err are copied out of the state below)
+            hipLaunchKernelGGL(k_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                               (const float*)st.err, c->d_out.as<float4>(), (int32_t*)nullptr, (float*)nullptr, (uint32_t)npix, 0u);
+        });
+    if (rc) return rc;
     HIP_TRY(c, hipEventRecord(log.end, s));
     HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out.as<void>(), npix * sizeof(float4), hipMemcpyDeviceToHost, s));
     if (spp_out) HIP_TRY(c, hipMemcpyAsync(spp_out, st.n, npix * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -2366,114 +2408,56 @@ int impl_denoise_views(rtw_ctx* c, const float* rgba_in, const float* albedo, co
 }
 
 // ---- rtw_probe_adaptive / rtw_probe_adaptive_device (rtw.h): rtw_probe's samples taken from checkpoint to checkpoint over the list of
-// the probes that are still active (rtw_probe_adaptive.h; the plan is rtw_probe_adaptive_plan.h's). The moments, the decision and the
-// compaction are rtw_render_adaptive's kernels over a frame of n x 1 probes with dilate 0.
+// the probes that are still active (rtw_probe_adaptive.h; the plan of a pass is rtw_probe_adaptive_plan.h's)
 typedef void (*ProbeListKernel)(const DScene, const ProbeListArgs);
-struct ProbeAdaptState {
-    float4 *accum, *upart;
-    double2* mom;
-    uint32_t *n, *total, *list[2], *offsets;
-    float* err;
-    unsigned long long* masks;
-};
 
-// the context's per-probe state for at least n probes: grown after the stream's pending work, kept until rtw_destroy
-int ensure_probe_adapt(rtw_ctx* c, rtw_ctx* d, size_t n, hipStream_t s, ProbeAdaptState& st) {
-    const ProbeAdaptiveLayout l = probe_adaptive_layout(n);  // (the layout for n fits in an allocation made for more probes)
-    HIP_TRY(c, d->padapt.grow(n, (size_t)l.bytes(), &s));
-    char* b = d->padapt.as<char>();
-    typedef ProbeAdaptiveLayout PL;
-    st.accum = (float4*)(b + l.off[PL::kAccum]); st.upart = (float4*)(b + l.off[PL::kUpart]); st.mom = (double2*)(b + l.off[PL::kMom]);
-    st.n = (uint32_t*)(b + l.off[PL::kN]); st.err = (float*)(b + l.off[PL::kErr]); st.total = (uint32_t*)(b + l.off[PL::kTotal]);
-    st.list[0] = (uint32_t*)(b + l.off[PL::kList0]); st.list[1] = (uint32_t*)(b + l.off[PL::kList1]);
-    st.masks = (unsigned long long*)(b + l.off[PL::kMasks]); st.offsets = (uint32_t*)(b + l.off[PL::kOffsets]);
-    return RTW_OK;
-}
-
-// One range of one pass as the list kernels take it: the members that ProbeListArgs and ViewListArgs have under these names
-struct ListPass {
-    const uint32_t* list;  // (position i of the range is list[1 + i])
-    float4* out;
-    uint32_t* queue;
-    unsigned long long* stats;
-    uint32_t n, n_blocks, run_blocks, n_units, job_units, n_jobs, divn_m, divn_s1, divn_s2, s_from;
-    unsigned grid;
-};
-
-// The checkpoint loop of rtw_probe_adaptive and rtw_views_adaptive over n entries (probes, or the pixels of the views at hand), on
-// stream s of device context d: per checkpoint one pass over the list of the active entries (rtw_probe_adaptive_plan.h: runs, ranges
-// that fit the slab cap), the family's decision, the compaction and one count read-back; it returns when `finish` has been issued.
-// `samples` receives the sum of the entries' sample counts. The counters add up in d->rad_ctl's rows, which the caller zeroed on s.
-// What a family hands in: `kernel`, its sampling kernel (for the occupancy); zero_depth, no segment is traced and every block sum is
-// 0; use_queue, the kernel takes its jobs from the queue word; and the four launches that differ, each given the state:
-//   sample(p)                          the sampling kernel over range p, block sums to p.out
-//   resolve(st, list, count, nb, blk0) the block sums of a range into the listed entries' sums and moments
-//   decide(st, grid, B, at_cap)        the stop rule after B blocks: masks and err
-//   finish(st, grid)                   the results
-template <class Sample, class Resolve, class Decide, class Finish>
-int adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, size_t n, const void* kernel, bool zero_depth, bool use_queue, const std::vector<int>& cps,
-                   hipStream_t s, uint64_t& samples, Sample sample, Resolve resolve, Decide decide, Finish finish) {
-    ProbeAdaptState st{};
-    int rc = ensure_probe_adapt(c, d, n, s, st);
-    if (rc) return rc;
-    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu(kernel, d->info.lds_bytes, 0);
+// One pass of rtw_probe_adaptive / rtw_views_adaptive, adaptive_run's `pass` for the list kernels: samples [n_from, n_to) of the
+// n_active entries of `list` on stream s of device context d, cut into ranges of list positions that fit the slab cap
+// (rtw_probe_adaptive_plan.h: runs, ranges, jobs), each range sampled into d->rad_slab and resolved from there. The counters add up
+// in d->rad_ctl's rows, which the caller zeroed on s. What a family hands in: max_grid, the workgroups its sampling kernel keeps
+// resident; zero_depth, no segment is traced and every block sum is 0; use_queue, the kernel takes its jobs from the queue word; and
+//   sample(p, grid)                the sampling kernel over range p (rtw_list_body.h ListPass), block sums to p.out
+//   resolve(list, count, nb, blk0) the block sums of a range into the listed entries' sums and moments
+template <class Sample, class Resolve>
+int list_pass(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, size_t max_grid, bool zero_depth, bool use_queue, const uint32_t* list0, size_t n_active, int n_from,
+              int n_to, hipStream_t s, Sample sample, Resolve resolve) {
     uint32_t* const queue = (uint32_t*)(d->rad_ctl.as<unsigned long long>() + kStatRows * 8);
-    const unsigned all_grid = pixel_grid(d, n);
-    const uint32_t n_waves = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(k_probe_adapt_init, dim3(all_grid), dim3(kBlock), 0, s, st.list[0], st.accum, st.upart, st.mom, st.n, st.err, st.total, (uint32_t)n);
-    HIP_TRY(c, hipGetLastError());
-    size_t n_active = n;
-    int cur = 0, n_prev = 0;
-    for (size_t kc = 0; kc < cps.size() && n_active > 0; kc++) {
-        const int n_k = cps[kc];
-        const uint32_t nb = probe_adaptive_pass_blocks(n_prev, n_k), blk0 = probe_adaptive_first_block(n_prev);
-        const uint32_t run_blocks = probe_adaptive_run_blocks(n_active, nb, max_grid * kBlock);
-        const uint32_t runs = probe_adaptive_runs(nb, run_blocks);
-        const uint64_t per = probe_adaptive_range_positions(n_active, nb, run_blocks, tune.radiance_slab_bytes);
-        if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
-        for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
-            const RadianceRange rg = radiance_range(n_active, per, r);
-            const uint32_t* const list = st.list[cur] + rg.first;
-            if (zero_depth) {
-                HIP_TRY(c, hipMemsetAsync(d->rad_slab.as<void>(), 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
-            } else {
-                ListPass p{};
-                p.list = list;
-                p.out = d->rad_slab.as<float4>();
-                p.queue = queue;
-                p.stats = d->rad_ctl.as<unsigned long long>();
-                p.n = (uint32_t)rg.count; p.n_blocks = nb; p.run_blocks = run_blocks; p.n_units = (uint32_t)(rg.count * runs);
-                p.grid = (unsigned)std::min<size_t>(((size_t)p.n_units + kBlock - 1) / kBlock, max_grid);
-                p.job_units = probe_adaptive_job_units(run_blocks, p.n_units, (size_t)p.grid * (kBlock / 64));
-                p.n_jobs = (uint32_t)radiance_n_jobs(p.n_units, p.job_units);
-                magic_div(p.n, p.divn_m, p.divn_s1, p.divn_s2);
-                p.s_from = (uint32_t)n_prev;
-                if (use_queue) HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
-                sample(p);
-                HIP_TRY(c, hipGetLastError());
-            }
-            resolve(st, list, (uint32_t)rg.count, nb, blk0);
+    const uint32_t nb = probe_adaptive_pass_blocks(n_from, n_to), blk0 = probe_adaptive_first_block(n_from);
+    const uint32_t run_blocks = probe_adaptive_run_blocks(n_active, nb, max_grid * kBlock);
+    const uint32_t runs = probe_adaptive_runs(nb, run_blocks);
+    const uint64_t per = probe_adaptive_range_positions(n_active, nb, run_blocks, tune.radiance_slab_bytes);
+    int rc;
+    if ((rc = radiance_slab(c, d, probe_adaptive_slab_bytes(per, nb), s)) != RTW_OK) return rc;
+    for (uint64_t r = 0, nr = radiance_n_ranges(n_active, per); r < nr; r++) {
+        const RadianceRange rg = radiance_range(n_active, per, r);
+        const uint32_t* const list = list0 + rg.first;
+        if (zero_depth) {
+            HIP_TRY(c, hipMemsetAsync(d->rad_slab.as<void>(), 0, (size_t)probe_adaptive_slab_bytes(rg.count, nb), s));
+        } else {
+            ListPass p{};
+            p.list = list;
+            p.out = d->rad_slab.as<float4>();
+            p.queue = queue;
+            p.stats = d->rad_ctl.as<unsigned long long>();
+            p.n = (uint32_t)rg.count; p.n_blocks = nb; p.run_blocks = run_blocks; p.n_units = (uint32_t)(rg.count * runs);
+            const unsigned grid = (unsigned)std::min<size_t>(((size_t)p.n_units + kBlock - 1) / kBlock, max_grid);
+            p.job_units = probe_adaptive_job_units(run_blocks, p.n_units, (size_t)grid * (kBlock / 64));
+            p.n_jobs = (uint32_t)radiance_n_jobs(p.n_units, p.job_units);
+            magic_div(p.n, p.divn_m, p.divn_s1, p.divn_s2);
+            p.s_from = (uint32_t)n_from;
+            if (use_queue) HIP_TRY(c, hipMemsetAsync(queue, 0, sizeof(uint32_t), s));
+            sample(p, grid);
             HIP_TRY(c, hipGetLastError());
         }
-        samples += (uint64_t)n_active * (uint64_t)(n_k - n_prev);
-        decide(st, std::min<unsigned>((n_waves + 3) / 4, (unsigned)d->n_cu * 8), (uint32_t)n_k / kSumBlock, kc + 1 == cps.size() ? 1u : 0u);
-        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long*)st.masks, st.offsets, n_waves, st.list[cur ^ 1]);
-        hipLaunchKernelGGL(k_adapt_compact, dim3(all_grid), dim3(kBlock), 0, s, (const unsigned long long*)st.masks, (const uint32_t*)st.offsets, st.n,
-                           st.list[cur ^ 1], (uint32_t)n, (uint32_t)n_k);
+        resolve(list, (uint32_t)rg.count, nb, blk0);
         HIP_TRY(c, hipGetLastError());
-        uint32_t cnt = 0;  // the next pass is planned on the active count: one read-back per checkpoint
-        HIP_TRY(c, hipMemcpyAsync(&cnt, st.list[cur ^ 1], sizeof cnt, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        n_active = cnt;
-        cur ^= 1;
-        n_prev = n_k;
     }
-    finish(st, all_grid);
-    HIP_TRY(c, hipGetLastError());
     return RTW_OK;
 }
 
-// n probes at d_probes (device) -> their results at d_out (and d_spp, d_err where not null); probe i on the stream of key_offset + i
+// n probes at d_probes (device) -> their results at d_out (and d_spp, d_err where not null); probe i on the stream of key_offset + i.
+// The family's loop over a frame of n x 1 probes with dilate 0; the state is the context's d->padapt, grown after the stream's
+// pending work and kept until rtw_destroy.
 int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float* d_probes, size_t n, const rtw_radiance_params* RP, int mode,
                          const rtw_adaptive* AD, const std::vector<int>& cps, uint32_t key_offset, float4* d_out, int32_t* d_spp, float* d_err,
                          hipStream_t s, uint64_t& samples) {
@@ -2482,37 +2466,38 @@ int probe_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const float
     if (!occ) apply_estimator(sc, RP->estimator);
     const ProbeListKernel k = occ ? (RP->rng_kind == RTW_RNG_TEA_LCG ? k_probe_occlusion_list<RTW_RNG_TEA_LCG> : k_probe_occlusion_list<RTW_RNG_PHILOX>)
                                   : RTW_PICK(k_probe_list, RP->rng_kind, sc.has_tex);
-    return adaptive_issue(
-        c, d, tune, n, (const void*)k, !occ && RP->max_depth == 0, !occ, cps, s, samples,
-        [&](const ListPass& p) {
-            ProbeListArgs a{};
-            a.probes = (const float4*)d_probes;
-            a.list = p.list; a.out = p.out; a.queue = p.queue; a.stats = p.stats;
-            a.n = p.n; a.n_blocks = p.n_blocks; a.run_blocks = p.run_blocks; a.n_units = p.n_units; a.job_units = p.job_units; a.n_jobs = p.n_jobs;
-            a.divn_m = p.divn_m; a.divn_s1 = p.divn_s1; a.divn_s2 = p.divn_s2;
-            a.s_from = p.s_from; a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth;
-            a.key0 = key_offset;
-            hipLaunchKernelGGL(k, dim3(p.grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+    AdaptiveState st{};
+    const int rc = adaptive_state(c, d->padapt, n, false, &s, st);
+    if (rc) return rc;
+    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, d->info.lds_bytes, 0);
+    ProbeListArgs a{};
+    a.probes = (const float4*)d_probes;
+    a.sample0 = (uint32_t)RP->sample_offset; a.seed = RP->seed; a.max_depth = (uint32_t)RP->max_depth; a.key0 = key_offset;
+    return adaptive_run(
+        c, d, st, adaptive_frames((uint32_t)n, 1u, 1, AD->threshold, 0), cps, s, samples, nullptr, nullptr,
+        [&](const uint32_t* list, size_t n_active, int n_from, int n_to) {
+            return list_pass(
+                c, d, tune, max_grid, !occ && RP->max_depth == 0, !occ, list, n_active, n_from, n_to, s,
+                [&](const ListPass& p, unsigned grid) {
+                    a.p = p;
+                    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+                },
+                [&](const uint32_t* range, uint32_t count, uint32_t nb, uint32_t blk0) {
+                    if (occ)
+                        hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const uint32_t>(), range, count,
+                                           nb, st.total, st.mom);
+                    else
+                        hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), range, count, nb,
+                                           blk0, st.accum, st.upart, st.mom);
+                });
         },
-        [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
-            if (occ)
-                hipLaunchKernelGGL(k_probe_adapt_resolve_counts, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const uint32_t>(), list, count, nb,
-                                   st.total, st.mom);
-            else
-                hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), list, count, nb, blk0,
-                                   st.accum, st.upart, st.mom);
-        },
-        [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // rtw_render_adaptive's rule over a frame of n x 1, dilate 0
-            hipLaunchKernelGGL(k_adapt_decide, dim3(grid), dim3(kBlock), 0, s, (const double2*)st.mom, (const uint32_t*)st.n, st.err, st.masks, (uint32_t)n, 1u,
-                               B, at_cap, AD->threshold, 0u);
-        },
-        [&](const ProbeAdaptState& st, unsigned grid) {
+        [&](unsigned grid) {
             if (occ)
                 hipLaunchKernelGGL(k_probe_adapt_finish_occlusion, dim3(grid), dim3(kBlock), 0, s, (const uint32_t*)st.total, (const uint32_t*)st.n,
                                    (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
-            else
-                hipLaunchKernelGGL(k_probe_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart,
-                                   (const uint32_t*)st.n, (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+            else  // (sum / (float)n_i) * pi
+                hipLaunchKernelGGL(k_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                                   (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n, 1u);
         });
 }
 
@@ -2590,9 +2575,8 @@ int impl_adaptive_probe(rtw_ctx* c, const float* probes, size_t n, const rtw_pro
 }
 
 // ---- rtw_views_adaptive / rtw_views_adaptive_device (rtw.h): rtw_views' samples taken from checkpoint to checkpoint over the list of
-// the pixels that are still active (rtw_view_adaptive.h). The loop, the plan of a pass and the per-pixel state are
-// rtw_probe_adaptive's with n = the pixels of the views at hand (the state lives in the same context-owned allocation); the decision
-// is k_view_adapt_decide's, dilated inside each view.
+// the pixels that are still active (rtw_view_adaptive.h). The family's loop over the flattened pixels of the views at hand, the rule
+// dilated inside each view; a pass is list_pass with k_view_list, and the per-pixel state lives in the allocation the probes use.
 typedef void (*ViewListKernel)(const DScene, const ViewListArgs);
 
 // n_views views at d_views (device) -> their frames at d_out (and d_spp, d_err where not null): pixel i of the outputs is flattened
@@ -2604,34 +2588,30 @@ int view_adaptive_issue(rtw_ctx* c, rtw_ctx* d, const Tuning& tune, const rtw_vi
     DScene sc = d->sc;
     apply_estimator(sc, RP->estimator);
     const ViewListKernel k = RTW_PICK(k_view_list, RP->rng_kind, sc.has_tex);
-    const ViewArgs va = view_frame_args(d_views, VP->width, VP->height, 0);  // pixel i of the list is pixel i of these views
-    ViewDecideArgs da{};
-    da.width = va.width; da.height = va.height; da.npix = (uint32_t)n;
-    da.divw_m = va.divw_m; da.divw_s1 = va.divw_s1; da.divw_s2 = va.divw_s2;
-    da.divf_m = va.divf_m; da.divf_s1 = va.divf_s1; da.divf_s2 = va.divf_s2;
-    da.dilate = (uint32_t)AD->dilate; da.threshold = AD->threshold;
-    return adaptive_issue(
-        c, d, tune, n, (const void*)k, RP->max_depth == 0, true, cps, s, samples,
-        [&](const ListPass& p) {
-            ViewListArgs a{};
-            a.v = va;
-            a.list = p.list; a.out = p.out; a.queue = p.queue; a.stats = p.stats;
-            a.n = p.n; a.n_blocks = p.n_blocks; a.run_blocks = p.run_blocks; a.n_units = p.n_units; a.job_units = p.job_units; a.n_jobs = p.n_jobs;
-            a.divn_m = p.divn_m; a.divn_s1 = p.divn_s1; a.divn_s2 = p.divn_s2;
-            a.s_from = p.s_from; a.sample0 = (uint32_t)RP->sample_offset; a.max_depth = (uint32_t)RP->max_depth;
-            hipLaunchKernelGGL(k, dim3(p.grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+    AdaptiveState st{};
+    const int rc = adaptive_state(c, d->padapt, n, false, &s, st);
+    if (rc) return rc;
+    const size_t max_grid = (size_t)d->n_cu * (size_t)path_wg_per_cu((const void*)k, d->info.lds_bytes, 0);
+    ViewListArgs a{};
+    a.v = view_frame_args(d_views, VP->width, VP->height, 0);  // pixel i of the list is pixel i of these views
+    a.sample0 = (uint32_t)RP->sample_offset; a.max_depth = (uint32_t)RP->max_depth;
+    return adaptive_run(
+        c, d, st, adaptive_frames(a.v.width, a.v.height, n_views, AD->threshold, AD->dilate), cps, s, samples, nullptr, nullptr,
+        [&](const uint32_t* list, size_t n_active, int n_from, int n_to) {
+            return list_pass(
+                c, d, tune, max_grid, RP->max_depth == 0, true, list, n_active, n_from, n_to, s,
+                [&](const ListPass& p, unsigned grid) {
+                    a.p = p;
+                    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), d->info.lds_bytes, s, sc, a);
+                },
+                [&](const uint32_t* range, uint32_t count, uint32_t nb, uint32_t blk0) {
+                    hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), range, count, nb, blk0,
+                                       st.accum, st.upart, st.mom);
+                });
         },
-        [&](const ProbeAdaptState& st, const uint32_t* list, uint32_t count, uint32_t nb, uint32_t blk0) {
-            hipLaunchKernelGGL(k_adapt_resolve_blocks, dim3(pixel_grid(d, count)), dim3(kBlock), 0, s, d->rad_slab.as<const float4>(), list, count, nb, blk0, st.accum,
-                               st.upart, st.mom);
-        },
-        [&](const ProbeAdaptState& st, unsigned grid, uint32_t B, uint32_t at_cap) {  // the rule dilated inside each view
-            da.B = B; da.at_cap = at_cap;
-            hipLaunchKernelGGL(k_view_adapt_decide, dim3(grid), dim3(kBlock), 0, s, (const double2*)st.mom, (const uint32_t*)st.n, st.err, st.masks, da);
-        },
-        [&](const ProbeAdaptState& st, unsigned grid) {
-            hipLaunchKernelGGL(k_view_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
-                               (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n);
+        [&](unsigned grid) {
+            hipLaunchKernelGGL(k_adapt_finish, dim3(grid), dim3(kBlock), 0, s, (const float4*)st.accum, (const float4*)st.upart, (const uint32_t*)st.n,
+                               (const float*)st.err, d_out, d_spp, d_err, (uint32_t)n, 0u);
         });
 }
 

@@ -1,8 +1,8 @@
 // rtw_probe_adaptive_plan.h — what one pass of rtw_probe_adaptive / rtw_probe_adaptive_device launches, decided on the host from sizes
 // alone (no HIP in here, in the style of rtw_radiance_plan.h): the blocks a pass adds to every listed probe, the run of whole blocks
 // that is one unit of work (R) and the units of one queue job (J), the block-sum slab in 64 bits, the cut of a list into ranges of
-// list positions that fit the slab cap, and the bytes of the per-probe state. tests/native/probe_adaptive_plan_check.cpp pins them
-// with g++.
+// list positions that fit the slab cap. The per-probe state is the adaptive family's (rtw_adaptive_plan.h, included here).
+// tests/native/probe_adaptive_plan_check.cpp pins them with g++.
 #pragma once
 #include <stdint.h>
 
@@ -10,6 +10,7 @@
 #include <cstddef>
 
 #include "../../include/rtw.h"
+#include "rtw_adaptive_plan.h"
 #include "rtw_radiance_plan.h"
 
 namespace rtwk {
@@ -54,22 +55,6 @@ inline uint32_t probe_adaptive_job_units(uint32_t run_blocks, uint64_t n_units, 
     const uint64_t balance = n_units / (64ull * std::max<uint64_t>(waves, 1) * 8ull);
     j = std::max<uint64_t>(1, std::min<uint64_t>(j, balance));
     return (uint32_t)(64ull * j);
-}
-
-// The per-probe state of a call over n probes (one context-owned allocation, sections 256-byte aligned): accum, upart (float4),
-// moments (double2), the stop count n, err, the occlusion total, two lists (a length word, then the positions), and the
-// compaction's masks and offsets (one per 64 probes).
-struct ProbeAdaptiveLayout {
-    enum { kAccum, kUpart, kMom, kN, kErr, kTotal, kList0, kList1, kMasks, kOffsets, kSections };
-    uint64_t off[kSections + 1];
-    uint64_t bytes() const { return off[kSections]; }
-};
-inline ProbeAdaptiveLayout probe_adaptive_layout(uint64_t n) {
-    const uint64_t nw = (n + 63) / 64;
-    const uint64_t sz[ProbeAdaptiveLayout::kSections] = {n * 16, n * 16, n * 16, n * 4, n * 4, n * 4, n * 4 + 4, n * 4 + 4, nw * 8, nw * 4};
-    ProbeAdaptiveLayout l{};
-    for (int k = 0; k < ProbeAdaptiveLayout::kSections; k++) l.off[k + 1] = l.off[k] + ((sz[k] + 255) & ~(uint64_t)255);
-    return l;
 }
 
 }  // namespace rtwk

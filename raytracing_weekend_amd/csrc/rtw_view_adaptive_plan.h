@@ -1,7 +1,7 @@
 // rtw_view_adaptive_plan.h — what rtw_views_adaptive / rtw_views_adaptive_device decide on the host from sizes alone (no HIP in here, in
 // the style of rtw_radiance_plan.h). A pass is rtw_probe_adaptive's (rtw_probe_adaptive_plan.h: the blocks of a pass, R, J, the slab,
 // the ranges of list positions and the per-entry state, with n = the pixels of the call or batch); what views add is the cut of the
-// host entry into batches of whole views and, restated here for the check, the pixel that k_view_adapt_decide reads for a tap.
+// host entry into batches of whole views and, restated here for the check, the pixel that k_adapt_decide (rtw_adaptive.h) reads for a tap.
 // tests/native/view_adaptive_plan_check.cpp pins them with g++.
 #pragma once
 #include <stdint.h>
@@ -30,7 +30,7 @@ inline RadianceRange view_adaptive_batch(uint64_t n_views, uint64_t per, uint64_
 inline uint64_t view_adaptive_chunk(uint64_t per, int32_t width, int32_t height) { return per * (uint64_t)(uint32_t)width * (uint64_t)(uint32_t)height; }
 
 // The pixel that tap (dx, dy), each in -1..1, of flattened pixel p reads under dilate = 1: p's own view, the row and the column
-// clamped to the frame (k_view_adapt_decide: view * width * height + yy * width + xx). It never leaves the view's frame.
+// clamped to the frame (k_adapt_decide: view * width * height + yy * width + xx). It never leaves the view's frame.
 inline uint64_t view_adaptive_neighbour(uint64_t p, int32_t width, int32_t height, int32_t dx, int32_t dy) {
     const ViewPixel v = view_pixel(p, width, height);
     const int64_t yy = std::min<int64_t>(std::max<int64_t>((int64_t)v.y + dy, 0), (int64_t)height - 1);

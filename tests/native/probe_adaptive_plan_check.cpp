@@ -1,7 +1,8 @@
 // CPU check of rtw_probe_adaptive's planning (raytracing_weekend_amd/csrc/rtw_probe_adaptive_plan.h), compiled with
 // g++ -fsanitize=address,undefined and run by tests/test_probe_adaptive_cpu.py: the blocks of every pass tile the probe's samples,
 // the runs of R blocks tile a pass, the ranges under a slab cap tile the list, nothing wraps at 2^31 - 1 probes, and J and R never
-// give zero work or more units than a launch may number. Prints "probe_adaptive_plan_check ok" and returns 0, or says what failed.
+// give zero work or more units than a launch may number; and the adaptive family's state layout (rtw_adaptive_plan.h), with and without
+// the renderer's `part`. Prints "probe_adaptive_plan_check ok" and returns 0, or says what failed.
 #include <cstdio>
 #include <vector>
 
@@ -99,16 +100,32 @@ int main() {
     CHECK(probe_adaptive_range_positions(kBig, 4, 4, 1ull << 62) == kBig && probe_adaptive_range_positions(kBig, 4, 1, 1ull << 62) == kBig / 4);
     CHECK(probe_adaptive_range_positions(kBig, 4, 4, 1ull << 30) == (1ull << 30) / 64);
     CHECK(probe_adaptive_range_positions(0, 4, 4, 1ull << 30) == 1);
-    // the state: sections in order, 256-byte aligned, every array inside the allocation
-    for (uint64_t n : {1ull, 63ull, 64ull, 65ull, 96ull, 131075ull, kBig}) {
-        const ProbeAdaptiveLayout l = probe_adaptive_layout(n);
-        const uint64_t nw = (n + 63) / 64;
-        const uint64_t need[ProbeAdaptiveLayout::kSections] = {n * 16, n * 16, n * 16, n * 4, n * 4, n * 4, n * 4 + 4, n * 4 + 4, nw * 8, nw * 4};
-        CHECK(l.off[0] == 0);
-        for (int k = 0; k < ProbeAdaptiveLayout::kSections; k++) CHECK(l.off[k] % 256 == 0 && l.off[k + 1] >= l.off[k] + need[k]);
-        CHECK(l.bytes() == l.off[ProbeAdaptiveLayout::kSections] && l.bytes() >= n * 68);
-        CHECK(probe_adaptive_layout(n + 1).bytes() >= l.bytes());
-    }
+    // the family's state (rtw_adaptive_plan.h), with and without the renderer's `part`: sections in order, 256-byte aligned, every
+    // array inside the allocation, no section's offset smaller for more entries
+    typedef AdaptiveLayout AL;
+    const auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+    for (const bool want_part : {false, true})
+        for (uint64_t n : {1ull, 63ull, 64ull, 65ull, 96ull, 131075ull, kBig}) {
+            const AL l = adaptive_layout(n, want_part);
+            const uint64_t nw = (n + 63) / 64;
+            uint64_t need[AL::kSections];
+            need[AL::kAccum] = n * 16; need[AL::kUpart] = n * 16; need[AL::kPart] = want_part ? n * 16 : 0; need[AL::kMom] = n * 16;
+            need[AL::kN] = n * 4; need[AL::kErr] = n * 4; need[AL::kTotal] = n * 4; need[AL::kList0] = n * 4 + 4; need[AL::kList1] = n * 4 + 4;
+            need[AL::kMasks] = nw * 8; need[AL::kOffsets] = nw * 4;
+            CHECK(l.off[0] == 0);
+            for (int k = 0; k < AL::kSections; k++) CHECK(l.off[k] % 256 == 0 && l.off[k + 1] >= l.off[k] + need[k]);
+            CHECK(l.off[AL::kPart + 1] - l.off[AL::kPart] == (want_part ? up(n * 16) : 0));  // a query's entry does not pay for `part`
+            CHECK(l.bytes() == l.off[AL::kSections] && l.bytes() >= n * (want_part ? 84 : 68));
+            const AL m = adaptive_layout(n + 1, want_part);
+            for (int k = 0; k <= AL::kSections; k++) CHECK(m.off[k] >= l.off[k]);
+            // without `part`: the bytes of the layout the probes had before the family shared it, section by section
+            if (!want_part)
+                CHECK(l.bytes() == 3 * up(n * 16) + 3 * up(n * 4) + 2 * up(n * 4 + 4) + up(nw * 8) + up(nw * 4));
+            else
+                CHECK(l.bytes() == adaptive_layout(n, false).bytes() + up(n * 16));
+        }
+    CHECK(adaptive_layout(1, false).bytes() == 10 * 256 && adaptive_layout(65, false).bytes() == 3 * 1280 + 3 * 512 + 2 * 512 + 2 * 256);
+    CHECK(adaptive_layout(kBig, false).bytes() == 3 * 34359738368ull + 5 * 8589934592ull + 268435456ull + 134217728ull);
     if (fails) return 1;
     printf("probe_adaptive_plan_check ok\n");
     return 0;

@@ -36,7 +36,7 @@ static void taps(int n_views, int w, int h) {
                         CHECK(q >= (uint64_t)v * frame && q < (uint64_t)(v + 1) * frame);  // never another view
                         CHECK(q < (uint64_t)n_views * frame);
                         if (dx == 0 && dy == 0) CHECK(q == p);
-                        // one view: k_adapt_decide's own index (rows = h)
+                        // one view: the frame's own index, which is how rtw_render_adaptive runs k_adapt_decide (its shard: height = rows)
                         if (n_views == 1) CHECK(q == (uint64_t)clampi(y + dy, 0, h - 1) * w + (uint64_t)clampi(x + dx, 0, w - 1));
                     }
                 seen[p]++;
@@ -134,7 +134,7 @@ int main() {
             }
             prev = n_k;
         }
-        const ProbeAdaptiveLayout l = probe_adaptive_layout(kBig);  // the per-pixel state of the largest call
+        const AdaptiveLayout l = adaptive_layout(kBig, false);  // the per-pixel state of the largest call
         CHECK(l.bytes() >= kBig * 68);
     }
     if (fails) return 1;

@@ -90,18 +90,17 @@ def test_extremes(gpu):
     assert (spp == 48).all() and np.array_equal(_bits(img), _bits(ref))
 
 
-@pytest.mark.parametrize("blob_kind", ["path", "tree"])
-def test_decisions_match_the_reference(gpu, blob_kind):
-    w, h, cap, mn = 32, 24, 256, 32
-    blob = abi.build_scene(0, w, h) if blob_kind == "path" else oracle.random_scene(5, w, h, n_prims=48)
+def _check_decisions(gpu, blob, w, h, cap, mn, depth, q, max_near=None):
+    """spp, err and the image against adaptive_ref fed with block sums from 16-spp renders, dilate 0 and 1, at a threshold that is the
+    q-quantile of the first checkpoint's errors. max_near: where given, the most pixels the tie rule may leave out."""
     gpu.upload_scene(blob)
     S = np.empty((cap // 16, h, w, 3), np.float32)
     for b in range(cap // 16):
-        img, _ = gpu.render(abi.make_params(w, h, 16, 8, sample_offset=16 * b))
+        img, _ = gpu.render(abi.make_params(w, h, 16, depth, sample_offset=16 * b))
         S[b] = img[..., :3] * np.float32(16)
-    p = abi.make_params(w, h, cap, 8)
+    p = abi.make_params(w, h, cap, depth)
     for dilate in (0, 1):
-        T = _threshold(gpu, p, mn, 0.6)
+        T = _threshold(gpu, p, mn, q)
         img, spp, err, _ = gpu.render_adaptive(p, T, min_spp=mn, dilate=dilate)
         rimg, rspp, rerr = ar.adaptive(S, T, mn, 0, cap, dilate)
         assert np.allclose(err, rerr, rtol=1e-6, atol=0), np.max(np.abs(err - rerr) / np.maximum(rerr, 1e-30))
@@ -116,8 +115,30 @@ def test_decisions_match_the_reference(gpu, blob_kind):
                 for dx in (-1, 0, 1):
                     near |= tie[np.clip(np.arange(h) + dy, 0, h - 1)][:, np.clip(np.arange(w) + dx, 0, w - 1)]
         ok = ~near
+        print(f"{w}x{h} dilate {dilate}: T {T!r}, {np.count_nonzero(near)} of {w * h} pixels left out, spp {dict(zip(*np.unique(rspp, return_counts=True)))}")
+        if max_near is not None:
+            assert np.count_nonzero(near) <= max_near, (np.count_nonzero(near), max_near)
         assert np.array_equal(spp[ok], rspp[ok]), np.count_nonzero(spp[ok] != rspp[ok])
         assert np.array_equal(_bits(img[ok]), _bits(rimg[ok]))
+
+
+# Beside the 32 x 24 frame, scene 0 is checked on the smallest frames with a partial last wave, a single column and a single row
+# (13 x 7, 1 x 37, 67 x 1; cap 96, depth 4): the stop rule runs through the kernel written for batches of views (one view of
+# width x rows), where the clamped 3x3 neighbourhood and the view-relative index can go wrong. There the threshold is the
+# 0.55-quantile of the first checkpoint's positive errors. On the CPU oracle's block sums (test_adaptive_cpu.py _oracle_blocks) 49 of
+# the 91, 28 of the 37 and 1 of the 67 pixels have one - the rest see nothing - so the quantile falls strictly between two pixels'
+# errors in the first two frames (0.55 * 48 and 0.55 * 27 are no integers) and on the one lit pixel's own error in the third: there
+# the reference leaves out 0, 0 and 1 pixels undilated and 0, 0 and 3 dilated. The tie rule may leave out at most a fifth of the frame.
+SMALL_FRAMES = [(13, 7), (1, 37), (67, 1)]
+
+
+@pytest.mark.parametrize("blob_kind", ["path", "tree"])
+def test_decisions_match_the_reference(gpu, blob_kind):
+    w, h = 32, 24
+    _check_decisions(gpu, abi.build_scene(0, w, h) if blob_kind == "path" else oracle.random_scene(5, w, h, n_prims=48), w, h, 256, 32, 8, 0.6)
+    if blob_kind == "path":
+        for w, h in SMALL_FRAMES:
+            _check_decisions(gpu, abi.build_scene(0, w, h), w, h, 96, 32, 4, 0.55, max_near=(w * h) // 5)
 
 
 # (RTW_POOL_PATHS with RTW_PATH=0: the wavefront pipeline with 3 samples per pixel and batch, two lanes; alone it would not act on
